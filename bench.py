@@ -8,7 +8,11 @@ traceback + results on the host, inputs resident in HBM when the timed region st
 One "step" = one pass of the hot path over one batch of --reads reads per GPU (default 2048; the
 full 100 000-read set is 49 such batches — 7.5e14 cells — and the per-batch rate is size-normalised).
 
-Launch:  python bench.py --gpus N --steps K --warmup W
+Launch:  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+  * plain run: set-up, W warm-up steps, K timed steps, the outputs of the last step (--dump-outputs) and the result line.
+  * --full: also the side measurements and checks (in-run parity, strong scaling, other engines / lengths / configs,
+    one-by-one calls, HBM traffic by rocprofv3 child passes, the PCIe-inclusive step, the CPU baseline); the --no-* options
+    switch single ones off again.
   * N = 1: runs in this process.
   * N > 1: this process touches no GPU; it starts `python -m torch.distributed.run --nproc-per-node N bench.py ...`
     as a CHILD (never exec), relays rank 0's JSON line and exits with the child's code.
@@ -717,6 +721,36 @@ def strong_config5(pgs, D, args, device):
             "score": res["score"], "pos": res["pos"], "planted_at": off + 1}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, ctx, last, rank, world, read_len):
+    """What the last timed step returned to its caller, as DIR/<name>.npy in float32 / float64: per alignment `score`, `pos`,
+    `end_x`, `end_y`, `cons_len`; both consensus strings of every alignment as byte codes, concatenated in alignment order
+    (`cons_x`, `cons_y`, split by cons_len); `best` = the step's merged (score, read).  Where that would pass 64 MB (a consensus
+    string is taken as at most 2 x read_len long), a fixed sample of the alignments (seed 0) is written; `read_index` names the
+    alignments written.  With several ranks each rank writes its own reads as rank<r>_<name>.npy."""
+    out, key = last
+    n = len(out["score"])
+    per_read = 4 + 8 * 5 + 2 * 4 * 2 * read_len
+    idx = np.arange(n)
+    if n * per_read > DUMP_LIMIT_BYTES:
+        idx = np.random.default_rng(0).permutation(n)[:DUMP_LIMIT_BYTES // per_read]
+    idx = np.sort(idx)
+    cons = [ctx.consensus(int(k)) for k in idx]                          # library memory: valid until the next call on ctx
+    codes = lambda s: np.frombuffer("".join(s).encode("latin-1"), dtype=np.uint8).astype(np.float32)
+    arrays = {"read_index": idx.astype(np.float64), "score": out["score"][idx].astype(np.float32)}
+    for f in ("pos", "end_x", "end_y", "cons_len"):
+        arrays[f] = np.asarray(out[f])[idx].astype(np.float64)
+    arrays["cons_x"] = codes(c[0] for c in cons)
+    arrays["cons_y"] = codes(c[1] for c in cons)
+    arrays["best"] = np.array([np.uint32(key >> 32).view(np.float32), 0xFFFFFFFF - (key & 0xFFFFFFFF)], dtype=np.float64)
+    os.makedirs(path, exist_ok=True)
+    prefix = "" if world == 1 else "rank%d_" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
+
+
 def worker(args):
     D = Dist(args)
     rank, world, local_rank = D.rank, D.world, D.local_rank
@@ -748,6 +782,9 @@ def worker(args):
         ctx.batch_upload([r.tobytes() for r in reads])
         ctx.batch_run(semantics=sem, match=args.match, mismatch=args.mismatch, gap=args.gap, flags=flags, raw=True)
         pcie = time.perf_counter() - tp
+    else:
+        # set-up: the first call sizes the library's device buffers (in a --full run the PCIe-inclusive step above does it)
+        ctx.batch_run(semantics=sem, match=args.match, mismatch=args.mismatch, gap=args.gap, flags=flags, raw=True)
     for _ in range(args.warmup):
         step()
     acc = {"kern_us": 0.0, "launches": 0, "locate_us": 0.0, "trace_us": 0.0}
@@ -759,6 +796,8 @@ def worker(args):
         acc["locate_us"] += tm["locate_us"]; acc["trace_us"] += tm["trace_us"]
         return r
     dt, last = timed(D, timed_step, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, last, rank, world, args.read_len)
     ki = ctx.last_kernel()                                                  # the instance the library chose (not re-derived here)
     # in-run verification (outside the timed region): the same resident batch once more on float32 cells — another kernel
     # instance, another candidate path (option force_f32) — every (score, pos, end_x, end_y, cons_len) must agree
@@ -896,14 +935,18 @@ def main():
     ap.add_argument("--match", type=float, default=3.0)
     ap.add_argument("--mismatch", type=float, default=-3.0)
     ap.add_argument("--gap", type=float, default=2.0, help="non-integer scoring selects the float32-cell kernel instance")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the N = 1 side measurements (other engines, configs 4 / 5, one-by-one calls)")
-    ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling passes")
-    ap.add_argument("--no-config5", action="store_true", help="skip everything that needs the 250 Mbp reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks (everything the --no-* options below switch off); "
+                         "without it the run times the headline workload only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the PCIe-inclusive step")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the N = 1 side measurements (other engines, configs 4 / 5, one-by-one calls)")
+    ap.add_argument("--no-strong", action="store_true", help="with --full: skip the strong-scaling passes")
+    ap.add_argument("--no-config5", action="store_true", help="with --full: skip everything that needs the 250 Mbp reference")
     ap.add_argument("--strong-reads", type=int, default=100_000,
                     help="total reads of the strong-scaling pass (all ranks together): all of configs[2] by default")
-    ap.add_argument("--no-traffic", action="store_true", help="do not measure HBM traffic with rocprofv3 child passes (replay profiles/pmc_traffic.json)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the in-run parity checks against other kernel instances")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: do not measure HBM traffic with rocprofv3 child passes (replay profiles/pmc_traffic.json)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the in-run parity checks against other kernel instances")
     ap.add_argument("--c4-sequences", type=int, default=561_356)
     ap.add_argument("--c5-ref-len", type=int, default=250_000_000)
     ap.add_argument("--c5-query-len", type=int, default=10_000)
@@ -912,6 +955,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_extras = args.no_strong = args.no_traffic = args.no_parity = True
     if "RANK" not in os.environ and args.gpus > 1:
         launch(args, sys.argv[1:])
     worker(args)

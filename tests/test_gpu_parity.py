@@ -159,8 +159,10 @@ def test_full_size_planted_reads(ctx, pgs):
 def _cpp_test_binary(name):
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if name in ("test_dropin_eigen.bin", "test_reference_gtests.bin"):
+        return os.path.join(root, "oracle", "_ref", name)                 # built with the reference driver (oracle/build_ref.sh)
     exe = os.path.join(root, "tests", "cpp", name)
-    if not os.path.exists(exe) and name not in ("test_dropin_eigen.bin", "test_reference_gtests.bin"):
+    if not os.path.exists(exe):
         import __graft_entry__ as g
         g.build()
     return exe
@@ -168,7 +170,7 @@ def _cpp_test_binary(name):
 
 def test_reference_gtest_files_compiled_in_place():
     """The reference's OWN test files (/root/reference/test/main.cpp, test_localaligner.cpp, test_skewedmatrix.cpp, …), compiled
-    where they lie against include/parseq/*.h and a build-owned minimal <gtest/gtest.h> (tests/cpp/build_dropin.sh), run on the
+    where they lie against include/parseq/*.h and a build-owned minimal <gtest/gtest.h> (oracle/build_ref.sh), run on the
     GPU: SWAligner_Test.Example_small_sequence_alignment / Verify_consensus_strings, SimilarityMatrix.SkewedMatrixIndex /
     SkewedMatrixDP — the four real tests of the reference.  Prebuilt where the reference exists (the binary
     travels to the GPU box); where it did not travel this is SKIPPED, not passed."""
@@ -176,7 +178,7 @@ def test_reference_gtest_files_compiled_in_place():
     import subprocess
     exe = _cpp_test_binary("test_reference_gtests.bin")
     if not os.path.exists(exe):
-        pytest.skip("tests/cpp/test_reference_gtests.bin was not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/test_reference_gtests.bin was not built (needs the reference sources at build time)")
     p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
     out = p.stdout.decode()
     assert p.returncode == 0 and "[  PASSED  ] 4 tests." in out, out
@@ -203,14 +205,14 @@ def test_cpp_dropin_binary():
 
 
 def test_cpp_dropin_binary_with_eigen():
-    """The same source compiled against the reference's vendored Eigen (tests/cpp/build_dropin.sh): Eigen::VectorXf
+    """The same source compiled against the reference's vendored Eigen (oracle/build_ref.sh): Eigen::VectorXf
     getTimings(), const Eigen::MatrixXf &get_matrix(), MatrixX8u raw storage.  The binary is prebuilt where the reference
     exists (it travels to the GPU box); where it did not travel this leg is SKIPPED, not passed."""
     import os
     import subprocess
     exe2 = _cpp_test_binary("test_dropin_eigen.bin")
     if not os.path.exists(exe2):
-        pytest.skip("tests/cpp/test_dropin_eigen.bin was not built (needs the reference's vendored Eigen zip at build time)")
+        pytest.skip("oracle/_ref/test_dropin_eigen.bin was not built (needs the reference's vendored Eigen zip at build time)")
     p = subprocess.run([exe2], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
     assert p.returncode == 0 and b"ALL OK" in p.stdout and b"Eigen signatures: ok" in p.stdout, p.stdout.decode()
 

@@ -28,7 +28,7 @@ done
 python3 $R/tools/lone_probe.py > $OUT/lone_reads_by_length.log 2>&1
 python3 $R/tools/lone_short.py > $OUT/lone_short_reads.log 2>&1
 cd $R
-python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 for t in bench_FETCH_SIZE:bench_WRITE_SIZE:bench_SQ_INSTS_VALU:bench_SQ_INSTS_LDS wide600_SQ_INSTS_VALU:wide600_SQ_INSTS_LDS u8_2048_SQ_INSTS_VALU:u8_2048_SQ_INSTS_LDS f32_2048_SQ_INSTS_VALU:f32_2048_SQ_INSTS_LDS; do
   dirs=$(echo $t | tr ':' '\n' | sed "s#^#$OUT/pmc_#" | tr '\n' ' ')
   name=$(echo $t | cut -d: -f1 | sed 's/_SQ_INSTS_VALU//; s/_FETCH_SIZE//')
