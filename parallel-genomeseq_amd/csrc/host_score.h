@@ -32,6 +32,7 @@ struct Bucket {
   bool twin = false;          // lone long query: two tiles of it per packed register (sw_score_kernel TWIN)
   bool comb = false;          // twin on 16-lane tiles, small alphabet: profile indexed by the pair of codes (COMB)
   bool unsat = false;         // uint8 engine swept by a float-engine instance WITHOUT saturation, maxima clamped at 255
+  bool mirror = false;        // kSemF16 bucket swept on MIRRORED cells (sw_score_kernel kSemF16M, lemma L14): scores stay within 1024
   bool sampled = false;       // running maximum folded every 4th step (sw_score_kernel MK = 4): sub-chunk values are lower bounds
                               // within 3 gaps of the truth; sub-chunks within that slack of the key are re-evaluated exactly
   bool opt_margin = false;    // sw_long_kernel: optimistic warm-up margin, certified afterwards (long_score_launch)
@@ -190,6 +191,14 @@ bool sampled_instance(int SL, int R) {
   return false;
 }
 
+// Mirrored float16 cells (kSemF16M, lemma L14) for a kSemF16 bucket of two-query tiles: every value of the sweep stays within
+// 1024 (smax * maxlen + smax: a cell's value and its diagonal term), where N = 1 - H / 2048 keeps to one float16 binade; 8- and
+// 16-lane tiles in one strip.  Option no_f16_mirror keeps today's cell.
+bool mirror_ok(const ScoreTable &t, const Bucket &b) {
+  return !opt().no_f16_mirror && t.integral && !b.twin && !b.strips && !b.satflag && (b.SL == 8 || b.SL == 16) &&
+         (int64_t)t.smax * b.maxlen + t.smax <= 1024 && t.gap >= 0 && t.gap <= 2040;
+}
+
 std::vector<Bucket> make_buckets(const RefData &ref, const QueryBatch &q, const ScoreTable &t, const mi355_sw_params &p, int64_t n,
                                  bool allow_sat = false, bool allow_sample = false) {
   std::vector<Bucket> out;
@@ -245,6 +254,7 @@ std::vector<Bucket> make_buckets(const RefData &ref, const QueryBatch &q, const 
           b.sampled = allow_sample && !b.strips && sampled_instance(b.SL, b.R) && !opt().no_sample &&
                       ref.ncodes - 1 >= 4 &&             // (two- and three-letter alphabets: random matches every other column)
                       (!opt().u8_sample_short || 0.3 * (double)t.smax * (double)b.maxlen + 3.0 * (double)t.gap < 230.0);
+          b.mirror = mirror_ok(t, b);
         }
         else if (twin16_ok && !b.strips && b.SL != 64) {
           b.sem = kSemF16; b.unsat = true; b.twin = true; twin_shape(ref, b);
@@ -271,6 +281,7 @@ std::vector<Bucket> make_buckets(const RefData &ref, const QueryBatch &q, const 
         b.sem = kSemF16;
         // the running maximum every 4th step, the sub-chunks within 3 gaps of the key re-evaluated exactly (sw_score_kernel MK; lemma L5)
         b.sampled = allow_sample && sampled_instance(b.SL, b.R) && !opt().no_sample;
+        b.mirror = mirror_ok(t, b);
       }
       // (Lemma L6.)  Beyond float16's exact range (reads above 680 bp at match 3) the packed int16 cell costs 4.5 ops.  The float16
       // cell still sweeps them when its clamp is allowed to SATURATE the values at 2048: if the true maximum M is below
@@ -452,6 +463,24 @@ int launch_score_f16(int R, int SL, bool strips, dim3 grid, size_t shmem, hipStr
 #define CASE_H(r) case r: launch_score(sw_score_kernel<r, SEM, false>, grid, shmem, st, a); return 0;
     CASE_H(2) CASE_H(4) CASE_H(6) CASE_H(8) CASE_H(10) CASE_H(12) CASE_H(16) CASE_H(20) CASE_H(24) CASE_H(32)
 #undef CASE_H
+  }
+  return -1;
+}
+
+// mirrored packed float16 cells (kSemF16M): the kSemF16 buckets whose values stay within 1024, 8- and 16-lane tiles in one strip
+int launch_score_f16m(int R, int SL, bool strips, dim3 grid, size_t shmem, hipStream_t st, const ScoreArgs &a) {
+  if (strips) return -1;
+  const bool mk = a.submax_out != nullptr;     // sampled running maximum (MK = 4)
+  switch ((mk ? 10000 : 0) + SL * 100 + R) {
+#define CASE_FM(sl, r) case sl * 100 + r: launch_score(sw_score_kernel<r, kSemF16M, false, sl>, grid, shmem, st, a); return 0;
+#define CASE_FMM(sl, r) case 10000 + sl * 100 + r: launch_score(sw_score_kernel<r, kSemF16M, false, sl, false, false, 4>, grid, shmem, st, a); return 0;
+    CASE_FM(8, 7) CASE_FM(8, 10) CASE_FM(8, 13) CASE_FM(8, 16) CASE_FM(8, 19) CASE_FM(8, 26) CASE_FM(8, 32)
+    CASE_FM(16, 2) CASE_FM(16, 4) CASE_FM(16, 6) CASE_FM(16, 8) CASE_FM(16, 10) CASE_FM(16, 12) CASE_FM(16, 16) CASE_FM(16, 20)
+    CASE_FM(16, 24) CASE_FM(16, 32)
+    CASE_FMM(8, 13) CASE_FMM(8, 16) CASE_FMM(8, 19) CASE_FMM(8, 26) CASE_FMM(8, 32)
+    CASE_FMM(16, 10) CASE_FMM(16, 12) CASE_FMM(16, 16) CASE_FMM(16, 20) CASE_FMM(16, 24) CASE_FMM(16, 32)
+#undef CASE_FM
+#undef CASE_FMM
   }
   return -1;
 }
@@ -908,6 +937,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   a.ncodes = ref.ncodes;
   if (b.sem == kSemF32) { const float gs = std::ldexp(t.gapf, -ctx->fshift); memcpy(&a.gap2, &gs, 4); }
   else if (sem_is_float(b.sem)) memcpy(&a.gap2, &t.gapf, 4);
+  else if (b.sem == kSemF16 && b.mirror) a.gap2 = (uint32_t)t.gap * 0x00010001u;   // added to the bit pattern of both halves
   else if (b.sem == kSemF16) a.gap2 = (uint32_t)half_bits(-(float)t.gap / kF16Scale) * 0x00010001u;
   else if (b.sem == kSemU8H) a.gap2 = (uint32_t)half_bits(-(float)t.gap / 256.0f) * 0x00010001u;
   else a.gap2 = (uint32_t)t.gap * 0x00010001u;
@@ -972,6 +1002,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
                      : b.sem == kSemU8H ? launch_score_twin<kSemU8H>(b.R, b.strips, grid, shmem, ctx->stream, a)
                      : b.sem == kSemU8 ? launch_score_twin<kSemU8>(b.R, b.strips, grid, shmem, ctx->stream, a)
                                        : launch_score_twin<kSemI16>(b.R, b.strips, grid, shmem, ctx->stream, a))
+           : b.sem == kSemF16 && b.mirror ? launch_score_f16m(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
            : b.sem == kSemF16 ? launch_score_f16<kSemF16>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
            : b.sem == kSemU8H ? launch_score_R<kSemU8H>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
            : b.sem == kSemU8 ? launch_score_R<kSemU8>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
@@ -982,8 +1013,9 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   HIPCHK(ctx, hipGetLastError());
   {
     static const char *cellname[] = {"i16", "u8i16", "f32", "u8f32", "f16", "u8f16"};
-    path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d,satflag=%d,unsat=%d,pow2=%d]", cellname[b.sem], b.SL, b.R, (int)b.strips,
-              (int)b.twin, (int)b.comb, (int)b.sampled, (int)b.satflag, (int)b.unsat, (int)((b.chunk_len & (b.chunk_len - 1)) == 0));
+    path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d,satflag=%d,unsat=%d,pow2=%d%s]", cellname[b.sem], b.SL, b.R, (int)b.strips,
+              (int)b.twin, (int)b.comb, (int)b.sampled, (int)b.satflag, (int)b.unsat, (int)((b.chunk_len & (b.chunk_len - 1)) == 0),
+              b.mirror ? ",mirror=1" : "");
   }
   if (b.sampled) {
     // grid.y = query positions of this launch, at most 65535 per filter launch
@@ -1028,7 +1060,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     ki.chunk_len = b.chunk_len; ki.sub_len = b.sub_len; ki.warm = a.warm; ki.cells = cells;
     ki.valu_ops_per_cell = valu_ops_per_cell(b);
     static const char *cellname[] = {"i16x2", "u8 as i16x2", "f32", "u8 as f32", "f16x2", "u8 as f16x2"};
-    std::snprintf(ki.name, sizeof ki.name, "sw_score_kernel<R=%d, %s, SL=%d%s%s>%s", b.R, cellname[b.sem], b.SL,
+    std::snprintf(ki.name, sizeof ki.name, "sw_score_kernel<R=%d, %s%s, SL=%d%s%s>%s", b.R, cellname[b.sem], b.mirror ? " mirrored" : "", b.SL,
                   b.strips ? ", strips" : "", b.twin ? (b.comb ? ", twin, code-pair profile" : ", twin") : "",
                   b.unsat ? " uint8 engine swept unsaturated, maxima clamped at 255"
                   : b.satflag ? (b.sampled ? " float engine swept saturating at 2048" : " float engine swept saturating at 2048, saturated sub-chunks re-evaluated exactly") : "");

@@ -60,6 +60,13 @@ constexpr int kSemU8H = 5;             // Similarity_Matrix_Skewed semantics in 
                                        // [0, 1] clamp of v_pk_add_f16 is then the saturation at 255 (the lower clamp, H = -1,
                                        // lies below the explicit floor 1/256), so a cell costs the same four ops as kSemF16
 constexpr uint32_t kU8HZero = 0x1C001C00u;   // float16 1/256 in both halves: H = 0
+constexpr int kSemF16M = 6;            // kSemF16 MIRRORED (DESIGN.md §3.3 lemma L14): cells hold N = 1 - H / 2048, which for 0 <= H <= 1024
+                                       // lies in ONE float16 binade [0.5, 1], where the bit pattern is linear in H (one ulp per score
+                                       // unit).  Larger scores are smaller cells ("maximum" is the packed minimum), the clamp's upper
+                                       // end 1.0 is the zero floor, and H - g is an integer add of g to both halves of the pattern at
+                                       // once: a double-rate VOP2 v_add_u32 instead of a VOP3P op.  The host picks it for the kSemF16
+                                       // buckets whose scores stay within 1024 (Bucket::mirror); what is published is H / 2048 again
+constexpr uint32_t kF16MZero = 0x3C003C00u;  // float16 1.0 in both halves: H = 0
 constexpr float kPadScoreF = -1.0e30f;
 __host__ __device__ constexpr bool sem_is_float(int sem) { return sem == kSemF32 || sem == kSemF32U8; }
 
@@ -179,6 +186,30 @@ template <> struct Cell<kSemU8H> : Cell<kSemF16> {
     T r; asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "s"(kU8HZero)); return r;
   }
 };
+// Mirrored packed float16 cells: the order is reversed (every "maximum" is a packed minimum) and the gap term is an integer add.
+template <> struct Cell<kSemF16M> : Cell<kSemF16> {
+  // clamp(N_nw - s): 1 - (H_nw + s) / 2048, exact while H_nw + s <= 1024; the upper clamp 1.0 is the zero floor (H_nw + s < 0)
+  static __device__ __forceinline__ T add(T d, T sc, uint32_t) {
+    T r; asm("v_pk_add_f16 %0, %1, %2 clamp" : "=v"(r) : "v"(d), "v"(sc)); return r;
+  }
+  static __device__ __forceinline__ T vmax(T a, T b) {
+    T r; asm("v_pk_min_f16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
+  }
+  static __device__ __forceinline__ T vmax3(T a, T b, T c) {
+    T r; asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
+  }
+  // H - g on the bit pattern: gap2 = g in both halves (no carry crosses them: a half is at most 0x3C00 + g).  Below H = g the
+  // pattern leaves [0.5, 1] upwards — a value above 1.0, which never wins the minimum against the clamped diagonal term.
+  // Inline asm, so that the compiler cannot fuse it into a half-rate v_add3_u32 / v_lshl_add_u32.  gap2 is a VGPR: a VOP2
+  // add with an SGPR operand issues at the VOP3P rate (profiles/r05_mirror_cell_rate.txt)
+  static __device__ __forceinline__ T sub_gap(T t, uint32_t gap2) {
+    T r; asm("v_add_u32 %0, %1, %2" : "=v"(r) : "v"(gap2), "v"(t)); return r;
+  }
+  // back to H / 2048 = 1 - N (exact: Sterbenz) for publishing
+  static __device__ __forceinline__ T unmirror(T n) {
+    T r; asm("v_pk_add_f16 %0, %1, %2 neg_lo:[1,0] neg_hi:[1,0]" : "=v"(r) : "v"(n), "s"(kF16MZero)); return r;
+  }
+};
 // float32 cells hold H * 2^-k with 2^k above every value of the call (a pure exponent shift: every add, subtract
 // and maximum commutes with it exactly), so that the [0, 1] clamp of the add is the zero floor and the cell takes the
 // same three ops as the packed float16 instance: add clamp, max3 with the two kept (H - g) terms, subtract g.
@@ -193,11 +224,11 @@ template <> struct Cell<kSemF32> : CellF<kSemF32> {
 template <> struct Cell<kSemF32U8> : CellF<kSemF32U8> {};
 
 // bit pattern of H = 0 in a cell register
-template <int SEM> __host__ __device__ constexpr uint32_t zero_bits() { return SEM == kSemU8H ? kU8HZero : 0u; }
+template <int SEM> __host__ __device__ constexpr uint32_t zero_bits() { return SEM == kSemU8H ? kU8HZero : (SEM == kSemF16M ? kF16MZero : 0u); }
 
 // three-input maximum where the cell type has one (packed float16), else two steps
 template <int SEM> __device__ __forceinline__ typename Cell<SEM>::T cell_max3(typename Cell<SEM>::T a, typename Cell<SEM>::T b, typename Cell<SEM>::T c) {
-  if constexpr (SEM == kSemF16 || SEM == kSemU8H) return Cell<SEM>::vmax3(a, b, c);
+  if constexpr (SEM == kSemF16 || SEM == kSemF16M || SEM == kSemU8H) return Cell<SEM>::vmax3(a, b, c);
   else return Cell<SEM>::vmax(Cell<SEM>::vmax(a, b), c);
 }
 
@@ -225,12 +256,13 @@ __device__ __forceinline__ uint32_t row_shr1(uint32_t v) {
 // 3 + 1/(2 MK) instead of 3.5 ops.
 template <int R, int SEM, bool STRIPS = false, int SL = 16, bool TWIN = false, bool COMB = false, int MK = 1>
 __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
-  static_assert(MK == 1 || (MK == 4 && !TWIN && ((SEM == kSemF16 && !STRIPS) || SEM == kSemF32)),
+  static_assert(MK == 1 || (MK == 4 && !TWIN && (((SEM == kSemF16 || SEM == kSemF16M) && !STRIPS) || SEM == kSemF32)),
                 "sampled maximum: packed float16 two-query tiles, or float32 cells (one query per tile)");
   static_assert(SL == 64 || SL == 16 || SL == 8, "a slot is a whole wavefront, a DPP row or half a DPP row");
   static_assert(!(STRIPS && SL == 8), "the strip-mined instances use whole DPP rows or whole wavefronts");
   static_assert(!TWIN || ((SL == 64 || SL == 16) && !sem_is_float(SEM) && R % 2 == 0), "twin tiles: packed cells on whole-wavefront or 16-lane tiles");
   static_assert(!COMB || (TWIN && !STRIPS), "the code-pair profile belongs to the twin instances");
+  static_assert(SEM != kSemF16M || (!TWIN && !STRIPS), "mirrored float16 cells: two-query tiles, one strip");
   constexpr bool HALF = TWIN && !COMB;                             // the profile holds 16-bit entries, two rows per dword
   constexpr int LS = HALF ? lane_stride(R / 2) : lane_stride(R);   // dwords between the profile rows of adjacent lanes
   constexpr int NQ4 = HALF ? (R / 2 + 3) / 4 : (R + 3) / 4;
@@ -298,11 +330,12 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
       } else {
         // 16-bit table entries: int16 scores, or float16 bit patterns for the packed float16 instance
         const int16_t *st = static_cast<const int16_t *>(a.stab);
-        constexpr int kPadEntry = SEM == kSemF16 ? (int)(int16_t)0xC800 /* float16 -8 = -16384 / 2048 */
+        constexpr int kPadEntry = (SEM == kSemF16 || SEM == kSemF16M) ? (int)(int16_t)0xC800 /* float16 -8 = -16384 / 2048 */
                                   : (SEM == kSemU8H ? (int)(int16_t)0xD400 /* float16 -64 = -16384 / 256 */ : kPadScore);
         const int sa = (i < mA) ? st[(int)xA[i] * a.ncodes + c] : kPadEntry;
         const int sb = (i < mB) ? st[(int)xB[i] * a.ncodes + c] : kPadEntry;
         e32 = (uint32_t)(uint16_t)sa | ((uint32_t)(uint16_t)sb << 16);
+        if (SEM == kSemF16M) e32 ^= 0x80008000u;                  // mirrored cells add -s (padding: +8, clamped to the floor)
       }
       prof[(c * PL + ll) * LS + r] = e32;
     }
@@ -398,13 +431,15 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   const int64_t total_steps = a.warm + a.chunk_len + SL;           // + SL-1 skew, + 1 max-fold drain
   const int nseg = (int)((total_steps + kSeg - 1) / kSeg);
 
-  T mx = C::from_bits(0u);
+  T mx = C::from_bits(zero_bits<SEM>());
   const int code_stride = PL * LS;                                 // dwords per reference code
   const int strip_rows = SL * R;
   const int mmax = mA > mB ? mA : mB;
   const int nstrips = STRIPS ? (mmax + strip_rows - 1) / strip_rows : 1;
   uint32_t first_lane_zero = ls == 0 ? 0u : 0xFFFFFFFFu;           // SL = 8: zero border row for lane 0 of the slot
   asm volatile("" : "+v"(first_lane_zero));                        // keep it a plain v_and_b32 (2 cycles), not a v_cndmask (4)
+  uint32_t first_lane_z = ls == 0 ? kF16MZero : 0u;                // kSemF16M: the border row's H = 0 on the tile's first lane
+  if constexpr (SEM == kSemF16M) asm volatile("" : "+v"(first_lane_z));
   // STRIPS: this tile's ping-pong boundary rows (global), and its LDS windows
   const size_t tile_id = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NSLOT + slot;
   uint32_t *brow0 = STRIPS ? a.brow + tile_id * 2 * (size_t)a.brow_stride : nullptr;
@@ -414,7 +449,8 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   // per-sub-chunk maximum -> per-query key.  Lanes lag lane 0 by up to SL-1 columns, so up to SL-1 trailing
   // columns of a sub-chunk are reported with the next one; the host widens its search accordingly.
   const int64_t subs_per_tile = a.chunk_len / a.sub_len;
-  uint32_t best_a = zero_bits<SEM>() & 0xFFFFu, best_b = best_a;   // this tile's best published value per query (H = 0: nothing to report)
+  // this tile's best published value per query (H = 0: nothing to report; mirrored cells publish H / 2048)
+  uint32_t best_a = (SEM == kSemF16M ? 0u : zero_bits<SEM>()) & 0xFFFFu, best_b = best_a;
   auto slot_max = [&]() -> uint32_t {                              // maximum of mx over the slot's lanes
     uint32_t m32 = C::bits(mx);
 #pragma unroll
@@ -470,19 +506,23 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
     }
   };
   auto publish = [&](int64_t sub) {
-    publish_value(sub, slot_max());
-    mx = C::from_bits(0u);
+    if constexpr (SEM == kSemF16M) publish_value(sub, C::unmirror(slot_max()));
+    else publish_value(sub, slot_max());
+    mx = C::from_bits(zero_bits<SEM>());
   };
   // STRIPS: a sub-chunk's maximum accumulates over all strips in LDS before it can be published
   uint32_t *submax = bwin + 2 * NSLOT * kSeg + slot * 64;
   auto fold_sub = [&](int64_t sub) {
     const uint32_t m32 = slot_max();
     if (ls == 0) submax[sub] = C::bits(C::vmax(C::from_bits(submax[sub]), C::from_bits(m32)));
-    mx = C::from_bits(0u);
+    mx = C::from_bits(zero_bits<SEM>());
   };
   if (STRIPS) {
     for (int e = ls; e < 64; e += SL) submax[e] = 0u;
   }
+  // the gap operand of sub_gap: the mirrored cell's integer add wants it in a VGPR (one copy, made once)
+  uint32_t gap_op = a.gap2;
+  if constexpr (SEM == kSemF16M) asm volatile("" : "+v"(gap_op));
   const int segs_per_sub = (int)(a.sub_len / kSeg);
   const int warm_segs = (int)(a.warm / kSeg);
   int64_t sub = 0;
@@ -530,10 +570,10 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
 #pragma unroll
     for (int r = 0; r < R; ++r) H[r] = C::from_bits(zero_bits<SEM>());
     uint32_t up_prev = zero_bits<SEM>();
-    constexpr bool kKeepsHg = SEM == kSemF16 || SEM == kSemF32;    // instances that keep H - g of every cell
+    constexpr bool kKeepsHg = SEM == kSemF16 || SEM == kSemF16M || SEM == kSemF32;   // instances that keep H - g of every cell
     T Hg[kKeepsHg ? R : 1];
 #pragma unroll
-    for (int r = 0; r < (kKeepsHg ? R : 1); ++r) Hg[r] = C::sub_gap(C::from_bits(0u), a.gap2);   // 0 - g
+    for (int r = 0; r < (kKeepsHg ? R : 1); ++r) Hg[r] = C::sub_gap(C::from_bits(zero_bits<SEM>()), gap_op);   // 0 - g
 
     for (int seg = 0; seg < nseg; ++seg) {
 #pragma unroll 4
@@ -567,10 +607,15 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
           up = shift_in(C::bits(H[R - 1]), bin_w[k]);
         } else {
           // zero border row H(0, .): bound_ctrl supplies it (no `old` operand to set up)
-          if (SEM == kSemU8H) {
+          if constexpr (SEM == kSemF16M && SL != 64) {
+            // bound_ctrl's zero, then one v_max_u32 with H = 0 on the tile's first lane: a cell N <= 1.0 in both halves is, as a
+            // 32-bit word, at most kF16MZero, so the maximum is kF16MZero there and the value of the lane above elsewhere
+            up = __builtin_elementwise_max(row_shr1(C::bits(H[R - 1])), first_lane_z);
+          } else if constexpr (zero_bits<SEM>() != 0u) {
             // the border row is the bit pattern of H = 0, not zero: `old` operand, and a bit-select for 8-lane tiles
-            up = shift_in(C::bits(H[R - 1]), kU8HZero);
-            if (SL == 8) up = (up & first_lane_zero) | (kU8HZero & ~first_lane_zero);
+            constexpr uint32_t Z = zero_bits<SEM>();
+            up = shift_in(C::bits(H[R - 1]), Z);
+            if (SL == 8) up = (up & first_lane_zero) | (Z & ~first_lane_zero);
           } else {
             if (SL == 64) up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)C::bits(H[R - 1]), 0x138 /*wave_shr:1*/, 0xf, 0xf, true);
             else up = row_shr1(C::bits(H[R - 1]));
@@ -582,11 +627,11 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
         up_prev = up;
         T tpend = C::from_bits(0u);
         (void)tpend;
-        if constexpr (SEM == kSemF16 || SEM == kSemF32) {
+        if constexpr (SEM == kSemF16 || SEM == kSemF16M || SEM == kSemF32) {
           // H = max(clamp0(NW + s), W - g, N - g): the cell keeps H (next step's diagonal) and H - g (this row's west
           // term next step, the row below's north term now) — add, maximum3, add per cell; the running maximum takes
           // two cells per maximum3
-          T ng = C::sub_gap(north, a.gap2);                        // (row above the lane's first) - g
+          T ng = C::sub_gap(north, gap_op);                        // (row above the lane's first) - g
 #pragma unroll
           for (int r = 0; r < R; ++r) {
             const T w = H[r];
@@ -599,7 +644,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
             }
             diag = w;
             H[r] = h;
-            ng = Hg[r] = C::sub_gap(h, a.gap2);
+            ng = Hg[r] = C::sub_gap(h, gap_op);
           }
         } else {
 #pragma unroll
