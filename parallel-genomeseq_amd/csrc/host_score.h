@@ -467,13 +467,15 @@ int launch_score_f16(int R, int SL, bool strips, dim3 grid, size_t shmem, hipStr
   return -1;
 }
 
-// mirrored packed float16 cells (kSemF16M): the kSemF16 buckets whose values stay within 1024, 8- and 16-lane tiles in one strip
+// mirrored packed float16 cells: the kSemF16 buckets whose values stay within 1024, 8- and 16-lane tiles in one strip; SEM =
+// kSemF16M (diagonal term as an integer add), or kSemF16MF (as a clamped float16 add: option no_f16m_int_diag)
+template <int SEM>
 int launch_score_f16m(int R, int SL, bool strips, dim3 grid, size_t shmem, hipStream_t st, const ScoreArgs &a) {
   if (strips) return -1;
   const bool mk = a.submax_out != nullptr;     // sampled running maximum (MK = 4)
   switch ((mk ? 10000 : 0) + SL * 100 + R) {
-#define CASE_FM(sl, r) case sl * 100 + r: launch_score(sw_score_kernel<r, kSemF16M, false, sl>, grid, shmem, st, a); return 0;
-#define CASE_FMM(sl, r) case 10000 + sl * 100 + r: launch_score(sw_score_kernel<r, kSemF16M, false, sl, false, false, 4>, grid, shmem, st, a); return 0;
+#define CASE_FM(sl, r) case sl * 100 + r: launch_score(sw_score_kernel<r, SEM, false, sl>, grid, shmem, st, a); return 0;
+#define CASE_FMM(sl, r) case 10000 + sl * 100 + r: launch_score(sw_score_kernel<r, SEM, false, sl, false, false, 4>, grid, shmem, st, a); return 0;
     CASE_FM(8, 7) CASE_FM(8, 10) CASE_FM(8, 13) CASE_FM(8, 16) CASE_FM(8, 19) CASE_FM(8, 26) CASE_FM(8, 32)
     CASE_FM(16, 2) CASE_FM(16, 4) CASE_FM(16, 6) CASE_FM(16, 8) CASE_FM(16, 10) CASE_FM(16, 12) CASE_FM(16, 16) CASE_FM(16, 20)
     CASE_FM(16, 24) CASE_FM(16, 32)
@@ -958,6 +960,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     a.flag_value = (uint32_t)half_bits(1.0f);                       // cells hold H / 2048: the clamp's upper end
   }
 
+  const bool idiag = b.sem == kSemF16 && b.mirror && !opt().no_f16m_int_diag;   // mirrored cells: diagonal term as an integer add
   const int nqw = (sem_is_float(b.sem) || b.twin) ? 1 : 2;          // queries per workgroup
   // keep single launches to a few seconds: split the bucket's pairs over several launches
   double range_cols = 0;
@@ -1002,7 +1005,8 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
                      : b.sem == kSemU8H ? launch_score_twin<kSemU8H>(b.R, b.strips, grid, shmem, ctx->stream, a)
                      : b.sem == kSemU8 ? launch_score_twin<kSemU8>(b.R, b.strips, grid, shmem, ctx->stream, a)
                                        : launch_score_twin<kSemI16>(b.R, b.strips, grid, shmem, ctx->stream, a))
-           : b.sem == kSemF16 && b.mirror ? launch_score_f16m(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
+           : b.sem == kSemF16 && b.mirror ? (idiag ? launch_score_f16m<kSemF16M>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
+                                                   : launch_score_f16m<kSemF16MF>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a))
            : b.sem == kSemF16 ? launch_score_f16<kSemF16>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
            : b.sem == kSemU8H ? launch_score_R<kSemU8H>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
            : b.sem == kSemU8 ? launch_score_R<kSemU8>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
@@ -1013,9 +1017,9 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   HIPCHK(ctx, hipGetLastError());
   {
     static const char *cellname[] = {"i16", "u8i16", "f32", "u8f32", "f16", "u8f16"};
-    path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d,satflag=%d,unsat=%d,pow2=%d%s]", cellname[b.sem], b.SL, b.R, (int)b.strips,
+    path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d,satflag=%d,unsat=%d,pow2=%d%s%s]", cellname[b.sem], b.SL, b.R, (int)b.strips,
               (int)b.twin, (int)b.comb, (int)b.sampled, (int)b.satflag, (int)b.unsat, (int)((b.chunk_len & (b.chunk_len - 1)) == 0),
-              b.mirror ? ",mirror=1" : "");
+              idiag ? ",idiag=1" : "", b.mirror ? ",mirror=1" : "");
   }
   if (b.sampled) {
     // grid.y = query positions of this launch, at most 65535 per filter launch
@@ -1060,7 +1064,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     ki.chunk_len = b.chunk_len; ki.sub_len = b.sub_len; ki.warm = a.warm; ki.cells = cells;
     ki.valu_ops_per_cell = valu_ops_per_cell(b);
     static const char *cellname[] = {"i16x2", "u8 as i16x2", "f32", "u8 as f32", "f16x2", "u8 as f16x2"};
-    std::snprintf(ki.name, sizeof ki.name, "sw_score_kernel<R=%d, %s%s, SL=%d%s%s>%s", b.R, cellname[b.sem], b.mirror ? " mirrored" : "", b.SL,
+    std::snprintf(ki.name, sizeof ki.name, "sw_score_kernel<R=%d, %s%s, SL=%d%s%s>%s", b.R, cellname[b.sem], b.mirror ? (idiag ? " mirrored, integer diagonal" : " mirrored") : "", b.SL,
                   b.strips ? ", strips" : "", b.twin ? (b.comb ? ", twin, code-pair profile" : ", twin") : "",
                   b.unsat ? " uint8 engine swept unsaturated, maxima clamped at 255"
                   : b.satflag ? (b.sampled ? " float engine swept saturating at 2048" : " float engine swept saturating at 2048, saturated sub-chunks re-evaluated exactly") : "");

@@ -65,10 +65,14 @@ constexpr int kSemF16M = 6;            // kSemF16 MIRRORED (DESIGN.md §3.3 lemm
                                        // unit).  Larger scores are smaller cells ("maximum" is the packed minimum), the clamp's upper
                                        // end 1.0 is the zero floor, and H - g is an integer add of g to both halves of the pattern at
                                        // once: a double-rate VOP2 v_add_u32 instead of a VOP3P op.  The host picks it for the kSemF16
-                                       // buckets whose scores stay within 1024 (Bucket::mirror); what is published is H / 2048 again
+                                       // buckets whose scores stay within 1024 (Bucket::mirror); what is published is H / 2048 again.
+                                       // The diagonal term is an integer add too (L14 (f)): the profile holds -s on the bit pattern
+                                       // of both halves, and the zero floor is the clamp of the cell's packed minimum3
+constexpr int kSemF16MF = 7;           // kSemF16M with the diagonal term as a clamped v_pk_add_f16 (option no_f16m_int_diag: the A/B)
 constexpr uint32_t kF16MZero = 0x3C003C00u;  // float16 1.0 in both halves: H = 0
 constexpr float kPadScoreF = -1.0e30f;
 __host__ __device__ constexpr bool sem_is_float(int sem) { return sem == kSemF32 || sem == kSemF32U8; }
+__host__ __device__ constexpr bool sem_is_mirror(int sem) { return sem == kSemF16M || sem == kSemF16MF; }
 
 // LDS stride (dwords) between the profile rows of two adjacent lanes: a multiple of 4 (b128
 // alignment) that is ≡ 4 (mod 8), so that the sixteen 16-byte windows of a ds_read_b128 lane
@@ -186,11 +190,18 @@ template <> struct Cell<kSemU8H> : Cell<kSemF16> {
     T r; asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "s"(kU8HZero)); return r;
   }
 };
-// Mirrored packed float16 cells: the order is reversed (every "maximum" is a packed minimum) and the gap term is an integer add.
+// Mirrored packed float16 cells: the order is reversed (every "maximum" is a packed minimum), and the diagonal and gap terms
+// are integer adds on the bit pattern of both halves at once.
 template <> struct Cell<kSemF16M> : Cell<kSemF16> {
-  // clamp(N_nw - s): 1 - (H_nw + s) / 2048, exact while H_nw + s <= 1024; the upper clamp 1.0 is the zero floor (H_nw + s < 0)
+  // N_nw - s on the bit pattern: sc = (-s_B) * 2^16 + (-s_A) mod 2^32, so that a borrow of the low half is absorbed by the high
+  // one; each half stays in [0, 0xFFFF] (L14 (f)).  Unclamped: for H_nw + s < 0 the pattern lies above 1.0 and cell_h's
+  // clamp returns the zero floor.  Inline asm, so that the compiler cannot fuse it into a half-rate three-operand add
   static __device__ __forceinline__ T add(T d, T sc, uint32_t) {
-    T r; asm("v_pk_add_f16 %0, %1, %2 clamp" : "=v"(r) : "v"(d), "v"(sc)); return r;
+    T r; asm("v_add_u32 %0, %1, %2" : "=v"(r) : "v"(sc), "v"(d)); return r;
+  }
+  // min(x, K_w, K_n, 1.0): the clamp's upper end is the zero floor of the diagonal term (K, N > 0, so the lower end never acts)
+  static __device__ __forceinline__ T vmax3_floor(T a, T b, T c) {
+    T r; asm("v_pk_minimum3_f16 %0, %1, %2, %3 clamp" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
   }
   static __device__ __forceinline__ T vmax(T a, T b) {
     T r; asm("v_pk_min_f16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
@@ -199,7 +210,7 @@ template <> struct Cell<kSemF16M> : Cell<kSemF16> {
     T r; asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
   }
   // H - g on the bit pattern: gap2 = g in both halves (no carry crosses them: a half is at most 0x3C00 + g).  Below H = g the
-  // pattern leaves [0.5, 1] upwards — a value above 1.0, which never wins the minimum against the clamped diagonal term.
+  // pattern leaves [0.5, 1] upwards — a value above 1.0, which never decides the cell: the zero floor 1.0 lies below it.
   // Inline asm, so that the compiler cannot fuse it into a half-rate v_add3_u32 / v_lshl_add_u32.  gap2 is a VGPR: a VOP2
   // add with an SGPR operand issues at the VOP3P rate (profiles/r05_mirror_cell_rate.txt)
   static __device__ __forceinline__ T sub_gap(T t, uint32_t gap2) {
@@ -208,6 +219,13 @@ template <> struct Cell<kSemF16M> : Cell<kSemF16> {
   // back to H / 2048 = 1 - N (exact: Sterbenz) for publishing
   static __device__ __forceinline__ T unmirror(T n) {
     T r; asm("v_pk_add_f16 %0, %1, %2 neg_lo:[1,0] neg_hi:[1,0]" : "=v"(r) : "v"(n), "s"(kF16MZero)); return r;
+  }
+};
+// The same cells with the diagonal term as one clamped float16 add of -s / 2048 (the profile holds float16 -s / 2048)
+template <> struct Cell<kSemF16MF> : Cell<kSemF16M> {
+  // clamp(N_nw - s): 1 - (H_nw + s) / 2048, exact while H_nw + s <= 1024; the upper clamp 1.0 is the zero floor (H_nw + s < 0)
+  static __device__ __forceinline__ T add(T d, T sc, uint32_t) {
+    T r; asm("v_pk_add_f16 %0, %1, %2 clamp" : "=v"(r) : "v"(d), "v"(sc)); return r;
   }
 };
 // float32 cells hold H * 2^-k with 2^k above every value of the call (a pure exponent shift: every add, subtract
@@ -224,12 +242,19 @@ template <> struct Cell<kSemF32> : CellF<kSemF32> {
 template <> struct Cell<kSemF32U8> : CellF<kSemF32U8> {};
 
 // bit pattern of H = 0 in a cell register
-template <int SEM> __host__ __device__ constexpr uint32_t zero_bits() { return SEM == kSemU8H ? kU8HZero : (SEM == kSemF16M ? kF16MZero : 0u); }
+template <int SEM> __host__ __device__ constexpr uint32_t zero_bits() { return SEM == kSemU8H ? kU8HZero : (sem_is_mirror(SEM) ? kF16MZero : 0u); }
 
 // three-input maximum where the cell type has one (packed float16), else two steps
 template <int SEM> __device__ __forceinline__ typename Cell<SEM>::T cell_max3(typename Cell<SEM>::T a, typename Cell<SEM>::T b, typename Cell<SEM>::T c) {
-  if constexpr (SEM == kSemF16 || SEM == kSemF16M || SEM == kSemU8H) return Cell<SEM>::vmax3(a, b, c);
+  if constexpr (SEM == kSemF16 || sem_is_mirror(SEM) || SEM == kSemU8H) return Cell<SEM>::vmax3(a, b, c);
   else return Cell<SEM>::vmax(Cell<SEM>::vmax(a, b), c);
+}
+
+// the cell's own maximum3 H = max(x, W - g, N - g) of the instances that keep H - g; with the integer diagonal term it also
+// applies the zero floor
+template <int SEM> __device__ __forceinline__ typename Cell<SEM>::T cell_h(typename Cell<SEM>::T x, typename Cell<SEM>::T w, typename Cell<SEM>::T n) {
+  if constexpr (SEM == kSemF16M) return Cell<SEM>::vmax3_floor(x, w, n);
+  else return Cell<SEM>::vmax3(x, w, n);
 }
 
 // value of the lane above inside the 16-lane DPP row, 0 for the first lane (row H(0,.) = 0)
@@ -256,13 +281,13 @@ __device__ __forceinline__ uint32_t row_shr1(uint32_t v) {
 // 3 + 1/(2 MK) instead of 3.5 ops.
 template <int R, int SEM, bool STRIPS = false, int SL = 16, bool TWIN = false, bool COMB = false, int MK = 1>
 __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
-  static_assert(MK == 1 || (MK == 4 && !TWIN && (((SEM == kSemF16 || SEM == kSemF16M) && !STRIPS) || SEM == kSemF32)),
+  static_assert(MK == 1 || (MK == 4 && !TWIN && (((SEM == kSemF16 || sem_is_mirror(SEM)) && !STRIPS) || SEM == kSemF32)),
                 "sampled maximum: packed float16 two-query tiles, or float32 cells (one query per tile)");
   static_assert(SL == 64 || SL == 16 || SL == 8, "a slot is a whole wavefront, a DPP row or half a DPP row");
   static_assert(!(STRIPS && SL == 8), "the strip-mined instances use whole DPP rows or whole wavefronts");
   static_assert(!TWIN || ((SL == 64 || SL == 16) && !sem_is_float(SEM) && R % 2 == 0), "twin tiles: packed cells on whole-wavefront or 16-lane tiles");
   static_assert(!COMB || (TWIN && !STRIPS), "the code-pair profile belongs to the twin instances");
-  static_assert(SEM != kSemF16M || (!TWIN && !STRIPS), "mirrored float16 cells: two-query tiles, one strip");
+  static_assert(!sem_is_mirror(SEM) || (!TWIN && !STRIPS), "mirrored float16 cells: two-query tiles, one strip");
   constexpr bool HALF = TWIN && !COMB;                             // the profile holds 16-bit entries, two rows per dword
   constexpr int LS = HALF ? lane_stride(R / 2) : lane_stride(R);   // dwords between the profile rows of adjacent lanes
   constexpr int NQ4 = HALF ? (R / 2 + 3) / 4 : (R + 3) / 4;
@@ -330,12 +355,21 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
       } else {
         // 16-bit table entries: int16 scores, or float16 bit patterns for the packed float16 instance
         const int16_t *st = static_cast<const int16_t *>(a.stab);
-        constexpr int kPadEntry = (SEM == kSemF16 || SEM == kSemF16M) ? (int)(int16_t)0xC800 /* float16 -8 = -16384 / 2048 */
+        constexpr int kPadEntry = (SEM == kSemF16 || sem_is_mirror(SEM)) ? (int)(int16_t)0xC800 /* float16 -8 = -16384 / 2048 */
                                   : (SEM == kSemU8H ? (int)(int16_t)0xD400 /* float16 -64 = -16384 / 256 */ : kPadScore);
         const int sa = (i < mA) ? st[(int)xA[i] * a.ncodes + c] : kPadEntry;
         const int sb = (i < mB) ? st[(int)xB[i] * a.ncodes + c] : kPadEntry;
         e32 = (uint32_t)(uint16_t)sa | ((uint32_t)(uint16_t)sb << 16);
-        if (SEM == kSemF16M) e32 ^= 0x80008000u;                  // mirrored cells add -s (padding: +8, clamped to the floor)
+        if (SEM == kSemF16MF) e32 ^= 0x80008000u;                 // mirrored cells add -s (padding: +8, clamped to the floor)
+        if (SEM == kSemF16M) {
+          // -s on the bit pattern (s = entry * 2048, exact), capped at 1024: from any cell (pattern >= 0x3800) that reaches
+          // the floor 0x3C00, as padding and every score <= -1024 do in the float add; the low half's borrow goes to the high half
+          auto neg_s = [](int h) {
+            const int s = (int)((float)__builtin_bit_cast(_Float16, (uint16_t)h) * kF16Scale);
+            return -s < 1024 ? -s : 1024;
+          };
+          e32 = (uint32_t)neg_s(sa) + ((uint32_t)neg_s(sb) << 16);
+        }
       }
       prof[(c * PL + ll) * LS + r] = e32;
     }
@@ -439,7 +473,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   uint32_t first_lane_zero = ls == 0 ? 0u : 0xFFFFFFFFu;           // SL = 8: zero border row for lane 0 of the slot
   asm volatile("" : "+v"(first_lane_zero));                        // keep it a plain v_and_b32 (2 cycles), not a v_cndmask (4)
   uint32_t first_lane_z = ls == 0 ? kF16MZero : 0u;                // kSemF16M: the border row's H = 0 on the tile's first lane
-  if constexpr (SEM == kSemF16M) asm volatile("" : "+v"(first_lane_z));
+  if constexpr (sem_is_mirror(SEM)) asm volatile("" : "+v"(first_lane_z));
   // STRIPS: this tile's ping-pong boundary rows (global), and its LDS windows
   const size_t tile_id = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NSLOT + slot;
   uint32_t *brow0 = STRIPS ? a.brow + tile_id * 2 * (size_t)a.brow_stride : nullptr;
@@ -450,7 +484,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   // columns of a sub-chunk are reported with the next one; the host widens its search accordingly.
   const int64_t subs_per_tile = a.chunk_len / a.sub_len;
   // this tile's best published value per query (H = 0: nothing to report; mirrored cells publish H / 2048)
-  uint32_t best_a = (SEM == kSemF16M ? 0u : zero_bits<SEM>()) & 0xFFFFu, best_b = best_a;
+  uint32_t best_a = (sem_is_mirror(SEM) ? 0u : zero_bits<SEM>()) & 0xFFFFu, best_b = best_a;
   auto slot_max = [&]() -> uint32_t {                              // maximum of mx over the slot's lanes
     uint32_t m32 = C::bits(mx);
 #pragma unroll
@@ -506,7 +540,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
     }
   };
   auto publish = [&](int64_t sub) {
-    if constexpr (SEM == kSemF16M) publish_value(sub, C::unmirror(slot_max()));
+    if constexpr (sem_is_mirror(SEM)) publish_value(sub, C::unmirror(slot_max()));
     else publish_value(sub, slot_max());
     mx = C::from_bits(zero_bits<SEM>());
   };
@@ -522,7 +556,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   }
   // the gap operand of sub_gap: the mirrored cell's integer add wants it in a VGPR (one copy, made once)
   uint32_t gap_op = a.gap2;
-  if constexpr (SEM == kSemF16M) asm volatile("" : "+v"(gap_op));
+  if constexpr (sem_is_mirror(SEM)) asm volatile("" : "+v"(gap_op));
   const int segs_per_sub = (int)(a.sub_len / kSeg);
   const int warm_segs = (int)(a.warm / kSeg);
   int64_t sub = 0;
@@ -570,7 +604,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
 #pragma unroll
     for (int r = 0; r < R; ++r) H[r] = C::from_bits(zero_bits<SEM>());
     uint32_t up_prev = zero_bits<SEM>();
-    constexpr bool kKeepsHg = SEM == kSemF16 || SEM == kSemF16M || SEM == kSemF32;   // instances that keep H - g of every cell
+    constexpr bool kKeepsHg = SEM == kSemF16 || sem_is_mirror(SEM) || SEM == kSemF32;   // instances that keep H - g of every cell
     T Hg[kKeepsHg ? R : 1];
 #pragma unroll
     for (int r = 0; r < (kKeepsHg ? R : 1); ++r) Hg[r] = C::sub_gap(C::from_bits(zero_bits<SEM>()), gap_op);   // 0 - g
@@ -607,7 +641,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
           up = shift_in(C::bits(H[R - 1]), bin_w[k]);
         } else {
           // zero border row H(0, .): bound_ctrl supplies it (no `old` operand to set up)
-          if constexpr (SEM == kSemF16M && SL != 64) {
+          if constexpr (sem_is_mirror(SEM) && SL != 64) {
             // bound_ctrl's zero, then one v_max_u32 with H = 0 on the tile's first lane: a cell N <= 1.0 in both halves is, as a
             // 32-bit word, at most kF16MZero, so the maximum is kF16MZero there and the value of the lane above elsewhere
             up = __builtin_elementwise_max(row_shr1(C::bits(H[R - 1])), first_lane_z);
@@ -627,7 +661,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
         up_prev = up;
         T tpend = C::from_bits(0u);
         (void)tpend;
-        if constexpr (SEM == kSemF16 || SEM == kSemF16M || SEM == kSemF32) {
+        if constexpr (SEM == kSemF16 || sem_is_mirror(SEM) || SEM == kSemF32) {
           // H = max(clamp0(NW + s), W - g, N - g): the cell keeps H (next step's diagonal) and H - g (this row's west
           // term next step, the row below's north term now) — add, maximum3, add per cell; the running maximum takes
           // two cells per maximum3
@@ -636,7 +670,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
           for (int r = 0; r < R; ++r) {
             const T w = H[r];
             const T x = C::add(diag, C::from_bits(p[r]), a.clamp2);
-            const T h = C::vmax3(x, Hg[r], ng);
+            const T h = cell_h<SEM>(x, Hg[r], ng);
             if (MK == 1 || (k & (MK - 1)) == MK - 1) {             // (compile-time per unrolled step)
               if (r & 1) mx = C::vmax3(mx, tpend, h);
               else if (r + 1 < R) tpend = h;
