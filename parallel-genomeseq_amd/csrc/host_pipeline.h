@@ -268,24 +268,16 @@ int locate_fast(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, cons
   // the uint8 order needs the storage-order key of every cell that equals the maximum: keyed tracking
   const bool wave_locate = wave_scoring_ok(p) && !opt().no_wave;
   const bool wave_keyed = p.semantics == MI355_SW_U8SAT;
-  auto key_score = [&](size_t k) {
-    float score;
-    if (qfloat[k] == 2) score = half_value((uint16_t)(keys[k] >> 32)) * kF16Scale;
-    else if (qfloat[k] == 3) score = (uint16_t)(keys[k] >> 32) ? half_value((uint16_t)(keys[k] >> 32)) * 256.0f - 1.0f : 0.0f;
-    else if (qfloat[k] == 4) { const uint32_t bits = (uint32_t)(keys[k] >> 32); memcpy(&score, &bits, 4); score = std::ldexp(score, ctx->fshift); }
-    else if (qfloat[k]) { const uint32_t bits = (uint32_t)(keys[k] >> 32); memcpy(&score, &bits, 4); }
-    else score = (float)(int)(keys[k] >> 32);
-    return score;
-  };
+  auto qscore = [&](size_t k) { return key_score(qfloat[k], (uint32_t)(keys[k] >> 32), ctx->fshift); };
   // long queries are few and each re-run occupies one workgroup: cut their sub-chunk into pieces (each with its
   // own margin) so that the idle CUs share the work
   size_t nlong = 0;                       // workgroups the long queries' sub-chunks need before cutting
   for (size_t k = 0; k < nq; ++k)
-    if (qfast[k] && q.len[k] > 512 && key_score(k) > 0) nlong += p.semantics == MI355_SW_U8SAT ? 5 : 1;
+    if (qfast[k] && q.len[k] > 512 && qscore(k) > 0) nlong += p.semantics == MI355_SW_U8SAT ? 5 : 1;
   for (size_t k = 0; k < nq; ++k) {
     if (!qfast[k]) continue;
     const unsigned long long key = keys[k];
-    const float score = key_score(k);
+    const float score = qscore(k);
     if (!(score > 0)) continue;
     const int64_t chunk_len = qchunk[k];           // sub-chunk granularity of this query's bucket
     const int64_t nchunks = (n + chunk_len - 1) / chunk_len;
@@ -646,7 +638,7 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
         for (int k = 0; k < b.count; ++k) {
           const int id = q.order[b.first + k];
           qfast[id] = 1; qchunk[id] = b.sub_len; qwarm[id] = b.warm; qsat[id] = b.sampled ? 2 : (b.satflag ? 1 : 0);
-          qfloat[id] = b.sem == kSemF16 ? 2 : (b.sem == kSemU8H ? 3 : (b.sem == kSemF32 ? 4 : (sem_is_float(b.sem) ? 1 : 0)));
+          qfloat[id] = key_kind(b);
         }
       }
       rc = score_fetch(ctx, nq, keys);
@@ -657,8 +649,7 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
       if (rc) return rc;
       if (!any_sat) {
         if (ctx->long_cert >= 0.0f && nq == 1) {                       // exact keys: the lone query's maximum as swept
-          float v; const uint32_t hi32 = (uint32_t)(keys[0] >> 32); memcpy(&v, &hi32, 4);
-          if (!margin_certified(std::ldexp(v, ctx->fshift))) continue;
+          if (!margin_certified(key_score(kKeyF32Scaled, (uint32_t)(keys[0] >> 32), ctx->fshift))) continue;
         }
         break;
       }
@@ -713,7 +704,7 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
         std::vector<int> tried;
         std::vector<float> qlow(nq, 0.0f);
         for (int id : offenders) {
-          if (qsat[id] != 2 || qfloat[id] != 2 || qchunk[id] <= (int64_t)q.len[id] + 64) continue;
+          if (qsat[id] != 2 || qfloat[id] != kKeyF16 || qchunk[id] <= (int64_t)q.len[id] + 64) continue;
           if (half_value((uint16_t)(keys[id] >> 32)) * kF16Scale != 255.0f) continue;
           const uint32_t *f = &first[(size_t)id * (K + 1)];
           const uint32_t cnt = f[0] & 0x7FFFFFFFu;
@@ -786,7 +777,7 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
           for (int k = 0; k < b.count; ++k) {
             const int id = qo.order[b.first + k];
             qchunk[id] = b.sub_len; qwarm[id] = b.warm; qsat[id] = 0;
-            qfloat[id] = b.sem == kSemF16 ? 2 : (b.sem == kSemU8H ? 3 : (b.sem == kSemF32 ? 4 : (sem_is_float(b.sem) ? 1 : 0)));
+            qfloat[id] = key_kind(b);
           }
         }
         std::vector<unsigned long long> keys2;
@@ -801,9 +792,7 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
       std::vector<float> qlower(nq, 0.0f);                          // the sweep's key: a lower bound of the query's maximum
       for (size_t k = 0; k < nq; ++k) {
         if (!qsat[k]) continue;
-        const uint32_t hi32 = (uint32_t)(keys[k] >> 32);
-        if (qfloat[k] == 2) qlower[k] = half_value((uint16_t)hi32) * kF16Scale;
-        else if (qfloat[k] == 4) { float v; memcpy(&v, &hi32, 4); qlower[k] = std::ldexp(v, ctx->fshift); }
+        qlower[k] = key_score(qfloat[k], (uint32_t)(keys[k] >> 32), ctx->fshift);   // (sampled and saturating sweeps: kKeyF16 or kKeyF32Scaled)
       }
       rc = locate_flagged(ctx, ref, q, rg, p, qchunk, qwarm, qlower, table, flagged, loc, qdone);
       if (rc) return rc;
@@ -1060,7 +1049,7 @@ int range_maxima(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
       if (rc) return rc;
       for (int k = 0; k < b.count; ++k) {
         const int id = q.order[b.first + k];
-        qfast[id] = 1; qfloat[id] = b.sem == kSemF16 ? 2 : (b.sem == kSemU8H ? 3 : (b.sem == kSemF32 ? 4 : (sem_is_float(b.sem) ? 1 : 0)));
+        qfast[id] = 1; qfloat[id] = key_kind(b);
         if (keep) { sc.qchunk[id] = b.sub_len; sc.qwarm[id] = b.warm; }
       }
     }
@@ -1074,15 +1063,7 @@ int range_maxima(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     if (keep) { std::copy(keys.begin(), keys.end(), sc.keys.begin()); sc.qfast = qfast; sc.qfloat = qfloat; sc.fshift = ctx->fshift; }
     for (size_t r = 0; r < sub.size(); ++r)
       for (size_t k = 0; k < nq; ++k)
-        if (qfast[k]) {
-          const uint32_t hi32 = (uint32_t)(keys[r * nq + k] >> 32);
-          float v;
-          if (qfloat[k] == 2) v = half_value((uint16_t)hi32) * kF16Scale;
-          else if (qfloat[k] == 3) v = (uint16_t)hi32 ? half_value((uint16_t)hi32) * 256.0f - 1.0f : 0.0f;
-          else if (qfloat[k] == 4) { memcpy(&v, &hi32, 4); v = std::ldexp(v, ctx->fshift); }
-          else if (qfloat[k]) memcpy(&v, &hi32, 4); else v = (float)hi32;
-          maxima[(lo + r) * nq + k] = v;
-        }
+        if (qfast[k]) maxima[(lo + r) * nq + k] = key_score(qfloat[k], (uint32_t)(keys[r * nq + k] >> 32), ctx->fshift);
     if (sampled) {
       // (nq == 1, one launch group.)  The keys above are lower bounds within 3 gaps: re-evaluate the contenders exactly.
       unsigned int nflag = 0;

@@ -46,33 +46,117 @@ struct Bucket {
   int64_t sub_len = 0;        // granularity at which tile maxima are reported (= what locate re-runs)
 };
 
+// ---- the compiled sw_score_kernel instances --------------------------------------------
+// Rows per lane of each tile shape.  The choosers below read these lists, and the table of instances is generated from them.
+constexpr int kR16[] = {2, 4, 6, 8, 10, 12, 16, 20, 24, 32};   // 16-lane tiles, one strip (<= 512 rows)
+constexpr int kR8[] = {7, 10, 13, 16, 19, 26, 32};             // 8-lane tiles: the common short-read lengths (<= 56, 80, 104, 128, 152, 208, 256 rows)
+constexpr int kR64[] = {10, 12, 16, 20, 24, 32};               // whole-wavefront tiles, one strip (<= 2048 rows)
+constexpr int kR16S[] = {32};                                  // 16-lane tiles in 512-row strips
+constexpr int kR64S[] = {20, 24, 32};                          // whole-wavefront tiles in strips
+constexpr int kR8M[] = {13, 16, 19, 26, 32};                   // sampled maximum (MK = 4) on 8-lane tiles
+constexpr int kR16M[] = {10, 12, 16, 20, 24, 32};              // ... on 16-lane and whole-wavefront tiles
+template <size_t N> constexpr bool listed(const int (&rs)[N], long r) { for (int v : rs) if (v == r) return true; return false; }
+
+// sw_score_kernel<R, sem, strips, SL, twin, comb, mk>
+struct ScoreInst {
+  int R, sem; bool strips; int SL; bool twin, comb; int mk;
+  constexpr bool operator==(const ScoreInst &o) const {
+    return R == o.R && sem == o.sem && strips == o.strips && SL == o.SL && twin == o.twin && comb == o.comb && mk == o.mk;
+  }
+};
+// One row per shape: the rows-per-lane list, the shape, and the cells (bit SEM) compiled on it
+struct ScoreShapes { const int *rs; size_t n; bool strips; int SL; bool twin, comb; int mk; unsigned sems; };
+constexpr unsigned kCellsPlain = 0x3Fu;                              // kSemI16 .. kSemU8H
+constexpr unsigned kCellsMirror = 1u << kSemF16M | 1u << kSemF16MF;
+constexpr unsigned kCellsTwin = 1u << kSemI16 | 1u << kSemU8 | 1u << kSemF16 | 1u << kSemU8H;
+constexpr unsigned kCellsF16 = 1u << kSemF16;
+constexpr unsigned kCellsSampled = 1u << kSemF32 | 1u << kSemF16;
+constexpr ScoreShapes kScoreShapes[] = {
+  {kR16, std::size(kR16), false, 16, false, false, 1, kCellsPlain | kCellsMirror},
+  {kR8, std::size(kR8), false, 8, false, false, 1, kCellsPlain | kCellsMirror},
+  {kR64, std::size(kR64), false, 64, false, false, 1, kCellsPlain},
+  {kR16S, std::size(kR16S), true, 16, false, false, 1, kCellsPlain},
+  {kR64S, std::size(kR64S), true, 64, false, false, 1, kCellsPlain},
+  {kR64, std::size(kR64), false, 64, true, false, 1, kCellsTwin},              // a lone query: two of its tiles per register
+  {kR64S, std::size(kR64S), true, 64, true, false, 1, kCellsTwin},
+  {kR16, std::size(kR16), false, 16, true, false, 1, kCellsF16},               // ... a short one on 16-lane tiles
+  {kR16, std::size(kR16), false, 16, true, true, 1, kCellsF16},                // ... with the code-pair profile
+  {kR16M, std::size(kR16M), false, 16, false, false, 4, kCellsSampled | kCellsMirror},
+  {kR8M, std::size(kR8M), false, 8, false, false, 4, kCellsSampled | kCellsMirror},
+  {kR16M, std::size(kR16M), false, 64, false, false, 4, kCellsSampled},
+  {kR64S, std::size(kR64S), true, 64, false, false, 4, 1u << kSemF32},         // a lone long query on float32 cells
+};
+constexpr size_t score_inst_count() {
+  size_t n = 0;
+  for (const ScoreShapes &g : kScoreShapes)
+    for (int sem = 0; sem < 8; ++sem) if (g.sems >> sem & 1u) n += g.n;
+  return n;
+}
+constexpr std::array<ScoreInst, score_inst_count()> score_insts() {
+  std::array<ScoreInst, score_inst_count()> out{};
+  size_t k = 0;
+  for (const ScoreShapes &g : kScoreShapes)
+    for (int sem = 0; sem < 8; ++sem)
+      if (g.sems >> sem & 1u)
+        for (size_t j = 0; j < g.n; ++j) out[k++] = ScoreInst{g.rs[j], sem, g.strips, g.SL, g.twin, g.comb, g.mk};
+  return out;
+}
+constexpr auto kScoreInsts = score_insts();
+constexpr bool score_compiled(const ScoreInst &want) {
+  for (const ScoreInst &i : kScoreInsts) if (i == want) return true;
+  return false;
+}
+// every shape a chooser below can name is compiled for the cells make_buckets may give it (mirror_ok: 8- and 16-lane tiles, one
+// strip; sampled_instance; the lone float32 query's sampled strips; twin_shape: 16-lane twins of the float16 cell)
+template <size_t N> constexpr bool score_compiled(const int (&rs)[N], bool strips, int SL, bool twin, bool comb, int mk, unsigned sems) {
+  for (int r : rs)
+    for (int sem = 0; sem < 8; ++sem)
+      if ((sems >> sem & 1u) && !score_compiled(ScoreInst{r, sem, strips, SL, twin, comb, mk})) return false;
+  return true;
+}
+static_assert(score_compiled(kR16, false, 16, false, false, 1, kCellsPlain | kCellsMirror) &&
+              score_compiled(kR8, false, 8, false, false, 1, kCellsPlain | kCellsMirror) &&
+              score_compiled(kR64, false, 64, false, false, 1, kCellsPlain) && score_compiled(kR16S, true, 16, false, false, 1, kCellsPlain) &&
+              score_compiled(kR64S, true, 64, false, false, 1, kCellsPlain), "pick_R, pick_R8, pick_shape64");
+static_assert(score_compiled(kR64, false, 64, true, false, 1, kCellsTwin) && score_compiled(kR64S, true, 64, true, false, 1, kCellsTwin) &&
+              score_compiled(kR16, false, 16, true, false, 1, kCellsF16) && score_compiled(kR16, false, 16, true, true, 1, kCellsF16), "twin tiles");
+static_assert(score_compiled(kR8M, false, 8, false, false, 4, kCellsSampled | kCellsMirror) &&
+              score_compiled(kR16M, false, 16, false, false, 4, kCellsSampled | kCellsMirror) &&
+              score_compiled(kR16M, false, 64, false, false, 4, kCellsSampled) && score_compiled(kR64S, true, 64, false, false, 4, 1u << kSemF32),
+              "sampled_instance");
+
+typedef void (*ScoreKernel)(const ScoreArgs);
+template <size_t... I> constexpr std::array<ScoreKernel, sizeof...(I)> score_kernels(std::index_sequence<I...>) {
+  static_assert((score_instance_ok<kScoreInsts[I].sem>(kScoreInsts[I].R, kScoreInsts[I].strips, kScoreInsts[I].SL, kScoreInsts[I].twin,
+                                                      kScoreInsts[I].comb, kScoreInsts[I].mk) && ...), "an illegal instance in the table");
+  return {&sw_score_kernel<kScoreInsts[I].R, kScoreInsts[I].sem, kScoreInsts[I].strips, kScoreInsts[I].SL, kScoreInsts[I].twin,
+                           kScoreInsts[I].comb, kScoreInsts[I].mk>...};
+}
+constexpr std::array<ScoreKernel, kScoreInsts.size()> kScoreKernels = score_kernels(std::make_index_sequence<kScoreInsts.size()>{});
+
 int pick_R(int maxlen) {
-  static const int rs[] = {2, 4, 6, 8, 10, 12, 16, 20, 24, 32};
   const int need = (maxlen + 15) / 16;
-  for (int r : rs) if (r >= need) return r;
+  for (int r : kR16) if (r >= need) return r;
   return 0;
 }
 
-// 8-lane tiles: instances for the common short-read lengths (<= 56, 80, 104, 128, 152, 208, 256 rows)
+// 8-lane tiles: instances for the common short-read lengths
 int pick_R8(int maxlen) {
-  static const int rs[] = {7, 10, 13, 16, 19, 26, 32};
   const int need = (maxlen + 7) / 8;
-  for (int r : rs) if (r >= need) return r;
+  for (int r : kR8) if (r >= need) return r;
   return 0;
 }
 
 // Whole-wavefront tiles (queries beyond 512 rows): rows per lane of one strip up to 2048 rows, or of the strips of
 // a longer query — the choice with the fewest padded rows (more rows per lane on ties: fewer strips).
 void pick_shape64(int len, int &R, bool &strips) {
-  static const int one[] = {10, 12, 16, 20, 24, 32};
   strips = len > 2048;
   if (!strips) {
-    for (int r : one) if (64 * r >= len) { R = r; return; }
+    for (int r : kR64) if (64 * r >= len) { R = r; return; }
   }
-  static const int many[] = {20, 24, 32};
-  { const long v = opt().strip_r; if (v == 20 || v == 24 || v == 32) { R = (int)v; return; } }   // tuning aid
+  { const long v = opt().strip_r; if (listed(kR64S, v)) { R = (int)v; return; } }   // tuning aid
   int64_t best = -1;
-  for (int r : many) {
+  for (int r : kR64S) {
     const int64_t rows = (int64_t)((len + 64 * r - 1) / (64 * r)) * 64 * r;
     if (best < 0 || rows <= best) { best = rows; R = r; }
   }
@@ -186,8 +270,8 @@ void twin_shape(const RefData &ref, Bucket &b) { b.SL = 16; b.R = pick_R(b.maxle
 
 // Length classes of the batch: one bucket per kernel instance (R), plus one strip-mined bucket.
 bool sampled_instance(int SL, int R) {
-  if (SL == 8) return R == 13 || R == 16 || R == 19 || R == 26 || R == 32;
-  if (SL == 16 || SL == 64) return R == 10 || R == 12 || R == 16 || R == 20 || R == 24 || R == 32;
+  if (SL == 8) return listed(kR8M, R);
+  if (SL == 16 || SL == 64) return listed(kR16M, R);
   return false;
 }
 
@@ -208,7 +292,7 @@ std::vector<Bucket> make_buckets(const RefData &ref, const QueryBatch &q, const 
   for (size_t pos = 0; pos < q.nq; ++pos) {
     const int len = q.len[q.order[pos]];
     bool strips = false;
-    int SL = 16, R = 32;
+    int SL = 16, R = kR16S[0];
     if (len <= kMaxRowsFast) pick_shape(len, SL, R);
     else if (wide_ok) { SL = 64; pick_shape64(len, R, strips); }
     else strips = true;
@@ -316,7 +400,7 @@ std::vector<Bucket> make_buckets(const RefData &ref, const QueryBatch &q, const 
       }
       // a lone long query on float32 cells (config 5): the same sampled maximum; integer scores only (exact arithmetic)
       if (b.sem == kSemF32 && b.count == 1 && b.SL == 64 && !b.twin && t.integral && allow_sample &&
-          (b.strips ? (b.R == 20 || b.R == 24 || b.R == 32) : sampled_instance(64, b.R)) && !opt().no_sample)
+          (b.strips ? listed(kR64S, b.R) : sampled_instance(64, b.R)) && !opt().no_sample)
         b.sampled = true;
       // ... and batches on float32 cells (fractional scoring; scores beyond 16 bits): the decay bound then holds up to the
       // rounding of three subtractions, which the filter's slack allows for (score_launch)
@@ -373,177 +457,51 @@ double valu_ops_per_cell(const Bucket &b) {
   return per_step / (double)(cells_per_row * R);
 }
 
-template <class K>
-void launch_score(K kernel, dim3 grid, size_t shmem, hipStream_t st, const ScoreArgs &a) {
-  // large alphabets x many rows per lane need more than the default 64 KiB of dynamic LDS
-  if (shmem > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-  hipLaunchKernelGGL(kernel, grid, dim3(256), shmem, st, a);
-}
-
-template <int SEM>
-int launch_score_twin(int R, bool strips, dim3 grid, size_t shmem, hipStream_t st, const ScoreArgs &a) {
-  if (strips) {
-    switch (R) {
-#define CASE_TS(r) case r: launch_score(sw_score_kernel<r, SEM, true, 64, true>, grid, shmem, st, a); return 0;
-      CASE_TS(20) CASE_TS(24) CASE_TS(32)
-#undef CASE_TS
-    }
-    return -1;
-  }
-  switch (R) {
-#define CASE_T(r) case r: launch_score(sw_score_kernel<r, SEM, false, 64, true>, grid, shmem, st, a); return 0;
-    CASE_T(10) CASE_T(12) CASE_T(16) CASE_T(20) CASE_T(24) CASE_T(32)
-#undef CASE_T
+// Launches the compiled instance `want`; -1: there is none
+int launch_score(const ScoreInst &want, dim3 grid, size_t shmem, hipStream_t st, const ScoreArgs &a) {
+  for (size_t k = 0; k < kScoreInsts.size(); ++k) {
+    if (!(kScoreInsts[k] == want)) continue;
+    // large alphabets x many rows per lane need more than the default 64 KiB of dynamic LDS
+    if (shmem > 48 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kScoreKernels[k]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    hipLaunchKernelGGL(kScoreKernels[k], grid, dim3(256), shmem, st, a);
+    return 0;
   }
   return -1;
 }
 
-// a lone short query on 16-lane tiles, two TILES of it per packed float16 register
-int launch_score_twin16(int R, bool comb, dim3 grid, size_t shmem, hipStream_t st, const ScoreArgs &a) {
-  if (comb) {
-    switch (R) {
-#define CASE_C16(r) case r: launch_score(sw_score_kernel<r, kSemF16, false, 16, true, true>, grid, shmem, st, a); return 0;
-      CASE_C16(2) CASE_C16(4) CASE_C16(6) CASE_C16(8) CASE_C16(10) CASE_C16(12) CASE_C16(16) CASE_C16(20) CASE_C16(24) CASE_C16(32)
-#undef CASE_C16
-    }
-    return -1;
-  }
-  switch (R) {
-#define CASE_T16(r) case r: launch_score(sw_score_kernel<r, kSemF16, false, 16, true>, grid, shmem, st, a); return 0;
-    CASE_T16(2) CASE_T16(4) CASE_T16(6) CASE_T16(8) CASE_T16(10) CASE_T16(12) CASE_T16(16) CASE_T16(20) CASE_T16(24) CASE_T16(32)
-#undef CASE_T16
-  }
-  return -1;
+// The kernel's cell type of bucket b: a kSemF16 bucket on mirrored cells takes kSemF16M, or kSemF16MF (option no_f16m_int_diag)
+int kernel_sem(const Bucket &b) {
+  if (b.sem == kSemF16 && b.mirror) return opt().no_f16m_int_diag ? kSemF16MF : kSemF16M;
+  return b.sem;
 }
 
-// packed float16 cells: reads whose scores stay within +-2048, 8- and 16-lane tiles
-template <int SEM>
-int launch_score_f16(int R, int SL, bool strips, dim3 grid, size_t shmem, hipStream_t st, const ScoreArgs &a) {
-  if (strips) {
-    if (SL == 16) { if (R != 32) return -1; launch_score(sw_score_kernel<32, SEM, true, 16>, grid, shmem, st, a); return 0; }
-    if (SL != 64) return -1;
-    switch (R) {
-#define CASE_HS(r) case r: launch_score(sw_score_kernel<r, SEM, true, 64>, grid, shmem, st, a); return 0;
-      CASE_HS(20) CASE_HS(24) CASE_HS(32)
-#undef CASE_HS
-    }
-    return -1;
+// What a score launch passes that depends on the kernel's cell type
+struct CellLaunch {
+  const void *tab;               // the score table the profile reads
+  uint32_t gap2;                 // ScoreArgs::gap2
+  uint32_t pubmax;               // uint8 engine swept without saturation: 255 as a cell value, the cap of what is published
+  uint32_t border;               // strip boundary rows start as H = 0
+  int queries;                   // per register
+  int value_bytes;               // one sub-chunk value of a sampled sweep
+  const char *cell, *tag, *name; // path note (cell=..., tag at its end) and kernel_info.name
+};
+CellLaunch cell_launch(const mi355_sw_ctx *ctx, const ScoreTable &t, int sem) {
+  const uint32_t g2 = (uint32_t)t.gap * 0x00010001u;             // (mirrored cells: added to the bit pattern of both halves)
+  const uint32_t h255 = (uint32_t)half_bits(255.0f / kF16Scale);
+  uint32_t f32gap, f32gs, f32cap;
+  const float gs = std::ldexp(t.gapf, -ctx->fshift), cap = std::ldexp(255.0f, -ctx->fshift);
+  memcpy(&f32gap, &t.gapf, 4); memcpy(&f32gs, &gs, 4); memcpy(&f32cap, &cap, 4);
+  switch (sem) {
+    case kSemI16:   return {ctx->stab.p, g2, 0u, 0u, 2, 2, "i16", "", "i16x2"};
+    case kSemU8:    return {ctx->stab.p, g2, 0u, 0u, 2, 2, "u8i16", "", "u8 as i16x2"};
+    case kSemF32:   return {ctx->ftab_s.p, f32gs, f32cap, 0u, 1, 4, "f32", "", "f32"};
+    case kSemF32U8: return {ctx->ftab.p, f32gap, 0u, 0u, 1, 4, "u8f32", "", "u8 as f32"};
+    case kSemF16:   return {ctx->htab.p, (uint32_t)half_bits(-(float)t.gap / kF16Scale) * 0x00010001u, h255, 0u, 2, 2, "f16", "", "f16x2"};
+    case kSemU8H:   return {ctx->htab8.p, (uint32_t)half_bits(-(float)t.gap / 256.0f) * 0x00010001u, 0u, Cell<kSemU8H>::kZero, 2, 2, "u8f16", "", "u8 as f16x2"};
+    case kSemF16M:  return {ctx->htab.p, g2, h255, 0u, 2, 2, "f16", ",idiag=1,mirror=1", "f16x2 mirrored, integer diagonal"};
+    default:        return {ctx->htab.p, g2, h255, 0u, 2, 2, "f16", ",mirror=1", "f16x2 mirrored"};   // kSemF16MF
   }
-  if (a.submax_out != nullptr) {                // sampled running maximum (MK = 4)
-    if constexpr (SEM == kSemF16) {
-      switch (SL * 100 + R) {
-#define CASE_M(sl, r) case sl * 100 + r: launch_score(sw_score_kernel<r, kSemF16, false, sl, false, false, 4>, grid, shmem, st, a); return 0;
-        CASE_M(8, 13) CASE_M(8, 16) CASE_M(8, 19) CASE_M(8, 26) CASE_M(8, 32)
-        CASE_M(16, 10) CASE_M(16, 12) CASE_M(16, 16) CASE_M(16, 20) CASE_M(16, 24) CASE_M(16, 32)
-        CASE_M(64, 10) CASE_M(64, 12) CASE_M(64, 16) CASE_M(64, 20) CASE_M(64, 24) CASE_M(64, 32)
-#undef CASE_M
-      }
-    }
-    return -1;
-  }
-  if (SL == 8) {
-    switch (R) {
-#define CASE_H8(r) case r: launch_score(sw_score_kernel<r, SEM, false, 8>, grid, shmem, st, a); return 0;
-      CASE_H8(7) CASE_H8(10) CASE_H8(13) CASE_H8(16) CASE_H8(19) CASE_H8(26) CASE_H8(32)
-#undef CASE_H8
-    }
-    return -1;
-  }
-  if (SL == 64) {
-    switch (R) {
-#define CASE_H64(r) case r: launch_score(sw_score_kernel<r, SEM, false, 64>, grid, shmem, st, a); return 0;
-      CASE_H64(10) CASE_H64(12) CASE_H64(16) CASE_H64(20) CASE_H64(24) CASE_H64(32)
-#undef CASE_H64
-    }
-    return -1;
-  }
-  if (SL != 16) return -1;
-  switch (R) {
-#define CASE_H(r) case r: launch_score(sw_score_kernel<r, SEM, false>, grid, shmem, st, a); return 0;
-    CASE_H(2) CASE_H(4) CASE_H(6) CASE_H(8) CASE_H(10) CASE_H(12) CASE_H(16) CASE_H(20) CASE_H(24) CASE_H(32)
-#undef CASE_H
-  }
-  return -1;
-}
-
-// mirrored packed float16 cells: the kSemF16 buckets whose values stay within 1024, 8- and 16-lane tiles in one strip; SEM =
-// kSemF16M (diagonal term as an integer add), or kSemF16MF (as a clamped float16 add: option no_f16m_int_diag)
-template <int SEM>
-int launch_score_f16m(int R, int SL, bool strips, dim3 grid, size_t shmem, hipStream_t st, const ScoreArgs &a) {
-  if (strips) return -1;
-  const bool mk = a.submax_out != nullptr;     // sampled running maximum (MK = 4)
-  switch ((mk ? 10000 : 0) + SL * 100 + R) {
-#define CASE_FM(sl, r) case sl * 100 + r: launch_score(sw_score_kernel<r, SEM, false, sl>, grid, shmem, st, a); return 0;
-#define CASE_FMM(sl, r) case 10000 + sl * 100 + r: launch_score(sw_score_kernel<r, SEM, false, sl, false, false, 4>, grid, shmem, st, a); return 0;
-    CASE_FM(8, 7) CASE_FM(8, 10) CASE_FM(8, 13) CASE_FM(8, 16) CASE_FM(8, 19) CASE_FM(8, 26) CASE_FM(8, 32)
-    CASE_FM(16, 2) CASE_FM(16, 4) CASE_FM(16, 6) CASE_FM(16, 8) CASE_FM(16, 10) CASE_FM(16, 12) CASE_FM(16, 16) CASE_FM(16, 20)
-    CASE_FM(16, 24) CASE_FM(16, 32)
-    CASE_FMM(8, 13) CASE_FMM(8, 16) CASE_FMM(8, 19) CASE_FMM(8, 26) CASE_FMM(8, 32)
-    CASE_FMM(16, 10) CASE_FMM(16, 12) CASE_FMM(16, 16) CASE_FMM(16, 20) CASE_FMM(16, 24) CASE_FMM(16, 32)
-#undef CASE_FM
-#undef CASE_FMM
-  }
-  return -1;
-}
-
-template <int SEM>
-int launch_score_R(int R, int SL, bool strips, dim3 grid, size_t shmem, hipStream_t st, const ScoreArgs &a) {
-  if (a.submax_out != nullptr) {                // sampled running maximum (MK = 4): a lone long query on float32 cells
-    if constexpr (SEM == kSemF32) {
-      if (SL == 8 || SL == 16) {                 // batches on float32 cells (fractional scoring)
-        if (strips) return -1;
-        switch (SL * 100 + R) {
-#define CASE_MB(sl, r) case sl * 100 + r: launch_score(sw_score_kernel<r, kSemF32, false, sl, false, false, 4>, grid, shmem, st, a); return 0;
-          CASE_MB(8, 13) CASE_MB(8, 16) CASE_MB(8, 19) CASE_MB(8, 26) CASE_MB(8, 32)
-          CASE_MB(16, 10) CASE_MB(16, 12) CASE_MB(16, 16) CASE_MB(16, 20) CASE_MB(16, 24) CASE_MB(16, 32)
-#undef CASE_MB
-        }
-        return -1;
-      }
-      if (SL != 64) return -1;
-      switch ((strips ? 100 : 0) + R) {
-#define CASE_MF(r) case r: launch_score(sw_score_kernel<r, kSemF32, false, 64, false, false, 4>, grid, shmem, st, a); return 0;
-#define CASE_MFS(r) case 100 + r: launch_score(sw_score_kernel<r, kSemF32, true, 64, false, false, 4>, grid, shmem, st, a); return 0;
-        CASE_MF(10) CASE_MF(12) CASE_MF(16) CASE_MF(20) CASE_MF(24) CASE_MF(32) CASE_MFS(20) CASE_MFS(24) CASE_MFS(32)
-#undef CASE_MF
-#undef CASE_MFS
-      }
-    }
-    return -1;
-  }
-  if (strips) {
-    if (SL == 16) { if (R != 32) return -1; launch_score(sw_score_kernel<32, SEM, true, 16>, grid, shmem, st, a); return 0; }
-    if (SL != 64) return -1;
-    switch (R) {
-#define CASE_S(r) case r: launch_score(sw_score_kernel<r, SEM, true, 64>, grid, shmem, st, a); return 0;
-      CASE_S(20) CASE_S(24) CASE_S(32)
-#undef CASE_S
-    }
-    return -1;
-  }
-  if (SL == 64) {
-    switch (R) {
-#define CASE_W(r) case r: launch_score(sw_score_kernel<r, SEM, false, 64>, grid, shmem, st, a); return 0;
-      CASE_W(10) CASE_W(12) CASE_W(16) CASE_W(20) CASE_W(24) CASE_W(32)
-#undef CASE_W
-    }
-    return -1;
-  }
-  if (SL == 8) {
-    switch (R) {
-#define CASE_R8(r) case r: launch_score(sw_score_kernel<r, SEM, false, 8>, grid, shmem, st, a); return 0;
-      CASE_R8(7) CASE_R8(10) CASE_R8(13) CASE_R8(16) CASE_R8(19) CASE_R8(26) CASE_R8(32)
-#undef CASE_R8
-    }
-    return -1;
-  }
-  switch (R) {
-#define CASE_R(r) case r: launch_score(sw_score_kernel<r, SEM, false>, grid, shmem, st, a); return 0;
-    CASE_R(2) CASE_R(4) CASE_R(6) CASE_R(8) CASE_R(10) CASE_R(12) CASE_R(16) CASE_R(20) CASE_R(24) CASE_R(32)
-#undef CASE_R
-  }
-  return -1;
 }
 
 // Granularity at which a tile reports its maxima = what the locate step re-runs.  uint8 engine: >= the query length
@@ -897,7 +855,10 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   const size_t nr = ranges.size();
   int64_t maxlen = 0;
   for (auto &r : ranges) maxlen = std::max(maxlen, r.hi - r.lo);
-  const size_t npairs = (sem_is_float(b.sem) || b.twin) ? (size_t)b.count : ((size_t)b.count + 1) / 2;   // queries per workgroup: 1 or 2
+  const int sem = kernel_sem(b);
+  const CellLaunch cl = cell_launch(ctx, t, sem);
+  const int nqw = b.twin ? 1 : cl.queries;                          // queries per workgroup
+  const size_t npairs = nqw == 1 ? (size_t)b.count : ((size_t)b.count + 1) / 2;
   // report maxima per sub-chunk of >= 256 columns (>= query length, so that the uint8 storage order stays
   // within two neighbouring sub-chunks): that is what locate re-runs; the strip-mined instance reports per tile
   b.sub_len = score_sub_len(p.semantics, b);
@@ -934,21 +895,11 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   a.qfirst = b.first;
   a.qcount = b.count;
   a.nq = (int)q.nq;
-  a.stab = b.sem == kSemF32 ? ctx->ftab_s.p
-           : (sem_is_float(b.sem) ? ctx->ftab.p : (b.sem == kSemF16 ? ctx->htab.p : (b.sem == kSemU8H ? ctx->htab8.p : ctx->stab.p)));
+  a.stab = cl.tab;
   a.ncodes = ref.ncodes;
-  if (b.sem == kSemF32) { const float gs = std::ldexp(t.gapf, -ctx->fshift); memcpy(&a.gap2, &gs, 4); }
-  else if (sem_is_float(b.sem)) memcpy(&a.gap2, &t.gapf, 4);
-  else if (b.sem == kSemF16 && b.mirror) a.gap2 = (uint32_t)t.gap * 0x00010001u;   // added to the bit pattern of both halves
-  else if (b.sem == kSemF16) a.gap2 = (uint32_t)half_bits(-(float)t.gap / kF16Scale) * 0x00010001u;
-  else if (b.sem == kSemU8H) a.gap2 = (uint32_t)half_bits(-(float)t.gap / 256.0f) * 0x00010001u;
-  else a.gap2 = (uint32_t)t.gap * 0x00010001u;
+  a.gap2 = cl.gap2;
   a.clamp2 = 255u * 0x00010001u;
-  a.pubmax = 0u;
-  if (b.unsat) {                                  // uint8 engine swept without saturation: clamp what is published
-    if (b.sem == kSemF32) { const float v = std::ldexp(255.0f, -ctx->fshift); memcpy(&a.pubmax, &v, 4); }
-    else a.pubmax = (uint32_t)half_bits(255.0f / kF16Scale);
-  }
+  a.pubmax = b.unsat ? cl.pubmax : 0u;            // uint8 engine swept without saturation: clamp what is published
   a.keys = io ? io->keys : ctx->keys.as<unsigned long long>();
   a.flag_count = nullptr; a.flag_list = nullptr; a.flag_cap = 0; a.flag_value = 0;
   a.submax_out = nullptr; a.submax_stride = 0;
@@ -960,8 +911,6 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     a.flag_value = (uint32_t)half_bits(1.0f);                       // cells hold H / 2048: the clamp's upper end
   }
 
-  const bool idiag = b.sem == kSemF16 && b.mirror && !opt().no_f16m_int_diag;   // mirrored cells: diagonal term as an integer add
-  const int nqw = (sem_is_float(b.sem) || b.twin) ? 1 : 2;          // queries per workgroup
   // keep single launches to a few seconds: split the bucket's pairs over several launches
   double range_cols = 0;
   for (auto &r : ranges) range_cols += (double)(r.hi - r.lo);
@@ -974,7 +923,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   size_t shmem = profile_lds_bytes(ref.ncodes, b.R, b.SL, b.twin, b.comb) + (size_t)(b.twin ? 2 : 1) * nslot * codebuf_bytes(b.SL);
   const int64_t nsub = cpr * (b.chunk_len / b.sub_len);                // sub-chunks of the range (sampled sweep: one value each)
   if (b.sampled) {
-    if (ctx->submax.ensure((size_t)pn * (size_t)nqw * (size_t)nsub * (b.sem == kSemF32 ? 4 : 2) + 64))
+    if (ctx->submax.ensure((size_t)pn * (size_t)nqw * (size_t)nsub * cl.value_bytes + 64))
       return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(sub-chunk values) failed");
     a.submax_out = ctx->submax.as<uint16_t>();
     a.submax_stride = nsub;
@@ -991,7 +940,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     if (bytes > ((size_t)64 << 30)) return fail(ctx, MI355_SW_ENOTSUP, "strip-mined sweep needs more than 64 GiB of boundary scratch");
     if (ctx->brow.ensure(bytes)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(strip boundary rows) failed");
     // boundary rows start as H = 0 (a non-zero bit pattern in the scaled float16 instance)
-    if (b.sem == kSemU8H) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->brow.p, (int)kU8HZero, bytes / 4, ctx->stream));
+    if (cl.border != 0u) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->brow.p, (int)cl.border, bytes / 4, ctx->stream));
     else HIPCHK(ctx, hipMemsetAsync(ctx->brow.p, 0, bytes, ctx->stream));
     a.brow = ctx->brow.as<uint32_t>();
     shmem += (size_t)2 * nslot * kSeg * 4 + (size_t)nslot * 64 * 4;   // boundary windows + per-sub-chunk maxima
@@ -1000,33 +949,17 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     for (int e = 0; e < 2; ++e) { hipEvent_t ev; HIPCHK(ctx, hipEventCreate(&ev)); ctx->score_ev.push_back(ev); }
   }
   HIPCHK(ctx, hipEventRecord(ctx->score_ev[ctx->score_ev_used], ctx->stream));
-  int rc = b.twin ? (b.sem == kSemF16 ? (b.SL == 64 ? launch_score_twin<kSemF16>(b.R, b.strips, grid, shmem, ctx->stream, a)
-                                                    : launch_score_twin16(b.R, b.comb, grid, shmem, ctx->stream, a))
-                     : b.sem == kSemU8H ? launch_score_twin<kSemU8H>(b.R, b.strips, grid, shmem, ctx->stream, a)
-                     : b.sem == kSemU8 ? launch_score_twin<kSemU8>(b.R, b.strips, grid, shmem, ctx->stream, a)
-                                       : launch_score_twin<kSemI16>(b.R, b.strips, grid, shmem, ctx->stream, a))
-           : b.sem == kSemF16 && b.mirror ? (idiag ? launch_score_f16m<kSemF16M>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
-                                                   : launch_score_f16m<kSemF16MF>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a))
-           : b.sem == kSemF16 ? launch_score_f16<kSemF16>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
-           : b.sem == kSemU8H ? launch_score_R<kSemU8H>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
-           : b.sem == kSemU8 ? launch_score_R<kSemU8>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
-           : b.sem == kSemF32U8 ? launch_score_R<kSemF32U8>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
-           : b.sem == kSemF32 ? launch_score_R<kSemF32>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a)
-                              : launch_score_R<kSemI16>(b.R, b.SL, b.strips, grid, shmem, ctx->stream, a);
-  if (rc) return fail(ctx, MI355_SW_ENOTSUP, "no score kernel instance for this R");
+  const ScoreInst inst{b.R, sem, b.strips, b.SL, b.twin, b.comb, a.submax_out != nullptr ? 4 : 1};
+  if (launch_score(inst, grid, shmem, ctx->stream, a)) return fail(ctx, MI355_SW_ENOTSUP, "no score kernel instance for this R");
   HIPCHK(ctx, hipGetLastError());
-  {
-    static const char *cellname[] = {"i16", "u8i16", "f32", "u8f32", "f16", "u8f16"};
-    path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d,satflag=%d,unsat=%d,pow2=%d%s%s]", cellname[b.sem], b.SL, b.R, (int)b.strips,
-              (int)b.twin, (int)b.comb, (int)b.sampled, (int)b.satflag, (int)b.unsat, (int)((b.chunk_len & (b.chunk_len - 1)) == 0),
-              idiag ? ",idiag=1" : "", b.mirror ? ",mirror=1" : "");
-  }
+  path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d,satflag=%d,unsat=%d,pow2=%d%s]", cl.cell, b.SL, b.R, (int)b.strips,
+            (int)b.twin, (int)b.comb, (int)b.sampled, (int)b.satflag, (int)b.unsat, (int)((b.chunk_len & (b.chunk_len - 1)) == 0), cl.tag);
   if (b.sampled) {
     // grid.y = query positions of this launch, at most 65535 per filter launch
     for (int f0 = 0; f0 < a.qcount; f0 += 65535) {
       const int fc = std::min(65535, a.qcount - f0);
       const dim3 fgrid((unsigned)std::min<int64_t>(64, (nsub + 255) / 256), (unsigned)fc);
-      const void *rows = reinterpret_cast<const uint8_t *>(a.submax_out) + (size_t)f0 * (size_t)nsub * (b.sem == kSemF32 ? 4 : 2);
+      const void *rows = reinterpret_cast<const uint8_t *>(a.submax_out) + (size_t)f0 * (size_t)nsub * cl.value_bytes;
       if (b.sem == kSemF32)
         hipLaunchKernelGGL(sw_sample_filter<true>, fgrid, dim3(256), 0, ctx->stream, rows, nsub, nsub,
                            (const int32_t *)a.qsel, a.qfirst + f0, fc, (const unsigned long long *)a.keys,
@@ -1063,8 +996,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     ki.cell = b.sem; ki.lanes = b.SL; ki.rows_per_lane = b.R; ki.strips = b.strips; ki.twin = b.twin;
     ki.chunk_len = b.chunk_len; ki.sub_len = b.sub_len; ki.warm = a.warm; ki.cells = cells;
     ki.valu_ops_per_cell = valu_ops_per_cell(b);
-    static const char *cellname[] = {"i16x2", "u8 as i16x2", "f32", "u8 as f32", "f16x2", "u8 as f16x2"};
-    std::snprintf(ki.name, sizeof ki.name, "sw_score_kernel<R=%d, %s%s, SL=%d%s%s>%s", b.R, cellname[b.sem], b.mirror ? (idiag ? " mirrored, integer diagonal" : " mirrored") : "", b.SL,
+    std::snprintf(ki.name, sizeof ki.name, "sw_score_kernel<R=%d, %s, SL=%d%s%s>%s", b.R, cl.name, b.SL,
                   b.strips ? ", strips" : "", b.twin ? (b.comb ? ", twin, code-pair profile" : ", twin") : "",
                   b.unsat ? " uint8 engine swept unsaturated, maxima clamped at 255"
                   : b.satflag ? (b.sampled ? " float engine swept saturating at 2048" : " float engine swept saturating at 2048, saturated sub-chunks re-evaluated exactly") : "");
@@ -1074,6 +1006,29 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     }
   }
   return 0;
+}
+
+// How the high 32 bits of a published key hold the score, by the bucket's cell type (mirrored cells publish H / 2048 again).
+// The device decode of sw_solo_kernel knows kKeyF16 and kKeyF32Scaled.
+enum KeyKind : char { kKeyInt = 0, kKeyF32 = 1, kKeyF16 = 2, kKeyU8H = 3, kKeyF32Scaled = 4 };
+KeyKind key_kind(const Bucket &b) {
+  switch (b.sem) {
+    case kSemF16:   return kKeyF16;         // float16 bits of H / 2048
+    case kSemU8H:   return kKeyU8H;         // float16 bits of (H + 1) / 256
+    case kSemF32:   return kKeyF32Scaled;   // float32 bits of H * 2^-fshift
+    case kSemF32U8: return kKeyF32;         // float32 bits of H
+    default:        return kKeyInt;         // H, below 2^16
+  }
+}
+float key_score(int kind, uint32_t hi, int fshift) {
+  float v;
+  switch (kind) {
+    case kKeyF16:       return half_value((uint16_t)hi) * kF16Scale;
+    case kKeyU8H:       return (uint16_t)hi ? half_value((uint16_t)hi) * 256.0f - 1.0f : 0.0f;
+    case kKeyF32Scaled: memcpy(&v, &hi, 4); return std::ldexp(v, fshift);
+    case kKeyF32:       memcpy(&v, &hi, 4); return v;
+    default:            return (float)hi;
+  }
 }
 
 constexpr int kRetryNoWait = 1;   // score_fetch: not an error — sweep again, tl_no_wait is set

@@ -45,8 +45,8 @@ int solo_align(mi355_sw_ctx *ctx, const RefData &ref, const char *x, size_t nx, 
   if (buckets.size() != 1) return 1;
   Bucket &b = buckets[0];
   for (const Range &r : ranges) if (!bucket_fast_ok(ref, table, b, r.hi - r.lo, p)) return 1;
-  const int keykind = b.sem == kSemF16 ? 2 : (b.sem == kSemF32 ? 4 : 0);
-  if (keykind == 0) return 1;
+  const KeyKind keykind = key_kind(b);
+  if (keykind != kKeyF16 && keykind != kKeyF32Scaled) return 1;     // (what sw_solo_kernel decodes)
   const Margin mg = table.margin((double)nx);
   if (!mg.finite()) return 1;
   // the largest window any candidate can need, and what it takes in LDS

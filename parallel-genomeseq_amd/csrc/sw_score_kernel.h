@@ -71,8 +71,6 @@ constexpr int kSemF16M = 6;            // kSemF16 MIRRORED (DESIGN.md §3.3 lemm
 constexpr int kSemF16MF = 7;           // kSemF16M with the diagonal term as a clamped v_pk_add_f16 (option no_f16m_int_diag: the A/B)
 constexpr uint32_t kF16MZero = 0x3C003C00u;  // float16 1.0 in both halves: H = 0
 constexpr float kPadScoreF = -1.0e30f;
-__host__ __device__ constexpr bool sem_is_float(int sem) { return sem == kSemF32 || sem == kSemF32U8; }
-__host__ __device__ constexpr bool sem_is_mirror(int sem) { return sem == kSemF16M || sem == kSemF16MF; }
 
 // LDS stride (dwords) between the profile rows of two adjacent lanes: a multiple of 4 (b128
 // alignment) that is ≡ 4 (mod 8), so that the sixteen 16-byte windows of a ds_read_b128 lane
@@ -128,10 +126,40 @@ __device__ __forceinline__ i16x2 as_i16x2(uint32_t v) { return __builtin_bit_cas
 __device__ __forceinline__ u16x2 as_u16x2(i16x2 v) { return __builtin_bit_cast(u16x2, v); }
 __device__ __forceinline__ i16x2 to_i16x2(u16x2 v) { return __builtin_bit_cast(i16x2, v); }
 
-// Cell arithmetic of the three instances.  A cell register is handled as raw 32 bits outside these helpers.
-template <int SEM> struct Cell {
+// value of the lane above inside the 16-lane DPP row, 0 for the first lane (row H(0,.) = 0)
+__device__ __forceinline__ uint32_t row_shr1(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /*row_shr:1*/, 0xf, 0xf, true);
+}
+
+// Cell<SEM> is the whole description of a cell type: its arithmetic, and every constant and rule of sw_score_kernel that depends
+// on it.  A cell register is handled as raw 32 bits outside these members.  CellBase holds the defaults.
+struct CellBase {
+  static constexpr int kQueries = 2;          // queries per register
+  static constexpr bool kFloat = false;       // float32 cells (one query per register, float table, float bits published)
+  static constexpr bool kMirror = false;      // mirrored float16 cells (lemma L14): cells hold N = 1 - H / 2048
+  static constexpr bool kKeepsHg = false;     // the cell keeps H - g of every row (add, cell_h, sub_gap per cell)
+  static constexpr bool kMax3 = false;        // vmax3 exists: the running maximum takes three inputs
+  static constexpr bool kGapInVgpr = false;   // the gap operand of sub_gap is kept in a VGPR
+  static constexpr uint32_t kZero = 0u;       // bit pattern of H = 0 in a cell register
+  static constexpr uint32_t kPubZero = 0u;    // published value of H = 0 (low half)
+  static constexpr int kPad = kPadScore;      // 16-bit profile entry of padding rows
+  // the packed profile entry of two 16-bit table entries: low half = query A (or the first tile), high half = B
+  static __device__ __forceinline__ uint32_t entry(int sa, int sb) { return (uint32_t)(uint16_t)sa | ((uint32_t)(uint16_t)sb << 16); }
+  // border row H(0, .) of a single-strip tile: the last row of the lane above, H = 0 on the tile's first lane (first_lane_zero:
+  // 0 on that lane, all ones elsewhere; first_lane_z: the bit pattern of H = 0 there, 0 elsewhere); bound_ctrl supplies the zero
+  template <int SL> static __device__ __forceinline__ uint32_t border(uint32_t v, uint32_t first_lane_zero, uint32_t) {
+    uint32_t up;
+    if (SL == 64) up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /*wave_shr:1*/, 0xf, 0xf, true);
+    else up = row_shr1(v);
+    if (SL == 8) up &= first_lane_zero;                            // lane 8 of the DPP row starts another tile
+    return up;
+  }
+  // what a tile publishes of its slot maximum
+  static __device__ __forceinline__ uint32_t published(uint32_t m32) { return m32; }
+};
+
+template <int SEM> struct Cell : CellBase {
   typedef i16x2 T;
-  static constexpr int kQueries = 2;
   static __device__ __forceinline__ T from_bits(uint32_t v) { return as_i16x2(v); }
   static __device__ __forceinline__ uint32_t bits(T v) { return as_u32(v); }
   static __device__ __forceinline__ T add(T d, T sc, uint32_t clamp2) {
@@ -145,9 +173,10 @@ template <int SEM> struct Cell {
   }
   static __device__ __forceinline__ T cell(T x, T y) { return __builtin_elementwise_max(x, y); }
 };
-template <int SEM> struct CellF {
+template <int SEM> struct CellF : CellBase {
   typedef float T;
   static constexpr int kQueries = 1;
+  static constexpr bool kFloat = true;
   static __device__ __forceinline__ T from_bits(uint32_t v) { return __uint_as_float(v); }
   static __device__ __forceinline__ uint32_t bits(T v) { return __float_as_uint(v); }
   static __device__ __forceinline__ T add(T d, T sc, uint32_t) { return SEM == kSemF32U8 ? fminf(d + sc, 255.0f) : d + sc; }
@@ -157,9 +186,11 @@ template <int SEM> struct CellF {
   static __device__ __forceinline__ T cell(T x, T y) { return fmaxf(fmaxf(x, y), 0.0f); }
 };
 // Packed float16 cells, handled as raw 32 bits (two halves); every operation is one VOP3P instruction.
-template <> struct Cell<kSemF16> {
+template <> struct Cell<kSemF16> : CellBase {
   typedef uint32_t T;
-  static constexpr int kQueries = 2;
+  static constexpr bool kKeepsHg = true;
+  static constexpr bool kMax3 = true;
+  static constexpr int kPad = (int)(int16_t)0xC800;                 // float16 -8 = -16384 / 2048
   static __device__ __forceinline__ T from_bits(uint32_t v) { return v; }
   static __device__ __forceinline__ uint32_t bits(T v) { return v; }
   // max(diag + score, 0): values are scaled into [0, 1), so the clamp modifier is exactly the zero floor
@@ -172,6 +203,8 @@ template <> struct Cell<kSemF16> {
   static __device__ __forceinline__ T vmax3(T a, T b, T c) {
     T r; asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
   }
+  // the cell's own maximum3 H = max(x, W - g, N - g) (the zero floor is the clamp of add)
+  static __device__ __forceinline__ T cell_h(T x, T w, T n) { return vmax3(x, w, n); }
   // gap2 holds -g in both halves; the zero floor is applied by cell()
   static __device__ __forceinline__ T sub_gap(T t, uint32_t gap2) {
     T r; asm("v_pk_add_f16 %0, %1, %2" : "=v"(r) : "v"(t), "s"(gap2)); return r;
@@ -181,6 +214,10 @@ template <> struct Cell<kSemF16> {
   }
 };
 template <> struct Cell<kSemU8H> : Cell<kSemF16> {
+  static constexpr bool kKeepsHg = false;
+  static constexpr uint32_t kZero = kU8HZero;
+  static constexpr uint32_t kPubZero = kU8HZero & 0xFFFFu;
+  static constexpr int kPad = (int)(int16_t)0xD400;                 // float16 -64 = -16384 / 256
   // adds(nw, +M) saturating at 255 / subs(nw, X): one clamped add in the (H + 1) / 256 representation
   static __device__ __forceinline__ T add(T d, T sc, uint32_t) {
     T r; asm("v_pk_add_f16 %0, %1, %2 clamp" : "=v"(r) : "v"(d), "v"(sc)); return r;
@@ -189,10 +226,28 @@ template <> struct Cell<kSemU8H> : Cell<kSemF16> {
   static __device__ __forceinline__ T cell(T x, T y) {
     T r; asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "s"(kU8HZero)); return r;
   }
+  // the border row is the bit pattern of H = 0, not zero: `old` operand, and a bit-select for 8-lane tiles
+  template <int SL> static __device__ __forceinline__ uint32_t border(uint32_t v, uint32_t first_lane_zero, uint32_t) {
+    uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp((int)kZero, (int)v, SL == 64 ? 0x138 /*wave_shr:1*/ : 0x111 /*row_shr:1*/, 0xf, 0xf, false);
+    if (SL == 8) up = (up & first_lane_zero) | (kZero & ~first_lane_zero);
+    return up;
+  }
 };
 // Mirrored packed float16 cells: the order is reversed (every "maximum" is a packed minimum), and the diagonal and gap terms
 // are integer adds on the bit pattern of both halves at once.
 template <> struct Cell<kSemF16M> : Cell<kSemF16> {
+  static constexpr bool kMirror = true;
+  static constexpr bool kGapInVgpr = true;   // a VOP2 add with an SGPR operand issues at the VOP3P rate (profiles/r05_mirror_cell_rate.txt)
+  static constexpr uint32_t kZero = kF16MZero;
+  // -s on the bit pattern (s = entry * 2048, exact), capped at 1024: from any cell (pattern >= 0x3800) that reaches the floor
+  // 0x3C00, as padding and every score <= -1024 do in the float add; the low half's borrow goes to the high half
+  static __device__ __forceinline__ uint32_t entry(int sa, int sb) {
+    auto neg_s = [](int h) {
+      const int s = (int)((float)__builtin_bit_cast(_Float16, (uint16_t)h) * kF16Scale);
+      return -s < 1024 ? -s : 1024;
+    };
+    return (uint32_t)neg_s(sa) + ((uint32_t)neg_s(sb) << 16);
+  }
   // N_nw - s on the bit pattern: sc = (-s_B) * 2^16 + (-s_A) mod 2^32, so that a borrow of the low half is absorbed by the high
   // one; each half stays in [0, 0xFFFF] (L14 (f)).  Unclamped: for H_nw + s < 0 the pattern lies above 1.0 and cell_h's
   // clamp returns the zero floor.  Inline asm, so that the compiler cannot fuse it into a half-rate three-operand add
@@ -200,7 +255,7 @@ template <> struct Cell<kSemF16M> : Cell<kSemF16> {
     T r; asm("v_add_u32 %0, %1, %2" : "=v"(r) : "v"(sc), "v"(d)); return r;
   }
   // min(x, K_w, K_n, 1.0): the clamp's upper end is the zero floor of the diagonal term (K, N > 0, so the lower end never acts)
-  static __device__ __forceinline__ T vmax3_floor(T a, T b, T c) {
+  static __device__ __forceinline__ T cell_h(T a, T b, T c) {
     T r; asm("v_pk_minimum3_f16 %0, %1, %2, %3 clamp" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
   }
   static __device__ __forceinline__ T vmax(T a, T b) {
@@ -211,55 +266,57 @@ template <> struct Cell<kSemF16M> : Cell<kSemF16> {
   }
   // H - g on the bit pattern: gap2 = g in both halves (no carry crosses them: a half is at most 0x3C00 + g).  Below H = g the
   // pattern leaves [0.5, 1] upwards — a value above 1.0, which never decides the cell: the zero floor 1.0 lies below it.
-  // Inline asm, so that the compiler cannot fuse it into a half-rate v_add3_u32 / v_lshl_add_u32.  gap2 is a VGPR: a VOP2
-  // add with an SGPR operand issues at the VOP3P rate (profiles/r05_mirror_cell_rate.txt)
+  // Inline asm, so that the compiler cannot fuse it into a half-rate v_add3_u32 / v_lshl_add_u32
   static __device__ __forceinline__ T sub_gap(T t, uint32_t gap2) {
     T r; asm("v_add_u32 %0, %1, %2" : "=v"(r) : "v"(gap2), "v"(t)); return r;
   }
-  // back to H / 2048 = 1 - N (exact: Sterbenz) for publishing
-  static __device__ __forceinline__ T unmirror(T n) {
+  // bound_ctrl's zero, then one v_max_u32 with H = 0 on the tile's first lane (first_lane_z): a cell N <= 1.0 in both halves is,
+  // as a 32-bit word, at most kF16MZero, so the maximum is kF16MZero there and the value of the lane above elsewhere (8- and
+  // 16-lane tiles)
+  template <int SL> static __device__ __forceinline__ uint32_t border(uint32_t v, uint32_t, uint32_t first_lane_z) {
+    return __builtin_elementwise_max(row_shr1(v), first_lane_z);
+  }
+  // back to H / 2048 = 1 - N (exact: Sterbenz) for publishing; the published zero is 0
+  static __device__ __forceinline__ uint32_t published(T n) {
     T r; asm("v_pk_add_f16 %0, %1, %2 neg_lo:[1,0] neg_hi:[1,0]" : "=v"(r) : "v"(n), "s"(kF16MZero)); return r;
   }
 };
 // The same cells with the diagonal term as one clamped float16 add of -s / 2048 (the profile holds float16 -s / 2048)
 template <> struct Cell<kSemF16MF> : Cell<kSemF16M> {
+  static __device__ __forceinline__ uint32_t entry(int sa, int sb) { return CellBase::entry(sa, sb) ^ 0x80008000u; }   // (padding: +8, clamped to the floor)
   // clamp(N_nw - s): 1 - (H_nw + s) / 2048, exact while H_nw + s <= 1024; the upper clamp 1.0 is the zero floor (H_nw + s < 0)
   static __device__ __forceinline__ T add(T d, T sc, uint32_t) {
     T r; asm("v_pk_add_f16 %0, %1, %2 clamp" : "=v"(r) : "v"(d), "v"(sc)); return r;
   }
+  static __device__ __forceinline__ T cell_h(T x, T w, T n) { return vmax3(x, w, n); }
 };
 // float32 cells hold H * 2^-k with 2^k above every value of the call (a pure exponent shift: every add, subtract
 // and maximum commutes with it exactly), so that the [0, 1] clamp of the add is the zero floor and the cell takes the
 // same three ops as the packed float16 instance: add clamp, max3 with the two kept (H - g) terms, subtract g.
 template <> struct Cell<kSemF32> : CellF<kSemF32> {
+  static constexpr bool kKeepsHg = true;
+  static constexpr bool kMax3 = true;
   static __device__ __forceinline__ T add(T d, T sc, uint32_t) {
     T r; asm("v_add_f32_e64 %0, %1, %2 clamp" : "=v"(r) : "v"(d), "v"(sc)); return r;
   }
   static __device__ __forceinline__ T vmax3(T a, T b, T c) {
     T r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
   }
+  static __device__ __forceinline__ T cell_h(T x, T w, T n) { return vmax3(x, w, n); }
 };
 template <> struct Cell<kSemF32U8> : CellF<kSemF32U8> {};
 
-// bit pattern of H = 0 in a cell register
-template <int SEM> __host__ __device__ constexpr uint32_t zero_bits() { return SEM == kSemU8H ? kU8HZero : (sem_is_mirror(SEM) ? kF16MZero : 0u); }
-
-// three-input maximum where the cell type has one (packed float16), else two steps
-template <int SEM> __device__ __forceinline__ typename Cell<SEM>::T cell_max3(typename Cell<SEM>::T a, typename Cell<SEM>::T b, typename Cell<SEM>::T c) {
-  if constexpr (SEM == kSemF16 || sem_is_mirror(SEM) || SEM == kSemU8H) return Cell<SEM>::vmax3(a, b, c);
-  else return Cell<SEM>::vmax(Cell<SEM>::vmax(a, b), c);
-}
-
-// the cell's own maximum3 H = max(x, W - g, N - g) of the instances that keep H - g; with the integer diagonal term it also
-// applies the zero floor
-template <int SEM> __device__ __forceinline__ typename Cell<SEM>::T cell_h(typename Cell<SEM>::T x, typename Cell<SEM>::T w, typename Cell<SEM>::T n) {
-  if constexpr (SEM == kSemF16M) return Cell<SEM>::vmax3_floor(x, w, n);
-  else return Cell<SEM>::vmax3(x, w, n);
-}
-
-// value of the lane above inside the 16-lane DPP row, 0 for the first lane (row H(0,.) = 0)
-__device__ __forceinline__ uint32_t row_shr1(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /*row_shr:1*/, 0xf, 0xf, true);
+// The legal instances sw_score_kernel<R, SEM, STRIPS, SL, TWIN, COMB, MK>: the kernel asserts it, and so does the host's table of
+// compiled instances (host_score.h)
+template <int SEM> __host__ __device__ constexpr bool score_instance_ok(int R, bool STRIPS, int SL, bool TWIN, bool COMB, int MK) {
+  typedef Cell<SEM> C;
+  return (SL == 64 || SL == 16 || SL == 8) &&                      // a slot is a whole wavefront, a DPP row or half a DPP row
+         !(STRIPS && SL == 8) &&                                   // the strip-mined instances use whole DPP rows or wavefronts
+         (!TWIN || ((SL == 64 || SL == 16) && !C::kFloat && R % 2 == 0)) &&   // twin tiles: packed cells, 64- or 16-lane tiles
+         (!COMB || (TWIN && !STRIPS)) &&                           // the code-pair profile belongs to the twin instances
+         (!C::kMirror || (!TWIN && !STRIPS && SL != 64)) &&        // mirrored cells: two-query 8- or 16-lane tiles, one strip
+         // sampled maximum: packed float16 two-query tiles in one strip, or float32 cells (one query per tile)
+         (MK == 1 || (MK == 4 && !TWIN && C::kKeepsHg && (C::kFloat || !STRIPS)));
 }
 
 // SL = lanes per tile ("slot"): 16 (one DPP row) or 8 (half a DPP row; the DPP shift then needs one mask op
@@ -281,13 +338,7 @@ __device__ __forceinline__ uint32_t row_shr1(uint32_t v) {
 // 3 + 1/(2 MK) instead of 3.5 ops.
 template <int R, int SEM, bool STRIPS = false, int SL = 16, bool TWIN = false, bool COMB = false, int MK = 1>
 __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
-  static_assert(MK == 1 || (MK == 4 && !TWIN && (((SEM == kSemF16 || sem_is_mirror(SEM)) && !STRIPS) || SEM == kSemF32)),
-                "sampled maximum: packed float16 two-query tiles, or float32 cells (one query per tile)");
-  static_assert(SL == 64 || SL == 16 || SL == 8, "a slot is a whole wavefront, a DPP row or half a DPP row");
-  static_assert(!(STRIPS && SL == 8), "the strip-mined instances use whole DPP rows or whole wavefronts");
-  static_assert(!TWIN || ((SL == 64 || SL == 16) && !sem_is_float(SEM) && R % 2 == 0), "twin tiles: packed cells on whole-wavefront or 16-lane tiles");
-  static_assert(!COMB || (TWIN && !STRIPS), "the code-pair profile belongs to the twin instances");
-  static_assert(!sem_is_mirror(SEM) || (!TWIN && !STRIPS), "mirrored float16 cells: two-query tiles, one strip");
+  static_assert(score_instance_ok<SEM>(R, STRIPS, SL, TWIN, COMB, MK), "no such sw_score_kernel instance (score_instance_ok)");
   constexpr bool HALF = TWIN && !COMB;                             // the profile holds 16-bit entries, two rows per dword
   constexpr int LS = HALF ? lane_stride(R / 2) : lane_stride(R);   // dwords between the profile rows of adjacent lanes
   constexpr int NQ4 = HALF ? (R / 2 + 3) / 4 : (R + 3) / 4;
@@ -334,42 +385,27 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
       if (COMB) {
         // entry (cA * ncodes + cB): low half = this row against the first tile's code, high half = against the second's
         const int16_t *st = static_cast<const int16_t *>(a.stab);
-        constexpr int kPadEntry = SEM == kSemF16 ? (int)(int16_t)0xC800 : (SEM == kSemU8H ? (int)(int16_t)0xD400 : kPadScore);
         const int cA = c / a.ncodes, cB = c - cA * a.ncodes;
-        const int sa = (i < mA) ? st[(int)xA[i] * a.ncodes + cA] : kPadEntry;
-        const int sb = (i < mA) ? st[(int)xA[i] * a.ncodes + cB] : kPadEntry;
-        prof[(c * PL + ll) * LS + r] = (uint32_t)(uint16_t)sa | ((uint32_t)(uint16_t)sb << 16);
+        const int sa = (i < mA) ? st[(int)xA[i] * a.ncodes + cA] : C::kPad;
+        const int sb = (i < mA) ? st[(int)xA[i] * a.ncodes + cB] : C::kPad;
+        prof[(c * PL + ll) * LS + r] = C::entry(sa, sb);
         continue;
       }
       if (TWIN) {
         const int16_t *st = static_cast<const int16_t *>(a.stab);
-        const int sa = (i < mA) ? st[(int)xA[i] * a.ncodes + c]
-                                : (SEM == kSemU8H ? (int)(int16_t)0xD400 /* float16 -64 */
-                                   : (SEM == kSemF16 ? (int)(int16_t)0xC800 /* float16 -8 */ : kPadScore));
+        const int sa = (i < mA) ? st[(int)xA[i] * a.ncodes + c] : C::kPad;
         reinterpret_cast<uint16_t *>(prof)[((c * PL + ll) * LS) * 2 + r] = (uint16_t)sa;
         continue;
       }
-      if (sem_is_float(SEM)) {
+      if (C::kFloat) {
         const float *ft = static_cast<const float *>(a.stab);
         e32 = __float_as_uint((i < mA) ? ft[(int)xA[i] * a.ncodes + c] : kPadScoreF);
       } else {
-        // 16-bit table entries: int16 scores, or float16 bit patterns for the packed float16 instance
+        // 16-bit table entries: int16 scores, or float16 bit patterns for the packed float16 instances
         const int16_t *st = static_cast<const int16_t *>(a.stab);
-        constexpr int kPadEntry = (SEM == kSemF16 || sem_is_mirror(SEM)) ? (int)(int16_t)0xC800 /* float16 -8 = -16384 / 2048 */
-                                  : (SEM == kSemU8H ? (int)(int16_t)0xD400 /* float16 -64 = -16384 / 256 */ : kPadScore);
-        const int sa = (i < mA) ? st[(int)xA[i] * a.ncodes + c] : kPadEntry;
-        const int sb = (i < mB) ? st[(int)xB[i] * a.ncodes + c] : kPadEntry;
-        e32 = (uint32_t)(uint16_t)sa | ((uint32_t)(uint16_t)sb << 16);
-        if (SEM == kSemF16MF) e32 ^= 0x80008000u;                 // mirrored cells add -s (padding: +8, clamped to the floor)
-        if (SEM == kSemF16M) {
-          // -s on the bit pattern (s = entry * 2048, exact), capped at 1024: from any cell (pattern >= 0x3800) that reaches
-          // the floor 0x3C00, as padding and every score <= -1024 do in the float add; the low half's borrow goes to the high half
-          auto neg_s = [](int h) {
-            const int s = (int)((float)__builtin_bit_cast(_Float16, (uint16_t)h) * kF16Scale);
-            return -s < 1024 ? -s : 1024;
-          };
-          e32 = (uint32_t)neg_s(sa) + ((uint32_t)neg_s(sb) << 16);
-        }
+        const int sa = (i < mA) ? st[(int)xA[i] * a.ncodes + c] : C::kPad;
+        const int sb = (i < mB) ? st[(int)xB[i] * a.ncodes + c] : C::kPad;
+        e32 = C::entry(sa, sb);
       }
       prof[(c * PL + ll) * LS + r] = e32;
     }
@@ -465,15 +501,15 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   const int64_t total_steps = a.warm + a.chunk_len + SL;           // + SL-1 skew, + 1 max-fold drain
   const int nseg = (int)((total_steps + kSeg - 1) / kSeg);
 
-  T mx = C::from_bits(zero_bits<SEM>());
+  T mx = C::from_bits(C::kZero);
   const int code_stride = PL * LS;                                 // dwords per reference code
   const int strip_rows = SL * R;
   const int mmax = mA > mB ? mA : mB;
   const int nstrips = STRIPS ? (mmax + strip_rows - 1) / strip_rows : 1;
   uint32_t first_lane_zero = ls == 0 ? 0u : 0xFFFFFFFFu;           // SL = 8: zero border row for lane 0 of the slot
   asm volatile("" : "+v"(first_lane_zero));                        // keep it a plain v_and_b32 (2 cycles), not a v_cndmask (4)
-  uint32_t first_lane_z = ls == 0 ? kF16MZero : 0u;                // kSemF16M: the border row's H = 0 on the tile's first lane
-  if constexpr (sem_is_mirror(SEM)) asm volatile("" : "+v"(first_lane_z));
+  uint32_t first_lane_z = ls == 0 ? C::kZero : 0u;                 // mirrored cells: the border row's H = 0 on the tile's first lane
+  if constexpr (C::kMirror) asm volatile("" : "+v"(first_lane_z));
   // STRIPS: this tile's ping-pong boundary rows (global), and its LDS windows
   const size_t tile_id = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NSLOT + slot;
   uint32_t *brow0 = STRIPS ? a.brow + tile_id * 2 * (size_t)a.brow_stride : nullptr;
@@ -483,8 +519,8 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   // per-sub-chunk maximum -> per-query key.  Lanes lag lane 0 by up to SL-1 columns, so up to SL-1 trailing
   // columns of a sub-chunk are reported with the next one; the host widens its search accordingly.
   const int64_t subs_per_tile = a.chunk_len / a.sub_len;
-  // this tile's best published value per query (H = 0: nothing to report; mirrored cells publish H / 2048)
-  uint32_t best_a = (sem_is_mirror(SEM) ? 0u : zero_bits<SEM>()) & 0xFFFFu, best_b = best_a;
+  // this tile's best published value per query (H = 0: nothing to report)
+  uint32_t best_a = C::kPubZero, best_b = best_a;
   auto slot_max = [&]() -> uint32_t {                              // maximum of mx over the slot's lanes
     uint32_t m32 = C::bits(mx);
 #pragma unroll
@@ -505,7 +541,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
     if (ls == 0 && active) {
       const unsigned long long tag = 0xFFFFFFFFull - (unsigned long long)(chunk * subs_per_tile + sub);
       unsigned long long *k = a.keys + (size_t)range * a.nq;
-      if (sem_is_float(SEM)) {
+      if (C::kFloat) {
         if (MK > 1 && a.submax_out != nullptr)                       // (one query per workgroup: launch-local position = pair)
           reinterpret_cast<uint32_t *>(a.submax_out)[(size_t)pair * (size_t)a.submax_stride + (size_t)(chunk * subs_per_tile + sub)] = m32;
         if (a.pubmax != 0u && m32 > a.pubmax) m32 = a.pubmax;       // non-negative floats order like their bits
@@ -540,23 +576,22 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
     }
   };
   auto publish = [&](int64_t sub) {
-    if constexpr (sem_is_mirror(SEM)) publish_value(sub, C::unmirror(slot_max()));
-    else publish_value(sub, slot_max());
-    mx = C::from_bits(zero_bits<SEM>());
+    publish_value(sub, C::published(slot_max()));
+    mx = C::from_bits(C::kZero);
   };
   // STRIPS: a sub-chunk's maximum accumulates over all strips in LDS before it can be published
   uint32_t *submax = bwin + 2 * NSLOT * kSeg + slot * 64;
   auto fold_sub = [&](int64_t sub) {
     const uint32_t m32 = slot_max();
     if (ls == 0) submax[sub] = C::bits(C::vmax(C::from_bits(submax[sub]), C::from_bits(m32)));
-    mx = C::from_bits(zero_bits<SEM>());
+    mx = C::from_bits(C::kZero);
   };
   if (STRIPS) {
     for (int e = ls; e < 64; e += SL) submax[e] = 0u;
   }
   // the gap operand of sub_gap: the mirrored cell's integer add wants it in a VGPR (one copy, made once)
   uint32_t gap_op = a.gap2;
-  if constexpr (sem_is_mirror(SEM)) asm volatile("" : "+v"(gap_op));
+  if constexpr (C::kGapInVgpr) asm volatile("" : "+v"(gap_op));
   const int segs_per_sub = (int)(a.sub_len / kSeg);
   const int warm_segs = (int)(a.warm / kSeg);
   int64_t sub = 0;
@@ -575,7 +610,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
     const bool rd = STRIPS && strip > 0, wr = STRIPS && strip + 1 < nstrips;
     // boundary values of stream positions seg*64 + VPL*ls .. +VPL-1
     auto bin_load = [&](int seg) -> uint4 {
-      if (!rd) return make_uint4(zero_bits<SEM>(), zero_bits<SEM>(), zero_bits<SEM>(), zero_bits<SEM>());
+      if (!rd) return make_uint4(C::kZero, C::kZero, C::kZero, C::kZero);
       if (VPL == 4) return *reinterpret_cast<const uint4 *>(bin_g + (size_t)seg * kSeg + 4 * ls);
       return make_uint4(bin_g[(size_t)seg * kSeg + ls], 0, 0, 0);
     };
@@ -593,7 +628,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
       window_put2(stage_load(0, true));
       nextcodes2 = stage_load(1, true);
     }
-    uint4 nextb = make_uint4(zero_bits<SEM>(), zero_bits<SEM>(), zero_bits<SEM>(), zero_bits<SEM>());
+    uint4 nextb = make_uint4(C::kZero, C::kZero, C::kZero, C::kZero);
     if (STRIPS) {
       bin_put(bin_load(0));
       nextb = bin_load(1);
@@ -602,12 +637,11 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
 
     T H[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) H[r] = C::from_bits(zero_bits<SEM>());
-    uint32_t up_prev = zero_bits<SEM>();
-    constexpr bool kKeepsHg = SEM == kSemF16 || sem_is_mirror(SEM) || SEM == kSemF32;   // instances that keep H - g of every cell
-    T Hg[kKeepsHg ? R : 1];
+    for (int r = 0; r < R; ++r) H[r] = C::from_bits(C::kZero);
+    uint32_t up_prev = C::kZero;
+    T Hg[C::kKeepsHg ? R : 1];
 #pragma unroll
-    for (int r = 0; r < (kKeepsHg ? R : 1); ++r) Hg[r] = C::sub_gap(C::from_bits(zero_bits<SEM>()), gap_op);   // 0 - g
+    for (int r = 0; r < (C::kKeepsHg ? R : 1); ++r) Hg[r] = C::sub_gap(C::from_bits(C::kZero), gap_op);   // 0 - g
 
     for (int seg = 0; seg < nseg; ++seg) {
 #pragma unroll 4
@@ -640,28 +674,14 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
           // lane 0 takes the previous strip's bottom row through the DPP `old` operand
           up = shift_in(C::bits(H[R - 1]), bin_w[k]);
         } else {
-          // zero border row H(0, .): bound_ctrl supplies it (no `old` operand to set up)
-          if constexpr (sem_is_mirror(SEM) && SL != 64) {
-            // bound_ctrl's zero, then one v_max_u32 with H = 0 on the tile's first lane: a cell N <= 1.0 in both halves is, as a
-            // 32-bit word, at most kF16MZero, so the maximum is kF16MZero there and the value of the lane above elsewhere
-            up = __builtin_elementwise_max(row_shr1(C::bits(H[R - 1])), first_lane_z);
-          } else if constexpr (zero_bits<SEM>() != 0u) {
-            // the border row is the bit pattern of H = 0, not zero: `old` operand, and a bit-select for 8-lane tiles
-            constexpr uint32_t Z = zero_bits<SEM>();
-            up = shift_in(C::bits(H[R - 1]), Z);
-            if (SL == 8) up = (up & first_lane_zero) | (Z & ~first_lane_zero);
-          } else {
-            if (SL == 64) up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)C::bits(H[R - 1]), 0x138 /*wave_shr:1*/, 0xf, 0xf, true);
-            else up = row_shr1(C::bits(H[R - 1]));
-            if (SL == 8) up &= first_lane_zero;                    // lane 8 of the DPP row starts another tile
-          }
+          up = C::template border<SL>(C::bits(H[R - 1]), first_lane_zero, first_lane_z);   // the zero border row H(0, .)
         }
         T diag = C::from_bits(up_prev);                            // H(i0-1, j-1)
         T north = C::from_bits(up);
         up_prev = up;
         T tpend = C::from_bits(0u);
         (void)tpend;
-        if constexpr (SEM == kSemF16 || sem_is_mirror(SEM) || SEM == kSemF32) {
+        if constexpr (C::kKeepsHg) {
           // H = max(clamp0(NW + s), W - g, N - g): the cell keeps H (next step's diagonal) and H - g (this row's west
           // term next step, the row below's north term now) — add, maximum3, add per cell; the running maximum takes
           // two cells per maximum3
@@ -670,7 +690,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
           for (int r = 0; r < R; ++r) {
             const T w = H[r];
             const T x = C::add(diag, C::from_bits(p[r]), a.clamp2);
-            const T h = cell_h<SEM>(x, Hg[r], ng);
+            const T h = C::cell_h(x, Hg[r], ng);
             if (MK == 1 || (k & (MK - 1)) == MK - 1) {             // (compile-time per unrolled step)
               if (r & 1) mx = C::vmax3(mx, tpend, h);
               else if (r + 1 < R) tpend = h;
@@ -686,10 +706,10 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
           const T w = H[r];
           const T x = C::add(diag, C::from_bits(p[r]), a.clamp2);
           const T t = C::vmax(w, north);
-          if (SEM == kSemU8H) {
+          if constexpr (C::kMax3) {
             // three-input maximum: two odd rows per running-maximum op (t covers cells (r, j-1) and (r-1, j))
             if ((r & 3) == 1) { if (r + 2 < R) tpend = t; else mx = C::vmax(mx, t); }
-            if ((r & 3) == 3) mx = cell_max3<SEM>(mx, tpend, t);
+            if ((r & 3) == 3) mx = C::vmax3(mx, tpend, t);
           } else if (r & 1) mx = C::vmax(mx, t);                   // covers (r, j-1) and (r-1, j)
           const T y = C::sub_gap(t, a.gap2);
           const T h = C::cell(x, y);

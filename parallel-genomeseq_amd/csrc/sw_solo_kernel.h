@@ -50,7 +50,7 @@ struct SoloArgs {
   int32_t m;
   const uint8_t *yref;             // first byte of the resident reference (ranges index it)
   int64_t sub_len;                 // granularity of the key's tag
-  int32_t keykind;                 // 2: float16 bits of H / 2048; 4: float32 bits of H * 2^-fshift
+  int32_t keykind;                 // host_score.h KeyKind: 2 (kKeyF16) float16 bits of H / 2048; 4 (kKeyF32Scaled) float32 bits of H * 2^-fshift
   int32_t fshift;
   float mg_smax, mg_g;             // margins (host_common.h Margin): gap columns per row <= mg_smax / mg_g
   int64_t warm;                    // the bucket's general margin
@@ -91,8 +91,8 @@ __global__ __launch_bounds__(64) void sw_solo_kernel(const SoloArgs a) {
   float score;
   {
     const uint32_t hi = (uint32_t)(key >> 32);
-    if (a.keykind == 2) score = (float)__builtin_bit_cast(_Float16, (unsigned short)hi) * 2048.0f;
-    else score = ldexpf(__uint_as_float(hi), a.fshift);
+    if (a.keykind == 2) score = (float)__builtin_bit_cast(_Float16, (unsigned short)hi) * 2048.0f;   // KeyKind kKeyF16
+    else score = ldexpf(__uint_as_float(hi), a.fshift);                                             // ... kKeyF32Scaled
   }
   if (!(score > 0.0f)) {                                // all-zero matrix: the defined no-match result
     if (c == 0 && l == 0) {
