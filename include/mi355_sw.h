@@ -179,6 +179,49 @@ int mi355_sw_best_range(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts,
 int mi355_sw_align_scored_range(mi355_sw_ctx *ctx, size_t range_index, const mi355_sw_params *params, int flags,
                                 mi355_sw_result *outs);
 
+/* ---- affine gaps: score and end cell --------------------------------------------------------------------------------
+ * A gap of k consecutive columns (or rows) costs gap_open + (k - 1) * gap_extend.  With s = f(x[i], y[j]) (identity or
+ * table, exactly as mi355_sw_params):
+ *
+ *   E(i,j) = max(E(i,j-1) - gap_extend, H(i,j-1) - gap_open)
+ *   F(i,j) = max(F(i-1,j) - gap_extend, H(i-1,j) - gap_open)
+ *   H(i,j) = max(0, H(i-1,j-1) + s, E(i,j), F(i,j))           H = 0 on the borders; E, F = -infinity there
+ *
+ * Score = max H.  End cell = the first maximum in column-major order (smallest column of y, then smallest row of x),
+ * 1-based: the float engine's rule (similaritymatrix.cpp:21-28).  An all-zero matrix gives score 0 and end 0 / 0.  With
+ * gap_open == gap_extend == g this is the linear recurrence of MI355_SW_F32, and score, end_x and end_y equal that
+ * engine's bit for bit.  No traceback (pos, consensus) under affine gaps yet.
+ *
+ * MI355_SW_EINVAL: a non-finite value, gap_extend <= 0, gap_open < gap_extend.
+ * MI355_SW_ENOTSUP (the message names the bound that was crossed) outside what the kernels compute exactly; a wrong
+ * number never comes back.  Always computed: integer-valued scores (match / mismatch, or the table's entries for any
+ * query byte against the reference's letters, and both gap costs) with smax * (longest query + 1) <= 2040 and
+ * gap_open <= 2040 (smax: the greatest substitution score), queries of 1..512 rows, any reference length, while the
+ * query profile fits LDS (53 reference letters at 512 rows, more for shorter queries).  Beyond that, integer scores are
+ * still computed wherever a (query, reference or range) problem has at most 2^26 cells; everything else is refused.
+ * Option no_affine_sweep (A/B, tests): every problem on the exact kernel, refused above 2^26 cells per problem.
+ * mi355_sw_last_path: "affine[cell=f16,SL=..,R=..]" when the sweep kernel ran, "affine_exact" when the exact kernel ran.
+ * mi355_sw_last_timings: [0] sweep kernel(s), [1] exact kernel (whole problems and end-cell windows), [3] whole call,
+ * [4] sweep launches, [5] cells swept. */
+typedef struct {
+  const float *lut;        /* as mi355_sw_params.lut */
+  float match, mismatch;   /* used when lut == NULL */
+  float gap_open;          /* cost of the first column (row) of a gap */
+  float gap_extend;        /* cost of every further one; 0 < gap_extend <= gap_open */
+} mi355_sw_affine_params;
+void mi355_sw_default_affine_params(mi355_sw_affine_params *p); /* 3 / -3 / open 5 / extend 1, no table */
+
+/* One alignment of x (rows) against y (columns); y stays resident as for mi355_sw_align. */
+int mi355_sw_affine_align(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, size_t ny,
+                          const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y);
+/* Every query of mi355_sw_batch_upload[_packed] against the reference of mi355_sw_set_reference: arrays of n_queries. */
+int mi355_sw_affine_batch_run(mi355_sw_ctx *ctx, const mi355_sw_affine_params *params,
+                              float *score, int64_t *end_x, int64_t *end_y);
+/* The affine counterpart of mi355_sw_score_ranges: maxima[k * n_queries + q], each range an independent problem with a
+ * zero left border. */
+int mi355_sw_affine_score_ranges(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,
+                                 const mi355_sw_affine_params *params, float *maxima);
+
 /* Host-only helper: piece ranges [left,right). Returns MI355_SW_ERANGE where the reference asserts. */
 int mi355_sw_make_string_range(int npiece, int64_t shortlen, int64_t longlen, float overlap_ratio,
                                int64_t *lefts, int64_t *rights);

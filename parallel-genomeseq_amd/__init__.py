@@ -6,6 +6,6 @@ include/mi355_sw.h).  Importing this package does not need a GPU; running an ali
 fails loudly without one — there is no CPU fallback."""
 from . import synth  # noqa: F401
 from . import capi  # noqa: F401
-from .aligner import (LocalAligner, OMPParallelLocalAligner, ParallelLocalAligner, SWAligner,  # noqa: F401
+from .aligner import (AffineSWAligner, LocalAligner, OMPParallelLocalAligner, ParallelLocalAligner, SWAligner,  # noqa: F401
                       Similarity_Matrix, Similarity_Matrix_Skewed, default_context)
 from .capi import F32, U8SAT, Context, MI355Error, MultiContext  # noqa: F401

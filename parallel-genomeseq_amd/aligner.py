@@ -95,6 +95,36 @@ class SWAligner(LocalAligner):
                                       lut=self._lut)
 
 
+class AffineSWAligner:
+    """Score and end cell under affine gaps (mi355_sw_affine_align; no counterpart in the reference, whose gap is linear): a gap
+    of k letters costs gap_open + (k - 1) * gap_extend.  `scoring` as for SWAligner.  No traceback yet: no getPos / consensus."""
+
+    def __init__(self, first_sequence, second_sequence, scoring=None, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0,
+                 context=None):
+        self.sequence_x, self.sequence_y = first_sequence, second_sequence
+        self.match, self.mismatch = float(match), float(mismatch)
+        self.gap_open, self.gap_extend = float(gap_open), float(gap_extend)
+        self._lut = None
+        if scoring is not None:
+            self._lut = _lut_from_function(scoring) if callable(scoring) else np.asarray(scoring, dtype=np.float32)
+        self._ctx = context
+        self.max_score, self._end = -1.0, (0, 0)
+
+    def calculateScore(self):
+        ctx = self._ctx if self._ctx is not None else default_context()
+        r = ctx.affine_align(self.sequence_x, self.sequence_y, match=self.match, mismatch=self.mismatch,
+                             gap_open=self.gap_open, gap_extend=self.gap_extend, lut=self._lut)
+        self.max_score, self._end = r["score"], (r["end_x"], r["end_y"])
+        return self.max_score
+
+    def getScore(self): return self.max_score
+
+    def getEnd(self):
+        """(row of first_sequence, column of second_sequence) of the first maximum in column-major order, 1-based; (0, 0) when
+        the score is 0."""
+        return self._end
+
+
 class ParallelLocalAligner:
     """localaligner.h:19-28"""
 

@@ -22,6 +22,7 @@ EXPORTS = [
     "mi355_sw_multi_rccl_version", "mi355_sw_multi_align_split", "mi355_sw_multi_set_reference",
     "mi355_sw_multi_align_batch", "mi355_sw_multi_last_timings",
     "mi355_sw_set_option", "mi355_sw_option_names", "mi355_sw_multi_set_option", "mi355_sw_last_counters", "mi355_sw_last_counter", "mi355_sw_batch_upload_packed", "mi355_sw_best_range", "mi355_sw_last_path",
+    "mi355_sw_default_affine_params", "mi355_sw_affine_align", "mi355_sw_affine_batch_run", "mi355_sw_affine_score_ranges",
 ]
 MULTI_RCCL = 1
 
@@ -29,6 +30,11 @@ MULTI_RCCL = 1
 class Params(C.Structure):
     _fields_ = [("lut", C.POINTER(C.c_float)), ("match", C.c_float), ("mismatch", C.c_float),
                 ("gap", C.c_float), ("semantics", C.c_int)]
+
+
+class AffineParams(C.Structure):
+    _fields_ = [("lut", C.POINTER(C.c_float)), ("match", C.c_float), ("mismatch", C.c_float),
+                ("gap_open", C.c_float), ("gap_extend", C.c_float)]
 
 
 class Result(C.Structure):
@@ -94,6 +100,16 @@ def make_params(semantics=F32, match=3.0, mismatch=-3.0, gap=2.0, lut=None):
         keep = np.ascontiguousarray(lut, dtype=np.float32).reshape(65536)
         p.lut = keep.ctypes.data_as(C.POINTER(C.c_float))
     p.match, p.mismatch, p.gap, p.semantics = match, mismatch, gap, semantics
+    return p, keep
+
+
+def make_affine_params(match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
+    p = AffineParams()
+    keep = None
+    if lut is not None:
+        keep = np.ascontiguousarray(lut, dtype=np.float32).reshape(65536)
+        p.lut = keep.ctypes.data_as(C.POINTER(C.c_float))
+    p.match, p.mismatch, p.gap_open, p.gap_extend = match, mismatch, gap_open, gap_extend
     return p, keep
 
 
@@ -294,6 +310,38 @@ class Context:
         self._chk(self._L.mi355_sw_align_scored_range(self._ctx, C.c_size_t(k), C.byref(p), C.c_int(flags), res))
         out = _take(res[query])
         self._L.mi355_sw_free_results(res, C.c_size_t(n))
+        return out
+
+    # -- affine gaps: score and end cell (mi355_sw_affine_*) -------------------------------------
+    def affine_align(self, x, y, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
+        """One alignment under affine gaps: dict(score, end_x, end_y), the end cell 1-based, 0 / 0 when the score is 0."""
+        x, y = _bytes(x), _bytes(y)
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        score, ex, ey = C.c_float(), C.c_int64(), C.c_int64()
+        self._chk(self._L.mi355_sw_affine_align(self._ctx, x, C.c_size_t(len(x)), y, C.c_size_t(len(y)), C.byref(p),
+                                                C.byref(score), C.byref(ex), C.byref(ey)))
+        return dict(score=float(score.value), end_x=int(ex.value), end_y=int(ey.value))
+
+    def affine_batch_run(self, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
+        """The resident batch against the resident reference under affine gaps: dict of arrays score, end_x, end_y."""
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        n = self._nbatch
+        score = np.zeros(n, dtype=np.float32)
+        ex = np.zeros(n, dtype=np.int64)
+        ey = np.zeros(n, dtype=np.int64)
+        self._chk(self._L.mi355_sw_affine_batch_run(self._ctx, C.byref(p), score.ctypes.data_as(C.POINTER(C.c_float)),
+                                                    ex.ctypes.data_as(C.POINTER(C.c_int64)), ey.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(score=score, end_x=ex, end_y=ey)
+
+    def affine_score_ranges(self, ranges, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
+        """Per-range affine maxima of every resident query: array [len(ranges), n_queries]."""
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        n = len(ranges)
+        lefts = (C.c_int64 * max(1, n))(*[r[0] for r in ranges])
+        rights = (C.c_int64 * max(1, n))(*[r[1] for r in ranges])
+        out = np.zeros((n, self._nbatch), dtype=np.float32)
+        self._chk(self._L.mi355_sw_affine_score_ranges(self._ctx, C.c_size_t(n), lefts, rights, C.byref(p),
+                                                       out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
     def align_batch(self, xs, y=None, **kw):

@@ -1,0 +1,339 @@
+// host_affine.h — affine-gap score and end cell: parameter checks, the sw_affine_kernel sweep and the sw_affine_exact_kernel
+// behind it (sw_affine_kernel.h).
+// Part of the single translation unit mi355_sw.hip (included there, in order; not a standalone header).
+namespace {
+
+constexpr int64_t kAffineSweepMinCols = 1024;        // shorter references (ranges) are whole problems of the exact kernel
+constexpr double kAffineExactCellsMax = 67108864.0;  // 2^26 cells: the largest whole problem one wavefront of the exact kernel takes
+constexpr int kAffineF16Bound = 2040;                // smax * (rows + 1) and gap_open of the sweep's float16 cells (H / 2048)
+
+// The scoring of one affine call over the reference's letters (any query byte against them, as plan_table)
+struct AffineTable {
+  std::vector<uint16_t> htab;     // [256][ncodes] float16 bits of s / 2048, scores below -2048 raised to it (the clamped
+                                  // diagonal term is 0 either way: H <= 2040); pad column last
+  int smax = 0, open = 0, ext = 0;
+};
+
+int affine_check(mi355_sw_ctx *ctx, const mi355_sw_affine_params *p) {
+  if (!ctx) return MI355_SW_EINVAL;
+  if (!p) return fail(ctx, MI355_SW_EINVAL, "params is NULL");
+  if (!std::isfinite(p->gap_open) || !std::isfinite(p->gap_extend) || (!p->lut && (!std::isfinite(p->match) || !std::isfinite(p->mismatch))))
+    return fail(ctx, MI355_SW_EINVAL, "affine scoring: a value is not finite");
+  if (!(p->gap_extend > 0.0f)) return fail(ctx, MI355_SW_EINVAL, "affine scoring: gap_extend must be positive");
+  if (p->gap_open < p->gap_extend) return fail(ctx, MI355_SW_EINVAL, "affine scoring: gap_open must be at least gap_extend");
+  return 0;
+}
+
+int affine_table(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_affine_params &p, AffineTable &t) {
+  const int nc = ref.ncodes;
+  if (p.gap_open != std::floor(p.gap_open) || p.gap_extend != std::floor(p.gap_extend))
+    return fail(ctx, MI355_SW_ENOTSUP, "affine scoring: gap costs must be integers");
+  if (p.gap_open > 16777216.0f) return fail(ctx, MI355_SW_ENOTSUP, "affine scoring: gap_open beyond 2^24");
+  t.open = (int)p.gap_open; t.ext = (int)p.gap_extend;
+  t.htab.assign((size_t)256 * nc, half_bits(-8.0f));
+  float smax = 0;
+  for (int a = 0; a < 256; ++a)
+    for (int c = 0; c < nc - 1; ++c) {
+      const float s = p.lut ? p.lut[(size_t)a * 256 + ref.byte_of[c]] : ((uint8_t)a == ref.byte_of[c] ? p.match : p.mismatch);
+      if (!std::isfinite(s)) return fail(ctx, MI355_SW_EINVAL, "affine scoring: a table entry is not finite");
+      if (s != std::floor(s)) return fail(ctx, MI355_SW_ENOTSUP, "affine scoring: substitution scores must be integers");
+      if (std::fabs(s) > 1.0e6f) return fail(ctx, MI355_SW_ENOTSUP, "affine scoring: substitution score beyond +-10^6");
+      smax = std::max(smax, s);
+      t.htab[(size_t)a * nc + c] = half_bits(std::min(2048.0f, std::max(-2048.0f, s)) / kF16Scale);
+    }
+  t.smax = (int)smax;
+  return 0;
+}
+
+typedef void (*AffineKernel)(const ScoreArgs, const uint32_t, const uint32_t);
+template <size_t... I> AffineKernel affine_kernel16(int R, std::index_sequence<I...>) {
+  AffineKernel k = nullptr;
+  ((kR16[I] == R ? (void)(k = &sw_affine_kernel<kR16[I], 16>) : (void)0), ...);
+  return k;
+}
+template <size_t... I> AffineKernel affine_kernel8(int R, std::index_sequence<I...>) {
+  AffineKernel k = nullptr;
+  ((kR8[I] == R ? (void)(k = &sw_affine_kernel<kR8[I], 8>) : (void)0), ...);
+  return k;
+}
+// the instance for a shape of pick_shape: every R of kR16 on 16 lanes, every R of kR8 on 8
+AffineKernel affine_kernel(int SL, int R) {
+  return SL == 8 ? affine_kernel8(R, std::make_index_sequence<std::size(kR8)>{}) : affine_kernel16(R, std::make_index_sequence<std::size(kR16)>{});
+}
+
+size_t affine_exact_lds(int m) { return (size_t)7 * (m + 2) * 4 + (size_t)m + 16; }
+
+// Runs jobs[lo, hi) on sw_affine_exact_kernel in one launch (ExactJob: q, ylo, nw, col_offset, own_lo, target -> best, ci, cj).
+int run_affine_exact(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const mi355_sw_affine_params &p,
+                     std::vector<ExactJob> &jobs, size_t lo, size_t hi) {
+  const size_t n = hi - lo;
+  if (n == 0) return 0;
+  size_t lds = 0;
+  for (size_t k = lo; k < hi; ++k) lds = std::max(lds, affine_exact_lds(q.len[jobs[k].q]));
+  if (lds > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine: query longer than the exact kernel's LDS diagonals hold");
+  path_note(ctx, "affine_exact");
+  if (ctx->probs.ensure(n * sizeof(ExactProblem)) || ctx->outs_f.ensure(n * 4) || ctx->outs_i.ensure(n * 16))
+    return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(exact scratch) failed");
+  std::vector<ExactProblem> pr(n);
+  for (size_t k = 0; k < n; ++k) {
+    const ExactJob &j = jobs[lo + k];
+    ExactProblem &e = pr[k];
+    e.x = q.bytes.as<uint8_t>() + q.off[j.q];
+    e.y = ref.bytes.as<uint8_t>() + j.ylo;
+    e.m = q.len[j.q];
+    e.nw = j.nw;
+    e.col_offset = j.col_offset;
+    e.full_n = j.full_n;
+    e.own_lo = j.own_lo;
+    e.square_quirk = 0;
+    e.target = j.target;
+    e.dirs = nullptr;
+    e.hout = nullptr;
+    e.best = ctx->outs_f.as<float>() + k;
+    e.cell = ctx->outs_i.as<int64_t>() + 2 * k;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactProblem), hipMemcpyHostToDevice, ctx->stream));
+  AffineScoring sc;
+  sc.lut = nullptr;
+  if (p.lut) {
+    if (ctx->lut.ensure(65536 * 4)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(scoring table) failed");
+    HIPCHK(ctx, hipMemcpyAsync(ctx->lut.p, p.lut, 65536 * 4, hipMemcpyHostToDevice, ctx->stream));
+    sc.lut = ctx->lut.as<float>();
+  }
+  sc.match = p.match; sc.mismatch = p.mismatch; sc.gap_open = p.gap_open; sc.gap_extend = p.gap_extend;
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sw_affine_exact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(sw_affine_exact_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactProblem>(), sc);
+  HIPCHK(ctx, hipGetLastError());
+  std::vector<float> bf(n);
+  std::vector<int64_t> ci(2 * n);
+  HIPCHK(ctx, hipMemcpyAsync(bf.data(), ctx->outs_f.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ci.data(), ctx->outs_i.p, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t k = 0; k < n; ++k) { jobs[lo + k].best = bf[k]; jobs[lo + k].ci = ci[2 * k]; jobs[lo + k].cj = ci[2 * k + 1]; }
+  return 0;
+}
+
+// One bucket of the batch on sw_affine_kernel over `ranges` (device copies in ctx->ranges, keys in ctx->keys).
+int affine_sweep_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const std::vector<Range> &ranges,
+                        const AffineTable &t, Bucket &b) {
+  const size_t nr = ranges.size();
+  int64_t maxlen = 0;
+  double range_cols = 0;
+  for (auto &r : ranges) { maxlen = std::max(maxlen, r.hi - r.lo); range_cols += (double)(r.hi - r.lo); }
+  const size_t npairs = ((size_t)b.count + 1) / 2;
+  b.sub_len = score_sub_len(MI355_SW_F32, b);
+  b.chunk_len = pick_chunk_len(maxlen, npairs * nr, b.warm, b.SL, false, b.maxlen, b.sub_len, b.sub_len);
+  if (b.sub_len > b.chunk_len || b.chunk_len % b.sub_len != 0) b.sub_len = b.chunk_len;
+  const int64_t cpr = (maxlen + b.chunk_len - 1) / b.chunk_len;
+  const int nslot = 256 / b.SL;
+  const int64_t cgroups = (cpr + nslot - 1) / nslot;
+  if ((double)npairs * (double)cgroups > 2.0e9) return fail(ctx, MI355_SW_ENOTSUP, "affine: grid too large");
+  AffineKernel kern = affine_kernel(b.SL, b.R);
+  if (!kern) return fail(ctx, MI355_SW_ENOTSUP, "affine: no sweep kernel instance for this tile shape");
+
+  ScoreArgs a;
+  memset(&a, 0, sizeof a);
+  a.refcodes = ref.codes.as<uint8_t>();
+  a.ref_len = (int64_t)ref.n;
+  a.range_lo = ctx->ranges.as<int64_t>();
+  a.range_hi = ctx->ranges.as<int64_t>() + nr;
+  a.chunk_len = b.chunk_len;
+  a.sub_len = b.sub_len;
+  a.warm = (cpr == 1) ? 0 : b.warm;              // a single tile per range starts at the range's own border
+  a.chunks_per_range = (int)cpr;
+  a.qbytes = q.bytes.as<uint8_t>();
+  a.qoff = q.offs.as<int64_t>();
+  a.qlen = q.lens.as<int32_t>();
+  a.qsel = q.sel.as<int32_t>();
+  a.nq = (int)q.nq;
+  a.stab = ctx->atab.p;
+  a.ncodes = ref.ncodes;
+  a.keys = ctx->keys.as<unsigned long long>();
+  const uint32_t nopen2 = (uint32_t)half_bits(-(float)t.open / kF16Scale) * 0x00010001u;
+  const uint32_t next2 = (uint32_t)half_bits(-(float)t.ext / kF16Scale) * 0x00010001u;
+  const size_t shmem = profile_lds_bytes(ref.ncodes, b.R, b.SL) + (size_t)nslot * codebuf_bytes(b.SL);
+  if (shmem > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  // keep single launches to a few seconds: split the bucket's pairs over several launches
+  const double cells_per_pair = 2.0 * std::max(1, b.maxlen) * std::max(1.0, range_cols);
+  const size_t pairs_per_launch = (size_t)std::max(1.0, std::min((double)npairs, 2.0e13 / cells_per_pair));
+  for (size_t p0 = 0; p0 < npairs; p0 += pairs_per_launch) {
+    const size_t pn = std::min(pairs_per_launch, npairs - p0);
+    a.qfirst = b.first + (int)(p0 * 2);
+    a.qcount = std::min(b.count - (int)(p0 * 2), (int)(pn * 2));
+    hipLaunchKernelGGL(kern, dim3((unsigned)(pn * cgroups), (unsigned)nr), dim3(256), shmem, ctx->stream, a, nopen2, next2);
+    HIPCHK(ctx, hipGetLastError());
+    ctx->timings[4] += 1;
+  }
+  path_note(ctx, "affine[cell=f16,SL=%d,R=%d]", b.SL, b.R);
+  double cells = 0;
+  for (int k = 0; k < b.count; ++k) cells += (double)q.len[q.order[b.first + k]] * range_cols;
+  ctx->timings[5] += cells;
+  if (cells > ctx->last_kernel.cells) {
+    mi355_sw_kernel_info &ki = ctx->last_kernel;
+    ki.cell = MI355_SW_CELL_F16; ki.lanes = b.SL; ki.rows_per_lane = b.R; ki.strips = 0; ki.twin = 0;
+    ki.chunk_len = b.chunk_len; ki.sub_len = b.sub_len; ki.warm = a.warm; ki.cells = cells;
+    // as valu_ops_per_cell (host_score.h): per step seven ops per row and a maximum3 per two rows, the overhead of the linear
+    // sweep (DPP move, profile address, code extract; border mask on 8-lane tiles) and F's DPP move (8 lanes: and its and-or),
+    // over the two cells of a register
+    ki.valu_ops_per_cell = (7.0 * b.R + (b.R + 1) / 2 + (b.SL == 8 ? 6.0 : 4.0)) / (2.0 * b.R);
+    std::snprintf(ki.name, sizeof ki.name, "sw_affine_kernel<R=%d, f16x2, SL=%d>", b.R, b.SL);
+  }
+  return 0;
+}
+
+// Affine score (and, for one range, end cell) of every query of `q` over each range of `ref`, each range an independent
+// problem.  maxima: [nranges][nq].  ends (may be null; one range only): [nq][2] = row, column relative to the range start.
+int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const std::vector<Range> &ranges,
+               const mi355_sw_affine_params &p, float *maxima, int64_t *ends) {
+  const size_t nq = q.nq, nr = ranges.size();
+  if (nq == 0 || nr == 0) return 0;
+  for (size_t k = 0; k < nq * nr; ++k) maxima[k] = 0.0f;
+  if (ends) for (size_t k = 0; k < 2 * nq; ++k) ends[k] = 0;
+  AffineTable t;
+  int rc = affine_table(ctx, ref, p, t);
+  if (rc) return rc;
+  if (t.smax <= 0) return 0;                                       // no positive cell: every maximum is 0
+  HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+  const Margin mg = make_margin((double)t.smax, (double)t.ext, true, 0.0);   // lemma L15: L1-L4 with g := gap_extend
+
+  // ---- which (query, range) the sweep takes -----------------------------------------------------------------------------
+  std::vector<char> rsweep(nr, 0), qfast(nq, 0);
+  std::vector<size_t> sweep_ranges;
+  for (size_t r = 0; r < nr; ++r)
+    if (!opt().no_affine_sweep && ranges[r].hi - ranges[r].lo >= kAffineSweepMinCols) { rsweep[r] = 1; sweep_ranges.push_back(r); }
+  std::vector<Bucket> buckets;
+  std::string why_slow;
+  if (!sweep_ranges.empty()) {
+    for (size_t pos = 0; pos < nq; ++pos) {
+      const int len = q.len[q.order[pos]];
+      if (len < 1) continue;
+      if (len > kMaxRowsFast) { why_slow = "query longer than 512 rows"; break; }   // (sorted by length: all further ones too)
+      int SL = 16, R = 2;
+      pick_shape(len, SL, R);
+      if (buckets.empty() || buckets.back().R != R || buckets.back().SL != SL) {
+        Bucket b;
+        b.first = (int)pos; b.R = R; b.SL = SL; b.sem = kSemF16;
+        buckets.push_back(b);
+      }
+      buckets.back().count++;
+      buckets.back().maxlen = std::max(buckets.back().maxlen, len);
+    }
+    for (Bucket &b : buckets) {
+      b.warm = std::min(kColsMax, (mg.cols(b.maxlen) + 63) / 64 * 64);
+      char msg[160];
+      msg[0] = 0;
+      if ((int64_t)t.smax * (b.maxlen + 1) > kAffineF16Bound)
+        std::snprintf(msg, sizeof msg, "smax * (rows + 1) = %lld exceeds %d", (long long)t.smax * (b.maxlen + 1), kAffineF16Bound);
+      else if (t.open > kAffineF16Bound) std::snprintf(msg, sizeof msg, "gap_open = %d exceeds %d", t.open, kAffineF16Bound);
+      else if (profile_lds_bytes(ref.ncodes, b.R, b.SL) > kProfileLdsMax || ref.ncodes > 256)
+        std::snprintf(msg, sizeof msg, "%d reference letters: the query profile of %d rows per lane does not fit LDS", ref.ncodes - 1, b.R);
+      b.fast = msg[0] == 0;
+      if (!b.fast) why_slow = msg;
+      if (b.fast) for (int k = 0; k < b.count; ++k) qfast[q.order[b.first + k]] = 1;
+    }
+  }
+
+  // ---- whole problems of the exact kernel: everything the sweep does not take ---------------------------------------------
+  std::vector<ExactJob> jobs;
+  for (size_t r = 0; r < nr; ++r) {
+    const int64_t n = ranges[r].hi - ranges[r].lo;
+    for (size_t k = 0; k < nq; ++k) {
+      if ((rsweep[r] && qfast[k]) || q.len[k] < 1 || n < 1) continue;
+      if ((double)q.len[k] * (double)n > kAffineExactCellsMax || (double)t.smax * ((double)q.len[k] + 1.0) >= 16777216.0) {
+        if (opt().no_affine_sweep) return fail(ctx, MI355_SW_ENOTSUP, "affine, option no_affine_sweep: a problem of more than 2^26 cells");
+        return fail(ctx, MI355_SW_ENOTSUP, "affine: " + (why_slow.empty() ? std::string("problem outside the sweep") : why_slow) +
+                                               " (beyond the sweep's float16 cells), and more than 2^26 cells for the exact kernel");
+      }
+      ExactJob j;
+      j.q = (int)k; j.ylo = ranges[r].lo; j.nw = (int32_t)n; j.col_offset = 0; j.full_n = n; j.own_lo = 1; j.quirk = 0;
+      j.target = -1.0f; j.want_dirs = false;
+      j.dirs_off = r;                                             // (no decisions here: the job's range)
+      jobs.push_back(j);
+    }
+  }
+  const size_t nwhole = jobs.size();
+
+  // ---- the sweep, 32768 ranges per launch group ------------------------------------------------------------------------------
+  bool any_fast = false;
+  for (const Bucket &b : buckets) any_fast |= b.fast;
+  if (any_fast) {
+    if (ctx->atab.ensure(t.htab.size() * 2 + 16)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine score table) failed");
+    ctx->h_atab = t.htab;                                          // (outlives the asynchronous copy)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->atab.p, ctx->h_atab.data(), ctx->h_atab.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+  }
+  for (size_t g0 = 0; any_fast && g0 < sweep_ranges.size(); g0 += 32768) {
+    const size_t g1 = std::min(sweep_ranges.size(), g0 + 32768), ng = g1 - g0;
+    std::vector<Range> sub(ng);
+    std::vector<int64_t> &rl = ctx->h_ranges;
+    rl.resize(2 * ng);
+    for (size_t k = 0; k < ng; ++k) { sub[k] = ranges[sweep_ranges[g0 + k]]; rl[k] = sub[k].lo; rl[ng + k] = sub[k].hi; }
+    if (ctx->ranges.ensure(rl.size() * 8) || ctx->keys.ensure(nq * ng * 8)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(score scratch) failed");
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ranges.p, rl.data(), rl.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->keys.p, 0, nq * ng * 8, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    for (Bucket &b : buckets) {
+      if (!b.fast) continue;
+      rc = affine_sweep_launch(ctx, ref, q, sub, t, b);
+      if (rc) return rc;
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    std::vector<unsigned long long> keys(nq * ng);
+    HIPCHK(ctx, hipMemcpyAsync(keys.data(), ctx->keys.p, keys.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->timings[0] += elapsed_us(ctx, ctx->ev[0], ctx->ev[1]);
+    for (size_t k = 0; k < ng; ++k)
+      for (size_t i = 0; i < nq; ++i)
+        if (qfast[i]) maxima[sweep_ranges[g0 + k] * nq + i] = key_score(kKeyF16, (uint32_t)(keys[k * nq + i] >> 32), 0);
+    if (!ends) continue;
+    // (one range.)  The end cell: the first sub-chunk that reached the maximum holds the first maximum in column-major order —
+    // or the up to SL - 1 trailing columns of the sub-chunk before it, reported with it — so one window per query, as the
+    // linear float engine's locate_fast.  Only cells equal to the maximum compete: lemma L3 with g := gap_extend.
+    const int64_t n = ranges[0].hi - ranges[0].lo;
+    for (const Bucket &b : buckets) {
+      if (!b.fast) continue;
+      for (int k = 0; k < b.count; ++k) {
+        const int id = q.order[b.first + k];
+        const float score = maxima[id];
+        if (!(score > 0)) continue;
+        const int64_t first = (int64_t)(0xFFFFFFFFull - (keys[id] & 0xFFFFFFFFull));
+        const double spare = std::max(0.0, mg.smax * (double)q.len[id] - (double)score);
+        const int64_t warm = std::min<int64_t>(b.warm, clamp_cols((double)q.len[id] + std::ceil(spare / mg.g) + 2.0));
+        const int64_t own_lo = std::max<int64_t>(0, first * b.sub_len - 63), own_hi = std::min((first + 1) * b.sub_len, n);
+        const int64_t wl = std::max<int64_t>(0, own_lo - warm);
+        ExactJob j;
+        j.q = id; j.ylo = ranges[0].lo + wl; j.nw = (int32_t)(own_hi - wl); j.col_offset = wl; j.full_n = n;
+        j.own_lo = (int32_t)(own_lo - wl + 1); j.quirk = 0; j.target = score; j.want_dirs = false;
+        j.dirs_off = 0;
+        jobs.push_back(j);
+      }
+    }
+  }
+
+  // ---- exact kernel: whole problems and end-cell windows ----------------------------------------------------------------------
+  if (!jobs.empty()) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    for (size_t lo = 0; lo < jobs.size(); lo += 65536) {
+      rc = run_affine_exact(ctx, ref, q, p, jobs, lo, std::min(jobs.size(), lo + 65536));
+      if (rc) return rc;
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+    for (size_t k = 0; k < jobs.size(); ++k) {
+      const ExactJob &j = jobs[k];
+      if (k < nwhole) {
+        maxima[j.dirs_off * nq + (size_t)j.q] = j.best > 0 ? j.best : 0.0f;
+        if (ends && j.best > 0) { ends[2 * j.q] = j.ci; ends[2 * j.q + 1] = j.cj; }
+      } else {
+        if (j.best != j.target) return fail(ctx, MI355_SW_ENODEV, "internal: maximum of the affine sweep not found again by the exact kernel");
+        ends[2 * j.q] = j.ci; ends[2 * j.q + 1] = j.cj;
+      }
+    }
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+  ctx->timings[3] += elapsed_us(ctx, ctx->ev[4], ctx->ev[5]);
+  return 0;
+}
+
+}  // namespace

@@ -8,6 +8,7 @@
 //   3. traceback       sw_wave_kernel / sw_strip_kernel (dirs) — window left of the argmax -> greedy decisions,
 //                      sw_wave_walk_kernel — the walk itself (smithwaterman.cpp:40-78)            host_wave.h
 //   (sw_exact_kernel + sw_walk_kernel, host_exact.h: table scoring on short queries, whole uint8 problems)
+//   affine gaps (score and end cell): sw_affine_kernel sweep + sw_affine_exact_kernel                 host_affine.h
 // Problems the score kernel does not cover (see bucket_fast_ok) run 2+3 on the whole matrix.
 // The host code is one translation unit; the fragments below are included in order.
 #include "../../include/mi355_sw.h"
@@ -40,6 +41,7 @@
 #include "sw_batch_kernels.h"
 #include "sw_solo_kernel.h"
 #include "sw_long_kernel.h"
+#include "sw_affine_kernel.h"
 
 using namespace mi355sw;
 
@@ -51,6 +53,7 @@ using namespace mi355sw;
 #include "host_saved.h"
 #include "host_pipeline.h"
 #include "host_solo.h"
+#include "host_affine.h"
 #include "host_multi.h"   // mi355_sw_multi_*: its own extern "C" block
 
 // ================================= C-ABI ======================================================
@@ -95,7 +98,7 @@ void mi355_sw_destroy(mi355_sw_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   DevBuf *bufs[] = {&c->qcnt, &c->sel2, &c->gcnt, &c->wlut, &c->ref.bytes, &c->ref.codes, &c->batch.bytes, &c->batch.lens, &c->keys, &c->ranges, &c->stab,
-                    &c->batch.offs, &c->batch.sel, &c->colsave, &c->rowsave, &c->pieces, &c->ftab, &c->ftab_s, &c->htab, &c->htab8, &c->soloblk, &c->flags, &c->submax, &c->lut, &c->probs, &c->dirs, &c->outs_f, &c->outs_i, &c->cons, &c->walkp, &c->hmat, &c->brow, &c->wprobs, &c->scan, &c->batch.cum, &c->ckpt, &c->first};
+                    &c->batch.offs, &c->batch.sel, &c->colsave, &c->rowsave, &c->pieces, &c->ftab, &c->ftab_s, &c->htab, &c->htab8, &c->soloblk, &c->flags, &c->submax, &c->lut, &c->probs, &c->dirs, &c->outs_f, &c->outs_i, &c->cons, &c->walkp, &c->hmat, &c->brow, &c->wprobs, &c->scan, &c->batch.cum, &c->ckpt, &c->first, &c->recs, &c->atab};
   for (DevBuf *b : bufs) b->release();
   c->adhoc.release(); c->one.release();
   c->pin_probs.release(); c->pin_walk.release(); c->pin_out.release(); c->pin_solo_up.release(); c->pin_solo_down.release();
@@ -359,6 +362,66 @@ int mi355_sw_score_ranges(mi355_sw_ctx *ctx, size_t nranges, const int64_t *left
   }
   (void)maxlen;
   return range_maxima(ctx, ctx->ref, q, ranges, *params, maxima);
+}
+
+void mi355_sw_default_affine_params(mi355_sw_affine_params *p) {
+  if (!p) return;
+  p->lut = nullptr; p->match = 3.0f; p->mismatch = -3.0f; p->gap_open = 5.0f; p->gap_extend = 1.0f;
+}
+
+int mi355_sw_affine_align(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, size_t ny,
+                          const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y) {
+  OptScope opt_scope_(ctx);
+  int rc = affine_check(ctx, params);
+  if (rc) return rc;
+  if (!score || !end_x || !end_y || (!x && nx) || (!y && ny)) return fail(ctx, MI355_SW_EINVAL, "null argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  reset_timings(ctx);
+  *score = 0.0f; *end_x = 0; *end_y = 0;
+  if (nx == 0 || ny == 0) return 0;
+  const RefData *ref = nullptr;
+  rc = adhoc_reference(ctx, y, ny, &ref);
+  if (!rc) rc = upload_queries(ctx, ctx->one, 1, &x, &nx);
+  int64_t end[2] = {0, 0};
+  if (!rc) rc = affine_run(ctx, *ref, ctx->one, std::vector<Range>{Range{0, (int64_t)ny}}, *params, score, end);
+  if (rc) return rc;
+  *end_x = end[0]; *end_y = end[1];
+  return 0;
+}
+
+int mi355_sw_affine_batch_run(mi355_sw_ctx *ctx, const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y) {
+  OptScope opt_scope_(ctx);
+  int rc = affine_check(ctx, params);
+  if (rc) return rc;
+  const size_t nq = ctx->batch.nq;
+  if (nq && (!score || !end_x || !end_y)) return fail(ctx, MI355_SW_EINVAL, "null argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  reset_timings(ctx);
+  if (nq == 0) return 0;
+  for (size_t k = 0; k < nq; ++k) { score[k] = 0.0f; end_x[k] = 0; end_y[k] = 0; }
+  if (ctx->ref.n == 0) return 0;
+  std::vector<int64_t> ends(2 * nq, 0);
+  rc = affine_run(ctx, ctx->ref, ctx->batch, std::vector<Range>{Range{0, (int64_t)ctx->ref.n}}, *params, score, ends.data());
+  if (rc) return rc;
+  for (size_t k = 0; k < nq; ++k) { end_x[k] = ends[2 * k]; end_y[k] = ends[2 * k + 1]; }
+  return 0;
+}
+
+int mi355_sw_affine_score_ranges(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,
+                                 const mi355_sw_affine_params *params, float *maxima) {
+  OptScope opt_scope_(ctx);
+  int rc = affine_check(ctx, params);
+  if (rc) return rc;
+  if (!lefts || !rights || !maxima) return fail(ctx, MI355_SW_EINVAL, "null argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  reset_timings(ctx);
+  if (ctx->batch.nq == 0 || nranges == 0) return 0;
+  std::vector<Range> ranges(nranges);
+  for (size_t k = 0; k < nranges; ++k) {
+    if (lefts[k] < 0 || rights[k] < lefts[k] || rights[k] > (int64_t)ctx->ref.n) return fail(ctx, MI355_SW_EINVAL, "range outside the resident reference");
+    ranges[k] = Range{lefts[k], rights[k]};
+  }
+  return affine_run(ctx, ctx->ref, ctx->batch, ranges, *params, maxima, nullptr);
 }
 
 int mi355_sw_best_range(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,

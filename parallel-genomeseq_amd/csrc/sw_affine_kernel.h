@@ -1,0 +1,300 @@
+// sw_affine_kernel.h — affine-gap (Gotoh) Smith-Waterman for gfx950 (MI355X), hand-written HIP: score and end cell.
+//
+//   E(i,j) = max(E(i,j-1) - e, H(i,j-1) - o)        a gap of k columns (rows) costs o + (k - 1) e, o >= e > 0
+//   F(i,j) = max(F(i-1,j) - e, H(i-1,j) - o)
+//   H(i,j) = max(0, H(i-1,j-1) + s, E(i,j), F(i,j))  H = 0 on the borders; E, F = -inf there
+//
+// Two kernels:
+//   * sw_affine_kernel<R, SL>: the anti-diagonal sweep, with the tile geometry of the two-query, one-strip instances of
+//     sw_score_kernel (sw_score_kernel.h): tile = query pair x chunk + warm-up columns, SL lanes x R rows, the LDS query
+//     profile read with ds_read_b128 at lane_stride, the code window refilled every 64 steps, per-sub-chunk maxima
+//     published as (max << 32 | ~sub-chunk) keys.  Cells are packed float16 holding H / 2048 (Cell<kSemF16>), both queries
+//     of a pair per register; per row the lane keeps H, E and Ho = H - o, and F runs down the lane's rows:
+//         x     = v_pk_add_f16 clamp(NW, s)                     the [0, 1] clamp is the zero floor
+//         E[r]  = pk_max(pk_add(E[r], -e), Ho[r])               Ho[r] still holds H(r, j-1) - o
+//         H     = v_pk_maximum3_f16(x, E[r], F)
+//         Ho[r] = pk_add(H, -o)
+//         F     = pk_max(pk_add(F, -e), Ho[r])                  F of the row below
+//     seven VOP3P ops per cell pair, and one maximum3 per two rows for the running maximum.  E and F never fall below -o
+//     (each is a maximum with some H - o >= -o), so every value is an integer multiple of 1/2048 within +-2048/2048: exact.
+//     Borders start at H = 0, E = F = -o, which gives the same cells as -inf.  Across lanes H and F each take one DPP
+//     row_shr:1 per step; the tile's first lane gets 0 and -o.
+//   * sw_affine_exact_kernel: float32 cells, one wavefront per (sub-)problem, three anti-diagonals of H and two each of E
+//     and F in LDS (as sw_exact_kernel keeps H); tracks the first maximum in column-major order (order_key<0>) among the
+//     window's own columns.  It finds the end cell inside the sub-chunk the sweep names, and computes whole problems that
+//     are too small for the sweep (or all of them under option no_affine_sweep).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sw_exact_kernel.h"
+#include "sw_score_kernel.h"
+
+namespace mi355sw {
+
+// legal instances: 8- or 16-lane tiles
+__host__ __device__ constexpr bool affine_instance_ok(int R, int SL) { return (SL == 8 || SL == 16) && R >= 1 && R <= 32; }
+
+// a: as for sw_score_kernel (stab = float16 bits of s / 2048, [256][ncodes], pad column last; gap2, clamp2, pubmax, flag_*,
+// submax_out, brow unused).  nopen2 / next2: float16 bits of -o / 2048 and -e / 2048 in both halves.
+template <int R, int SL>
+__global__ __launch_bounds__(256) void sw_affine_kernel(const ScoreArgs a, const uint32_t nopen2, const uint32_t next2) {
+  static_assert(affine_instance_ok(R, SL), "no such sw_affine_kernel instance");
+  typedef Cell<kSemF16> C;
+  typedef uint32_t T;
+  constexpr int LS = lane_stride(R);                               // dwords between the profile rows of adjacent lanes
+  constexpr int NQ4 = (R + 3) / 4;
+  constexpr int NSLOT = 256 / SL;                                  // tiles per workgroup
+  constexpr int CPL = kSeg / SL;                                   // reference codes fetched per lane per segment (4 or 8)
+  constexpr int PL = 16;                                           // lane positions of the profile
+  constexpr int HIST = hist_bytes(SL);
+  constexpr int CB = codebuf_bytes(SL);
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  uint32_t *prof = smem;                                           // [ncodes][PL lane positions][LS]
+  uint8_t *codebuf = reinterpret_cast<uint8_t *>(smem + a.ncodes * PL * LS);
+
+  const int tid = threadIdx.x;
+  const int ls = tid & (SL - 1);                                   // lane within the tile
+  const int slot = tid / SL;
+  const int cgroups = (a.chunks_per_range + NSLOT - 1) / NSLOT;
+  const int pair = blockIdx.x / cgroups;
+  const int cg = blockIdx.x - pair * cgroups;
+  const int range = blockIdx.y;
+  const bool hasB = (2 * pair + 1) < a.qcount;
+  const int qA = a.qsel[a.qfirst + 2 * pair];
+  const int qB = hasB ? a.qsel[a.qfirst + 2 * pair + 1] : qA;
+  const int mA = a.qlen[qA], mB = a.qlen[qB];
+
+  // ---- query profile of this workgroup's pair: rows 0 .. SL*R - 1, padding rows score -8 (the clamp's floor) ------------
+  {
+    const uint8_t *xA = a.qbytes + a.qoff[qA];
+    const uint8_t *xB = a.qbytes + a.qoff[qB];
+    const int16_t *st = static_cast<const int16_t *>(a.stab);
+    const int per_code = PL * R;
+    for (int e = tid; e < a.ncodes * per_code; e += 256) {
+      const int c = e / per_code;
+      const int rem = e - c * per_code;
+      const int ll = rem / R, r = rem - ll * R;
+      const int i = (ll & (SL - 1)) * R + r;                       // (SL = 8: positions 8..15 repeat 0..7)
+      const int sa = (i < mA) ? st[(int)xA[i] * a.ncodes + c] : C::kPad;
+      const int sb = (i < mB) ? st[(int)xB[i] * a.ncodes + c] : C::kPad;
+      prof[(c * PL + ll) * LS + r] = C::entry(sa, sb);
+    }
+  }
+
+  // ---- this slot's tile ---------------------------------------------------------------------------------------------------
+  const int64_t rlo = a.range_lo[range], rhi = a.range_hi[range];
+  const int64_t nchunks = (rhi - rlo + a.chunk_len - 1) / a.chunk_len;
+  const int64_t chunk = (int64_t)cg * NSLOT + slot;
+  const bool active = chunk < nchunks;
+  const int64_t own_lo = rlo + chunk * a.chunk_len;
+  const int64_t own_hi = (own_lo + a.chunk_len < rhi) ? own_lo + a.chunk_len : rhi;
+  const int64_t s0 = own_lo - a.warm;                              // reference index of stream position 0
+  const uint32_t pad = (uint32_t)(a.ncodes - 1);
+  const uint32_t pad4 = pad * 0x01010101u;
+
+  // codes of stream positions seg*64 + CPL*ls .. +CPL-1 (pad outside [rlo, own_hi))
+  struct Codes { uint32_t w[CPL / 4]; };
+  auto stage_load = [&](int seg) -> Codes {
+    Codes out;
+    const int64_t c0 = s0 + (int64_t)seg * kSeg + CPL * ls;
+#pragma unroll
+    for (int d = 0; d < CPL / 4; ++d) {
+      uint32_t w = 0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int64_t col = c0 + 4 * d + b;
+        const bool ok = active && col >= rlo && col < own_hi;
+        const uint32_t code = ok ? (uint32_t)a.refcodes[col] : pad;
+        w |= code << (8 * b);
+      }
+      out.w[d] = w;
+    }
+    return out;
+  };
+  uint8_t *buf = codebuf + slot * CB;
+  uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
+  const uint8_t *buf_lane = buf + HIST - ls;                       // + k = code of step k
+  const uint32_t *prof_lane = prof + (tid & (PL - 1)) * LS;
+  auto window_put = [&](const Codes &c) {
+#pragma unroll
+    for (int d = 0; d < CPL / 4; ++d) buf32[HIST / 4 + (CPL / 4) * ls + d] = c.w[d];
+  };
+
+  const int64_t total_steps = a.warm + a.chunk_len + SL;           // + SL-1 skew, + 1 drain
+  const int nseg = (int)((total_steps + kSeg - 1) / kSeg);
+  const int code_stride = PL * LS;
+
+  // border values of the tile's first lane: H(0, .) = 0 and F(1, .) = -o.  16 lanes: the DPP `old` operand; 8 lanes: lane 8 of
+  // the DPP row starts another tile, one and-or per value
+  uint32_t keep_mask = ls == 0 ? 0u : 0xFFFFFFFFu;
+  uint32_t f_border = ls == 0 ? nopen2 : 0u;
+  asm volatile("" : "+v"(keep_mask), "+v"(f_border));
+
+  // per-sub-chunk maximum -> per-query key, as sw_score_kernel: lanes lag lane 0 by up to SL-1 columns, so up to SL-1 trailing
+  // columns of a sub-chunk are reported with the next one; the host widens its search accordingly
+  const int64_t subs_per_tile = a.chunk_len / a.sub_len;
+  uint32_t best_a = 0u, best_b = 0u;                               // this tile's best published value per query
+  T mx = 0u;
+  auto publish = [&](int64_t sub) {
+    uint32_t m32 = mx;
+#pragma unroll
+    for (int off = SL / 2; off >= 1; off >>= 1) m32 = C::vmax(m32, (uint32_t)__shfl_xor((int)m32, off, SL));
+    // only a sub-chunk that strictly beats the tile's earlier ones can become the query's (max, first sub-chunk) key
+    if (ls == 0 && active) {
+      const unsigned long long tag = 0xFFFFFFFFull - (unsigned long long)(chunk * subs_per_tile + sub);
+      unsigned long long *k = a.keys + (size_t)range * a.nq;
+      const uint32_t va = m32 & 0xFFFFu, vb = m32 >> 16;           // (non-negative float16 values order like their bits)
+      auto key_max = [&](unsigned long long *addr, unsigned long long v) {
+        if (v > __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(addr, v);
+      };
+      if (va > best_a) { best_a = va; key_max(k + qA, ((unsigned long long)va << 32) | tag); }
+      if (hasB && vb > best_b) { best_b = vb; key_max(k + qB, ((unsigned long long)vb << 32) | tag); }
+    }
+    mx = 0u;
+  };
+  const int segs_per_sub = (int)(a.sub_len / kSeg);
+  const int warm_segs = (int)(a.warm / kSeg);
+  int64_t sub = 0;
+
+  Codes nextcodes = stage_load(0);
+  if (ls < HIST / 4) buf32[ls] = pad4;                             // history in front of the first segment = padding
+  window_put(nextcodes);
+  nextcodes = stage_load(1);
+  __syncthreads();                                                 // profile + first window ready
+
+  T H[R], E[R], Ho[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) { H[r] = 0u; E[r] = nopen2; Ho[r] = nopen2; }
+  uint32_t up_prev = 0u;
+  T fdown = nopen2;                                                // F of the row below this lane's last row, last step
+
+  for (int seg = 0; seg < nseg; ++seg) {
+#pragma unroll 2
+    for (int k = 0; k < kSeg; ++k) {
+      const uint32_t c = (uint32_t)buf_lane[k];
+      const u32x4 *pp = static_cast<const u32x4 *>(__builtin_assume_aligned(prof_lane + c * code_stride, 16));
+      uint32_t p[NQ4 * 4];
+#pragma unroll
+      for (int q = 0; q < NQ4; ++q) {
+        const u32x4 v = pp[q];
+        p[4 * q + 0] = v.x; p[4 * q + 1] = v.y; p[4 * q + 2] = v.z; p[4 * q + 3] = v.w;
+      }
+      // last row of the lane above at this lane's column: H, and the F it hands down
+      uint32_t up, f;
+      if (SL == 16) {
+        up = row_shr1(H[R - 1]);
+        f = (uint32_t)__builtin_amdgcn_update_dpp((int)nopen2, (int)fdown, 0x111 /*row_shr:1*/, 0xf, 0xf, false);
+      } else {
+        up = row_shr1(H[R - 1]) & keep_mask;
+        f = (row_shr1(fdown) & keep_mask) | f_border;
+      }
+      T diag = up_prev;                                            // H(i0-1, j-1)
+      up_prev = up;
+      T tpend = 0u;
+      (void)tpend;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const T w = H[r];
+        const T x = C::add(diag, p[r], 0u);
+        E[r] = C::vmax(C::sub_gap(E[r], next2), Ho[r]);
+        const T h = C::vmax3(x, E[r], f);
+        if (r & 1) mx = C::vmax3(mx, tpend, h);
+        else if (r + 1 < R) tpend = h;
+        else mx = C::vmax(mx, h);
+        diag = w;
+        H[r] = h;
+        Ho[r] = C::sub_gap(h, nopen2);
+        f = C::vmax(C::sub_gap(f, next2), Ho[r]);
+      }
+      fdown = f;
+    }
+    // slide the code window: keep the last HIST bytes as history, append the prefetched segment
+    {
+      const uint32_t h = buf32[kSeg / 4 + (ls & 3)];
+      if (ls < HIST / 4) buf32[ls] = h;
+    }
+    window_put(nextcodes);
+    nextcodes = stage_load(seg + 2);
+    // lane 0 has just finished a sub-chunk (and it is not the tile's last): report and restart the maximum
+    const int done = seg + 1 - warm_segs;
+    if (done > 0 && done % segs_per_sub == 0 && done / segs_per_sub < subs_per_tile) publish(sub++);
+  }
+  publish(sub);                                                    // the tile's last (or only) sub-chunk
+}
+
+struct AffineScoring {
+  const float *lut;       // device 256x256 or null
+  float match, mismatch, gap_open, gap_extend;
+};
+
+// One wavefront per problem (ExactProblem of sw_exact_kernel.h; dirs, hout, full_n and square_quirk unused).  The diagonals are
+// indexed by the row: cell (i, jl) of diagonal d = i + jl sits at index i.  A wavefront executes its LDS operations in order,
+// so no barrier is needed between diagonals.
+__global__ __launch_bounds__(64) void sw_affine_exact_kernel(const ExactProblem *probs, const AffineScoring sc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  const ExactProblem P = probs[blockIdx.x];
+  const int lane = threadIdx.x;
+  const int m = P.m, nw = P.nw;
+  const int plen = m + 2;
+  float *Hb = reinterpret_cast<float *>(smem_raw);                 // 3 x H, 2 x E, 2 x F
+  float *H0 = Hb, *H1 = Hb + plen, *H2 = Hb + 2 * plen;
+  float *E0 = Hb + 3 * plen, *E1 = Hb + 4 * plen, *F0 = Hb + 5 * plen, *F1 = Hb + 6 * plen;
+  uint8_t *xs = reinterpret_cast<uint8_t *>(Hb + 7 * plen);
+  const float ninf = -__builtin_inff();
+  for (int k = lane; k < 3 * plen; k += 64) Hb[k] = 0.0f;
+  for (int k = lane; k < 4 * plen; k += 64) E0[k] = ninf;
+  for (int k = lane; k < m; k += 64) xs[k] = P.x[k];
+
+  float best = -1.0f;
+  unsigned long long bkey = ~0ull;
+  int64_t bi = 0, bj = 0;
+  const float go = sc.gap_open, ge = sc.gap_extend;
+
+  float *Hc = H0, *Hp = H1, *Hpp = H2, *Ec = E0, *Ep = E1, *Fc = F0, *Fp = F1;
+  // diagonals d = i + jl; d = 0 and 1 are all border (already initialised)
+  for (int d = 2; d <= m + nw; ++d) {
+    { float *t = Hpp; Hpp = Hp; Hp = Hc; Hc = t; }
+    { float *t = Ep; Ep = Ec; Ec = t; }
+    { float *t = Fp; Fp = Fc; Fc = t; }
+    // border cells of this diagonal: row 0 (index 0) and column 0 (index d)
+    if (lane == 0) {
+      Hc[0] = 0.0f; Fc[0] = ninf; Ec[0] = ninf;
+      if (d <= m) { Hc[d] = 0.0f; Ec[d] = ninf; Fc[d] = ninf; }
+    }
+    const int ilo = d - nw > 1 ? d - nw : 1;
+    const int ihi = d - 1 < m ? d - 1 : m;
+    for (int i = ilo + lane; i <= ihi; i += 64) {
+      const int jl = d - i;
+      const uint8_t xa = xs[i - 1], yb = P.y[jl - 1];
+      const float s = sc.lut ? sc.lut[(int)xa * 256 + yb] : (xa == yb ? sc.match : sc.mismatch);
+      const float e = fmaxf(Ep[i] - ge, Hp[i] - go);               // (i, jl-1) on d-1
+      const float f = fmaxf(Fp[i - 1] - ge, Hp[i - 1] - go);       // (i-1, jl) on d-1
+      const float h = fmaxf(fmaxf(Hpp[i - 1] + s, 0.0f), fmaxf(e, f));
+      Hc[i] = h; Ec[i] = e; Fc[i] = f;
+      if (jl >= P.own_lo && h > 0.0f) {
+        const bool cand = (P.target >= 0.0f) ? (h == P.target) : (h >= best);
+        if (cand) {
+          const int64_t jt = P.col_offset + jl;
+          const unsigned long long key = order_key<0>(i, jt, m, 0);
+          if (h > best || key < bkey) { best = h; bkey = key; bi = i; bj = jt; }
+        }
+      }
+    }
+  }
+  // wave reduction: larger value first, then smaller key
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float ob = __shfl_xor(best, off);
+    const unsigned long long ok = __shfl_xor(bkey, off);
+    const long long oi = __shfl_xor((long long)bi, off);
+    const long long oj = __shfl_xor((long long)bj, off);
+    if (ob > best || (ob == best && ok < bkey)) { best = ob; bkey = ok; bi = oi; bj = oj; }
+  }
+  if (lane == 0) {
+    if (P.best) *P.best = best;
+    if (P.cell) { P.cell[0] = best > 0.0f ? bi : 0; P.cell[1] = best > 0.0f ? bj : 0; }
+  }
+}
+
+}  // namespace mi355sw
