@@ -179,7 +179,7 @@ int mi355_sw_best_range(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts,
 int mi355_sw_align_scored_range(mi355_sw_ctx *ctx, size_t range_index, const mi355_sw_params *params, int flags,
                                 mi355_sw_result *outs);
 
-/* ---- affine gaps: score and end cell --------------------------------------------------------------------------------
+/* ---- affine gaps: score, end cell and traceback -------------------------------------------------------------------
  * A gap of k consecutive columns (or rows) costs gap_open + (k - 1) * gap_extend.  With s = f(x[i], y[j]) (identity or
  * table, exactly as mi355_sw_params):
  *
@@ -190,7 +190,28 @@ int mi355_sw_align_scored_range(mi355_sw_ctx *ctx, size_t range_index, const mi3
  * Score = max H.  End cell = the first maximum in column-major order (smallest column of y, then smallest row of x),
  * 1-based: the float engine's rule (similaritymatrix.cpp:21-28).  An all-zero matrix gives score 0 and end 0 / 0.  With
  * gap_open == gap_extend == g this is the linear recurrence of MI355_SW_F32, and score, end_x and end_y equal that
- * engine's bit for bit.  No traceback (pos, consensus) under affine gaps yet.
+ * engine's bit for bit.
+ *
+ * Traceback (mi355_sw_affine_align_trace, mi355_sw_affine_batch_trace).  Scores are integers, so every equality below is
+ * exact in float32.  The walk starts in state M at the end cell and follows the recurrence:
+ *
+ *   state M at (i,j):  H(i,j) == 0                    stop: this cell is not part of the alignment
+ *                      H(i,j) == H(i-1,j-1) + s       emit (x[i], y[j]), go to M at (i-1, j-1)
+ *                      H(i,j) == E(i,j)               go to state E at (i, j), nothing emitted yet
+ *                      else (H(i,j) == F(i,j))        go to state F at (i, j)
+ *   state E at (i,j):  emit ('-', y[j]);  E(i,j) == H(i,j-1) - gap_open ? M at (i, j-1) : E at (i, j-1)
+ *   state F at (i,j):  emit (x[i], '-');  F(i,j) == H(i-1,j) - gap_open ? M at (i-1, j) : F at (i-1, j)
+ *
+ * The first case that holds wins (diagonal over E over F), and opening a gap wins a tie with extending it: the shortest
+ * gap.  The result follows the conventions of mi355_sw_result: cons_x / cons_y are REVERSED strings (from the end cell
+ * to the beginning of the alignment) with '-' for gaps, NUL terminated, in one allocation released by
+ * mi355_sw_free_result(s); pos is the 1-based column of y of the last pair emitted, i.e. the alignment's first column
+ * (begin_y); end_x / end_y are the end cell.  Score 0 gives pos 0, empty strings and cons_len 0.  The alignment's first row
+ * is begin_x = end_x + 1 - (number of bytes of cons_x other than '-').  timings_us[0] (and [1]) is the sweep time of the
+ * call.  The strings are an optimal alignment under the recurrence: their value under (f, gap_open, gap_extend) is the
+ * score.  With gap_open == gap_extend score and end cell equal the linear float engine's, but the strings are NOT that
+ * engine's: the reference's traceback (smithwaterman.cpp:40-78) greedily follows the largest neighbour,
+ * not the recurrence.
  *
  * MI355_SW_EINVAL: a non-finite value, gap_extend <= 0, gap_open < gap_extend.
  * MI355_SW_ENOTSUP (the message names the bound that was crossed) outside what the kernels compute exactly; a wrong
@@ -200,9 +221,12 @@ int mi355_sw_align_scored_range(mi355_sw_ctx *ctx, size_t range_index, const mi3
  * query profile fits LDS (53 reference letters at 512 rows, more for shorter queries).  Beyond that, integer scores are
  * still computed wherever a (query, reference or range) problem has at most 2^26 cells; everything else is refused.
  * Option no_affine_sweep (A/B, tests): every problem on the exact kernel, refused above 2^26 cells per problem.
- * mi355_sw_last_path: "affine[cell=f16,SL=..,R=..]" when the sweep kernel ran, "affine_exact" when the exact kernel ran.
- * mi355_sw_last_timings: [0] sweep kernel(s), [1] exact kernel (whole problems and end-cell windows), [3] whole call,
- * [4] sweep launches, [5] cells swept. */
+ * The traceback calls follow the same rules; in addition one alignment whose decision window needs more
+ * than 2^30 bytes is refused with MI355_SW_ENOTSUP.
+ * mi355_sw_last_path: "affine[cell=f16,SL=..,R=..]" when the sweep kernel ran, "affine_exact" when the exact kernel ran,
+ * "affine_trace" when the traceback kernel ran.
+ * mi355_sw_last_timings: [0] sweep kernel(s), [1] exact kernel (whole problems and end-cell windows), [2] traceback kernel,
+ * [3] whole call, [4] sweep launches, [5] cells swept. */
 typedef struct {
   const float *lut;        /* as mi355_sw_params.lut */
   float match, mismatch;   /* used when lut == NULL */
@@ -217,6 +241,11 @@ int mi355_sw_affine_align(mi355_sw_ctx *ctx, const char *x, size_t nx, const cha
 /* Every query of mi355_sw_batch_upload[_packed] against the reference of mi355_sw_set_reference: arrays of n_queries. */
 int mi355_sw_affine_batch_run(mi355_sw_ctx *ctx, const mi355_sw_affine_params *params,
                               float *score, int64_t *end_x, int64_t *end_y);
+/* The same two calls with the traceback: pos and the reversed consensus strings by the rule above.  out / outs (n_queries
+ * results) must not be NULL (MI355_SW_EINVAL); release the strings with mi355_sw_free_result(s). */
+int mi355_sw_affine_align_trace(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, size_t ny,
+                                const mi355_sw_affine_params *params, mi355_sw_result *out);
+int mi355_sw_affine_batch_trace(mi355_sw_ctx *ctx, const mi355_sw_affine_params *params, mi355_sw_result *outs);
 /* The affine counterpart of mi355_sw_score_ranges: maxima[k * n_queries + q], each range an independent problem with a
  * zero left border. */
 int mi355_sw_affine_score_ranges(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,

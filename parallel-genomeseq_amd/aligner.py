@@ -97,10 +97,12 @@ class SWAligner(LocalAligner):
 
 class AffineSWAligner:
     """Score and end cell under affine gaps (mi355_sw_affine_align; no counterpart in the reference, whose gap is linear): a gap
-    of k letters costs gap_open + (k - 1) * gap_extend.  `scoring` as for SWAligner.  No traceback yet: no getPos / consensus."""
+    of k letters costs gap_open + (k - 1) * gap_extend.  `scoring` as for SWAligner.  traceback=True: calculateScore also walks
+    the alignment back (mi355_sw_affine_align_trace, the rule of include/mi355_sw.h) and getPos / getConsensus_x / getConsensus_y
+    (reversed strings, as SWAligner's) / getBegin / getCigar return it."""
 
     def __init__(self, first_sequence, second_sequence, scoring=None, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0,
-                 context=None):
+                 context=None, traceback=False):
         self.sequence_x, self.sequence_y = first_sequence, second_sequence
         self.match, self.mismatch = float(match), float(mismatch)
         self.gap_open, self.gap_extend = float(gap_open), float(gap_extend)
@@ -109,15 +111,49 @@ class AffineSWAligner:
             self._lut = _lut_from_function(scoring) if callable(scoring) else np.asarray(scoring, dtype=np.float32)
         self._ctx = context
         self.max_score, self._end = -1.0, (0, 0)
+        self.traceback = bool(traceback)
+        self.pos, self._begin, self._cigar = 0, (0, 0), ""
+        self.consensus_x, self.consensus_y = "", ""
 
     def calculateScore(self):
         ctx = self._ctx if self._ctx is not None else default_context()
-        r = ctx.affine_align(self.sequence_x, self.sequence_y, match=self.match, mismatch=self.mismatch,
-                             gap_open=self.gap_open, gap_extend=self.gap_extend, lut=self._lut)
+        call = ctx.affine_align_trace if self.traceback else ctx.affine_align
+        r = call(self.sequence_x, self.sequence_y, match=self.match, mismatch=self.mismatch,
+                 gap_open=self.gap_open, gap_extend=self.gap_extend, lut=self._lut)
         self.max_score, self._end = r["score"], (r["end_x"], r["end_y"])
+        if self.traceback:
+            self.pos, self._begin, self._cigar = r["pos"], (r["begin_x"], r["begin_y"]), r["cigar"]
+            self.consensus_x, self.consensus_y = r["cons_x"], r["cons_y"]
         return self.max_score
 
     def getScore(self): return self.max_score
+
+    def _traced(self):
+        if not self.traceback:
+            raise RuntimeError("AffineSWAligner was constructed with traceback=False")
+
+    def getPos(self):
+        self._traced()
+        return self.pos
+
+    def getConsensus_x(self):
+        self._traced()
+        return self.consensus_x
+
+    def getConsensus_y(self):
+        self._traced()
+        return self.consensus_y
+
+    def getBegin(self):
+        """(row of first_sequence, column of second_sequence) of the alignment's first pair, 1-based; (0, 0) when the score is 0."""
+        self._traced()
+        return self._begin
+
+    def getCigar(self):
+        """Forward run-length string: M letter pair, I letter of first_sequence against a gap, D letter of second_sequence
+        against a gap."""
+        self._traced()
+        return self._cigar
 
     def getEnd(self):
         """(row of first_sequence, column of second_sequence) of the first maximum in column-major order, 1-based; (0, 0) when

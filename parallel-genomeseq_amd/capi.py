@@ -23,6 +23,7 @@ EXPORTS = [
     "mi355_sw_multi_align_batch", "mi355_sw_multi_last_timings",
     "mi355_sw_set_option", "mi355_sw_option_names", "mi355_sw_multi_set_option", "mi355_sw_last_counters", "mi355_sw_last_counter", "mi355_sw_batch_upload_packed", "mi355_sw_best_range", "mi355_sw_last_path",
     "mi355_sw_default_affine_params", "mi355_sw_affine_align", "mi355_sw_affine_batch_run", "mi355_sw_affine_score_ranges",
+    "mi355_sw_affine_align_trace", "mi355_sw_affine_batch_trace",
 ]
 MULTI_RCCL = 1
 
@@ -126,6 +127,31 @@ def _take(r):
     cy = C.string_at(r.cons_y, r.cons_len).decode("latin-1") if r.cons_len else ""
     return dict(score=float(r.score), pos=int(r.pos), end_x=int(r.end_x), end_y=int(r.end_y),
                 cons_x=cx, cons_y=cy, timings_us=(float(r.timings_us[0]), float(r.timings_us[1])))
+
+
+def cigar(cons_x, cons_y):
+    """Forward run-length string of an alignment given as the REVERSED consensus pair of a result: M = a letter pair (match or
+    mismatch), I = a query letter against '-' (cons_y == '-'), D = a reference letter against '-' (cons_x == '-')."""
+    if len(cons_x) != len(cons_y):
+        raise ValueError("cigar: consensus strings of different lengths")
+    out, last, run = [], "", 0
+    for a, b in zip(reversed(cons_x), reversed(cons_y)):
+        op = "D" if a == "-" else ("I" if b == "-" else "M")
+        if op != last and run:
+            out.append("%d%s" % (run, last))
+            run = 0
+        last, run = op, run + 1
+    if run:
+        out.append("%d%s" % (run, last))
+    return "".join(out)
+
+
+def _take_affine(r):
+    cx = C.string_at(r.cons_x, r.cons_len).decode("latin-1") if r.cons_len else ""
+    cy = C.string_at(r.cons_y, r.cons_len).decode("latin-1") if r.cons_len else ""
+    ex, score = int(r.end_x), float(r.score)
+    return dict(score=score, end_x=ex, end_y=int(r.end_y), begin_x=(ex + 1 - (len(cx) - cx.count("-"))) if score > 0 else 0,
+                begin_y=int(r.pos), pos=int(r.pos), cons_x=cx, cons_y=cy, cigar=cigar(cx, cy))
 
 
 class Context:
@@ -312,7 +338,7 @@ class Context:
         self._L.mi355_sw_free_results(res, C.c_size_t(n))
         return out
 
-    # -- affine gaps: score and end cell (mi355_sw_affine_*) -------------------------------------
+    # -- affine gaps: score, end cell, traceback (mi355_sw_affine_*) -------------------------------------
     def affine_align(self, x, y, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
         """One alignment under affine gaps: dict(score, end_x, end_y), the end cell 1-based, 0 / 0 when the score is 0."""
         x, y = _bytes(x), _bytes(y)
@@ -332,6 +358,34 @@ class Context:
         self._chk(self._L.mi355_sw_affine_batch_run(self._ctx, C.byref(p), score.ctypes.data_as(C.POINTER(C.c_float)),
                                                     ex.ctypes.data_as(C.POINTER(C.c_int64)), ey.ctypes.data_as(C.POINTER(C.c_int64))))
         return dict(score=score, end_x=ex, end_y=ey)
+
+    def affine_align_trace(self, x, y, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
+        """affine_align with the traceback (mi355_sw_affine_align_trace): dict(score, end_x, end_y, begin_x, begin_y, pos, cons_x,
+        cons_y, cigar).  cons_x / cons_y are reversed (end cell first), pos == begin_y is the alignment's first column of y,
+        begin_x its first row of x (1-based; 0 when the score is 0), cigar the forward run-length string (capi.cigar)."""
+        x, y = _bytes(x), _bytes(y)
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        r = Result()
+        self._chk(self._L.mi355_sw_affine_align_trace(self._ctx, x, C.c_size_t(len(x)), y, C.c_size_t(len(y)), C.byref(p), C.byref(r)))
+        out = _take_affine(r)
+        self._L.mi355_sw_free_result(C.byref(r))
+        return out
+
+    def affine_batch_trace(self, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
+        """affine_batch_run with the traceback (mi355_sw_affine_batch_trace): dict of arrays score, end_x, end_y, begin_x, begin_y,
+        pos and of lists of strings cons_x, cons_y, cigar, one entry per resident query."""
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        n = self._nbatch
+        res = (Result * max(1, n))()
+        self._chk(self._L.mi355_sw_affine_batch_trace(self._ctx, C.byref(p), res))
+        rows = [_take_affine(res[k]) for k in range(n)]
+        self._L.mi355_sw_free_results(res, C.c_size_t(n))
+        out = dict(score=np.array([r["score"] for r in rows], dtype=np.float32))
+        for k in ("end_x", "end_y", "begin_x", "begin_y", "pos"):
+            out[k] = np.array([r[k] for r in rows], dtype=np.int64)
+        for k in ("cons_x", "cons_y", "cigar"):
+            out[k] = [r[k] for r in rows]
+        return out
 
     def affine_score_ranges(self, ranges, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
         """Per-range affine maxima of every resident query: array [len(ranges), n_queries]."""

@@ -1,10 +1,11 @@
-// host_affine.h — affine-gap score and end cell: parameter checks, the sw_affine_kernel sweep and the sw_affine_exact_kernel
-// behind it (sw_affine_kernel.h).
+// host_affine.h — affine-gap score, end cell and traceback: parameter checks, the sw_affine_kernel sweep, the
+// sw_affine_exact_kernel behind it and sw_affine_trace_kernel (sw_affine_kernel.h).
 // Part of the single translation unit mi355_sw.hip (included there, in order; not a standalone header).
 namespace {
 
 constexpr int64_t kAffineSweepMinCols = 1024;        // shorter references (ranges) are whole problems of the exact kernel
 constexpr double kAffineExactCellsMax = 67108864.0;  // 2^26 cells: the largest whole problem one wavefront of the exact kernel takes
+constexpr size_t kAffineTraceDirsMax = (size_t)1 << 30;   // decision bytes of one launch group of sw_affine_trace_kernel (ctx->dirs)
 constexpr int kAffineF16Bound = 2040;                // smax * (rows + 1) and gap_open of the sweep's float16 cells (H / 2048)
 
 // The scoring of one affine call over the reference's letters (any query byte against them, as plan_table)
@@ -183,14 +184,119 @@ int affine_sweep_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch 
   return 0;
 }
 
+// Traceback of every query with a positive score (one range): one sw_affine_trace_kernel problem per query over rows
+// 1 .. end_x and the L17 window of columns behind the end cell, in launch groups of at most
+// kAffineTraceDirsMax decision bytes.  tout[nq]: views into ctx->arenas.
+int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_affine_params &p,
+                 const AffineTable &t, const float *score, const int64_t *ends, std::vector<TraceOut> &tout) {
+  struct Job { int q; int32_t m, nw; int64_t wl; bool clamped; size_t dirs_off, cons_off; };
+  std::vector<Job> jobs;
+  for (size_t k = 0; k < q.nq; ++k) {
+    if (!(score[k] > 0)) continue;
+    const int64_t ex = ends[2 * k], ey = ends[2 * k + 1];
+    const double spare = std::max(0.0, (double)t.smax * (double)ex - (double)score[k]);
+    const double W = (double)ex + std::ceil(spare / (double)t.ext) + 2.0;
+    Job j;
+    j.q = (int)k; j.m = (int32_t)ex;
+    j.clamped = W >= (double)ey;
+    const int64_t nw = j.clamped ? ey : (int64_t)W;
+    if (nw > (int64_t)kAffineTraceDirsMax || dirs_bytes(ex, nw) > kAffineTraceDirsMax) {
+      char msg[200];
+      std::snprintf(msg, sizeof msg, "affine traceback: a window of %lld rows x %lld columns needs more than %zu decision bytes",
+                    (long long)ex, (long long)nw, kAffineTraceDirsMax);
+      return fail(ctx, MI355_SW_ENOTSUP, msg);
+    }
+    j.nw = (int32_t)nw;
+    j.wl = ey - nw;
+    j.dirs_off = j.cons_off = 0;
+    if (affine_exact_lds(j.m) > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine traceback: alignment of more rows than the exact kernel's LDS diagonals hold");
+    jobs.push_back(j);
+  }
+  if (jobs.empty()) return 0;
+  path_note(ctx, "affine_trace");
+  AffineScoring sc;
+  sc.lut = nullptr;
+  if (p.lut) {
+    if (ctx->lut.ensure(65536 * 4)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(scoring table) failed");
+    HIPCHK(ctx, hipMemcpyAsync(ctx->lut.p, p.lut, 65536 * 4, hipMemcpyHostToDevice, ctx->stream));
+    sc.lut = ctx->lut.as<float>();
+  }
+  sc.match = p.match; sc.mismatch = p.mismatch; sc.gap_open = p.gap_open; sc.gap_extend = p.gap_extend;
+  for (size_t lo = 0; lo < jobs.size();) {
+    size_t hi = lo, dirs_total = 0, cons_total = 0, lds = 0;
+    while (hi < jobs.size() && hi - lo < 65536) {
+      Job &j = jobs[hi];
+      const size_t db = (dirs_bytes(j.m, j.nw) + 15) & ~(size_t)15;
+      if (hi > lo && dirs_total + db > kAffineTraceDirsMax) break;
+      j.dirs_off = dirs_total; dirs_total += db;
+      j.cons_off = cons_total; cons_total += 2 * ((size_t)j.m + (size_t)j.nw);
+      lds = std::max(lds, affine_exact_lds(j.m));
+      ++hi;
+    }
+    const size_t n = hi - lo;
+    if (ctx->wprobs.ensure(n * sizeof(AffineTraceProblem)) || ctx->walkp.ensure(n * 24) || ctx->dirs.ensure(dirs_total) ||
+        ctx->cons.ensure(cons_total + 16))
+      return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine traceback scratch) failed");
+    std::vector<AffineTraceProblem> pr(n);
+    for (size_t k = 0; k < n; ++k) {
+      const Job &j = jobs[lo + k];
+      AffineTraceProblem &a = pr[k];
+      memset(&a, 0, sizeof a);
+      a.e.x = q.bytes.as<uint8_t>() + q.off[j.q];
+      a.e.y = ref.bytes.as<uint8_t>() + rg.lo + j.wl;
+      a.e.m = j.m; a.e.nw = j.nw;
+      a.e.col_offset = j.wl;
+      a.e.own_lo = 1;
+      a.e.target = score[j.q];
+      a.e.dirs = ctx->dirs.as<uint8_t>() + j.dirs_off;
+      a.cap = j.m + j.nw;
+      a.cons_x = ctx->cons.as<char>() + j.cons_off;
+      a.cons_y = a.cons_x + a.cap;
+      a.clamped = j.clamped ? 1 : 0;
+      a.out = ctx->walkp.as<int64_t>() + 3 * k;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr.data(), n * sizeof(AffineTraceProblem), hipMemcpyHostToDevice, ctx->stream));
+    if (lds > 48 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sw_affine_trace_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    hipLaunchKernelGGL(sw_affine_trace_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<AffineTraceProblem>(), sc);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+    std::vector<int64_t> wo(3 * n);
+    std::vector<char> cons(cons_total);
+    HIPCHK(ctx, hipMemcpyAsync(wo.data(), ctx->walkp.p, n * 24, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cons.data(), ctx->cons.p, cons_total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->timings[2] += elapsed_us(ctx, ctx->ev[6], ctx->ev[7]);
+    ctx->arenas.push_back(std::move(cons));
+    const char *base = ctx->arenas.back().data();
+    for (size_t k = 0; k < n; ++k) {
+      const Job &j = jobs[lo + k];
+      const int64_t len = wo[3 * k], st = wo[3 * k + 2];
+      if (st == 1) return fail(ctx, MI355_SW_ENODEV, "internal: the affine traceback left its window (lemma L17)");
+      if (st == 2) return fail(ctx, MI355_SW_ENODEV, "internal: the affine traceback exceeded its string capacity");
+      if (st != 0) return fail(ctx, MI355_SW_ENODEV, "internal: the end cell of the affine traceback window does not hold the score");
+      TraceOut &o = tout[j.q];
+      o.len = (size_t)len;
+      o.cx = base + j.cons_off;
+      o.cy = base + j.cons_off + (size_t)j.m + (size_t)j.nw;
+      o.pos = (uint32_t)wo[3 * k + 1];
+    }
+    lo = hi;
+  }
+  return 0;
+}
+
 // Affine score (and, for one range, end cell) of every query of `q` over each range of `ref`, each range an independent
 // problem.  maxima: [nranges][nq].  ends (may be null; one range only): [nq][2] = row, column relative to the range start.
+// tout (may be null; needs ends): the traceback of every query, [nq] (affine_trace).
 int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const std::vector<Range> &ranges,
-               const mi355_sw_affine_params &p, float *maxima, int64_t *ends) {
+               const mi355_sw_affine_params &p, float *maxima, int64_t *ends, std::vector<TraceOut> *tout = nullptr) {
   const size_t nq = q.nq, nr = ranges.size();
   if (nq == 0 || nr == 0) return 0;
   for (size_t k = 0; k < nq * nr; ++k) maxima[k] = 0.0f;
   if (ends) for (size_t k = 0; k < 2 * nq; ++k) ends[k] = 0;
+  if (tout) tout->assign(nq, TraceOut());
   AffineTable t;
   int rc = affine_table(ctx, ref, p, t);
   if (rc) return rc;
@@ -330,6 +436,10 @@ int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const
         ends[2 * j.q] = j.ci; ends[2 * j.q + 1] = j.cj;
       }
     }
+  }
+  if (tout && ends) {
+    rc = affine_trace(ctx, ref, q, ranges[0], p, t, maxima, ends, *tout);
+    if (rc) return rc;
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
   ctx->timings[3] += elapsed_us(ctx, ctx->ev[4], ctx->ev[5]);

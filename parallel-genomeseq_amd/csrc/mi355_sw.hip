@@ -8,7 +8,7 @@
 //   3. traceback       sw_wave_kernel / sw_strip_kernel (dirs) — window left of the argmax -> greedy decisions,
 //                      sw_wave_walk_kernel — the walk itself (smithwaterman.cpp:40-78)            host_wave.h
 //   (sw_exact_kernel + sw_walk_kernel, host_exact.h: table scoring on short queries, whole uint8 problems)
-//   affine gaps (score and end cell): sw_affine_kernel sweep + sw_affine_exact_kernel                 host_affine.h
+//   affine gaps (score, end cell, traceback): sw_affine_kernel sweep + sw_affine_exact / _trace_kernel  host_affine.h
 // Problems the score kernel does not cover (see bucket_fast_ok) run 2+3 on the whole matrix.
 // The host code is one translation unit; the fragments below are included in order.
 #include "../../include/mi355_sw.h"
@@ -404,6 +404,54 @@ int mi355_sw_affine_batch_run(mi355_sw_ctx *ctx, const mi355_sw_affine_params *p
   rc = affine_run(ctx, ctx->ref, ctx->batch, std::vector<Range>{Range{0, (int64_t)ctx->ref.n}}, *params, score, ends.data());
   if (rc) return rc;
   for (size_t k = 0; k < nq; ++k) { end_x[k] = ends[2 * k]; end_y[k] = ends[2 * k + 1]; }
+  return 0;
+}
+
+int mi355_sw_affine_align_trace(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, size_t ny,
+                                const mi355_sw_affine_params *params, mi355_sw_result *out) {
+  OptScope opt_scope_(ctx);
+  int rc = affine_check(ctx, params);
+  if (rc) return rc;
+  if (!out || (!x && nx) || (!y && ny)) return fail(ctx, MI355_SW_EINVAL, "null argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  reset_timings(ctx);
+  memset(out, 0, sizeof *out);
+  float score = 0.0f;
+  int64_t end[2] = {0, 0};
+  std::vector<TraceOut> tout(1);
+  if (nx != 0 && ny != 0) {
+    const RefData *ref = nullptr;
+    rc = adhoc_reference(ctx, y, ny, &ref);
+    if (!rc) rc = upload_queries(ctx, ctx->one, 1, &x, &nx);
+    if (!rc) rc = affine_run(ctx, *ref, ctx->one, std::vector<Range>{Range{0, (int64_t)ny}}, *params, &score, end, &tout);
+    if (rc) return rc;
+  }
+  set_result(*out, score, end[0], end[1], &tout[0]);
+  out->timings_us[0] = out->timings_us[1] = (float)ctx->timings[0];
+  return 0;
+}
+
+int mi355_sw_affine_batch_trace(mi355_sw_ctx *ctx, const mi355_sw_affine_params *params, mi355_sw_result *outs) {
+  OptScope opt_scope_(ctx);
+  int rc = affine_check(ctx, params);
+  if (rc) return rc;
+  const size_t nq = ctx->batch.nq;
+  if (!outs) return fail(ctx, MI355_SW_EINVAL, "outs is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  reset_timings(ctx);
+  if (nq == 0) return 0;
+  memset(outs, 0, nq * sizeof *outs);
+  std::vector<float> score(nq, 0.0f);
+  std::vector<int64_t> ends(2 * nq, 0);
+  std::vector<TraceOut> tout(nq);
+  if (ctx->ref.n != 0) {
+    rc = affine_run(ctx, ctx->ref, ctx->batch, std::vector<Range>{Range{0, (int64_t)ctx->ref.n}}, *params, score.data(), ends.data(), &tout);
+    if (rc) return rc;
+  }
+  for (size_t k = 0; k < nq; ++k) {
+    set_result(outs[k], score[k], ends[2 * k], ends[2 * k + 1], &tout[k]);
+    outs[k].timings_us[0] = outs[k].timings_us[1] = (float)ctx->timings[0];
+  }
   return 0;
 }
 

@@ -1,10 +1,10 @@
-// sw_affine_kernel.h — affine-gap (Gotoh) Smith-Waterman for gfx950 (MI355X), hand-written HIP: score and end cell.
+// sw_affine_kernel.h — affine-gap (Gotoh) Smith-Waterman for gfx950 (MI355X), hand-written HIP: score, end cell, traceback.
 //
 //   E(i,j) = max(E(i,j-1) - e, H(i,j-1) - o)        a gap of k columns (rows) costs o + (k - 1) e, o >= e > 0
 //   F(i,j) = max(F(i-1,j) - e, H(i-1,j) - o)
 //   H(i,j) = max(0, H(i-1,j-1) + s, E(i,j), F(i,j))  H = 0 on the borders; E, F = -inf there
 //
-// Two kernels:
+// Three kernels:
 //   * sw_affine_kernel<R, SL>: the anti-diagonal sweep, with the tile geometry of the two-query, one-strip instances of
 //     sw_score_kernel (sw_score_kernel.h): tile = query pair x chunk + warm-up columns, SL lanes x R rows, the LDS query
 //     profile read with ds_read_b128 at lane_stride, the code window refilled every 64 steps, per-sub-chunk maxima
@@ -23,6 +23,8 @@
 //     and F in LDS (as sw_exact_kernel keeps H); tracks the first maximum in column-major order (order_key<0>) among the
 //     window's own columns.  It finds the end cell inside the sub-chunk the sweep names, and computes whole problems that
 //     are too small for the sweep (or all of them under option no_affine_sweep).
+//   * sw_affine_trace_kernel: the same cells (affine_exact_fill) over the window behind an end cell (lemma L17), one decision
+//     byte per cell, and the walk over them by the traceback rule of include/mi355_sw.h: pos and the reversed consensus strings.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -228,12 +230,17 @@ struct AffineScoring {
   float match, mismatch, gap_open, gap_extend;
 };
 
-// One wavefront per problem (ExactProblem of sw_exact_kernel.h; dirs, hout, full_n and square_quirk unused).  The diagonals are
+// Decision byte of one cell of sw_affine_trace_kernel (diagonal-major, as ExactProblem::dirs): where H came from, in the priority
+// of the traceback rule (include/mi355_sw.h), and whether E / F continued a gap instead of opening one.
+enum : int { kAffStop = 0, kAffDiag = 1, kAffE = 2, kAffF = 3, kAffEExt = 4, kAffFExt = 8 };
+
+// One wavefront per problem (ExactProblem of sw_exact_kernel.h; hout, full_n and square_quirk unused).  The diagonals are
 // indexed by the row: cell (i, jl) of diagonal d = i + jl sits at index i.  A wavefront executes its LDS operations in order,
-// so no barrier is needed between diagonals.
-__global__ __launch_bounds__(64) void sw_affine_exact_kernel(const ExactProblem *probs, const AffineScoring sc) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
-  const ExactProblem P = probs[blockIdx.x];
+// so no barrier is needed between diagonals.  TRACE: every cell also stores its decision byte to P.dirs and nothing competes
+// for the maximum; the value of the corner cell (m, nw) comes back in `best` of every lane.
+struct AffineBest { float best; int64_t i, j; };
+template <bool TRACE>
+__device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, const AffineScoring sc, uint8_t *smem_raw) {
   const int lane = threadIdx.x;
   const int m = P.m, nw = P.nw;
   const int plen = m + 2;
@@ -250,6 +257,7 @@ __global__ __launch_bounds__(64) void sw_affine_exact_kernel(const ExactProblem 
   unsigned long long bkey = ~0ull;
   int64_t bi = 0, bj = 0;
   const float go = sc.gap_open, ge = sc.gap_extend;
+  const int dstride = m < nw ? m : nw;
 
   float *Hc = H0, *Hp = H1, *Hpp = H2, *Ec = E0, *Ep = E1, *Fc = F0, *Fp = F1;
   // diagonals d = i + jl; d = 0 and 1 are all border (already initialised)
@@ -268,11 +276,17 @@ __global__ __launch_bounds__(64) void sw_affine_exact_kernel(const ExactProblem 
       const int jl = d - i;
       const uint8_t xa = xs[i - 1], yb = P.y[jl - 1];
       const float s = sc.lut ? sc.lut[(int)xa * 256 + yb] : (xa == yb ? sc.match : sc.mismatch);
-      const float e = fmaxf(Ep[i] - ge, Hp[i] - go);               // (i, jl-1) on d-1
-      const float f = fmaxf(Fp[i - 1] - ge, Hp[i - 1] - go);       // (i-1, jl) on d-1
-      const float h = fmaxf(fmaxf(Hpp[i - 1] + s, 0.0f), fmaxf(e, f));
+      const float eo = Hp[i] - go, fo = Hp[i - 1] - go;            // a gap opened from (i, jl-1) / (i-1, jl) on d-1
+      const float e = fmaxf(Ep[i] - ge, eo);
+      const float f = fmaxf(Fp[i - 1] - ge, fo);
+      const float x = Hpp[i - 1] + s;
+      const float h = fmaxf(fmaxf(x, 0.0f), fmaxf(e, f));
       Hc[i] = h; Ec[i] = e; Fc[i] = f;
-      if (jl >= P.own_lo && h > 0.0f) {
+      if (TRACE) {
+        const int src = h == 0.0f ? kAffStop : h == x ? kAffDiag : h == e ? kAffE : kAffF;
+        P.dirs[(size_t)d * (size_t)dstride + (size_t)(i - ilo)] = (uint8_t)(src | (e != eo ? kAffEExt : 0) | (f != fo ? kAffFExt : 0));
+        if (d == m + nw) best = h;                                 // (one cell, one lane)
+      } else if (jl >= P.own_lo && h > 0.0f) {
         const bool cand = (P.target >= 0.0f) ? (h == P.target) : (h >= best);
         if (cand) {
           const int64_t jt = P.col_offset + jl;
@@ -291,10 +305,80 @@ __global__ __launch_bounds__(64) void sw_affine_exact_kernel(const ExactProblem 
     const long long oj = __shfl_xor((long long)bj, off);
     if (ob > best || (ob == best && ok < bkey)) { best = ob; bkey = ok; bi = oi; bj = oj; }
   }
-  if (lane == 0) {
+  return AffineBest{best, bi, bj};
+}
+
+__global__ __launch_bounds__(64) void sw_affine_exact_kernel(const ExactProblem *probs, const AffineScoring sc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  const ExactProblem P = probs[blockIdx.x];
+  const AffineBest r = affine_exact_fill<false>(P, sc, smem_raw);
+  const float best = r.best;
+  const int64_t bi = r.i, bj = r.j;
+  if (threadIdx.x == 0) {
     if (P.best) *P.best = best;
     if (P.cell) { P.cell[0] = best > 0.0f ? bi : 0; P.cell[1] = best > 0.0f ? bj : 0; }
   }
+}
+
+// Traceback under affine gaps: the window [end_y - nw, end_y] x rows 1 .. end_x of one alignment (lemma L17), so
+// the end cell is the window's corner (e.m, e.nw).  e.target = the score, e.dirs = dirs_bytes(m, nw) bytes; e.best, e.cell,
+// e.own_lo unused.
+struct AffineTraceProblem {
+  ExactProblem e;
+  char *cons_x;           // capacity cap each: reversed, '-' for gaps, not terminated
+  char *cons_y;
+  int32_t cap;
+  int32_t clamped;        // the window starts at the range's first column: its left border is the problem's own
+  // outputs: [0] consensus length, [1] pos (true column of the last letter pair), [2] status: 0 ok, 1 the walk left an
+  // unclamped window, 2 capacity exceeded, 3 the corner cell does not hold the score
+  int64_t *out;
+};
+
+// Fills the window as sw_affine_exact_kernel does (the same cells: affine_exact_fill), one decision byte per cell, then lane 0
+// walks them from the corner by the rule of include/mi355_sw.h: state M follows bits 0-1, states E / F emit one gap letter and
+// close the gap unless their extension bit is set (the opening wins a tie: the shortest gap).
+__global__ __launch_bounds__(64) void sw_affine_trace_kernel(const AffineTraceProblem *probs, const AffineScoring sc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  const AffineTraceProblem T = probs[blockIdx.x];
+  const ExactProblem &P = T.e;
+  const float corner = affine_exact_fill<true>(P, sc, smem_raw).best;
+  // the walk reads what other lanes of this wavefront stored: wait for the stores, then keep the loads behind the barrier
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int m = P.m, nw = P.nw;
+  const int dstride = m < nw ? m : nw;
+  int i = m, jl = nw, len = 0, state = kAffDiag;                   // kAffDiag stands for state M
+  int64_t status = corner == P.target ? 0 : 3, pos = 0;
+  while (status == 0) {
+    if (i <= 0 || jl <= 0) {                                       // border: H = 0, stop
+      if (jl <= 0 && !T.clamped) status = 1;
+      break;
+    }
+    const int d = i + jl;
+    const int ilo = d - nw > 1 ? d - nw : 1;
+    const int dir = P.dirs[(size_t)d * (size_t)dstride + (size_t)(i - ilo)];
+    if (state == kAffDiag) {
+      const int src = dir & 3;
+      if (src == kAffStop) break;
+      if (src != kAffDiag) { state = src; continue; }
+    }
+    if (len >= T.cap) { status = 2; break; }
+    if (state == kAffDiag) {
+      T.cons_x[len] = (char)P.x[i - 1]; T.cons_y[len] = (char)P.y[jl - 1]; ++len;
+      pos = P.col_offset + jl; --i; --jl;
+    } else if (state == kAffE) {
+      T.cons_x[len] = '-'; T.cons_y[len] = (char)P.y[jl - 1]; ++len;
+      pos = P.col_offset + jl;
+      if (!(dir & kAffEExt)) state = kAffDiag;
+      --jl;
+    } else {
+      T.cons_x[len] = (char)P.x[i - 1]; T.cons_y[len] = '-'; ++len;
+      if (!(dir & kAffFExt)) state = kAffDiag;
+      --i;
+    }
+  }
+  T.out[0] = len; T.out[1] = pos; T.out[2] = status;
 }
 
 }  // namespace mi355sw
