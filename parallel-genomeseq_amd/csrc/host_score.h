@@ -33,8 +33,9 @@ struct Bucket {
   bool comb = false;          // twin on 16-lane tiles, small alphabet: profile indexed by the pair of codes (COMB)
   bool unsat = false;         // uint8 engine swept by a float-engine instance WITHOUT saturation, maxima clamped at 255
   bool mirror = false;        // kSemF16 bucket swept on MIRRORED cells (sw_score_kernel kSemF16M, lemma L14): scores stay within 1024
-  bool sampled = false;       // running maximum folded every 4th step (sw_score_kernel MK = 4): sub-chunk values are lower bounds
-                              // within 3 gaps of the truth; sub-chunks within that slack of the key are re-evaluated exactly
+  bool sampled = false;       // running maximum folded every 4th step (sw_score_kernel MK = 4), in one strip on every sample_rows-th row:
+                              // sub-chunk values are lower bounds within sample_slack of the truth; sub-chunks within that slack of
+                              // the key are re-evaluated exactly
   bool opt_margin = false;    // sw_long_kernel: optimistic warm-up margin, certified afterwards (long_score_launch)
   bool longp = false;         // lone long query on sw_long_kernel: the strips of a tile pipelined over the wavefronts of a workgroup
   int nstrips = 0;            // ... strips (= wavefronts) per tile
@@ -274,6 +275,17 @@ bool sampled_instance(int SL, int R) {
   if (SL == 16 || SL == 64) return listed(kR16M, R);
   return false;
 }
+constexpr int kScoreMK = 4;                   // sw_score_kernel folds the running maximum every kScoreMK-th step when it samples ...
+// ... and, in one strip, only every sample_rows(b)-th row of a lane (fold_row_stride, sw_score_kernel.h)
+int sample_rows(const Bucket &b) { return b.strips ? 1 : fold_row_stride(b.R, kScoreMK); }
+// The ONE slack of a sampled sw_score_kernel sweep (lemma L5), in score units: a cell holding M is seen at the next folded step in
+// the next folded row of its lane, sample_rows - 1 gaps down its column and kScoreMK - 1 gaps along the row.  Float32 cells with
+// fractional scores: the decay bound then holds up to the rounding of that many subtractions.
+float sample_slack(const ScoreTable &t, const Bucket &b) {
+  const float subs = (float)(sample_rows(b) - 1 + kScoreMK - 1);
+  if (b.sem != kSemF32) return subs * (float)t.gap;
+  return subs * t.gapf + (t.integral ? 0.0f : subs / 3.0f * std::ldexp(t.smaxf * (float)(b.maxlen + 1), -20));
+}
 
 // Mirrored float16 cells (kSemF16M, lemma L14) for a kSemF16 bucket of two-query tiles: every value of the sweep stays within
 // 1024 (smax * maxlen + smax: a cell's value and its diagonal term), where N = 1 - H / 2048 keeps to one float16 binade; 8- and
@@ -326,7 +338,7 @@ std::vector<Bucket> make_buckets(const RefData &ref, const QueryBatch &q, const 
         if (b.count >= 2) {
           b.sem = kSemF16; b.unsat = true; b.twin = false;
           // sampled maximum: every cell that holds the uint8 maximum reads at least that in the unsaturated sweep (a clamp at
-          // 255 only lowers values), hence >= it - 3 gaps at the next folded step: its sub-chunk is a candidate
+          // 255 only lowers values), hence >= it - sample_slack at the next folded step and row: its sub-chunk is a candidate
           // ... provided a random background stays clear of 255: with cheap gaps it grows with the read (about 0.2 M per
           // row at 3 / -3 / 2), longer reads reach 255 everywhere and every sub-chunk would be a candidate (measured: 1000 bp
           // reads overflow the flag budget and the call repeats the sweep unsampled)
@@ -363,7 +375,7 @@ std::vector<Bucket> make_buckets(const RefData &ref, const QueryBatch &q, const 
       if (fits && !t.htab.empty() && !b.strips && b.count >= 2 &&
           (int64_t)t.smax * b.maxlen + t.smax <= 2040 && !opt().no_f16) {
         b.sem = kSemF16;
-        // the running maximum every 4th step, the sub-chunks within 3 gaps of the key re-evaluated exactly (sw_score_kernel MK; lemma L5)
+        // the running maximum every 4th step, the sub-chunks within sample_slack of the key re-evaluated exactly (sw_score_kernel MK; lemma L5)
         b.sampled = allow_sample && sampled_instance(b.SL, b.R) && !opt().no_sample;
         b.mirror = mirror_ok(t, b);
       }
@@ -378,7 +390,7 @@ std::vector<Bucket> make_buckets(const RefData &ref, const QueryBatch &q, const 
                !opt().no_f16 && !opt().no_satflag) {
         b.sem = kSemF16; b.satflag = true;
         // with the sampled maximum the flags come from the filter alone (threshold: key - slack, key <= cap): a cell that holds
-        // the true maximum reads 2048 in the saturating sweep and >= 2048 - 3 gaps at the next folded step
+        // the true maximum reads 2048 in the saturating sweep and >= 2048 - sample_slack at the next folded step and row (a capped cell passes cap - g down)
         b.sampled = allow_sample && sampled_instance(b.SL, b.R) && !opt().no_sample;
       }
       // a lone query would fill both halves of every packed register with itself: the float32 instance (one query per
@@ -403,7 +415,7 @@ std::vector<Bucket> make_buckets(const RefData &ref, const QueryBatch &q, const 
           (b.strips ? listed(kR64S, b.R) : sampled_instance(64, b.R)) && !opt().no_sample)
         b.sampled = true;
       // ... and batches on float32 cells (fractional scoring; scores beyond 16 bits): the decay bound then holds up to the
-      // rounding of three subtractions, which the filter's slack allows for (score_launch)
+      // rounding of the slack's subtractions, which the filter's slack allows for (sample_slack)
       if (b.sem == kSemF32 && b.count >= 2 && !b.twin && !b.strips && (b.SL == 8 || b.SL == 16) && sampled_instance(b.SL, b.R) &&
           allow_sample && !opt().no_sample)
         b.sampled = true;
@@ -445,10 +457,13 @@ double valu_ops_per_cell(const Bucket &b) {
   const double over = b.SL == 8 ? 4.0 : 3.0;
   double per_step;
   int cells_per_row = 2;
+  // sw_score_kernel's cells that keep H - g: one maximum3 per two folded rows, on a sampled sweep every kScoreMK-th step only
+  const int folded = b.sampled ? (R + sample_rows(b) - 1) / sample_rows(b) : R;
+  const double fold = (b.sampled ? 1.0 / kScoreMK : 1.0) * ((folded + 1) / 2);
   switch (b.sem) {
-    case kSemF32:   per_step = 3.0 * R + (b.sampled ? (b.longp ? 1.0 / kLongMK : 0.25) : 1.0) * ((R + 1) / 2) + 1 + over; cells_per_row = 1; break;   // add clamp, max3, sub; max3 per two cells
+    case kSemF32:   per_step = 3.0 * R + (b.longp ? (b.sampled ? 1.0 / kLongMK : 1.0) * ((R + 1) / 2) : fold) + 1 + over; cells_per_row = 1; break;   // add clamp, max3, sub; max3 per two cells
     case kSemF32U8: per_step = 6.0 * R + (R + 1) / 2 + over; cells_per_row = 1; break;          // add, min, max, sub, max, max
-    case kSemF16:   per_step = 3.0 * R + (b.sampled ? 0.25 : 1.0) * ((R + 1) / 2) + 1 + over; break;
+    case kSemF16:   per_step = 3.0 * R + fold + 1 + over; break;
     case kSemU8H:   { const int odd = R / 2; per_step = 4.0 * R + odd / 2 + odd % 2 + R % 2 + over; break; }
     case kSemU8:    per_step = 5.0 * R + (R + 1) / 2 + R % 2 + over; break;
     default:        per_step = 4.0 * R + (R + 1) / 2 + R % 2 + over; break;
@@ -949,11 +964,13 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     for (int e = 0; e < 2; ++e) { hipEvent_t ev; HIPCHK(ctx, hipEventCreate(&ev)); ctx->score_ev.push_back(ev); }
   }
   HIPCHK(ctx, hipEventRecord(ctx->score_ev[ctx->score_ev_used], ctx->stream));
-  const ScoreInst inst{b.R, sem, b.strips, b.SL, b.twin, b.comb, a.submax_out != nullptr ? 4 : 1};
+  char rows_note[16] = "";                                           // sampled launches: the row stride of the fold
+  if (b.sampled) std::snprintf(rows_note, sizeof rows_note, ",rows=%d", sample_rows(b));
+  const ScoreInst inst{b.R, sem, b.strips, b.SL, b.twin, b.comb, a.submax_out != nullptr ? kScoreMK : 1};
   if (launch_score(inst, grid, shmem, ctx->stream, a)) return fail(ctx, MI355_SW_ENOTSUP, "no score kernel instance for this R");
   HIPCHK(ctx, hipGetLastError());
-  path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d,satflag=%d,unsat=%d,pow2=%d%s]", cl.cell, b.SL, b.R, (int)b.strips,
-            (int)b.twin, (int)b.comb, (int)b.sampled, (int)b.satflag, (int)b.unsat, (int)((b.chunk_len & (b.chunk_len - 1)) == 0), cl.tag);
+  path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d%s,satflag=%d,unsat=%d,pow2=%d%s]", cl.cell, b.SL, b.R, (int)b.strips,
+            (int)b.twin, (int)b.comb, (int)b.sampled, rows_note, (int)b.satflag, (int)b.unsat, (int)((b.chunk_len & (b.chunk_len - 1)) == 0), cl.tag);
   if (b.sampled) {
     // grid.y = query positions of this launch, at most 65535 per filter launch
     for (int f0 = 0; f0 < a.qcount; f0 += 65535) {
@@ -963,19 +980,19 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
       if (b.sem == kSemF32)
         hipLaunchKernelGGL(sw_sample_filter<true>, fgrid, dim3(256), 0, ctx->stream, rows, nsub, nsub,
                            (const int32_t *)a.qsel, a.qfirst + f0, fc, (const unsigned long long *)a.keys,
-                           std::ldexp(3.0f * t.gapf + (t.integral ? 0.0f : std::ldexp(t.smaxf * (float)(b.maxlen + 1), -20)), -ctx->fshift),
+                           std::ldexp(sample_slack(t, b), -ctx->fshift),
                            ctx->flags.as<unsigned int>(), reinterpret_cast<uint2 *>(ctx->flags.as<unsigned int>() + 2), ctx->flag_cap,
-                           ctx->qcnt.as<unsigned int>(), query_flag_cap(q.nq));
+                           ctx->qcnt.as<unsigned int>(), query_flag_cap(q.nq), 0u, true);
       else
         hipLaunchKernelGGL(sw_sample_filter<false>, fgrid, dim3(256), 0, ctx->stream, rows, nsub, nsub,
-                           (const int32_t *)a.qsel, a.qfirst + f0, fc, (const unsigned long long *)a.keys, 3.0f * (float)t.gap,
+                           (const int32_t *)a.qsel, a.qfirst + f0, fc, (const unsigned long long *)a.keys, sample_slack(t, b),
                            ctx->flags.as<unsigned int>(), reinterpret_cast<uint2 *>(ctx->flags.as<unsigned int>() + 2), ctx->flag_cap,
-                           ctx->qcnt.as<unsigned int>(), query_flag_cap(q.nq));
+                           ctx->qcnt.as<unsigned int>(), query_flag_cap(q.nq), 0u, true);
       // uint8 engine: the first candidates, in order, of the queries over their cap (settled without a second sweep when the
       // key sits at 255, align_range_core)
       if (b.unsat && b.sem != kSemF32 && nr == 1 && !opt().no_first) {
         hipLaunchKernelGGL(sw_sample_first<false>, dim3((unsigned)fc), dim3(64), 0, ctx->stream, rows, nsub, nsub,
-                           (const int32_t *)a.qsel, a.qfirst + f0, fc, (const unsigned long long *)a.keys, 3.0f * (float)t.gap,
+                           (const int32_t *)a.qsel, a.qfirst + f0, fc, (const unsigned long long *)a.keys, sample_slack(t, b),
                            (const unsigned int *)ctx->qcnt.as<unsigned int>(), query_flag_cap(q.nq), 0u, ctx->first.as<uint32_t>());
         ctx->first_valid = true;
         path_note(ctx, "sample_first");
@@ -1002,7 +1019,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
                   : b.satflag ? (b.sampled ? " float engine swept saturating at 2048" : " float engine swept saturating at 2048, saturated sub-chunks re-evaluated exactly") : "");
     if (b.sampled) {
       const size_t at = std::strlen(ki.name);
-      std::snprintf(ki.name + at, sizeof ki.name - at, "; maximum folded every 4th step (candidates re-evaluated)");
+      std::snprintf(ki.name + at, sizeof ki.name - at, "; maximum folded every 4th step (candidates re-evaluated), row stride %d", sample_rows(b));
     }
   }
   return 0;

@@ -110,8 +110,8 @@ struct ScoreArgs {
   unsigned int *flag_count;
   uint2 *flag_list;          // {query id, sub-chunk index in the range}
   uint32_t flag_cap, flag_value;
-  // Sampled running maximum (template parameter MK > 1): the per-sub-chunk values — lower bounds within (MK - 1) * gap of
-  // the truth — of launch-local query position p, sub-chunk s go to submax_out[p * submax_stride + s]; sw_sample_filter
+  // Sampled running maximum (template parameter MK > 1): the per-sub-chunk values — lower bounds within (RK - 1 + MK - 1) * gap
+  // of the truth (fold_row_stride) — of launch-local query position p, sub-chunk s go to submax_out[p * submax_stride + s]; sw_sample_filter
   // turns those within that slack of the query's final key into flagged sub-chunks.  Null: not in use.
   uint16_t *submax_out;
   int64_t submax_stride;
@@ -318,6 +318,12 @@ template <int SEM> __host__ __device__ constexpr bool score_instance_ok(int R, b
          // sampled maximum: packed float16 two-query tiles in one strip, or float32 cells (one query per tile)
          (MK == 1 || (MK == 4 && !TWIN && C::kKeepsHg && (C::kFloat || !STRIPS)));
 }
+// Row stride of the sampled running maximum (lemma L5): a one-strip MK > 1 instance folds, at a folded step, only the rows r of a
+// lane with r % RK == RK - 1, and the lane's last.  A cell holding M passes M - g to the row below it in the same column and step
+// (the N - g term), so the next folded row of the lane reads >= M - (RK - 1) g at once: the slack of the sweep's sub-chunk values
+// is (RK - 1 + MK - 1) g (host_score.h sample_slack).  MK = 1 and the strip-mined instances fold every row.
+constexpr int kFoldRowStride = 5;
+__host__ __device__ constexpr int fold_row_stride(int R, int MK) { return MK == 1 ? 1 : (R < kFoldRowStride ? R : kFoldRowStride); }
 
 // SL = lanes per tile ("slot"): 16 (one DPP row) or 8 (half a DPP row; the DPP shift then needs one mask op
 // per step, but 8*R rows fit the read length more tightly: 150 bp = 8 x 19 rows instead of 16 x 10).
@@ -333,9 +339,10 @@ template <int SEM> __host__ __device__ constexpr bool score_instance_ok(int R, b
 // costs in the two-query instances.
 // MK > 1 (packed float16, two-query tiles): the running maximum is folded only every MK-th step.  A cell holding the
 // maximum M decays by exactly one gap per column along its row (H(i, j + k) >= M - k g), so the value seen at the next
-// folded step is within (MK - 1) g of M: the sweep's sub-chunk values become lower bounds with that slack, every
+// folded step is within (MK - 1) g of M: the sweep's sub-chunk values become lower bounds with a slack, every
 // sub-chunk within the slack of the query's final key is re-evaluated exactly (host_pipeline.h), and the cell costs
-// 3 + 1/(2 MK) instead of 3.5 ops.
+// 3 + 1/(2 MK) instead of 3.5 ops.  In one strip the folded step takes only every RK-th row of the lane (fold_row_stride):
+// the same cell also decays by one gap per row down its column, within the lane and within the step.
 template <int R, int SEM, bool STRIPS = false, int SL = 16, bool TWIN = false, bool COMB = false, int MK = 1>
 __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   static_assert(score_instance_ok<SEM>(R, STRIPS, SL, TWIN, COMB, MK), "no such sw_score_kernel instance (score_instance_ok)");
@@ -348,6 +355,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   constexpr int HIST = hist_bytes(SL);
   constexpr int CB = codebuf_bytes(SL);
   constexpr int VPL = kSeg / SL >= 4 ? 4 : 1;                      // boundary-row values moved per lane per segment
+  constexpr int RK = STRIPS ? 1 : fold_row_stride(R, MK);          // rows between two folded rows of a lane
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t *prof = smem;                                           // [ncodes (COMB: ncodes^2)][PL lane positions][LS]
   uint8_t *codebuf = reinterpret_cast<uint8_t *>(smem + (COMB ? a.ncodes * a.ncodes : a.ncodes) * PL * LS);
@@ -691,9 +699,11 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
             const T w = H[r];
             const T x = C::add(diag, C::from_bits(p[r]), a.clamp2);
             const T h = C::cell_h(x, Hg[r], ng);
-            if (MK == 1 || (k & (MK - 1)) == MK - 1) {             // (compile-time per unrolled step)
-              if (r & 1) mx = C::vmax3(mx, tpend, h);
-              else if (r + 1 < R) tpend = h;
+            if ((MK == 1 || (k & (MK - 1)) == MK - 1) &&           // (compile-time per unrolled step and row)
+                (r % RK == RK - 1 || r == R - 1)) {
+              constexpr int NF = (R + RK - 1) / RK;                // folded rows of a lane; this one is number r / RK
+              if ((r / RK) & 1) mx = C::vmax3(mx, tpend, h);
+              else if (r / RK + 1 < NF) tpend = h;
               else mx = C::vmax(mx, h);
             }
             diag = w;
@@ -778,19 +788,23 @@ __global__ __launch_bounds__(256) void sw_sample_filter(const void *submax, int6
                                                         int qfirst, int qcount, const unsigned long long *keys, float slack,
                                                         unsigned int *flag_count, uint2 *flag_list, uint32_t flag_cap,
                                                         unsigned int *qcnt = nullptr, uint32_t per_query_cap = 0,
-                                                        uint32_t sub_offset = 0) {
+                                                        uint32_t sub_offset = 0, bool low_keys_blind = false) {
   const int pos = blockIdx.y;
   if (pos >= qcount) return;
   const int q = qsel[qfirst + pos];
   const float best = F32V ? __uint_as_float((uint32_t)(keys[q] >> 32))
                           : (float)__builtin_bit_cast(_Float16, (uint16_t)(keys[q] >> 32)) * 2048.0f;
-  if (!(best > 0.0f)) return;
+  // low_keys_blind (sw_score_kernel's sweeps): a key within the slack of zero says nothing — a maximum that small may have decayed to
+  // zero before the fold saw it, in any sub-chunk.  Then every sub-chunk is a candidate, the empty ones included (on a long reference
+  // that exceeds the query's cap, and the query is swept again exactly)
   const float thr = best - slack;
+  const bool blind = low_keys_blind && !(thr > 0.0f);
+  if (!blind && !(best > 0.0f)) return;
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nsub; s += (int64_t)gridDim.x * blockDim.x) {
     const size_t at = (size_t)pos * (size_t)stride + (size_t)s;
     const float v = F32V ? __uint_as_float(static_cast<const uint32_t *>(submax)[at])
                          : (float)__builtin_bit_cast(_Float16, static_cast<const uint16_t *>(submax)[at]) * 2048.0f;
-    if (v > 0.0f && v >= thr) {
+    if (blind || (v > 0.0f && v >= thr)) {
       if (qcnt != nullptr && atomicAdd(&qcnt[q], 1u) > per_query_cap) continue;
       const unsigned int at = atomicAdd(flag_count, 1u);
       if (at < flag_cap) flag_list[at] = make_uint2((unsigned int)q, (unsigned int)s + sub_offset);
