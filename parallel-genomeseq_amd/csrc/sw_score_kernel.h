@@ -20,6 +20,9 @@
 //     streamed through a small per-slot LDS byte window (coalesced global loads, once per 64 steps).
 //   * float16 / float32 cells: H = max3(clamp(NW + s), W - g, N - g) with H - g kept per cell — add, maximum3, add,
 //     and one maximum3 per two cells for the running maximum: 3.5 ops per cell.
+//     A mirrored float16 cell (kSemF16M) keeps ONLY K = H - g (bit pattern N + g) of every row: its diagonal add is an
+//     integer add, so the profile entry carries -g as well and the next step's diagonal is read from the kept K
+//     ((N + g) + (-s - g) = N - s mod 2^32); the lane above hands its K down as the border row.
 //     Integer cells: add, max(W, N), sat-sub, max — the running maximum is folded into t = max(W, N), which the
 //     recurrence needs anyway, on odd rows only (t_r covers cell (r, j-1) and cell (r-1, j)): 4.5 ops per cell.
 //
@@ -138,6 +141,7 @@ struct CellBase {
   static constexpr bool kFloat = false;       // float32 cells (one query per register, float table, float bits published)
   static constexpr bool kMirror = false;      // mirrored float16 cells (lemma L14): cells hold N = 1 - H / 2048
   static constexpr bool kKeepsHg = false;     // the cell keeps H - g of every row (add, cell_h, sub_gap per cell)
+  static constexpr bool kDiagFromHg = false;  // ... and ONLY that: the diagonal term is read from the kept H - g (L14 (g))
   static constexpr bool kMax3 = false;        // vmax3 exists: the running maximum takes three inputs
   static constexpr bool kGapInVgpr = false;   // the gap operand of sub_gap is kept in a VGPR
   static constexpr uint32_t kZero = 0u;       // bit pattern of H = 0 in a cell register
@@ -145,6 +149,8 @@ struct CellBase {
   static constexpr int kPad = kPadScore;      // 16-bit profile entry of padding rows
   // the packed profile entry of two 16-bit table entries: low half = query A (or the first tile), high half = B
   static __device__ __forceinline__ uint32_t entry(int sa, int sb) { return (uint32_t)(uint16_t)sa | ((uint32_t)(uint16_t)sb << 16); }
+  // what the gap adds to a packed entry of a cell whose diagonal is read from H - g (kDiagFromHg)
+  static __device__ __forceinline__ uint32_t entry_gap(uint32_t e, uint32_t) { return e; }
   // border row H(0, .) of a single-strip tile: the last row of the lane above, H = 0 on the tile's first lane (first_lane_zero:
   // 0 on that lane, all ones elsewhere; first_lane_z: the bit pattern of H = 0 there, 0 elsewhere); bound_ctrl supplies the zero
   template <int SL> static __device__ __forceinline__ uint32_t border(uint32_t v, uint32_t first_lane_zero, uint32_t) {
@@ -237,6 +243,7 @@ template <> struct Cell<kSemU8H> : Cell<kSemF16> {
 // are integer adds on the bit pattern of both halves at once.
 template <> struct Cell<kSemF16M> : Cell<kSemF16> {
   static constexpr bool kMirror = true;
+  static constexpr bool kDiagFromHg = true;  // diagonal and gap terms are both integer adds: K = H - g (pattern N + g) is all a row keeps
   static constexpr bool kGapInVgpr = true;   // a VOP2 add with an SGPR operand issues at the VOP3P rate (profiles/r05_mirror_cell_rate.txt)
   static constexpr uint32_t kZero = kF16MZero;
   // -s on the bit pattern (s = entry * 2048, exact), capped at 1024: from any cell (pattern >= 0x3800) that reaches the floor
@@ -248,6 +255,9 @@ template <> struct Cell<kSemF16M> : Cell<kSemF16> {
     };
     return (uint32_t)neg_s(sa) + ((uint32_t)neg_s(sb) << 16);
   }
+  // the diagonal is read as K_nw = N_nw + g: the entry carries -g in both halves as well, ONE subtraction modulo 2^32, so that
+  // K_nw + entry is the same 32-bit word as N_nw + (-s) (L14 (g))
+  static __device__ __forceinline__ uint32_t entry_gap(uint32_t e, uint32_t gap2) { return e - gap2; }
   // N_nw - s on the bit pattern: sc = (-s_B) * 2^16 + (-s_A) mod 2^32, so that a borrow of the low half is absorbed by the high
   // one; each half stays in [0, 0xFFFF] (L14 (f)).  Unclamped: for H_nw + s < 0 the pattern lies above 1.0 and cell_h's
   // clamp returns the zero floor.  Inline asm, so that the compiler cannot fuse it into a half-rate three-operand add
@@ -272,7 +282,8 @@ template <> struct Cell<kSemF16M> : Cell<kSemF16> {
   }
   // bound_ctrl's zero, then one v_max_u32 with H = 0 on the tile's first lane (first_lane_z): a cell N <= 1.0 in both halves is,
   // as a 32-bit word, at most kF16MZero, so the maximum is kF16MZero there and the value of the lane above elsewhere (8- and
-  // 16-lane tiles)
+  // 16-lane tiles).  kDiagFromHg: v is the lane above's K <= kF16MZero + gap2 (both halves, hence the word), and first_lane_z
+  // holds kF16MZero + gap2 — the K of H = 0
   template <int SL> static __device__ __forceinline__ uint32_t border(uint32_t v, uint32_t, uint32_t first_lane_z) {
     return __builtin_elementwise_max(row_shr1(v), first_lane_z);
   }
@@ -283,6 +294,7 @@ template <> struct Cell<kSemF16M> : Cell<kSemF16> {
 };
 // The same cells with the diagonal term as one clamped float16 add of -s / 2048 (the profile holds float16 -s / 2048)
 template <> struct Cell<kSemF16MF> : Cell<kSemF16M> {
+  static constexpr bool kDiagFromHg = false;                        // a float add: patterns above 1.0 are not linear, the row keeps H too
   static __device__ __forceinline__ uint32_t entry(int sa, int sb) { return CellBase::entry(sa, sb) ^ 0x80008000u; }   // (padding: +8, clamped to the floor)
   // clamp(N_nw - s): 1 - (H_nw + s) / 2048, exact while H_nw + s <= 1024; the upper clamp 1.0 is the zero floor (H_nw + s < 0)
   static __device__ __forceinline__ T add(T d, T sc, uint32_t) {
@@ -414,6 +426,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
         const int sa = (i < mA) ? st[(int)xA[i] * a.ncodes + c] : C::kPad;
         const int sb = (i < mB) ? st[(int)xB[i] * a.ncodes + c] : C::kPad;
         e32 = C::entry(sa, sb);
+        if constexpr (C::kDiagFromHg) e32 = C::entry_gap(e32, a.gap2);   // (every row of every lane, padding rows included)
       }
       prof[(c * PL + ll) * LS + r] = e32;
     }
@@ -516,7 +529,8 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   const int nstrips = STRIPS ? (mmax + strip_rows - 1) / strip_rows : 1;
   uint32_t first_lane_zero = ls == 0 ? 0u : 0xFFFFFFFFu;           // SL = 8: zero border row for lane 0 of the slot
   asm volatile("" : "+v"(first_lane_zero));                        // keep it a plain v_and_b32 (2 cycles), not a v_cndmask (4)
-  uint32_t first_lane_z = ls == 0 ? C::kZero : 0u;                 // mirrored cells: the border row's H = 0 on the tile's first lane
+  // mirrored cells: the border row's H = 0 on the tile's first lane (kDiagFromHg: as K = H - g, like the rest of the border row)
+  uint32_t first_lane_z = ls == 0 ? (C::kDiagFromHg ? C::kZero + a.gap2 : C::kZero) : 0u;
   if constexpr (C::kMirror) asm volatile("" : "+v"(first_lane_z));
   // STRIPS: this tile's ping-pong boundary rows (global), and its LDS windows
   const size_t tile_id = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NSLOT + slot;
@@ -643,13 +657,14 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
     }
     __syncthreads();                                               // profile + first window ready
 
-    T H[R];
+    constexpr int HN = C::kDiagFromHg ? 1 : R, GN = C::kKeepsHg ? R : 1;   // (kDiagFromHg: no H[], Hg[] is the whole state)
+    T H[HN];
 #pragma unroll
-    for (int r = 0; r < R; ++r) H[r] = C::from_bits(C::kZero);
-    uint32_t up_prev = C::kZero;
-    T Hg[C::kKeepsHg ? R : 1];
+    for (int r = 0; r < HN; ++r) H[r] = C::from_bits(C::kZero);
+    uint32_t up_prev = C::kDiagFromHg ? C::kZero + a.gap2 : C::kZero;
+    T Hg[GN];
 #pragma unroll
-    for (int r = 0; r < (C::kKeepsHg ? R : 1); ++r) Hg[r] = C::sub_gap(C::from_bits(C::kZero), gap_op);   // 0 - g
+    for (int r = 0; r < GN; ++r) Hg[r] = C::sub_gap(C::from_bits(C::kZero), gap_op);   // 0 - g
 
     for (int seg = 0; seg < nseg; ++seg) {
 #pragma unroll 4
@@ -680,9 +695,10 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
         uint32_t up;                                               // H(i0-1, j) of the lane above
         if (STRIPS) {
           // lane 0 takes the previous strip's bottom row through the DPP `old` operand
-          up = shift_in(C::bits(H[R - 1]), bin_w[k]);
+          up = shift_in(C::bits(H[HN - 1]), bin_w[k]);
         } else {
-          up = C::template border<SL>(C::bits(H[R - 1]), first_lane_zero, first_lane_z);   // the zero border row H(0, .)
+          // the zero border row H(0, .); kDiagFromHg: the lane above hands over its K, and the border row is K throughout
+          up = C::template border<SL>(C::bits(C::kDiagFromHg ? Hg[GN - 1] : H[HN - 1]), first_lane_zero, first_lane_z);
         }
         T diag = C::from_bits(up_prev);                            // H(i0-1, j-1)
         T north = C::from_bits(up);
@@ -693,10 +709,16 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
           // H = max(clamp0(NW + s), W - g, N - g): the cell keeps H (next step's diagonal) and H - g (this row's west
           // term next step, the row below's north term now) — add, maximum3, add per cell; the running maximum takes
           // two cells per maximum3
-          T ng = C::sub_gap(north, gap_op);                        // (row above the lane's first) - g
+          // kDiagFromHg: only H - g is kept — `up`, `diag` and `w` are H - g too, and the profile entry takes the gap back
+          // (Cell::entry_gap), so that x is the same word: no add for ng, no H[]
+          T ng;
+          if constexpr (C::kDiagFromHg) ng = north;
+          else ng = C::sub_gap(north, gap_op);                     // (row above the lane's first) - g
 #pragma unroll
           for (int r = 0; r < R; ++r) {
-            const T w = H[r];
+            T w;
+            if constexpr (C::kDiagFromHg) w = Hg[r];
+            else w = H[r];
             const T x = C::add(diag, C::from_bits(p[r]), a.clamp2);
             const T h = C::cell_h(x, Hg[r], ng);
             if ((MK == 1 || (k & (MK - 1)) == MK - 1) &&           // (compile-time per unrolled step and row)
@@ -707,7 +729,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
               else mx = C::vmax(mx, h);
             }
             diag = w;
-            H[r] = h;
+            if constexpr (!C::kDiagFromHg) H[r] = h;
             ng = Hg[r] = C::sub_gap(h, gap_op);
           }
         } else {
@@ -727,10 +749,10 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
           H[r] = h;
           north = h;
         }
-        if (R & 1) mx = C::vmax(mx, H[R - 1]);                     // odd R: the last (even) row is in no tracked t
+        if (R & 1) mx = C::vmax(mx, H[HN - 1]);                    // odd R: the last (even) row is in no tracked t
         }
         if (STRIPS) {
-          if (ls == SL - 1) bout_w[k] = C::bits(H[R - 1]);         // bottom row at stream position seg*64+k-(SL-1)
+          if (ls == SL - 1) bout_w[k] = C::bits(H[HN - 1]);        // bottom row at stream position seg*64+k-(SL-1)
         }
       }
       // slide the code window: keep the last HIST bytes as history, append the prefetched segment
