@@ -218,15 +218,22 @@ int mi355_sw_align_scored_range(mi355_sw_ctx *ctx, size_t range_index, const mi3
  * number never comes back.  Always computed: integer-valued scores (match / mismatch, or the table's entries for any
  * query byte against the reference's letters, and both gap costs) with smax * (longest query + 1) <= 2040 and
  * gap_open <= 2040 (smax: the greatest substitution score), queries of 1..512 rows, any reference length, while the
- * query profile fits LDS (53 reference letters at 512 rows, more for shorter queries).  Beyond that, integer scores are
- * still computed wherever a (query, reference or range) problem has at most 2^26 cells; everything else is refused.
+ * query profile fits LDS (53 reference letters at 512 rows, more for shorter queries).  Also always computed: queries of any
+ * length (the database sequences of a search) against a reference, or a range of it, of 1..512 letters, with integer-valued
+ * scores, smax * (letters + 1) < 2^18 and gap_open < 2^18, while the profile of the byte classes fits LDS (96 KiB: 127
+ * classes of bytes with equal scores up to 160 letters, 75 up to 320, 41 up to 512; a 20-letter table has 21).  Beyond both, integer scores are still
+ * computed wherever a (query, reference or range) problem has at most 2^26 cells and the query at most about 5 600 rows;
+ * everything else is refused.
  * Option no_affine_sweep (A/B, tests): every problem on the exact kernel, refused above 2^26 cells per problem.
- * The traceback calls follow the same rules; in addition one alignment whose decision window needs more
- * than 2^30 bytes is refused with MI355_SW_ENOTSUP.
- * mi355_sw_last_path: "affine[cell=f16,SL=..,R=..]" when the sweep kernel ran, "affine_exact" when the exact kernel ran,
- * "affine_trace" when the traceback kernel ran.
- * mi355_sw_last_timings: [0] sweep kernel(s), [1] exact kernel (whole problems and end-cell windows), [2] traceback kernel,
- * [3] whole call, [4] sweep launches, [5] cells swept. */
+ * Option no_affine_prof (A/B, tests): references (ranges) of at most 512 letters on the exact kernel as well.
+ * The traceback calls follow the same rules; in addition one alignment whose decision window (DESIGN.md §3.8, L17 and L18:
+ * the columns and the rows an alignment into the end cell can reach) needs more than 2^30 bytes, or has more than about
+ * 5 600 rows, is refused with MI355_SW_ENOTSUP.
+ * mi355_sw_last_path: "affine[cell=f16,SL=..,R=..]" when the sweep kernel ran, "affine_prof[R=..]" when the kernel for
+ * references of at most 512 letters ran (calls of fewer than 2^18 cells stay on the exact kernel), "affine_exact" when the
+ * exact kernel ran, "affine_trace" when the traceback kernel ran.
+ * mi355_sw_last_timings: [0] sweep kernel(s) (both of them), [1] exact kernel (whole problems and end-cell windows),
+ * [2] traceback kernel, [3] whole call, [4] sweep launches, [5] cells swept. */
 typedef struct {
   const float *lut;        /* as mi355_sw_params.lut */
   float match, mismatch;   /* used when lut == NULL */

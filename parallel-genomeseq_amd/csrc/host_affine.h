@@ -1,5 +1,6 @@
 // host_affine.h — affine-gap score, end cell and traceback: parameter checks, the sw_affine_kernel sweep, the
-// sw_affine_exact_kernel behind it and sw_affine_trace_kernel (sw_affine_kernel.h).
+// sw_affine_exact_kernel behind it, sw_affine_trace_kernel (sw_affine_kernel.h) and, for references (ranges) of
+// at most 512 letters, sw_affine_prof_kernel (sw_affine_prof_kernel.h).
 // Part of the single translation unit mi355_sw.hip (included there, in order; not a standalone header).
 namespace {
 
@@ -184,32 +185,201 @@ int affine_sweep_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch 
   return 0;
 }
 
-// Traceback of every query with a positive score (one range): one sw_affine_trace_kernel problem per query over rows
-// 1 .. end_x and the L17 window of columns behind the end cell, in launch groups of at most
-// kAffineTraceDirsMax decision bytes.  tout[nq]: views into ctx->arenas.
+// ---- sw_affine_prof_kernel (sw_affine_prof_kernel.h): ranges of at most kWaveMaxLanesSide columns ----------------------------
+constexpr double kAffineProfBound = 262144.0;        // 2^18: smax * (columns + 1) and gap_open, so that the key's five mantissa bits stay free
+constexpr size_t kAffineProfLdsMax = 96 * 1024;      // the profile budget of wave_prof_ok
+constexpr double kAffineProfMinCells = 262144.0;     // 2^18: a range whose problems hold fewer cells in all stays on the exact kernel, as before
+constexpr size_t kAffineProfGroupProblems = (size_t)1 << 22;   // problems between two downloads of (best, cell)
+
+// The classes of x's bytes: bytes with identical score rows against the reference's letters share a profile row.
+struct AffineProfPlan {
+  bool ok = false;
+  int nclass = 0;                 // incl. the last one, "outside" (steps in front of and beyond a stream)
+  uint8_t cls[256];
+  std::vector<int> rep;           // a byte of every class but the last
+};
+
+inline float affine_score(const RefData &ref, const mi355_sw_affine_params &p, int a, int c) {
+  return p.lut ? p.lut[(size_t)a * 256 + ref.byte_of[c]] : ((uint8_t)a == ref.byte_of[c] ? p.match : p.mismatch);
+}
+
+void affine_prof_plan(const RefData &ref, const mi355_sw_affine_params &p, const AffineTable &t, AffineProfPlan &plan) {
+  plan.ok = false;
+  const int nl = ref.ncodes - 1;
+  if (opt().no_affine_prof || nl < 1 || nl > 255 || (double)t.open >= kAffineProfBound) return;
+  plan.rep.clear();
+  for (int a = 0; a < 256; ++a) {
+    int c = 0;
+    for (; c < (int)plan.rep.size(); ++c) {
+      bool same = true;
+      for (int l = 0; l < nl && same; ++l) same = affine_score(ref, p, a, l) == affine_score(ref, p, plan.rep[c], l);
+      if (same) break;
+    }
+    if (c == (int)plan.rep.size()) {
+      if (c == 255) return;                                        // (256 classes with "outside": the window holds bytes)
+      plan.rep.push_back(a);
+    }
+    plan.cls[a] = (uint8_t)c;
+  }
+  plan.nclass = (int)plan.rep.size() + 1;
+  plan.ok = true;
+}
+
+bool affine_prof_range_ok(const AffineProfPlan &plan, const AffineTable &t, int64_t n) {
+  if (!plan.ok || n < 1 || n > kWaveMaxLanesSide) return false;
+  if ((double)t.smax * ((double)n + 1.0) >= kAffineProfBound) return false;
+  return (size_t)plan.nclass * 16 * lane_stride(wave_prof_R((int)n)) * 4 <= kAffineProfLdsMax;
+}
+
+template <int R>
+void launch_affine_prof(hipStream_t st, size_t lds, unsigned blocks, const WaveProblem *dp, int n, const AffineProfArgs &sa) {
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sw_affine_prof_kernel<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((sw_affine_prof_kernel<R>), dim3(blocks), dim3(256), lds, st, dp, n, sa);
+}
+
+// Every non-empty query of the batch against each range of `which` (indices into `ranges`, all affine_prof_range_ok): one launch
+// of sw_affine_prof_kernel per range over descriptors that batch_wave_setup builds on the device, longest sequence first; (best,
+// cell) of a group of ranges come down in one copy.  maxima / ends as affine_run.
+int affine_prof_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const std::vector<Range> &ranges,
+                    const std::vector<size_t> &which, const mi355_sw_affine_params &p, const AffineTable &t,
+                    const AffineProfPlan &plan, float *maxima, int64_t *ends) {
+  const size_t nq = q.nq;
+  size_t first = 0;
+  while (first < nq && q.len[q.order[first]] < 1) ++first;          // (sorted by length: the empty queries lead)
+  const size_t count = nq - first;
+  if (count == 0 || which.empty()) return 0;
+  if (count > ((size_t)1 << 30)) return fail(ctx, MI355_SW_ENOTSUP, "affine: more than 2^30 queries");
+  int64_t nmax = 0;
+  for (size_t r : which) nmax = std::max(nmax, ranges[r].hi - ranges[r].lo);
+  // cells hold H * 2^-k, 2^k above every value of the call (as wave_prof_launch)
+  const int k = std::max(1, std::ilogb((double)t.smax * ((double)nmax + 1.0) + 1.0) + 2);
+  const int nl = ref.ncodes - 1;
+  // class scores and the byte -> class table: [nclass][nl] floats, then 256 bytes
+  const size_t tab_floats = (size_t)plan.nclass * nl;
+  ctx->h_aprof.assign(tab_floats + 64, 0.0f);                      // (outlives the asynchronous copy)
+  for (int c = 0; c < plan.nclass; ++c)
+    for (int l = 0; l < nl; ++l)
+      ctx->h_aprof[(size_t)c * nl + l] = c + 1 < plan.nclass ? std::ldexp(affine_score(ref, p, plan.rep[c], l) + (float)t.open, -k) : kPadScoreF;
+  memcpy(ctx->h_aprof.data() + tab_floats, plan.cls, 256);
+  if (ctx->aprof.ensure((tab_floats + 64) * 4)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine profile classes) failed");
+  HIPCHK(ctx, hipMemcpyAsync(ctx->aprof.p, ctx->h_aprof.data(), (tab_floats + 64) * 4, hipMemcpyHostToDevice, ctx->stream));
+  AffineProfArgs sa;
+  sa.ctab = ctx->aprof.as<float>();
+  sa.cls = reinterpret_cast<const uint8_t *>(ctx->aprof.as<float>() + tab_floats);
+  sa.nclass = plan.nclass; sa.nletters = nl;
+  sa.open_s = std::ldexp((float)t.open, -k); sa.ext_s = std::ldexp((float)t.ext, -k);
+  sa.unscale = std::ldexp(1.0f, k);
+
+  const size_t per_group = std::max<size_t>(1, kAffineProfGroupProblems / count);
+  const unsigned blocks = (unsigned)((count + 15) / 16);
+  double row_sum = 0;
+  for (size_t s = first; s < nq; ++s) row_sum += (double)q.len[q.order[s]];
+  for (size_t g0 = 0; g0 < which.size(); g0 += per_group) {
+    const size_t ng = std::min(per_group, which.size() - g0), np = ng * count;
+    const size_t o_cell = (np * 4 + 15) & ~(size_t)15;
+    if (ctx->wprobs.ensure(np * sizeof(WaveProblem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16) ||
+        ctx->pin_out.ensure(o_cell + np * 16))
+      return fail(ctx, MI355_SW_ENOMEM, "affine: allocation of the batch scratch failed");
+    BatchWaveArgs a;
+    memset(&a, 0, sizeof a);
+    a.qbytes = q.bytes.as<uint8_t>(); a.qoff = q.offs.as<int64_t>(); a.qlen = q.lens.as<int32_t>();
+    a.qsel = q.sel.as<int32_t>(); a.qcum = q.cum.as<int64_t>();
+    a.first = (int)first; a.count = (int)count; a.orient = 1; a.W = 1;
+    for (size_t g = 0; g < ng; ++g) {                               // the descriptors: lanes = the CODES of the range, stream = x
+      const Range &rg = ranges[which[g0 + g]];
+      a.ref = ref.codes.as<uint8_t>() + rg.lo; a.nref = rg.hi - rg.lo;
+      a.R = wave_prof_R((int)a.nref);
+      a.probs = ctx->wprobs.as<WaveProblem>() + g * count;
+      a.best = ctx->outs_f.as<float>() + g * count;
+      a.cell = ctx->outs_i.as<int64_t>() + 2 * g * count;
+      hipLaunchKernelGGL(batch_wave_setup, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    for (size_t g = 0; g < ng; ++g) {
+      const Range &rg = ranges[which[g0 + g]];
+      const int n = (int)(rg.hi - rg.lo), R = wave_prof_R(n);
+      const size_t lds = (size_t)plan.nclass * 16 * lane_stride(R) * 4;
+      const WaveProblem *dp = ctx->wprobs.as<WaveProblem>() + g * count;
+      if (R == 9) launch_affine_prof<9>(ctx->stream, lds, blocks, dp, (int)count, sa);
+      else if (R == 10) launch_affine_prof<10>(ctx->stream, lds, blocks, dp, (int)count, sa);
+      else if (R == 20) launch_affine_prof<20>(ctx->stream, lds, blocks, dp, (int)count, sa);
+      else launch_affine_prof<32>(ctx->stream, lds, blocks, dp, (int)count, sa);
+      HIPCHK(ctx, hipGetLastError());
+      path_note(ctx, "affine_prof[R=%d]", R);
+      ctx->timings[4] += 1;
+      const double cells = row_sum * (double)n;
+      ctx->timings[5] += cells;
+      if (cells > ctx->last_kernel.cells) {
+        mi355_sw_kernel_info &ki = ctx->last_kernel;
+        ki.cell = MI355_SW_CELL_F32; ki.lanes = 16; ki.rows_per_lane = R; ki.strips = 0; ki.twin = 0;
+        ki.chunk_len = n; ki.sub_len = n; ki.warm = 0; ki.cells = cells;
+        // per step and lane: seven ops and the key's v_or per cell, a maximum3 per two cells for the lane's best key, and seven of
+        // overhead (two DPP moves, the profile address: multiply-add and shift, and compare, select, maximum for the first row)
+        ki.valu_ops_per_cell = (8.0 * R + (R + 1) / 2 + 7.0) / (double)R;
+        std::snprintf(ki.name, sizeof ki.name, "sw_affine_prof_kernel<R=%d, f32>", R);
+      }
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    uint8_t *pin = ctx->pin_out.as<uint8_t>();
+    const float *h_best = reinterpret_cast<const float *>(pin);
+    const int64_t *h_cell = reinterpret_cast<const int64_t *>(pin + o_cell);
+    HIPCHK(ctx, hipMemcpyAsync(pin, ctx->outs_f.p, np * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(pin + o_cell, ctx->outs_i.p, np * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->timings[0] += elapsed_us(ctx, ctx->ev[0], ctx->ev[1]);
+    for (size_t g = 0; g < ng; ++g) {
+      const size_t r = which[g0 + g];
+      for (size_t kk = 0; kk < count; ++kk) {
+        const int id = q.order[batch_sorted_pos((int)first, (int)count, (int)kk)];
+        const float best = h_best[g * count + kk];
+        maxima[r * nq + (size_t)id] = best > 0 ? best : 0.0f;
+        if (ends && best > 0) { ends[2 * id] = h_cell[2 * (g * count + kk)]; ends[2 * id + 1] = h_cell[2 * (g * count + kk) + 1]; }
+      }
+    }
+  }
+  return 0;
+}
+
+// Traceback of every query with a positive score (one range): one sw_affine_trace_kernel problem per query over the window
+// behind the end cell — the L17 window of columns and the L18 window of rows, each where it is shorter than the matrix
+//  — in launch groups of at most kAffineTraceDirsMax decision bytes.  tout[nq]: views into ctx->arenas.
 int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_affine_params &p,
                  const AffineTable &t, const float *score, const int64_t *ends, std::vector<TraceOut> &tout) {
-  struct Job { int q; int32_t m, nw; int64_t wl; bool clamped; size_t dirs_off, cons_off; };
+  struct Job { int q; int32_t m, nw; int64_t wl, row_lo; bool clamped, row_clamped; size_t dirs_off, cons_off; };
   std::vector<Job> jobs;
   for (size_t k = 0; k < q.nq; ++k) {
     if (!(score[k] > 0)) continue;
     const int64_t ex = ends[2 * k], ey = ends[2 * k + 1];
     const double spare = std::max(0.0, (double)t.smax * (double)ex - (double)score[k]);
     const double W = (double)ex + std::ceil(spare / (double)t.ext) + 2.0;
+    // lemma L18, the mirror image of L17: at most end_y diagonal or horizontal steps, hence at most (smax end_y - score) / e rows of gaps
+    const double spare_r = std::max(0.0, (double)t.smax * (double)ey - (double)score[k]);
+    const double Wr = (double)ey + std::ceil(spare_r / (double)t.ext) + 2.0;
     Job j;
-    j.q = (int)k; j.m = (int32_t)ex;
+    j.q = (int)k;
+    j.row_clamped = Wr >= (double)ex;
+    const int64_t mw = j.row_clamped ? ex : (int64_t)Wr;
+    j.row_lo = ex - mw;
     j.clamped = W >= (double)ey;
     const int64_t nw = j.clamped ? ey : (int64_t)W;
-    if (nw > (int64_t)kAffineTraceDirsMax || dirs_bytes(ex, nw) > kAffineTraceDirsMax) {
+    if (nw > (int64_t)kAffineTraceDirsMax || mw > (int64_t)kAffineTraceDirsMax || dirs_bytes(mw, nw) > kAffineTraceDirsMax) {
       char msg[200];
       std::snprintf(msg, sizeof msg, "affine traceback: a window of %lld rows x %lld columns needs more than %zu decision bytes",
-                    (long long)ex, (long long)nw, kAffineTraceDirsMax);
+                    (long long)mw, (long long)nw, kAffineTraceDirsMax);
       return fail(ctx, MI355_SW_ENOTSUP, msg);
     }
+    j.m = (int32_t)mw;
     j.nw = (int32_t)nw;
     j.wl = ey - nw;
     j.dirs_off = j.cons_off = 0;
-    if (affine_exact_lds(j.m) > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine traceback: alignment of more rows than the exact kernel's LDS diagonals hold");
+    if (affine_exact_lds(j.m) > kExactLdsMax) {
+      char msg[200];
+      std::snprintf(msg, sizeof msg, "affine traceback: a window of %lld rows x %lld columns has more rows than the exact kernel's LDS diagonals hold",
+                    (long long)mw, (long long)nw);
+      return fail(ctx, MI355_SW_ENOTSUP, msg);
+    }
     jobs.push_back(j);
   }
   if (jobs.empty()) return 0;
@@ -242,7 +412,7 @@ int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
       const Job &j = jobs[lo + k];
       AffineTraceProblem &a = pr[k];
       memset(&a, 0, sizeof a);
-      a.e.x = q.bytes.as<uint8_t>() + q.off[j.q];
+      a.e.x = q.bytes.as<uint8_t>() + q.off[j.q] + j.row_lo;
       a.e.y = ref.bytes.as<uint8_t>() + rg.lo + j.wl;
       a.e.m = j.m; a.e.nw = j.nw;
       a.e.col_offset = j.wl;
@@ -253,6 +423,7 @@ int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
       a.cons_x = ctx->cons.as<char>() + j.cons_off;
       a.cons_y = a.cons_x + a.cap;
       a.clamped = j.clamped ? 1 : 0;
+      a.row_clamped = j.row_clamped ? 1 : 0;
       a.out = ctx->walkp.as<int64_t>() + 3 * k;
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr.data(), n * sizeof(AffineTraceProblem), hipMemcpyHostToDevice, ctx->stream));
@@ -273,7 +444,7 @@ int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     for (size_t k = 0; k < n; ++k) {
       const Job &j = jobs[lo + k];
       const int64_t len = wo[3 * k], st = wo[3 * k + 2];
-      if (st == 1) return fail(ctx, MI355_SW_ENODEV, "internal: the affine traceback left its window (lemma L17)");
+      if (st == 1) return fail(ctx, MI355_SW_ENODEV, "internal: the affine traceback left its window (lemmas L17, L18)");
       if (st == 2) return fail(ctx, MI355_SW_ENODEV, "internal: the affine traceback exceeded its string capacity");
       if (st != 0) return fail(ctx, MI355_SW_ENODEV, "internal: the end cell of the affine traceback window does not hold the score");
       TraceOut &o = tout[j.q];
@@ -303,6 +474,28 @@ int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const
   if (t.smax <= 0) return 0;                                       // no positive cell: every maximum is 0
   HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
   const Margin mg = make_margin((double)t.smax, (double)t.ext, true, 0.0);   // lemma L15: L1-L4 with g := gap_extend
+
+  // ---- ranges of at most 512 columns: every non-empty query is a problem of sw_affine_prof_kernel, whatever its length ---------
+  // (a range whose problems hold fewer than kAffineProfMinCells cells in all, every one within the exact kernel's LDS, is so
+  // little work that it stays where it was: one launch of the exact kernel)
+  std::vector<char> rprof(nr, 0);
+  std::vector<size_t> prof_ranges;
+  AffineProfPlan plan;
+  bool any_short = false;
+  for (size_t r = 0; r < nr; ++r) any_short |= ranges[r].hi - ranges[r].lo >= 1 && ranges[r].hi - ranges[r].lo <= kWaveMaxLanesSide;
+  if (any_short) affine_prof_plan(ref, p, t, plan);
+  double batch_rows = 0;
+  for (size_t k = 0; k < nq; ++k) batch_rows += (double)q.len[k];
+  const bool exact_holds_all = affine_exact_lds(q.maxlen) <= kExactLdsMax;
+  for (size_t r = 0; r < nr; ++r) {
+    const int64_t n = ranges[r].hi - ranges[r].lo;
+    if (!affine_prof_range_ok(plan, t, n) || (exact_holds_all && batch_rows * (double)n < kAffineProfMinCells)) continue;
+    rprof[r] = 1; prof_ranges.push_back(r);
+  }
+  if (!prof_ranges.empty()) {
+    rc = affine_prof_run(ctx, ref, q, ranges, prof_ranges, p, t, plan, maxima, ends);
+    if (rc) return rc;
+  }
 
   // ---- which (query, range) the sweep takes -----------------------------------------------------------------------------
   std::vector<char> rsweep(nr, 0), qfast(nq, 0);
@@ -346,7 +539,7 @@ int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const
   for (size_t r = 0; r < nr; ++r) {
     const int64_t n = ranges[r].hi - ranges[r].lo;
     for (size_t k = 0; k < nq; ++k) {
-      if ((rsweep[r] && qfast[k]) || q.len[k] < 1 || n < 1) continue;
+      if (rprof[r] || (rsweep[r] && qfast[k]) || q.len[k] < 1 || n < 1) continue;
       if ((double)q.len[k] * (double)n > kAffineExactCellsMax || (double)t.smax * ((double)q.len[k] + 1.0) >= 16777216.0) {
         if (opt().no_affine_sweep) return fail(ctx, MI355_SW_ENOTSUP, "affine, option no_affine_sweep: a problem of more than 2^26 cells");
         return fail(ctx, MI355_SW_ENOTSUP, "affine: " + (why_slow.empty() ? std::string("problem outside the sweep") : why_slow) +

@@ -14,7 +14,7 @@ constexpr size_t kExactLdsMax = 159 * 1024;    // dynamic part; the wide instanc
 #define MI355_SW_BOOL_OPTIONS(X) \
   X(no_f16) X(no_unsat) X(no_sample) X(no_satflag) X(no_solo) X(no_wave) X(no_comb) X(no_twin) X(no_wide) X(no_strip) \
   X(no_quant) X(no_devlist) X(no_ref_cache) X(no_strip_groups) X(u8_long_twin) X(long_twin) X(no_long) \
-  X(no_requery) X(force_f32) X(no_long_p32) X(no_opt_margin) X(no_wave_prof) X(no_wave_window) X(no_first) X(no_long_save) X(u8_sample_short) X(no_wave_pieces) X(no_u8_early) X(no_wave_f16) X(no_devlist_by_id) X(no_f16_mirror) X(no_f16m_int_diag) X(no_affine_sweep) X(trace)
+  X(no_requery) X(force_f32) X(no_long_p32) X(no_opt_margin) X(no_wave_prof) X(no_wave_window) X(no_first) X(no_long_save) X(u8_sample_short) X(no_wave_pieces) X(no_u8_early) X(no_wave_f16) X(no_devlist_by_id) X(no_f16_mirror) X(no_f16m_int_diag) X(no_affine_sweep) X(no_affine_prof) X(trace)
 #define MI355_SW_INT_OPTIONS(X) X(strip_r) X(slot) X(few_r) X(chunk) X(long_pipes) X(long_wgs) X(long_sub) X(long_r) X(long_groups) X(assume_cus) X(long_save_what)
 struct Options {
 #define X(n) bool n = false;
@@ -329,6 +329,8 @@ struct mi355_sw_ctx {
   DevBuf colsave, rowsave, pieces, recs;
   DevBuf atab;                    // affine calls: the sweep's float16 score table (host_affine.h)
   std::vector<uint16_t> h_atab;
+  DevBuf aprof;                   // affine calls: class scores [nclass][letters] and the byte -> class table of sw_affine_prof_kernel
+  std::vector<float> h_aprof;
   std::vector<uint8_t> h_pieces;  // host side of the piece table of the running call (host_batch.h)
   size_t saved_locates = 0, saved_traces = 0, saved_fallbacks = 0;   // finish steps of the running call that started from saved state / fell back
   DevBuf qcnt, sel2, gcnt, wlut, ckpt, first, keys, ranges, stab, ftab, ftab_s, htab, htab8, soloblk, flags, submax, lut, probs, dirs, outs_f, outs_i, cons, walkp, hmat, brow, wprobs, scan;

@@ -8,7 +8,8 @@
 //   3. traceback       sw_wave_kernel / sw_strip_kernel (dirs) — window left of the argmax -> greedy decisions,
 //                      sw_wave_walk_kernel — the walk itself (smithwaterman.cpp:40-78)            host_wave.h
 //   (sw_exact_kernel + sw_walk_kernel, host_exact.h: table scoring on short queries, whole uint8 problems)
-//   affine gaps (score, end cell, traceback): sw_affine_kernel sweep + sw_affine_exact / _trace_kernel  host_affine.h
+//   affine gaps (score, end cell, traceback): sw_affine_kernel sweep + sw_affine_exact / _trace_kernel, and
+//                      sw_affine_prof_kernel for references (ranges) of at most 512 letters           host_affine.h
 // Problems the score kernel does not cover (see bucket_fast_ok) run 2+3 on the whole matrix.
 // The host code is one translation unit; the fragments below are included in order.
 #include "../../include/mi355_sw.h"
@@ -42,6 +43,7 @@
 #include "sw_solo_kernel.h"
 #include "sw_long_kernel.h"
 #include "sw_affine_kernel.h"
+#include "sw_affine_prof_kernel.h"
 
 using namespace mi355sw;
 
@@ -98,7 +100,7 @@ void mi355_sw_destroy(mi355_sw_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   DevBuf *bufs[] = {&c->qcnt, &c->sel2, &c->gcnt, &c->wlut, &c->ref.bytes, &c->ref.codes, &c->batch.bytes, &c->batch.lens, &c->keys, &c->ranges, &c->stab,
-                    &c->batch.offs, &c->batch.sel, &c->colsave, &c->rowsave, &c->pieces, &c->ftab, &c->ftab_s, &c->htab, &c->htab8, &c->soloblk, &c->flags, &c->submax, &c->lut, &c->probs, &c->dirs, &c->outs_f, &c->outs_i, &c->cons, &c->walkp, &c->hmat, &c->brow, &c->wprobs, &c->scan, &c->batch.cum, &c->ckpt, &c->first, &c->recs, &c->atab};
+                    &c->batch.offs, &c->batch.sel, &c->colsave, &c->rowsave, &c->pieces, &c->ftab, &c->ftab_s, &c->htab, &c->htab8, &c->soloblk, &c->flags, &c->submax, &c->lut, &c->probs, &c->dirs, &c->outs_f, &c->outs_i, &c->cons, &c->walkp, &c->hmat, &c->brow, &c->wprobs, &c->scan, &c->batch.cum, &c->ckpt, &c->first, &c->recs, &c->atab, &c->aprof};
   for (DevBuf *b : bufs) b->release();
   c->adhoc.release(); c->one.release();
   c->pin_probs.release(); c->pin_walk.release(); c->pin_out.release(); c->pin_solo_up.release(); c->pin_solo_down.release();

@@ -320,8 +320,8 @@ __global__ __launch_bounds__(64) void sw_affine_exact_kernel(const ExactProblem 
   }
 }
 
-// Traceback under affine gaps: the window [end_y - nw, end_y] x rows 1 .. end_x of one alignment (lemma L17), so
-// the end cell is the window's corner (e.m, e.nw).  e.target = the score, e.dirs = dirs_bytes(m, nw) bytes; e.best, e.cell,
+// Traceback under affine gaps: the window [end_y - nw, end_y] x [end_x - m, end_x] of one alignment (lemmas L17 and L18, DESIGN.md
+// §3.8: e.x is the first row of the window), so the end cell is the window's corner (e.m, e.nw).  e.target = the score, e.dirs = dirs_bytes(m, nw) bytes; e.best, e.cell,
 // e.own_lo unused.
 struct AffineTraceProblem {
   ExactProblem e;
@@ -329,8 +329,9 @@ struct AffineTraceProblem {
   char *cons_y;
   int32_t cap;
   int32_t clamped;        // the window starts at the range's first column: its left border is the problem's own
+  int32_t row_clamped;    // the window starts at the query's first row (e.x = x): its top border is the problem's own (lemma L18)
   // outputs: [0] consensus length, [1] pos (true column of the last letter pair), [2] status: 0 ok, 1 the walk left an
-  // unclamped window, 2 capacity exceeded, 3 the corner cell does not hold the score
+  // unclamped window (by its left or its top border), 2 capacity exceeded, 3 the corner cell does not hold the score
   int64_t *out;
 };
 
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(64) void sw_affine_trace_kernel(const AffineTracePr
   int64_t status = corner == P.target ? 0 : 3, pos = 0;
   while (status == 0) {
     if (i <= 0 || jl <= 0) {                                       // border: H = 0, stop
-      if (jl <= 0 && !T.clamped) status = 1;
+      if ((jl <= 0 && !T.clamped) || (i <= 0 && !T.row_clamped)) status = 1;
       break;
     }
     const int d = i + jl;

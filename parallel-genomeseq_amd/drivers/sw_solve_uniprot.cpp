@@ -1,7 +1,9 @@
 // sw_solve_uniprot — the many-alignment batch of the reference driver src/mpi_sw_solve_uniprot.cpp
 // (each database sequence as FIRST argument, the query protein as SECOND, SWAligner<Similarity_Matrix>,
 // default scoring, :120-122) as ONE device batch instead of an MPI task farm with a writer rank.
-//   sw_solve_uniprot [query.fasta] [db] [out.csv] [--count=N] [--devices=all|0,1,...] [--rccl]
+//   sw_solve_uniprot [query.fasta] [db] [out.csv] [--count=N] [--devices=all|0,1,...] [--rccl] [--affine=OPEN,EXTEND [--trace]]
+// --affine: the same batch under affine gaps (mi355_sw_affine_batch_run; with --trace mi355_sw_affine_batch_trace), default
+// match / mismatch, one device; pos_pred is the alignment's first column with --trace, else 0.
 // --devices (or MI355_SW_DEVICES): the database sequences are dealt to several GPUs of the node (query replicated, no
 // exchange during compute) in place of the reference's MPI worker ranks (:95-138); --rccl (or MI355_SW_MULTI_RCCL=1)
 // merges the per-device best (score, index) with ncclAllReduce(ncclMax, ncclUint64) instead of on the host.
@@ -60,7 +62,30 @@ int main(int argc, char **argv) {
   double t[6];
   std::vector<float> score(seqs.size());
   std::vector<uint32_t> pos(seqs.size());
-  if (multi) {
+  if (a.has("affine")) {
+    if (multi) { std::cerr << "--affine runs on one device" << std::endl; return 2; }
+    mi355_sw_affine_params ap;
+    mi355_sw_default_affine_params(&ap);
+    const std::string v = a.get("affine", "");
+    const size_t comma = v.find(',');
+    if (comma == std::string::npos) { std::cerr << "--affine=OPEN,EXTEND" << std::endl; return 2; }
+    ap.gap_open = std::stof(v.substr(0, comma)); ap.gap_extend = std::stof(v.substr(comma + 1));
+    std::string all;
+    std::vector<int64_t> offs(seqs.size() + 1, 0);
+    for (size_t k = 0; k < seqs.size(); ++k) { all += seqs[k]; offs[k + 1] = (int64_t)all.size(); }
+    parseq::check(mi355_sw_batch_upload_packed(ctx, seqs.size(), all.data(), offs.data()), "batch_upload_packed");
+    if (a.has("trace")) {
+      std::vector<mi355_sw_result> res(seqs.size());
+      parseq::check(mi355_sw_affine_batch_trace(ctx, &ap, res.data()), "affine_batch_trace");
+      for (size_t k = 0; k < seqs.size(); ++k) { score[k] = res[k].score; pos[k] = res[k].pos; }
+      mi355_sw_free_results(res.data(), res.size());
+    } else {
+      std::vector<int64_t> ex(seqs.size()), ey(seqs.size());
+      parseq::check(mi355_sw_affine_batch_run(ctx, &ap, score.data(), ex.data(), ey.data()), "affine_batch_run");
+    }
+    mi355_sw_last_timings(ctx, t);
+    std::cout << "affine " << ap.gap_open << " / " << ap.gap_extend << ": " << mi355_sw_last_path(ctx) << std::endl;
+  } else if (multi) {
     std::vector<const char *> xs(seqs.size());
     std::vector<size_t> nxs(seqs.size());
     for (size_t k = 0; k < seqs.size(); ++k) { xs[k] = seqs[k].data(); nxs[k] = seqs[k].size(); }
