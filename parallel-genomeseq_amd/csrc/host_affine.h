@@ -26,6 +26,23 @@ int affine_check(mi355_sw_ctx *ctx, const mi355_sw_affine_params *p) {
   return 0;
 }
 
+// the score of byte a of x against the reference's letter with code c
+inline float affine_score(const RefData &ref, const mi355_sw_affine_params &p, int a, int c) {
+  return p.lut ? p.lut[(size_t)a * 256 + ref.byte_of[c]] : ((uint8_t)a == ref.byte_of[c] ? p.match : p.mismatch);
+}
+
+// the scoring as the exact and the traceback kernel take it: the 256 x 256 table, where there is one, goes to the device
+int affine_scoring(mi355_sw_ctx *ctx, const mi355_sw_affine_params &p, AffineScoring &sc) {
+  sc.lut = nullptr;
+  if (p.lut) {
+    if (ctx->lut.ensure(65536 * 4)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(scoring table) failed");
+    HIPCHK(ctx, hipMemcpyAsync(ctx->lut.p, p.lut, 65536 * 4, hipMemcpyHostToDevice, ctx->stream));
+    sc.lut = ctx->lut.as<float>();
+  }
+  sc.match = p.match; sc.mismatch = p.mismatch; sc.gap_open = p.gap_open; sc.gap_extend = p.gap_extend;
+  return 0;
+}
+
 int affine_table(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_affine_params &p, AffineTable &t) {
   const int nc = ref.ncodes;
   if (p.gap_open != std::floor(p.gap_open) || p.gap_extend != std::floor(p.gap_extend))
@@ -36,7 +53,7 @@ int affine_table(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_affine_pa
   float smax = 0;
   for (int a = 0; a < 256; ++a)
     for (int c = 0; c < nc - 1; ++c) {
-      const float s = p.lut ? p.lut[(size_t)a * 256 + ref.byte_of[c]] : ((uint8_t)a == ref.byte_of[c] ? p.match : p.mismatch);
+      const float s = affine_score(ref, p, a, c);
       if (!std::isfinite(s)) return fail(ctx, MI355_SW_EINVAL, "affine scoring: a table entry is not finite");
       if (s != std::floor(s)) return fail(ctx, MI355_SW_ENOTSUP, "affine scoring: substitution scores must be integers");
       if (std::fabs(s) > 1.0e6f) return fail(ctx, MI355_SW_ENOTSUP, "affine scoring: substitution score beyond +-10^6");
@@ -96,16 +113,8 @@ int run_affine_exact(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
   }
   HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactProblem), hipMemcpyHostToDevice, ctx->stream));
   AffineScoring sc;
-  sc.lut = nullptr;
-  if (p.lut) {
-    if (ctx->lut.ensure(65536 * 4)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(scoring table) failed");
-    HIPCHK(ctx, hipMemcpyAsync(ctx->lut.p, p.lut, 65536 * 4, hipMemcpyHostToDevice, ctx->stream));
-    sc.lut = ctx->lut.as<float>();
-  }
-  sc.match = p.match; sc.mismatch = p.mismatch; sc.gap_open = p.gap_open; sc.gap_extend = p.gap_extend;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sw_affine_exact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(sw_affine_exact_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactProblem>(), sc);
+  { int rc = affine_scoring(ctx, p, sc); if (rc) return rc; }
+  launch_dyn_lds(&sw_affine_exact_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactProblem>(), sc);
   HIPCHK(ctx, hipGetLastError());
   std::vector<float> bf(n);
   std::vector<int64_t> ci(2 * n);
@@ -155,8 +164,6 @@ int affine_sweep_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch 
   const uint32_t nopen2 = (uint32_t)half_bits(-(float)t.open / kF16Scale) * 0x00010001u;
   const uint32_t next2 = (uint32_t)half_bits(-(float)t.ext / kF16Scale) * 0x00010001u;
   const size_t shmem = profile_lds_bytes(ref.ncodes, b.R, b.SL) + (size_t)nslot * codebuf_bytes(b.SL);
-  if (shmem > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
   // keep single launches to a few seconds: split the bucket's pairs over several launches
   const double cells_per_pair = 2.0 * std::max(1, b.maxlen) * std::max(1.0, range_cols);
   const size_t pairs_per_launch = (size_t)std::max(1.0, std::min((double)npairs, 2.0e13 / cells_per_pair));
@@ -164,7 +171,7 @@ int affine_sweep_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch 
     const size_t pn = std::min(pairs_per_launch, npairs - p0);
     a.qfirst = b.first + (int)(p0 * 2);
     a.qcount = std::min(b.count - (int)(p0 * 2), (int)(pn * 2));
-    hipLaunchKernelGGL(kern, dim3((unsigned)(pn * cgroups), (unsigned)nr), dim3(256), shmem, ctx->stream, a, nopen2, next2);
+    launch_dyn_lds(kern, dim3((unsigned)(pn * cgroups), (unsigned)nr), dim3(256), shmem, ctx->stream, a, nopen2, next2);
     HIPCHK(ctx, hipGetLastError());
     ctx->timings[4] += 1;
   }
@@ -199,10 +206,6 @@ struct AffineProfPlan {
   std::vector<int> rep;           // a byte of every class but the last
 };
 
-inline float affine_score(const RefData &ref, const mi355_sw_affine_params &p, int a, int c) {
-  return p.lut ? p.lut[(size_t)a * 256 + ref.byte_of[c]] : ((uint8_t)a == ref.byte_of[c] ? p.match : p.mismatch);
-}
-
 void affine_prof_plan(const RefData &ref, const mi355_sw_affine_params &p, const AffineTable &t, AffineProfPlan &plan) {
   plan.ok = false;
   const int nl = ref.ncodes - 1;
@@ -228,14 +231,7 @@ void affine_prof_plan(const RefData &ref, const mi355_sw_affine_params &p, const
 bool affine_prof_range_ok(const AffineProfPlan &plan, const AffineTable &t, int64_t n) {
   if (!plan.ok || n < 1 || n > kWaveMaxLanesSide) return false;
   if ((double)t.smax * ((double)n + 1.0) >= kAffineProfBound) return false;
-  return (size_t)plan.nclass * 16 * lane_stride(wave_prof_R((int)n)) * 4 <= kAffineProfLdsMax;
-}
-
-template <int R>
-void launch_affine_prof(hipStream_t st, size_t lds, unsigned blocks, const WaveProblem *dp, int n, const AffineProfArgs &sa) {
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sw_affine_prof_kernel<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((sw_affine_prof_kernel<R>), dim3(blocks), dim3(256), lds, st, dp, n, sa);
+  return wave_prof_lds(plan.nclass, wave_prof_R((int)n)) <= kAffineProfLdsMax;
 }
 
 // Every non-empty query of the batch against each range of `which` (indices into `ranges`, all affine_prof_range_ok): one launch
@@ -300,12 +296,10 @@ int affine_prof_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, 
     for (size_t g = 0; g < ng; ++g) {
       const Range &rg = ranges[which[g0 + g]];
       const int n = (int)(rg.hi - rg.lo), R = wave_prof_R(n);
-      const size_t lds = (size_t)plan.nclass * 16 * lane_stride(R) * 4;
       const WaveProblem *dp = ctx->wprobs.as<WaveProblem>() + g * count;
-      if (R == 9) launch_affine_prof<9>(ctx->stream, lds, blocks, dp, (int)count, sa);
-      else if (R == 10) launch_affine_prof<10>(ctx->stream, lds, blocks, dp, (int)count, sa);
-      else if (R == 20) launch_affine_prof<20>(ctx->stream, lds, blocks, dp, (int)count, sa);
-      else launch_affine_prof<32>(ctx->stream, lds, blocks, dp, (int)count, sa);
+      with_wave_R(R, [&](auto r) {
+        launch_dyn_lds(&sw_affine_prof_kernel<decltype(r)::value>, dim3(blocks), dim3(256), wave_prof_lds(plan.nclass, R), ctx->stream, dp, (int)count, sa);
+      });
       HIPCHK(ctx, hipGetLastError());
       path_note(ctx, "affine_prof[R=%d]", R);
       ctx->timings[4] += 1;
@@ -385,13 +379,7 @@ int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   if (jobs.empty()) return 0;
   path_note(ctx, "affine_trace");
   AffineScoring sc;
-  sc.lut = nullptr;
-  if (p.lut) {
-    if (ctx->lut.ensure(65536 * 4)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(scoring table) failed");
-    HIPCHK(ctx, hipMemcpyAsync(ctx->lut.p, p.lut, 65536 * 4, hipMemcpyHostToDevice, ctx->stream));
-    sc.lut = ctx->lut.as<float>();
-  }
-  sc.match = p.match; sc.mismatch = p.mismatch; sc.gap_open = p.gap_open; sc.gap_extend = p.gap_extend;
+  { int rc = affine_scoring(ctx, p, sc); if (rc) return rc; }
   for (size_t lo = 0; lo < jobs.size();) {
     size_t hi = lo, dirs_total = 0, cons_total = 0, lds = 0;
     while (hi < jobs.size() && hi - lo < 65536) {
@@ -427,10 +415,8 @@ int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
       a.out = ctx->walkp.as<int64_t>() + 3 * k;
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr.data(), n * sizeof(AffineTraceProblem), hipMemcpyHostToDevice, ctx->stream));
-    if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sw_affine_trace_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-    hipLaunchKernelGGL(sw_affine_trace_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<AffineTraceProblem>(), sc);
+    launch_dyn_lds(&sw_affine_trace_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<AffineTraceProblem>(), sc);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     std::vector<int64_t> wo(3 * n);

@@ -23,12 +23,6 @@ int device_scan(mi355_sw_ctx *ctx, int64_t *v, int64_t n, int64_t *total_dev) {
   return 0;
 }
 
-template <int R, int ORIENT>
-void launch_wave_batch(bool dirs, unsigned blocks, hipStream_t st, const WaveProblem *pr, int n, const WaveScoring &sc) {
-  if (dirs) hipLaunchKernelGGL((sw_wave_kernel<R, ORIENT, false, true, true>), dim3(blocks), dim3(256), 0, st, pr, n, sc);
-  else hipLaunchKernelGGL((sw_wave_kernel<R, ORIENT, false, true, false>), dim3(blocks), dim3(256), 0, st, pr, n, sc);
-}
-
 // loc / tout / handled are indexed by query id.  Long ranges are cut so that a launch's decisions fit the scratch
 // budget; a single problem beyond it is left to the windowed path (handled stays 0).
 int exact_full_device(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_params &p,
@@ -168,12 +162,11 @@ int exact_full_device(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q
     if (!f16) prof_rc = prof ? launch_wave_prof(ctx, ref, p, R, (int)nref, true, want_trace, pblocks, dp, (int)nprob) : 1;
     if (prof_rc < 0) return prof_rc;
     if (prof_rc == 0 && npieces) hipLaunchKernelGGL(batch_seq_results, dim3(sblocks), dim3(256), 0, ctx->stream, a);
-#define BATCH_WAVE(r)                                                                                                   \
-  if (orient == 0) launch_wave_batch<r, 0>(want_trace, blocks, ctx->stream, dp, (int)n, sc);                            \
-  else launch_wave_batch<r, 1>(want_trace, blocks, ctx->stream, dp, (int)n, sc);
-    if (prof_rc == 0) { }
-    else if (R == 10) { BATCH_WAVE(10) } else if (R == 20) { BATCH_WAVE(20) } else { BATCH_WAVE(32) }
-#undef BATCH_WAVE
+    if (prof_rc != 0) {
+      const WaveKernel kern = wave_kernel(R, orient, false, true, want_trace, false);
+      if (!kern) return fail(ctx, MI355_SW_EINVAL, "internal: no wave kernel instance for nine rows per lane");
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, ctx->stream, dp, (int)n, sc);
+    }
   }
   HIPCHK(ctx, hipGetLastError());
   path_note(ctx, "devlist[orient=%d,R=%d,prof=%d,f16=%d,windows=%d,trace=%d,pieces=%d]", orient, R, (int)prof, f16, (int)windows, (int)want_trace, (int)(npieces != 0));

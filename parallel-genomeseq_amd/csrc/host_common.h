@@ -378,6 +378,13 @@ struct OptScope {
     }                                                                                      \
   } while (0)
 
+// A launch with `lds` bytes of dynamic LDS: beyond 48 KiB the kernel has to be allowed the size first.
+template <class... P, class... A>
+void launch_dyn_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+}
+
 // One tag per kernel family / pipeline decision of the running call, each at most once (mi355_sw_last_path: what the parity
 // tests assert a switch ENGAGED with — a switch that is silently ignored would still give the oracle's answers).
 void path_note(mi355_sw_ctx *ctx, const char *fmt, ...) __attribute__((format(printf, 2, 3)));

@@ -36,39 +36,59 @@ struct WaveJob {
   size_t dirs_off = 0;
 };
 
+// The one place that turns rows per lane into a template argument, for every kernel of the wave family (sw_wave_common.h):
+// f(std::integral_constant<int, R>) for R = 9 (the profile kernels only: wave_prof_R), 10, 20, else 32.
+template <class F>
+void with_wave_R(int R, F f) {
+  if (R == 9) f(std::integral_constant<int, 9>{});
+  else if (R == 10) f(std::integral_constant<int, 10>{});
+  else if (R == 20) f(std::integral_constant<int, 20>{});
+  else f(std::integral_constant<int, 32>{});
+}
+
+// The sw_wave_kernel instance of a launch: tracking, decisions or both; keyed tracking (lanes = rows of x).  Null for nine rows per
+// lane, which wave_R never picks: the kernel has no such instance.
+typedef void (*WaveKernel)(const WaveProblem *, int, const WaveScoring);
 template <int R, int ORIENT, bool U8>
-void launch_wave_flags(bool track, bool dirs, unsigned blocks, hipStream_t st, const WaveProblem *pr, int n, const WaveScoring &sc) {
-  if (track && dirs) hipLaunchKernelGGL((sw_wave_kernel<R, ORIENT, U8, true, true>), dim3(blocks), dim3(256), 0, st, pr, n, sc);
-  else if (track) hipLaunchKernelGGL((sw_wave_kernel<R, ORIENT, U8, true, false>), dim3(blocks), dim3(256), 0, st, pr, n, sc);
-  else hipLaunchKernelGGL((sw_wave_kernel<R, ORIENT, U8, false, true>), dim3(blocks), dim3(256), 0, st, pr, n, sc);
+WaveKernel wave_kernel_flags(bool track, bool dirs) {
+  if (track && dirs) return &sw_wave_kernel<R, ORIENT, U8, true, true>;
+  return track ? &sw_wave_kernel<R, ORIENT, U8, true, false> : &sw_wave_kernel<R, ORIENT, U8, false, true>;
+}
+WaveKernel wave_kernel(int R, int orient, bool u8, bool track, bool dirs, bool keyed) {
+  WaveKernel k = nullptr;
+  with_wave_R(R, [&](auto r) {
+    constexpr int kR = decltype(r)::value;
+    if constexpr (kR != 9) {
+      if (keyed) k = u8 ? &sw_wave_kernel<kR, 0, true, true, false, true> : &sw_wave_kernel<kR, 0, false, true, false, true>;
+      else if (orient == 0) k = u8 ? wave_kernel_flags<kR, 0, true>(track, dirs) : wave_kernel_flags<kR, 0, false>(track, dirs);
+      else k = u8 ? wave_kernel_flags<kR, 1, true>(track, dirs) : wave_kernel_flags<kR, 1, false>(track, dirs);
+    }
+  });
+  return k;
 }
 
-template <int R>
-void launch_wave_keyed(bool u8, unsigned blocks, hipStream_t st, const WaveProblem *pr, int n, const WaveScoring &sc) {
-  if (u8) hipLaunchKernelGGL((sw_wave_kernel<R, 0, true, true, false, true>), dim3(blocks), dim3(256), 0, st, pr, n, sc);
-  else hipLaunchKernelGGL((sw_wave_kernel<R, 0, false, true, false, true>), dim3(blocks), dim3(256), 0, st, pr, n, sc);
+// the power of two 2^e, e in [-10, 10], that all three scores are multiples of: the largest one, or 0 where there is none
+float score_quantum(const mi355_sw_params &p) {
+  for (int e = 10; e >= -10; --e) {
+    const float c = std::ldexp(1.0f, e);
+    if (std::floor(p.match / c) == p.match / c && std::floor(p.mismatch / c) == p.mismatch / c && std::floor(p.gap / c) == p.gap / c) return c;
+  }
+  return 0.0f;
 }
 
-template <int R>
-void launch_wave_R(int orient, bool u8, bool track, bool dirs, unsigned blocks, hipStream_t st, const WaveProblem *pr, int n, const WaveScoring &sc) {
-  if (orient == 0) { if (u8) launch_wave_flags<R, 0, true>(track, dirs, blocks, st, pr, n, sc); else launch_wave_flags<R, 0, false>(track, dirs, blocks, st, pr, n, sc); }
-  else { if (u8) launch_wave_flags<R, 1, true>(track, dirs, blocks, st, pr, n, sc); else launch_wave_flags<R, 1, false>(track, dirs, blocks, st, pr, n, sc); }
-}
+// bytes of a profile of `nrows` codes or classes for the kernels with R cells per lane (sw_wave_common.h: wave_fill_profile)
+size_t wave_prof_lds(int nrows, int R) { return (size_t)nrows * 16 * lane_stride(R) * 4; }
 
 // sw_wave_prof_kernel for a launch whose lanes hold columns of the reference range (ORIENT 1), float engine, identity scoring:
 // the query profile over the shared lane side + the three-op cell (sw_wave_kernel.h).  Returns 1 when it does not apply
 // (the caller launches sw_wave_kernel), 0 when launched, < 0 on error.
 bool wave_prof_ok(const RefData &ref, const mi355_sw_params &p, int R, int na, bool track) {
   if (opt().no_wave_prof || p.semantics != MI355_SW_F32 || !wave_scoring_ok(p) || ref.ncodes < 2 || ref.ncodes > 256) return false;
-  if ((size_t)ref.ncodes * 16 * lane_stride(R) * 4 > 96 * 1024) return false;   // (alphabets of > 120 letters at R = 10)
+  if (wave_prof_lds(ref.ncodes, R) > 96 * 1024) return false;      // (alphabets of > 120 letters at R = 10)
   // The tracking key borrows the five lowest mantissa bits of a cell (sw_wave_kernel.h): every reachable value must be a
   // multiple of q = 2^e below 2^18 q — scores that are multiples of q, and match * (lane side + 1) < 2^18 q.
   if (track) {
-    float q = 0.0f;
-    for (int e = 10; e >= -10 && q == 0.0f; --e) {
-      const float c = std::ldexp(1.0f, e);
-      if (std::floor(p.match / c) == p.match / c && std::floor(p.mismatch / c) == p.mismatch / c && std::floor(p.gap / c) == p.gap / c) q = c;
-    }
+    const float q = score_quantum(p);
     if (q == 0.0f || (double)p.match * ((double)na + 1.0) >= 262144.0 * (double)q) return false;
   }
   return true;
@@ -91,7 +111,7 @@ int wave_tables(mi355_sw_ctx *ctx, const RefData &ref) {
 int launch_wave_prof(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_params &p, int R, int na, bool track, bool dirs,
                      unsigned blocks, const WaveProblem *dp, int n) {
   if (!wave_prof_ok(ref, p, R, na, track)) return 1;
-  const size_t lds = (size_t)ref.ncodes * 16 * lane_stride(R) * 4;
+  const size_t lds = wave_prof_lds(ref.ncodes, R);
   { int rc_t = wave_tables(ctx, ref); if (rc_t) return rc_t; }
   WaveProfArgs sa;
   sa.lut = ctx->wlut.as<uint8_t>();
@@ -101,28 +121,14 @@ int launch_wave_prof(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_param
   const int k = std::max(1, std::min(100, std::ilogb((double)p.match * ((double)na + 1.0) + 1.0) + 2));
   sa.match_s = std::ldexp(p.match, -k); sa.mismatch_s = std::ldexp(p.mismatch, -k); sa.gap_s = std::ldexp(p.gap, -k);
   sa.unscale = std::ldexp(1.0f, k);
-  {
-    // states saved by sw_wave_prof16_kernel hold H / (q 2048), q = the power of two all three scores are multiples of
-    float q = 1.0f;
-    for (int e = 10; e >= -10; --e) {
-      const float c = std::ldexp(1.0f, e);
-      if (std::floor(p.match / c) == p.match / c && std::floor(p.mismatch / c) == p.mismatch / c && std::floor(p.gap / c) == p.gap / c) { q = c; break; }
-    }
-    sa.ck16_scale = std::ldexp(q, 11 - k);
-  }
-#define WAVE_PROF(r)                                                                                                                  \
-  {                                                                                                                                   \
-    if (lds > 48 * 1024) {                                                                                                            \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sw_wave_prof_kernel<r, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sw_wave_prof_kernel<r, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sw_wave_prof_kernel<r, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    }                                                                                                                                 \
-    if (track && dirs) hipLaunchKernelGGL((sw_wave_prof_kernel<r, true, true>), dim3(blocks), dim3(256), lds, ctx->stream, dp, n, sa);  \
-    else if (track) hipLaunchKernelGGL((sw_wave_prof_kernel<r, true, false>), dim3(blocks), dim3(256), lds, ctx->stream, dp, n, sa);   \
-    else hipLaunchKernelGGL((sw_wave_prof_kernel<r, false, true>), dim3(blocks), dim3(256), lds, ctx->stream, dp, n, sa);              \
-  }
-  if (R == 9) WAVE_PROF(9) else if (R == 10) WAVE_PROF(10) else if (R == 20) WAVE_PROF(20) else WAVE_PROF(32)
-#undef WAVE_PROF
+  // states saved by sw_wave_prof16_kernel hold H / (q 2048), q = the score quantum (1 where there is none: that kernel then never ran)
+  const float q = score_quantum(p);
+  sa.ck16_scale = std::ldexp(q != 0.0f ? q : 1.0f, 11 - k);
+  with_wave_R(R, [&](auto r) {
+    constexpr int kR = decltype(r)::value;
+    auto kern = track && dirs ? &sw_wave_prof_kernel<kR, true, true> : track ? &sw_wave_prof_kernel<kR, true, false> : &sw_wave_prof_kernel<kR, false, true>;
+    launch_dyn_lds(kern, dim3(blocks), dim3(256), lds, ctx->stream, dp, n, sa);
+  });
   return 0;
 }
 
@@ -135,16 +141,11 @@ int launch_wave_prof(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_param
 int launch_wave_prof16(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_params &p, int R, int na, int64_t max_stream,
                        const WaveProblem *dp, int n) {
   if (opt().no_wave_f16 || (R != 9 && R != 10) || max_stream > 65000 || !wave_prof_ok(ref, p, R, na, true)) return 1;
-  float q = 0.0f;
-  int e = 10;
-  for (; e >= -10 && q == 0.0f; --e) {
-    const float c = std::ldexp(1.0f, e);
-    if (std::floor(p.match / c) == p.match / c && std::floor(p.mismatch / c) == p.mismatch / c && std::floor(p.gap / c) == p.gap / c) { q = c; break; }
-  }
+  const float q = score_quantum(p);
   if (q == 0.0f) return 1;
   const double lim = 2048.0 * (double)q;
   if ((double)p.match * ((double)na + 1.0) >= lim || std::fabs((double)p.mismatch) >= lim || (double)p.gap >= lim || !(p.gap > 0.0f)) return 1;
-  const size_t lds = 2 * (size_t)ref.ncodes * 16 * lane_stride(R) * 4;
+  const size_t lds = 2 * wave_prof_lds(ref.ncodes, R);             // (one profile per half)
   if (lds > 60 * 1024) return 1;
   int rc = wave_tables(ctx, ref);
   if (rc) return rc;
@@ -157,14 +158,10 @@ int launch_wave_prof16(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_par
   sa.ngap2 = (uint32_t)half_bits(-p.gap / unit) * 0x00010001u;
   sa.unscale = unit;
   const unsigned blocks = (unsigned)((n + 31) / 32);
-#define WAVE_PROF16(r)                                                                                                               \
-  {                                                                                                                                   \
-    if (lds > 48 * 1024)                                                                                                              \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sw_wave_prof16_kernel<r>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((sw_wave_prof16_kernel<r>), dim3(blocks), dim3(256), lds, ctx->stream, dp, n, sa);                             \
-  }
-  if (R == 9) WAVE_PROF16(9) else WAVE_PROF16(10)
-#undef WAVE_PROF16
+  with_wave_R(R, [&](auto r) {
+    constexpr int kR = decltype(r)::value;
+    if constexpr (kR <= 10) launch_dyn_lds(&sw_wave_prof16_kernel<kR>, dim3(blocks), dim3(256), lds, ctx->stream, dp, n, sa);   // (R is 9 or 10: above)
+  });
   return 0;
 }
 
@@ -221,16 +218,11 @@ int run_wave(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const R
     prof_rc = launch_wave_prof(ctx, ref, p, R, (int)nref, track, dirs, blocks, dp, (int)n);
     if (prof_rc < 0) return prof_rc;
   }
-  if (prof_rc == 0) {
+  if (prof_rc != 0) {
+    const WaveKernel kern = wave_kernel(R, orient, u8, track, dirs, keyed);
+    if (!kern) return fail(ctx, MI355_SW_EINVAL, "internal: no wave kernel instance for nine rows per lane");
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, ctx->stream, dp, (int)n, sc);
   }
-  else if (keyed) {
-    if (R == 10) launch_wave_keyed<10>(u8, blocks, ctx->stream, dp, (int)n, sc);
-    else if (R == 20) launch_wave_keyed<20>(u8, blocks, ctx->stream, dp, (int)n, sc);
-    else launch_wave_keyed<32>(u8, blocks, ctx->stream, dp, (int)n, sc);
-  }
-  else if (R == 10) launch_wave_R<10>(orient, u8, track, dirs, blocks, ctx->stream, dp, (int)n, sc);
-  else if (R == 20) launch_wave_R<20>(orient, u8, track, dirs, blocks, ctx->stream, dp, (int)n, sc);
-  else launch_wave_R<32>(orient, u8, track, dirs, blocks, ctx->stream, dp, (int)n, sc);
   HIPCHK(ctx, hipGetLastError());
   path_note(ctx, "wave[orient=%d,R=%d,track=%d,dirs=%d,keyed=%d,prof=%d,u8=%d]", orient, R, (int)track, (int)dirs, (int)keyed, (int)(prof_rc == 0), (int)u8);
   if (track) {

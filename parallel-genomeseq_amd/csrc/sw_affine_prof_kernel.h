@@ -1,10 +1,9 @@
 // sw_affine_prof_kernel.h — affine-gap (Gotoh) database search against ONE SHORT second sequence, hand-written HIP for gfx950.
 //
-// The affine, table-scoring sibling of sw_wave_prof_kernel<R, TRACK = true, DIRS = false> (sw_wave_kernel.h) and the third score
-// kernel of the affine path (sw_affine_kernel.h): many database sequences x, each against the same y of at most
-// 512 letters (a range of the resident reference).  Geometry as there: 256 threads = 16 slots of 16 lanes, one problem per slot,
-// lane l holds columns l R .. l R + R - 1 of y, the rows of x stream through the slot's code window (64-step segments behind a
-// 16-byte history, prefetched one segment ahead), lane l works on row k - l at step k.
+// The third score kernel of the affine path (sw_affine_kernel.h): many database sequences x, each against the same
+// y of at most 512 letters (a range of the resident reference).  Slot geometry, stream window and winner: sw_wave_common.h; lane l
+// holds columns l R .. l R + R - 1 of y, the rows of x stream.  The affine, table-scoring counterpart of sw_wave_prof_kernel<R,
+// TRACK = true, DIRS = false> (sw_wave_kernel.h).
 //
 //   E(i,j) = max(E(i,j-1) - e, H(i,j-1) - o)     runs along the columns of y: down the lane's R columns within a step (Erun),
 //                                                handed to the next lane by one DPP row_shr:1
@@ -26,15 +25,11 @@
 // same row of scores against the reference's letters (identity scoring: one per letter of y and one for all others; a 20-letter
 // table: 21); one more class, "outside", for the steps in front of and beyond the stream.  Padding columns (j >= |y|) and the
 // outside class score kPadScoreF: their H is max(0, E, F), strictly below a real cell (L15 (e)), so they never win.
-//
-// The end cell is the first maximum in column-major order (include/mi355_sw.h): per lane one orderable key, bits(H) | (31 -
-// column in the lane) — the five lowest mantissa bits of every cell are zero — folded by v_max3_f32 two cells at a time, and per
-// step a strict '>' that keeps the first row; then (value, smaller column, smaller row) across the sixteen lanes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sw_wave_kernel.h"
+#include "sw_wave_common.h"
 
 namespace mi355sw {
 
@@ -52,12 +47,10 @@ struct AffineProfArgs {
 template <int R>
 __global__ __launch_bounds__(256) void sw_affine_prof_kernel(const WaveProblem *probs, int nprob, const AffineProfArgs sa) {
   static_assert(R >= 1 && R <= 32, "the key holds the column within the lane in five bits");
-  constexpr int LS = lane_stride(R);                               // dwords between the profile rows of adjacent lanes
-  constexpr int NQ4 = (R + 3) / 4;
   extern __shared__ __attribute__((aligned(16))) uint32_t apsmem[];
   __shared__ __attribute__((aligned(16))) uint8_t win[16 * kWaveBuf];
   __shared__ uint8_t cls_s[256];
-  float *prof = reinterpret_cast<float *>(apsmem);                 // [nclass][16][LS]
+  float *prof = reinterpret_cast<float *>(apsmem);                 // [nclass][16][lane_stride(R)]
   const int tid = threadIdx.x;
   const int l = tid & 15;
   const int slot = tid >> 4;
@@ -78,32 +71,19 @@ __global__ __launch_bounds__(256) void sw_affine_prof_kernel(const WaveProblem *
     const int j = ll * R + r;
     float v = kPadScoreF;                                          // padding columns: the clamp makes 0 of them
     if (j < na) v = sa.ctab[c * sa.nletters + (int)ycodes[j]];
-    prof[(c * 16 + ll) * LS + r] = v;
+    prof[(c * 16 + ll) * lane_stride(R) + r] = v;
   }
   __syncthreads();
 
-  // stream window of CLASSES: 16 B history + 64 B segment per slot, refilled every 64 steps
+  // stream window of CLASSES (in front of the first row and beyond the last: `outside`)
+  auto stage_load = [&](int seg) -> uint32_t {
+    return wave_stage_word(xb, nb, seg * kWaveSeg + 4 * l, [&](bool in, uint32_t byte) { return in ? (uint32_t)cls_s[byte] : outside; });
+  };
+  int nseg, steps4;
+  wave_steps(nb, 16, nseg, steps4);
   uint8_t *buf = win + slot * kWaveBuf;
   uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
   const uint8_t *buf_lane = buf + 16 - l;
-  auto stage_load = [&](int seg) -> uint32_t {
-    const int c0 = seg * kWaveSeg + 4 * l;
-    uint32_t w = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int t = c0 + k;
-      const uint32_t ch = (uint32_t)t < (uint32_t)nb ? (uint32_t)cls_s[xb[t]] : outside;
-      w |= ch << (8 * k);
-    }
-    return w;
-  };
-  // steps this wavefront needs: the longest of its four slots (+ 15 of skew, + 1); wave-uniform
-  int steps = nb + 16;
-  steps = max(steps, __shfl_xor(steps, 16));
-  steps = max(steps, __shfl_xor(steps, 32));
-  const int nseg = (steps + kWaveSeg - 1) / kWaveSeg;
-  const int steps4 = (steps + 3) & ~3;                             // the last segment stops at the wavefront's last step (in fours)
-
   uint32_t nextc = stage_load(0);
   if (l < 4) buf32[l] = outside * 0x01010101u;                     // history in front of the first row
   buf32[4 + l] = nextc;
@@ -117,9 +97,8 @@ __global__ __launch_bounds__(256) void sw_affine_prof_kernel(const WaveProblem *
   for (int r = 0; r < R; ++r) { F[r] = -ov; Ho[r] = -ov; }
   float up_prev = -ov;                                             // Ho of the previous lane's last column, one row up
   float eout = -ov;                                                // E this lane hands to the next one
-  float blk = 0.0f;                                                // this lane's best key (value | 31 - column in the lane) ...
-  int tl = 0;                                                      // ... and the row it was first seen at
-  const float *prof_lane = prof + l * LS;
+  WaveKeyFold key;
+  const float *prof_lane = prof + l * lane_stride(R);
 
   for (int seg = 0; seg < nseg; ++seg) {
     const int kq = min(kWaveSeg, steps4 - seg * kWaveSeg) >> 2;
@@ -129,10 +108,10 @@ __global__ __launch_bounds__(256) void sw_affine_prof_kernel(const WaveProblem *
         const int k = 4 * k4 + ku;
         const int t = seg * kWaveSeg + k - l;                      // this lane's row of x (0-based)
         const uint32_t c = (uint32_t)buf_lane[k];
-        const u32x4 *pp = static_cast<const u32x4 *>(__builtin_assume_aligned(prof_lane + c * (16 * LS), 16));
-        uint32_t p[NQ4 * 4];
+        const u32x4 *pp = static_cast<const u32x4 *>(__builtin_assume_aligned(prof_lane + c * (16 * lane_stride(R)), 16));
+        uint32_t p[(R + 3) / 4 * 4];
 #pragma unroll
-        for (int q = 0; q < NQ4; ++q) {
+        for (int q = 0; q < (R + 3) / 4; ++q) {
           const u32x4 v = pp[q];
           p[4 * q + 0] = v.x; p[4 * q + 1] = v.y; p[4 * q + 2] = v.z; p[4 * q + 3] = v.w;
         }
@@ -151,10 +130,7 @@ __global__ __launch_bounds__(256) void sw_affine_prof_kernel(const WaveProblem *
           asm("v_sub_f32 %0, %1, %2" : "=v"(f) : "v"(F[r]), "v"(ev));
           asm("v_max_f32 %0, %1, %2" : "=v"(f) : "v"(f), "v"(w));
           asm("v_max3_f32 %0, %1, %2, %3" : "=v"(h) : "v"(x), "v"(f), "v"(erun));
-          const float hk = __uint_as_float(__float_as_uint(h) | (uint32_t)(31 - r));     // (value, smaller column first)
-          if (r & 1) asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(tpend), "v"(hk));
-          else if (r + 1 < R) tpend = hk;
-          else m = fmaxf(m, hk);
+          WaveKeyFold::cell<R>(r, h, m, tpend);
           asm("v_sub_f32 %0, %1, %2" : "=v"(ho) : "v"(h), "v"(ov));
           asm("v_sub_f32 %0, %1, %2" : "=v"(es) : "v"(erun), "v"(ev));
           asm("v_max_f32 %0, %1, %2" : "=v"(erun) : "v"(es), "v"(ho));
@@ -163,10 +139,7 @@ __global__ __launch_bounds__(256) void sw_affine_prof_kernel(const WaveProblem *
           diag = w;
         }
         eout = erun;
-        // strict '>': an equal key (same value, same column) at a later row does not replace the first.  Rows beyond the stream's
-        // end and padding columns hold values strictly below some real cell: they can lead a lane for a while, never the slot.
-        tl = m > blk ? t : tl;
-        blk = fmaxf(blk, m);
+        key.end(t, m);
       }
     }
     const uint32_t hist = buf32[kWaveSeg / 4 + (l & 3)];
@@ -175,23 +148,11 @@ __global__ __launch_bounds__(256) void sw_affine_prof_kernel(const WaveProblem *
     nextc = stage_load(seg + 2);
   }
 
-  // the lane's winner -> across the 16 lanes: value, then column of y, then row of x
-  const uint32_t kb = __float_as_uint(blk);
-  float bv = __uint_as_float(kb & ~31u) * sa.unscale;
-  long long bj = (long long)l * R + (31 - (int)(kb & 31u)) + 1, bi = (long long)tl + 1;
-  if (!(bv > 0.0f)) { bv = 0.0f; bi = 0; bj = 0; }
-#pragma unroll
-  for (int off = 8; off >= 1; off >>= 1) {
-    const float obv = __shfl_xor(bv, off, 16);
-    const long long oi = __shfl_xor(bi, off, 16);
-    const long long oj = __shfl_xor(bj, off, 16);
-    if (obv > bv || (obv == bv && obv > 0.0f && (oj < bj || (oj == bj && oi < bi)))) { bv = obv; bi = oi; bj = oj; }
-  }
-  if (l == 0 && active) {
-    *probs[pid].best = bv;
-    probs[pid].cell[0] = bv > 0.0f ? bi : 0;
-    probs[pid].cell[1] = bv > 0.0f ? bj : 0;
-  }
+  float bv;
+  long long bi, bj;
+  key.template winner<R>(l, sa.unscale, 0, bv, bi, bj);
+  slot_first_max(bv, bi, bj);
+  wave_store_winner(probs + pid, active, l, bv, bi, bj);
 }
 
 }  // namespace mi355sw

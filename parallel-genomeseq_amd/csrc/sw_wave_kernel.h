@@ -19,49 +19,14 @@
 #include <stdint.h>
 
 #include "sw_exact_kernel.h"   // kDir*
-#include "sw_score_kernel.h"   // lane_stride, u32x4, kPadScoreF
+#include "sw_wave_common.h"    // WaveProblem, the slot window, step count, profile and winner fold
 
 namespace mi355sw {
-
-struct WaveProblem {
-  const uint8_t *a;      // sequence held on lanes: x (ORIENT 0) or y (ORIENT 1); na <= 16*R
-  const uint8_t *b;      // streamed sequence: window of y (ORIENT 0) or window of x (ORIENT 1)
-  int32_t na, nb;
-  int64_t b_offset;      // true (1-based) stream index = b_offset + t + 1 for stream position t
-  uint32_t *dirs;        // DIRS: [nb + 15][16][W] packed decisions (2 bits per cell, cell r of a lane at bit 2*(r%16)); lane l's
-                         // decisions for stream position t are in row t + l (the step they were made at); or null
-  float *best;           // TRACK: maximum (0 when no positive cell)
-  int64_t *cell;         // TRACK: [2] = row (into x), column (into y), 1-based, of the first maximum
-  // KEYED tracking (ORIENT 0): the first cell in the engine's storage order (order_key<>, sw_exact_kernel.h) among
-  // the cells equal to `target` at stream positions >= own_lo; best = target when found, else -1
-  float target;
-  int32_t own_lo;
-  int64_t full_n;        // |y| of the full problem (uint8 storage order)
-  // sw_wave_prof_kernel only (checkpointed whole problems, host_batch.h).  TRACK without DIRS: where the state of the slot's
-  // wavefront is saved after every kCkptEvery-th step (null: nowhere).  DIRS without TRACK: k0 > 0 resumes the problem at step k0
-  // (a multiple of kCkptEvery) from the state saved there; nb is then the END of the rows to run, dirs rows count from step k0.
-  float *ckpt;
-  int32_t k0;
-  // DIRS resumed from a state sw_wave_prof16_kernel saved: that kernel stores its packed registers as they are, one row of
-  // 16 x (R + 1) dwords per saved state for the PAIR of problems a slot runs (ckpt of the pair's first problem); 1 / 2 = this
-  // problem was the low / high half (0: float32 states of its own, sw_wave_prof_kernel<TRACK>)
-  int32_t ck_half;
-  // DIRS of a window that ENDS at the argmax (host_batch.h): the walk only moves up and to the left, so decisions are wanted of
-  // the lanes up to the argmax column's; the launch then runs nb - k0 + lanes_used steps instead of nb - k0 + 16 (0: all lanes)
-  int32_t lanes_used;
-};
 
 struct WaveScoring {
   float match, mismatch, gap;
   float u8M, u8X, u8G;   // uint8 engine parameters as floats
 };
-
-constexpr int kWaveSeg = 64;
-constexpr int kWaveBuf = 16 + kWaveSeg;
-constexpr int kCkptEvery = 32;           // steps between two saved states of a checkpointed pass (sw_wave_prof_kernel / sw_wave_prof16_kernel);
-                                         // 16 was measured: decision pass 1.51 -> 1.32 ms, first pass 2.81 -> 2.93 ms, twice the states: not taken
-constexpr int kCkptPerSeg = kWaveSeg / kCkptEvery;
-static_assert(kWaveSeg % kCkptEvery == 0 && kCkptEvery % 4 == 0, "states are saved inside and at the end of every 64-step segment");
 
 template <int R, int ORIENT, bool U8, bool TRACK, bool DIRS, bool KEYED = false>
 __global__ __launch_bounds__(256) void sw_wave_kernel(const WaveProblem *probs, int nprob, const WaveScoring sc) {
@@ -72,10 +37,7 @@ __global__ __launch_bounds__(256) void sw_wave_kernel(const WaveProblem *probs, 
   const int slot = tid >> 4;
   const int pid = blockIdx.x * 16 + slot;
   const bool active = pid < nprob;
-  WaveProblem P;
-  if (active) P = probs[pid];
-  else { P.a = nullptr; P.b = nullptr; P.na = 0; P.nb = 0; P.b_offset = 0; P.dirs = nullptr; P.best = nullptr; P.cell = nullptr;
-         P.target = -1.0f; P.own_lo = 0; P.full_n = 0; P.ckpt = nullptr; P.k0 = 0; P.ck_half = 0; P.lanes_used = 0; }
+  const WaveProblem P = wave_problem_or_idle(probs, pid, nprob);
   const int na = P.na, nb = P.nb;
 
   // this lane's R characters of the short side (0xFFFF = padding, never equal to a byte)
@@ -86,7 +48,9 @@ __global__ __launch_bounds__(256) void sw_wave_kernel(const WaveProblem *probs, 
     ca[r] = (ai < na) ? (uint32_t)P.a[ai] : 0xFFFFu;
   }
 
-  // stream window: 16 B history + 64 B segment per slot, refilled every 64 steps (as sw_score_kernel.h)
+  // Stream window of raw bytes (sw_wave_common.h; positions outside the stream: 0, and marked in the step loop), whole segments.
+  // Stage load, step count and the 16-lane reduction below are written out, not wave_stage_word / wave_steps / slot_first_max:
+  // with those the keyed instances' step loop compiles to other instructions and several instances to other register counts.
   uint8_t *buf = win + slot * kWaveBuf;
   uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
   const uint8_t *buf_lane = buf + 16 - l;
@@ -101,7 +65,6 @@ __global__ __launch_bounds__(256) void sw_wave_kernel(const WaveProblem *probs, 
     }
     return w;
   };
-  // steps this wavefront needs: the longest of its four slots (+15 skew); wave-uniform
   int steps = nb + 16;
   steps = max(steps, __shfl_xor(steps, 16));
   steps = max(steps, __shfl_xor(steps, 32));
@@ -241,11 +204,7 @@ __global__ __launch_bounds__(256) void sw_wave_kernel(const WaveProblem *probs, 
       const long long oj = __shfl_xor(bj, off, 16);
       if (ov > bv || (ov == bv && ov > 0.0f && (oj < bj || (oj == bj && oi < bi)))) { bv = ov; bi = oi; bj = oj; }
     }
-    if (l == 0 && active) {
-      *P.best = bv;
-      P.cell[0] = bv > 0.0f ? bi : 0;
-      P.cell[1] = bv > 0.0f ? bj : 0;
-    }
+    wave_store_winner(&P, active, l, bv, bi, bj);
   }
 }
 
@@ -278,60 +237,43 @@ struct WaveProfArgs {
 
 template <int R, bool TRACK, bool DIRS>
 __global__ __launch_bounds__(256) void sw_wave_prof_kernel(const WaveProblem *probs, int nprob, const WaveProfArgs sa) {
-  constexpr int LS = lane_stride(R);                               // dwords between the profile rows of adjacent lanes
-  constexpr int NQ4 = (R + 3) / 4;
   extern __shared__ __attribute__((aligned(16))) uint32_t wsmem[];
   __shared__ __attribute__((aligned(16))) uint8_t win[16 * kWaveBuf];
   __shared__ uint8_t lut_s[256];
-  float *prof = reinterpret_cast<float *>(wsmem);                  // [ncodes][16][LS]
+  float *prof = reinterpret_cast<float *>(wsmem);                  // [ncodes][16][lane_stride(R)]
   const int tid = threadIdx.x;
   const int l = tid & 15;
   const int slot = tid >> 4;
   const int pid = blockIdx.x * 16 + slot;
   const bool active = pid < nprob;
-  WaveProblem P;
-  if (active) P = probs[pid];
-  else { P.a = nullptr; P.b = nullptr; P.na = 0; P.nb = 0; P.b_offset = 0; P.dirs = nullptr; P.best = nullptr; P.cell = nullptr;
-         P.target = -1.0f; P.own_lo = 0; P.full_n = 0; P.ckpt = nullptr; P.k0 = 0; P.ck_half = 0; P.lanes_used = 0; }
+  const WaveProblem P = wave_problem_or_idle(probs, pid, nprob);
   const int nb = P.nb;
   // the lane side is the same for every problem of the launch (the range of the resident reference)
   const uint8_t *ya = probs[blockIdx.x * 16].a;
   const int na = probs[blockIdx.x * 16].na;
   const uint32_t other = (uint32_t)(sa.ncodes - 1);
   lut_s[tid] = sa.lut[tid];
-  for (int e = tid; e < sa.ncodes * 16 * R; e += 256) {
-    const int c = e / (16 * R);
-    const int rem = e - c * 16 * R;
-    const int ll = rem / R, r = rem - ll * R;
-    const int j = ll * R + r;
-    float v = kPadScoreF;                                          // padding columns: clamp to 0, never a maximum
-    if (j < na) v = ((uint32_t)c < other && ya[j] == sa.byte_of[c]) ? sa.match_s : sa.mismatch_s;
-    prof[(c * 16 + ll) * LS + r] = v;
-  }
+  wave_fill_profile<R>(sa.ncodes, [&](int at, int c, int j) {      // (padding columns: clamp to 0, never a maximum)
+    prof[at] = j >= na ? kPadScoreF : ((uint32_t)c < other && ya[j] == sa.byte_of[c]) ? sa.match_s : sa.mismatch_s;
+  });
   __syncthreads();
 
-  // stream window of CODES: 16 B history + 64 B segment per slot, refilled every 64 steps
-  uint8_t *buf = win + slot * kWaveBuf;
-  uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
-  const uint8_t *buf_lane = buf + 16 - l;
+  // stream window of CODES (outside the stream: `other`, matches nothing)
   const int k0 = (DIRS && !TRACK) ? P.k0 : 0;                       // first step of this launch (a resumed problem: > 0)
-  auto stage_load = [&](int seg) -> uint32_t {                     // (seg = -1: the sixteen positions in front of step k0)
-    const int c0 = k0 + seg * kWaveSeg + 4 * l;
-    uint32_t w = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int t = c0 + k;
-      const uint32_t ch = ((uint32_t)t < (uint32_t)nb && (seg >= 0 || l >= 12)) ? (uint32_t)lut_s[P.b[t]] : other;   // outside the stream: matches nothing
-      w |= ch << (8 * k);
-    }
-    return w;
+  auto stage_load = [&](int seg) -> uint32_t {                     // (seg = -1: the sixteen positions in front of step k0, in lanes 12 .. 15)
+    return wave_stage_word(P.b, (seg >= 0 || l >= 12) ? nb : 0, k0 + seg * kWaveSeg + 4 * l,
+                           [&](bool in, uint32_t byte) { return in ? (uint32_t)lut_s[byte] : other; });
   };
+  // (the step count and the 16-lane reduction by hand, not wave_steps / slot_first_max: with them the loops get other s_nop
+  // padding and the TRACK instances one or two more registers)
   int steps = nb - k0 + ((DIRS && !TRACK && P.lanes_used > 0) ? P.lanes_used : 16);
   steps = max(steps, __shfl_xor(steps, 16));
   steps = max(steps, __shfl_xor(steps, 32));
   const int nseg = (steps + kWaveSeg - 1) / kWaveSeg;
   const int steps4 = (steps + 3) & ~3;                             // the last segment stops at the wavefront's last step (in fours)
-
+  uint8_t *buf = win + slot * kWaveBuf;
+  uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
+  const uint8_t *buf_lane = buf + 16 - l;
   uint32_t nextc = stage_load(0);
   {
     // history: the 16 positions in front of the first step (lanes 12..15 of stage_load(-1) cover k0 - 16 .. k0 - 1)
@@ -366,9 +308,8 @@ __global__ __launch_bounds__(256) void sw_wave_prof_kernel(const WaveProblem *pr
 #pragma unroll
     for (int r = 0; r < R; ++r) { H[r] = 0.0f; Hg[r] = -gv; }
   }
-  float blk = 0.0f;                                                // TRACK: this lane's best key (value | 31 - column in the lane) ...
-  int tl = 0;                                                      // ... and the stream position it was first seen at
-  const float *prof_lane = prof + l * LS;
+  WaveKeyFold key;                                                 // TRACK
+  const float *prof_lane = prof + l * lane_stride(R);
 
   // TRACK without DIRS: the slot's wavefront as it stands after step kCkptEvery (c + 1) - 1 — what a later launch needs to
   // resume there
@@ -389,10 +330,10 @@ __global__ __launch_bounds__(256) void sw_wave_prof_kernel(const WaveProblem *pr
       const int k = 4 * k4 + ku;
       const int t = k0 + seg * kWaveSeg + k - l;                   // this lane's stream position
       const uint32_t c = (uint32_t)buf_lane[k];
-      const u32x4 *pp = static_cast<const u32x4 *>(__builtin_assume_aligned(prof_lane + c * (16 * LS), 16));
-      uint32_t p[NQ4 * 4];
+      const u32x4 *pp = static_cast<const u32x4 *>(__builtin_assume_aligned(prof_lane + c * (16 * lane_stride(R)), 16));
+      uint32_t p[(R + 3) / 4 * 4];
 #pragma unroll
-      for (int q = 0; q < NQ4; ++q) {
+      for (int q = 0; q < (R + 3) / 4; ++q) {
         const u32x4 v = pp[q];
         p[4 * q + 0] = v.x; p[4 * q + 1] = v.y; p[4 * q + 2] = v.z; p[4 * q + 3] = v.w;
       }
@@ -432,25 +373,14 @@ __global__ __launch_bounds__(256) void sw_wave_prof_kernel(const WaveProblem *pr
           asm("v_addc_co_u32_e64 %0, %1, %2, %2, %3" : "=v"(dpack[r >> 4]), "=s"(carry_out) : "v"(dpack[r >> 4]), "s"(b_hi));
           (void)carry_out;
         }
-        if (TRACK) {
-          const float hk = __uint_as_float(__float_as_uint(h) | (uint32_t)(31 - r));     // (value, smaller column first)
-          if (r & 1) asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(tpend), "v"(hk));
-          else if (r + 1 < R) tpend = hk;
-          else m = fmaxf(m, hk);
-        }
+        if (TRACK) WaveKeyFold::cell<R>(r, h, m, tpend);
         diag = w;
         H[r] = h;
         north = h;
         asm("v_sub_f32 %0, %1, %2" : "=v"(ng) : "v"(h), "v"(gv));
         Hg[r] = ng;
       }
-      if (TRACK) {
-        // strict '>': an equal key (same value, same column) at a later row does not replace the first.  Cells beyond the
-        // stream's end and padding columns hold values strictly below some real cell: they can lead a lane for a while, never
-        // the slot.
-        tl = m > blk ? t : tl;
-        blk = fmaxf(blk, m);
-      }
+      if (TRACK) key.end(t, m);
       if (DIRS) {
         // row = the STEP (t + l): the sixteen lanes of a slot write one contiguous 64 W-byte row per step
         if (P.dirs != nullptr && t >= 0 && t < nb) {
@@ -474,11 +404,9 @@ __global__ __launch_bounds__(256) void sw_wave_prof_kernel(const WaveProblem *pr
   }
 
   if (TRACK) {
-    // the lane's winner -> across the 16 lanes: value, then column of y, then row of x
-    const uint32_t kb = __float_as_uint(blk);
-    float bv = __uint_as_float(kb & ~31u) * sa.unscale;
-    long long bj = (long long)l * R + (31 - (int)(kb & 31u)) + 1, bi = P.b_offset + tl + 1;
-    if (!(bv > 0.0f)) { bv = 0.0f; bi = 0; bj = 0; }
+    float bv;
+    long long bi, bj;
+    key.template winner<R>(l, sa.unscale, P.b_offset, bv, bi, bj);
 #pragma unroll
     for (int off = 8; off >= 1; off >>= 1) {
       const float ov = __shfl_xor(bv, off, 16);
@@ -486,11 +414,7 @@ __global__ __launch_bounds__(256) void sw_wave_prof_kernel(const WaveProblem *pr
       const long long oj = __shfl_xor(bj, off, 16);
       if (ov > bv || (ov == bv && ov > 0.0f && (oj < bj || (oj == bj && oi < bi)))) { bv = ov; bi = oi; bj = oj; }
     }
-    if (l == 0 && active) {
-      *P.best = bv;
-      P.cell[0] = bv > 0.0f ? bi : 0;
-      P.cell[1] = bv > 0.0f ? bj : 0;
-    }
+    wave_store_winner(&P, active, l, bv, bi, bj);
   }
 }
 
@@ -547,43 +471,26 @@ __global__ __launch_bounds__(256) void sw_wave_prof16_kernel(const WaveProblem *
   const int na = probs[0].na;
   const uint32_t other = (uint32_t)(sa.ncodes - 1);
   lut_s[tid] = sa.lut[tid];
-  for (int e = tid; e < sa.ncodes * 16 * R; e += 256) {
-    const int c = e / (16 * R);
-    const int rem = e - c * 16 * R;
-    const int ll = rem / R, r = rem - ll * R;
-    const int j = ll * R + r;
-    uint32_t v = kProf16Pad;
-    if (j < na) v = ((uint32_t)c < other && ya[j] == sa.byte_of[c]) ? sa.match_h : sa.mismatch_h;
-    profLo[(c * 16 + ll) * LS + r] = v | (kProf16One << 16);
-    profHi[(c * 16 + ll) * LS + r] = kProf16One | (v << 16);
-  }
+  wave_fill_profile<R>(sa.ncodes, [&](int at, int c, int j) {
+    const uint32_t v = j >= na ? kProf16Pad : ((uint32_t)c < other && ya[j] == sa.byte_of[c]) ? sa.match_h : sa.mismatch_h;
+    profLo[at] = v | (kProf16One << 16);
+    profHi[at] = kProf16One | (v << 16);
+  });
   __syncthreads();
 
-  // stream windows of CODES, one per half: 16 B history + 64 B segment, refilled every 64 steps
+  // stream windows of CODES, one per half (outside the stream: `other`, matches nothing)
+  auto code_of = [&](bool in, uint32_t byte) { return in ? (uint32_t)lut_s[byte] : other; };
+  auto loadA = [&](int seg) -> uint32_t { return wave_stage_word(bA, nbA, seg * kWaveSeg + 4 * l, code_of); };
+  auto loadB = [&](int seg) -> uint32_t { return wave_stage_word(bB, nbB, seg * kWaveSeg + 4 * l, code_of); };
+  int nseg, steps4;
+  wave_steps(max(nbA, nbB), 16, nseg, steps4);
   uint8_t *bufA = win + (2 * slot) * kWaveBuf, *bufB = bufA + kWaveBuf;
   uint32_t *bufA32 = reinterpret_cast<uint32_t *>(bufA), *bufB32 = reinterpret_cast<uint32_t *>(bufB);
   const uint8_t *bufA_lane = bufA + 16 - l, *bufB_lane = bufB + 16 - l;
-  auto stage_load = [&](const uint8_t *b, int nb, int seg) -> uint32_t {
-    const int c0 = seg * kWaveSeg + 4 * l;
-    uint32_t w = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int t = c0 + k;
-      const uint32_t ch = (uint32_t)t < (uint32_t)nb ? (uint32_t)lut_s[b[t]] : other;     // outside the stream: matches nothing
-      w |= ch << (8 * k);
-    }
-    return w;
-  };
-  int steps = max(nbA, nbB) + 16;
-  steps = max(steps, __shfl_xor(steps, 16));
-  steps = max(steps, __shfl_xor(steps, 32));
-  const int nseg = (steps + kWaveSeg - 1) / kWaveSeg;
-  const int steps4 = (steps + 3) & ~3;
-
-  uint32_t nextA = stage_load(bA, nbA, 0), nextB = stage_load(bB, nbB, 0);
+  uint32_t nextA = loadA(0), nextB = loadB(0);
   if (l < 4) { bufA32[l] = other * 0x01010101u; bufB32[l] = other * 0x01010101u; }
   bufA32[4 + l] = nextA; bufB32[4 + l] = nextB;
-  nextA = stage_load(bA, nbA, 1); nextB = stage_load(bB, nbB, 1);
+  nextA = loadA(1); nextB = loadB(1);
 
   uint32_t gv = sa.ngap2;
   asm volatile("" : "+v"(gv));
@@ -663,7 +570,7 @@ __global__ __launch_bounds__(256) void sw_wave_prof16_kernel(const WaveProblem *
     const uint32_t histA = bufA32[kWaveSeg / 4 + (l & 3)], histB = bufB32[kWaveSeg / 4 + (l & 3)];
     if (l < 4) { bufA32[l] = histA; bufB32[l] = histB; }
     bufA32[4 + l] = nextA; bufB32[4 + l] = nextB;
-    nextA = stage_load(bA, nbA, seg + 2); nextB = stage_load(bB, nbB, seg + 2);
+    nextA = loadA(seg + 2); nextB = loadB(seg + 2);
   }
 
   // per half: the lane's winner -> across the 16 lanes: value, then column of y, then row of x
@@ -679,13 +586,7 @@ __global__ __launch_bounds__(256) void sw_wave_prof16_kernel(const WaveProblem *
     const long long boff = active ? probs[half ? pidB : pidA].b_offset : 0;
     long long bj = (long long)l * R + (15 - (int)(kb & 15u)) + 1, bi = boff + tl + 1;
     if (!(bv > 0.0f)) { bv = 0.0f; bi = 0; bj = 0; }
-#pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 16);
-      const long long oi = __shfl_xor(bi, off, 16);
-      const long long oj = __shfl_xor(bj, off, 16);
-      if (ov > bv || (ov == bv && ov > 0.0f && (oj < bj || (oj == bj && oi < bi)))) { bv = ov; bi = oi; bj = oj; }
-    }
+    slot_first_max(bv, bi, bj);
     if (l == 0 && active) {
       const WaveProblem *P = probs + (half ? pidB : pidA);
       const bool undecided = kmax >= kProf16KeyLimit;
