@@ -226,12 +226,19 @@ int mi355_sw_align_scored_range(mi355_sw_ctx *ctx, size_t range_index, const mi3
  * everything else is refused.
  * Option no_affine_sweep (A/B, tests): every problem on the exact kernel, refused above 2^26 cells per problem.
  * Option no_affine_prof (A/B, tests): references (ranges) of at most 512 letters on the exact kernel as well.
+ * Lists of pairs (mi355_sw_affine_pairs_run, mi355_sw_affine_pairs_trace): a pair is always computed by the pair kernel when its
+ * query has 1..512 rows and its window 1..2^20 columns, with integer-valued scores, smax * (rows + 1) < 2^18 and
+ * gap_open < 2^18, while the score table [reference letters + 1][classes of query bytes with equal scores + 1] fits 32 KiB of
+ * LDS (a 20-letter table: 25 x 21 entries) — whatever the size of the call.  Every other pair is a whole problem of the exact
+ * kernel under its limits (2^26 cells, about 5 600 rows); one pair beyond those fails the whole call with MI355_SW_ENOTSUP.
+ * Option no_affine_pairs (A/B, tests): every pair on the exact kernel.
  * The traceback calls follow the same rules; in addition one alignment whose decision window (DESIGN.md §3.8, L17 and L18:
  * the columns and the rows an alignment into the end cell can reach) needs more than 2^30 bytes, or has more than about
  * 5 600 rows, is refused with MI355_SW_ENOTSUP.
  * mi355_sw_last_path: "affine[cell=f16,SL=..,R=..]" when the sweep kernel ran, "affine_prof[R=..]" when the kernel for
  * references of at most 512 letters ran (calls of fewer than 2^18 cells stay on the exact kernel), "affine_exact" when the
- * exact kernel ran, "affine_trace" when the traceback kernel ran.
+ * exact kernel ran, "affine_trace" when the traceback kernel ran, "affine_pair[R=..]" once per instance of the pair kernel
+ * that ran.
  * mi355_sw_last_timings: [0] sweep kernel(s) (both of them), [1] exact kernel (whole problems and end-cell windows),
  * [2] traceback kernel, [3] whole call, [4] sweep launches, [5] cells swept. */
 typedef struct {
@@ -257,6 +264,24 @@ int mi355_sw_affine_batch_trace(mi355_sw_ctx *ctx, const mi355_sw_affine_params 
  * zero left border. */
 int mi355_sw_affine_score_ranges(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,
                                  const mi355_sw_affine_params *params, float *maxima);
+
+/* npairs independent problems: resident query query[k] (index into the batch of mi355_sw_batch_upload[_packed]) against the
+ * window [lefts[k], rights[k]) of the resident reference (0-based, half open, as mi355_sw_affine_score_ranges).  Each pair is
+ * a stand-alone problem with zero borders: score[k], end_x[k], end_y[k] are exactly what
+ * mi355_sw_affine_align(x_query[k], y + lefts[k], rights[k] - lefts[k]) returns; end_y is relative to the window start
+ * (1-based; the caller adds lefts[k]), 0 / 0 / 0 for an empty query, an empty window or no positive cell.  A query may occur
+ * in any number of pairs; windows may overlap, touch column 0 or end at the reference's last column.  Results come back in
+ * the caller's pair order.  npairs == 0 returns 0 and writes nothing.  MI355_SW_EINVAL: a NULL array, query[k] outside
+ * [0, n_queries), lefts[k] < 0, rights[k] < lefts[k] or rights[k] > the reference length; the scoring checks and
+ * MI355_SW_ENOTSUP as for every affine call (bounds: the paragraph above).  After any error the context stays usable.
+ * mi355_sw_last_timings: [0] pair kernel, [1] exact kernel, [2] traceback kernel, [3] whole call, [4] pair-kernel launches,
+ * [5] cells of the pair kernel. */
+int mi355_sw_affine_pairs_run(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
+                              const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y);
+/* The same with the traceback: outs[k] as mi355_sw_affine_align_trace on that slice (pos relative to the window start);
+ * outs must not be NULL; release the strings with mi355_sw_free_results. */
+int mi355_sw_affine_pairs_trace(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
+                                const mi355_sw_affine_params *params, mi355_sw_result *outs);
 
 /* Host-only helper: piece ranges [left,right). Returns MI355_SW_ERANGE where the reference asserts. */
 int mi355_sw_make_string_range(int npiece, int64_t shortlen, int64_t longlen, float overlap_ratio,

@@ -23,7 +23,7 @@ EXPORTS = [
     "mi355_sw_multi_align_batch", "mi355_sw_multi_last_timings",
     "mi355_sw_set_option", "mi355_sw_option_names", "mi355_sw_multi_set_option", "mi355_sw_last_counters", "mi355_sw_last_counter", "mi355_sw_batch_upload_packed", "mi355_sw_best_range", "mi355_sw_last_path",
     "mi355_sw_default_affine_params", "mi355_sw_affine_align", "mi355_sw_affine_batch_run", "mi355_sw_affine_score_ranges",
-    "mi355_sw_affine_align_trace", "mi355_sw_affine_batch_trace",
+    "mi355_sw_affine_align_trace", "mi355_sw_affine_batch_trace", "mi355_sw_affine_pairs_run", "mi355_sw_affine_pairs_trace",
 ]
 MULTI_RCCL = 1
 
@@ -396,6 +396,50 @@ class Context:
         out = np.zeros((n, self._nbatch), dtype=np.float32)
         self._chk(self._L.mi355_sw_affine_score_ranges(self._ctx, C.c_size_t(n), lefts, rights, C.byref(p),
                                                        out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    @staticmethod
+    def _pair_arrays(query, lefts, rights):
+        q = np.ascontiguousarray(query, dtype=np.int32).reshape(-1)
+        lo = np.ascontiguousarray(lefts, dtype=np.int64).reshape(-1)
+        hi = np.ascontiguousarray(rights, dtype=np.int64).reshape(-1)
+        if not (len(q) == len(lo) == len(hi)):
+            raise ValueError("query, lefts and rights must have the same length")
+        return q, lo, hi
+
+    def affine_pairs_run(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
+        """Pair k = resident query query[k] against the window [lefts[k], rights[k]) of the resident reference, each a stand-alone
+        problem (mi355_sw_affine_pairs_run): dict of arrays score, end_x, end_y in the caller's order; end_y is relative to the
+        window start.  query, lefts, rights: numpy int arrays or lists."""
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        q, lo, hi = self._pair_arrays(query, lefts, rights)
+        n = len(q)
+        score = np.zeros(n, dtype=np.float32)
+        ex = np.zeros(n, dtype=np.int64)
+        ey = np.zeros(n, dtype=np.int64)
+        self._chk(self._L.mi355_sw_affine_pairs_run(self._ctx, C.c_size_t(n), q.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    lo.ctypes.data_as(C.POINTER(C.c_int64)), hi.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    C.byref(p), score.ctypes.data_as(C.POINTER(C.c_float)),
+                                                    ex.ctypes.data_as(C.POINTER(C.c_int64)), ey.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(score=score, end_x=ex, end_y=ey)
+
+    def affine_pairs_trace(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
+        """affine_pairs_run with the traceback (mi355_sw_affine_pairs_trace): the dict shape of affine_batch_trace, one entry per pair;
+        begin_y / pos are relative to the window start."""
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        q, lo, hi = self._pair_arrays(query, lefts, rights)
+        n = len(q)
+        res = (Result * max(1, n))()
+        self._chk(self._L.mi355_sw_affine_pairs_trace(self._ctx, C.c_size_t(n), q.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      lo.ctypes.data_as(C.POINTER(C.c_int64)), hi.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      C.byref(p), res))
+        rows = [_take_affine(res[k]) for k in range(n)]
+        self._L.mi355_sw_free_results(res, C.c_size_t(n))
+        out = dict(score=np.array([r["score"] for r in rows], dtype=np.float32))
+        for k in ("end_x", "end_y", "begin_x", "begin_y", "pos"):
+            out[k] = np.array([r[k] for r in rows], dtype=np.int64)
+        for k in ("cons_x", "cons_y", "cigar"):
+            out[k] = [r[k] for r in rows]
         return out
 
     def align_batch(self, xs, y=None, **kw):

@@ -1,6 +1,7 @@
 // host_affine.h — affine-gap score, end cell and traceback: parameter checks, the sw_affine_kernel sweep, the
 // sw_affine_exact_kernel behind it, sw_affine_trace_kernel (sw_affine_kernel.h) and, for references (ranges) of
-// at most 512 letters, sw_affine_prof_kernel (sw_affine_prof_kernel.h).
+// at most 512 letters, sw_affine_prof_kernel (sw_affine_prof_kernel.h); for lists of (query, window) pairs, sw_affine_pair_kernel
+// (sw_affine_pair_kernel.h).
 // Part of the single translation unit mi355_sw.hip (included there, in order; not a standalone header).
 namespace {
 
@@ -206,10 +207,11 @@ struct AffineProfPlan {
   std::vector<int> rep;           // a byte of every class but the last
 };
 
-void affine_prof_plan(const RefData &ref, const mi355_sw_affine_params &p, const AffineTable &t, AffineProfPlan &plan) {
+// the classes alone (sw_affine_prof_kernel and sw_affine_pair_kernel)
+void affine_byte_classes(const RefData &ref, const mi355_sw_affine_params &p, const AffineTable &t, AffineProfPlan &plan) {
   plan.ok = false;
   const int nl = ref.ncodes - 1;
-  if (opt().no_affine_prof || nl < 1 || nl > 255 || (double)t.open >= kAffineProfBound) return;
+  if (nl < 1 || nl > 255 || (double)t.open >= kAffineProfBound) return;
   plan.rep.clear();
   for (int a = 0; a < 256; ++a) {
     int c = 0;
@@ -226,6 +228,12 @@ void affine_prof_plan(const RefData &ref, const mi355_sw_affine_params &p, const
   }
   plan.nclass = (int)plan.rep.size() + 1;
   plan.ok = true;
+}
+
+void affine_prof_plan(const RefData &ref, const mi355_sw_affine_params &p, const AffineTable &t, AffineProfPlan &plan) {
+  plan.ok = false;
+  if (opt().no_affine_prof) return;
+  affine_byte_classes(ref, p, t, plan);
 }
 
 bool affine_prof_range_ok(const AffineProfPlan &plan, const AffineTable &t, int64_t n) {
@@ -336,23 +344,29 @@ int affine_prof_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, 
   return 0;
 }
 
-// Traceback of every query with a positive score (one range): one sw_affine_trace_kernel problem per query over the window
-// behind the end cell — the L17 window of columns and the L18 window of rows, each where it is shorter than the matrix
-//  — in launch groups of at most kAffineTraceDirsMax decision bytes.  tout[nq]: views into ctx->arenas.
-int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_affine_params &p,
-                 const AffineTable &t, const float *score, const int64_t *ends, std::vector<TraceOut> &tout) {
-  struct Job { int q; int32_t m, nw; int64_t wl, row_lo; bool clamped, row_clamped; size_t dirs_off, cons_off; };
+// One alignment to trace back: query q of the batch against the range of the reference that starts at column lo, with the score
+// and the end cell (row, column relative to lo, 1-based) its score pass found.
+struct AffineTraceItem { int q; int64_t lo; float score; int64_t ex, ey; };
+
+// Traceback of every item with a positive score: one sw_affine_trace_kernel problem per item over the window behind the end
+// cell — the L17 window of columns and the L18 window of rows, each where it is shorter than the matrix, clamped
+// at the item's own left border and at row 1 — in launch groups of at most kAffineTraceDirsMax decision bytes.
+// tout[items.size()]: views into ctx->arenas.
+int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const std::vector<AffineTraceItem> &items,
+                 const mi355_sw_affine_params &p, const AffineTable &t, std::vector<TraceOut> &tout) {
+  struct Job { size_t item; int32_t m, nw; int64_t wl, row_lo; bool clamped, row_clamped; size_t dirs_off, cons_off; };
   std::vector<Job> jobs;
-  for (size_t k = 0; k < q.nq; ++k) {
-    if (!(score[k] > 0)) continue;
-    const int64_t ex = ends[2 * k], ey = ends[2 * k + 1];
-    const double spare = std::max(0.0, (double)t.smax * (double)ex - (double)score[k]);
+  for (size_t k = 0; k < items.size(); ++k) {
+    const float score = items[k].score;
+    if (!(score > 0)) continue;
+    const int64_t ex = items[k].ex, ey = items[k].ey;
+    const double spare = std::max(0.0, (double)t.smax * (double)ex - (double)score);
     const double W = (double)ex + std::ceil(spare / (double)t.ext) + 2.0;
     // lemma L18, the mirror image of L17: at most end_y diagonal or horizontal steps, hence at most (smax end_y - score) / e rows of gaps
-    const double spare_r = std::max(0.0, (double)t.smax * (double)ey - (double)score[k]);
+    const double spare_r = std::max(0.0, (double)t.smax * (double)ey - (double)score);
     const double Wr = (double)ey + std::ceil(spare_r / (double)t.ext) + 2.0;
     Job j;
-    j.q = (int)k;
+    j.item = k;
     j.row_clamped = Wr >= (double)ex;
     const int64_t mw = j.row_clamped ? ex : (int64_t)Wr;
     j.row_lo = ex - mw;
@@ -400,12 +414,12 @@ int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
       const Job &j = jobs[lo + k];
       AffineTraceProblem &a = pr[k];
       memset(&a, 0, sizeof a);
-      a.e.x = q.bytes.as<uint8_t>() + q.off[j.q] + j.row_lo;
-      a.e.y = ref.bytes.as<uint8_t>() + rg.lo + j.wl;
+      a.e.x = q.bytes.as<uint8_t>() + q.off[items[j.item].q] + j.row_lo;
+      a.e.y = ref.bytes.as<uint8_t>() + items[j.item].lo + j.wl;
       a.e.m = j.m; a.e.nw = j.nw;
       a.e.col_offset = j.wl;
       a.e.own_lo = 1;
-      a.e.target = score[j.q];
+      a.e.target = items[j.item].score;
       a.e.dirs = ctx->dirs.as<uint8_t>() + j.dirs_off;
       a.cap = j.m + j.nw;
       a.cons_x = ctx->cons.as<char>() + j.cons_off;
@@ -433,7 +447,7 @@ int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
       if (st == 1) return fail(ctx, MI355_SW_ENODEV, "internal: the affine traceback left its window (lemmas L17, L18)");
       if (st == 2) return fail(ctx, MI355_SW_ENODEV, "internal: the affine traceback exceeded its string capacity");
       if (st != 0) return fail(ctx, MI355_SW_ENODEV, "internal: the end cell of the affine traceback window does not hold the score");
-      TraceOut &o = tout[j.q];
+      TraceOut &o = tout[j.item];
       o.len = (size_t)len;
       o.cx = base + j.cons_off;
       o.cy = base + j.cons_off + (size_t)j.m + (size_t)j.nw;
@@ -617,7 +631,193 @@ int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const
     }
   }
   if (tout && ends) {
-    rc = affine_trace(ctx, ref, q, ranges[0], p, t, maxima, ends, *tout);
+    std::vector<AffineTraceItem> items(nq);                          // every query of the batch against the one range
+    for (size_t k = 0; k < nq; ++k) items[k] = AffineTraceItem{(int)k, ranges[0].lo, maxima[k], ends[2 * k], ends[2 * k + 1]};
+    rc = affine_trace(ctx, ref, q, items, p, t, *tout);
+    if (rc) return rc;
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+  ctx->timings[3] += elapsed_us(ctx, ctx->ev[4], ctx->ev[5]);
+  return 0;
+}
+
+// ---- sw_affine_pair_kernel (sw_affine_pair_kernel.h): a list of (query, window of the resident reference) pairs -----------------
+constexpr int64_t kAffinePairColsMax = (int64_t)1 << 20;   // columns of one window: keeps the slowest slot of a launch to about 2^20 steps
+                                                          // of at most 32 rows — an estimate from the kernel's op count (some 0.3 s at
+                                                          // R = 32); nobody has measured it
+constexpr size_t kAffinePairLdsMax = 32 * 1024;            // the workgroup's score table [letters + 1][classes + 1]
+constexpr size_t kAffinePairGroupProblems = (size_t)1 << 22;   // problems between two downloads of (best, cell)
+
+size_t affine_pair_lds(const RefData &ref, const AffineProfPlan &plan) { return (size_t)ref.ncodes * (size_t)plan.nclass * 4; }
+
+// the instance of the least R of kPairR with 16 R >= rows (0: none)
+int affine_pair_R(int rows) {
+  for (int R : kPairR) if (16 * R >= rows) return R;
+  return 0;
+}
+typedef void (*AffinePairKernel)(const AffinePairProblem *, int, const AffinePairArgs);
+template <size_t... I> AffinePairKernel affine_pair_kernel(int R, std::index_sequence<I...>) {
+  AffinePairKernel k = nullptr;
+  ((kPairR[I] == R ? (void)(k = &sw_affine_pair_kernel<kPairR[I]>) : (void)0), ...);
+  return k;
+}
+
+// npairs independent problems: query qid[k] of `q` against [lefts[k], rights[k]) of `ref` (validated by the caller), each with
+// zero borders.  score[npairs]; ends[npairs][2] = row, column relative to the window start; tout (may be null): the traceback of
+// every pair (affine_trace).  A pair of 1..512 rows and 1..2^20 columns under the bounds of the header takes sw_affine_pair_kernel,
+// every other one is a whole problem of the exact kernel; results come back in the caller's order.
+int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, size_t npairs, const int32_t *qid, const int64_t *lefts,
+                 const int64_t *rights, const mi355_sw_affine_params &p, float *score, int64_t *ends, std::vector<TraceOut> *tout) {
+  for (size_t k = 0; k < npairs; ++k) { score[k] = 0.0f; ends[2 * k] = 0; ends[2 * k + 1] = 0; }
+  if (tout) tout->assign(npairs, TraceOut());
+  AffineTable t;
+  int rc = affine_table(ctx, ref, p, t);
+  if (rc) return rc;
+  if (t.smax <= 0) return 0;                                       // no positive cell: every maximum is 0
+  HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+  AffineProfPlan plan;
+  if (!opt().no_affine_pairs) {
+    affine_byte_classes(ref, p, t, plan);
+    if (!plan.ok && ref.ncodes >= 2 && ref.ncodes <= 256 && (double)t.open < kAffineProfBound) {
+      // a table that scores all 256 bytes differently: every byte is its own class
+      plan.rep.resize(256);
+      for (int a = 0; a < 256; ++a) { plan.cls[a] = (uint8_t)a; plan.rep[a] = a; }
+      plan.nclass = 257;
+      plan.ok = true;
+    }
+  }
+  const bool table_ok = plan.ok && affine_pair_lds(ref, plan) <= kAffinePairLdsMax;
+
+  // ---- which kernel a pair takes ---------------------------------------------------------------------------------------------------
+  if (npairs > 0xFFFFFFFFull) return fail(ctx, MI355_SW_ENOTSUP, "affine pairs: more than 2^32 pairs");
+  std::vector<uint32_t> fast;                                      // pair indices of sw_affine_pair_kernel
+  std::vector<ExactJob> jobs;
+  int mmax = 0;
+  for (size_t k = 0; k < npairs; ++k) {
+    const int m = q.len[qid[k]];
+    const int64_t n = rights[k] - lefts[k];
+    if (m < 1 || n < 1) continue;
+    if (table_ok && m <= kMaxRowsFast && n <= kAffinePairColsMax && (double)t.smax * ((double)m + 1.0) < kAffineProfBound) {
+      fast.push_back((uint32_t)k);
+      mmax = std::max(mmax, m);
+      continue;
+    }
+    if ((double)m * (double)n > kAffineExactCellsMax || (double)t.smax * ((double)m + 1.0) >= 16777216.0) {
+      char msg[240];
+      std::snprintf(msg, sizeof msg, "affine pairs: pair %zu (%d rows x %lld columns) is outside the pair kernel (1..512 rows, 1..2^20 columns, "
+                    "smax * (rows + 1) < 2^18, gap_open < 2^18) and has more than 2^26 cells for the exact kernel", k, m, (long long)n);
+      return fail(ctx, MI355_SW_ENOTSUP, msg);
+    }
+    if (affine_exact_lds(m) > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine pairs: query longer than the exact kernel's LDS diagonals hold");
+    ExactJob j;
+    j.q = qid[k]; j.ylo = lefts[k]; j.nw = (int32_t)n; j.col_offset = 0; j.full_n = n; j.own_lo = 1; j.quirk = 0;
+    j.target = -1.0f; j.want_dirs = false;
+    j.dirs_off = k;                                                // (no decisions here: the job's pair)
+    jobs.push_back(j);
+  }
+
+  // ---- sw_affine_pair_kernel: by instance, longest window first, so that the slots of a wavefront run similar step counts ---------
+  if (!fast.empty()) {
+    std::sort(fast.begin(), fast.end(), [&](uint32_t a, uint32_t b) {
+      const int Ra = affine_pair_R(q.len[qid[a]]), Rb = affine_pair_R(q.len[qid[b]]);
+      if (Ra != Rb) return Ra < Rb;
+      const int64_t na = rights[a] - lefts[a], nb = rights[b] - lefts[b];
+      return na != nb ? na > nb : a < b;
+    });
+    // cells hold H * 2^-k, 2^k above every value of the call (as affine_prof_run)
+    const int k = std::max(1, std::ilogb((double)t.smax * ((double)mmax + 1.0) + 1.0) + 2);
+    const int nl = ref.ncodes - 1, nrows = nl + 1, ncls = plan.nclass;
+    const size_t tab_floats = (size_t)nrows * ncls;
+    ctx->h_aprof.assign(tab_floats + 64, kPadScoreF);               // (outlives the asynchronous copy)
+    for (int l = 0; l < nl; ++l)
+      for (int c = 0; c + 1 < ncls; ++c)
+        ctx->h_aprof[(size_t)l * ncls + c] = std::ldexp(affine_score(ref, p, plan.rep[c], l) + (float)t.open, -k);
+    memcpy(ctx->h_aprof.data() + tab_floats, plan.cls, 256);
+    if (ctx->aprof.ensure((tab_floats + 64) * 4)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine pair table) failed");
+    HIPCHK(ctx, hipMemcpyAsync(ctx->aprof.p, ctx->h_aprof.data(), (tab_floats + 64) * 4, hipMemcpyHostToDevice, ctx->stream));
+    AffinePairArgs sa;
+    sa.tab = ctx->aprof.as<float>();
+    sa.cls = reinterpret_cast<const uint8_t *>(ctx->aprof.as<float>() + tab_floats);
+    sa.nrows = nrows; sa.ncls = ncls;
+    sa.open_s = std::ldexp((float)t.open, -k); sa.ext_s = std::ldexp((float)t.ext, -k);
+    sa.unscale = std::ldexp(1.0f, k);
+    for (size_t g0 = 0; g0 < fast.size(); g0 += kAffinePairGroupProblems) {
+      const size_t np = std::min(kAffinePairGroupProblems, fast.size() - g0);
+      const size_t o_cell = (np * 4 + 15) & ~(size_t)15;
+      if (ctx->wprobs.ensure(np * sizeof(AffinePairProblem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16) ||
+          ctx->pin_probs.ensure(np * sizeof(AffinePairProblem)) || ctx->pin_out.ensure(o_cell + np * 16))
+        return fail(ctx, MI355_SW_ENOMEM, "affine pairs: allocation of the pair scratch failed");
+      AffinePairProblem *pr = ctx->pin_probs.as<AffinePairProblem>();
+      for (size_t i = 0; i < np; ++i) {                              // one upload of the pair list
+        const uint32_t id = fast[g0 + i];
+        pr[i].x = q.bytes.as<uint8_t>() + q.off[qid[id]];
+        pr[i].y = ref.codes.as<uint8_t>() + lefts[id];
+        pr[i].m = q.len[qid[id]];
+        pr[i].n = (int32_t)(rights[id] - lefts[id]);
+      }
+      HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr, np * sizeof(AffinePairProblem), hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+      for (size_t i0 = 0; i0 < np;) {                                // one launch per instance
+        const int R = affine_pair_R(pr[i0].m);
+        size_t i1 = i0;
+        double cells = 0;
+        while (i1 < np && affine_pair_R(pr[i1].m) == R) { cells += (double)pr[i1].m * (double)pr[i1].n; ++i1; }
+        AffinePairKernel kern = affine_pair_kernel(R, std::make_index_sequence<std::size(kPairR)>{});
+        if (!kern) return fail(ctx, MI355_SW_ENODEV, "internal: no sw_affine_pair_kernel instance for this query");
+        sa.best = ctx->outs_f.as<float>() + i0;
+        sa.cell = ctx->outs_i.as<int64_t>() + 2 * i0;
+        launch_dyn_lds(kern, dim3((unsigned)((i1 - i0 + 15) / 16)), dim3(256), tab_floats * 4, ctx->stream,
+                       ctx->wprobs.as<AffinePairProblem>() + i0, (int)(i1 - i0), sa);
+        HIPCHK(ctx, hipGetLastError());
+        path_note(ctx, "affine_pair[R=%d]", R);
+        ctx->timings[4] += 1;
+        ctx->timings[5] += cells;
+        if (cells > ctx->last_kernel.cells) {
+          mi355_sw_kernel_info &ki = ctx->last_kernel;
+          ki.cell = MI355_SW_CELL_F32; ki.lanes = 16; ki.rows_per_lane = R; ki.strips = 0; ki.twin = 0;
+          ki.chunk_len = pr[i0].n; ki.sub_len = pr[i0].n; ki.warm = 0; ki.cells = cells;
+          // per step and lane: seven ops, the table address' v_add and the key's v_or per cell, a maximum3 per two cells for the
+          // step's best key, and twelve of overhead as compiled (two DPP moves and their two copies, the row pointer's multiply
+          // and add, the column, the code's address, and compare, two selects and the v_or of the value-only key update)
+          ki.valu_ops_per_cell = (9.0 * R + (R + 1) / 2 + 12.0) / (double)R;
+          std::snprintf(ki.name, sizeof ki.name, "sw_affine_pair_kernel<R=%d>", R);
+        }
+        i0 = i1;
+      }
+      HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+      uint8_t *pin = ctx->pin_out.as<uint8_t>();
+      const float *h_best = reinterpret_cast<const float *>(pin);
+      const int64_t *h_cell = reinterpret_cast<const int64_t *>(pin + o_cell);
+      HIPCHK(ctx, hipMemcpyAsync(pin, ctx->outs_f.p, np * 4, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipMemcpyAsync(pin + o_cell, ctx->outs_i.p, np * 16, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      ctx->timings[0] += elapsed_us(ctx, ctx->ev[0], ctx->ev[1]);
+      for (size_t i = 0; i < np; ++i) {
+        const uint32_t id = fast[g0 + i];
+        if (!(h_best[i] > 0)) continue;
+        score[id] = h_best[i]; ends[2 * (size_t)id] = h_cell[2 * i]; ends[2 * (size_t)id + 1] = h_cell[2 * i + 1];
+      }
+    }
+  }
+
+  // ---- exact kernel: every other pair as a whole problem ---------------------------------------------------------------------------
+  if (!jobs.empty()) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    for (size_t lo = 0; lo < jobs.size(); lo += 65536) {
+      rc = run_affine_exact(ctx, ref, q, p, jobs, lo, std::min(jobs.size(), lo + 65536));
+      if (rc) return rc;
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+    for (const ExactJob &j : jobs) {
+      if (!(j.best > 0)) continue;
+      score[j.dirs_off] = j.best; ends[2 * j.dirs_off] = j.ci; ends[2 * j.dirs_off + 1] = j.cj;
+    }
+  }
+  if (tout) {
+    std::vector<AffineTraceItem> items(npairs);
+    for (size_t k = 0; k < npairs; ++k) items[k] = AffineTraceItem{qid[k], lefts[k], score[k], ends[2 * k], ends[2 * k + 1]};
+    rc = affine_trace(ctx, ref, q, items, p, t, *tout);
     if (rc) return rc;
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));

@@ -9,7 +9,8 @@
 //                      sw_wave_walk_kernel — the walk itself (smithwaterman.cpp:40-78)            host_wave.h
 //   (sw_exact_kernel + sw_walk_kernel, host_exact.h: table scoring on short queries, whole uint8 problems)
 //   affine gaps (score, end cell, traceback): sw_affine_kernel sweep + sw_affine_exact / _trace_kernel, and
-//                      sw_affine_prof_kernel for references (ranges) of at most 512 letters           host_affine.h
+//                      sw_affine_prof_kernel for references (ranges) of at most 512 letters,
+//                      sw_affine_pair_kernel for lists of (query, window) pairs                      host_affine.h
 // Problems the score kernel does not cover (see bucket_fast_ok) run 2+3 on the whole matrix.
 // The host code is one translation unit; the fragments below are included in order.
 #include "../../include/mi355_sw.h"
@@ -44,6 +45,7 @@
 #include "sw_long_kernel.h"
 #include "sw_affine_kernel.h"
 #include "sw_affine_prof_kernel.h"
+#include "sw_affine_pair_kernel.h"
 
 using namespace mi355sw;
 
@@ -472,6 +474,59 @@ int mi355_sw_affine_score_ranges(mi355_sw_ctx *ctx, size_t nranges, const int64_
     ranges[k] = Range{lefts[k], rights[k]};
   }
   return affine_run(ctx, ctx->ref, ctx->batch, ranges, *params, maxima, nullptr);
+}
+
+// the arguments of the two pairs calls: 0, or MI355_SW_EINVAL with the message set
+static int affine_pairs_check(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights) {
+  if (!query || !lefts || !rights) return fail(ctx, MI355_SW_EINVAL, "null argument");
+  for (size_t k = 0; k < npairs; ++k) {
+    if (query[k] < 0 || (size_t)query[k] >= ctx->batch.nq) return fail(ctx, MI355_SW_EINVAL, "pair: query index outside the resident batch");
+    if (lefts[k] < 0 || rights[k] < lefts[k] || rights[k] > (int64_t)ctx->ref.n) return fail(ctx, MI355_SW_EINVAL, "pair: window outside the resident reference");
+  }
+  return 0;
+}
+
+int mi355_sw_affine_pairs_run(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
+                              const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y) {
+  OptScope opt_scope_(ctx);
+  int rc = affine_check(ctx, params);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  reset_timings(ctx);
+  if (npairs == 0) return 0;
+  if (!score || !end_x || !end_y) return fail(ctx, MI355_SW_EINVAL, "null argument");
+  rc = affine_pairs_check(ctx, npairs, query, lefts, rights);
+  if (rc) return rc;
+  std::vector<float> sc(npairs, 0.0f);
+  std::vector<int64_t> ends(2 * npairs, 0);
+  rc = affine_pairs(ctx, ctx->ref, ctx->batch, npairs, query, lefts, rights, *params, sc.data(), ends.data(), nullptr);
+  if (rc) return rc;
+  for (size_t k = 0; k < npairs; ++k) { score[k] = sc[k]; end_x[k] = ends[2 * k]; end_y[k] = ends[2 * k + 1]; }
+  return 0;
+}
+
+int mi355_sw_affine_pairs_trace(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
+                                const mi355_sw_affine_params *params, mi355_sw_result *outs) {
+  OptScope opt_scope_(ctx);
+  int rc = affine_check(ctx, params);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  reset_timings(ctx);
+  if (npairs == 0) return 0;
+  if (!outs) return fail(ctx, MI355_SW_EINVAL, "outs is NULL");
+  rc = affine_pairs_check(ctx, npairs, query, lefts, rights);
+  if (rc) return rc;
+  std::vector<float> sc(npairs, 0.0f);
+  std::vector<int64_t> ends(2 * npairs, 0);
+  std::vector<TraceOut> tout(npairs);
+  rc = affine_pairs(ctx, ctx->ref, ctx->batch, npairs, query, lefts, rights, *params, sc.data(), ends.data(), &tout);
+  if (rc) return rc;
+  memset(outs, 0, npairs * sizeof *outs);
+  for (size_t k = 0; k < npairs; ++k) {
+    set_result(outs[k], sc[k], ends[2 * k], ends[2 * k + 1], &tout[k]);
+    outs[k].timings_us[0] = outs[k].timings_us[1] = (float)ctx->timings[0];
+  }
+  return 0;
 }
 
 int mi355_sw_best_range(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,

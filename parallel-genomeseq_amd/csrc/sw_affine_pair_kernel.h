@@ -1,0 +1,181 @@
+// sw_affine_pair_kernel.h — affine-gap (Gotoh) score and end cell of a LIST OF PAIRS (query, window of the resident reference),
+// hand-written HIP for gfx950.
+//
+// The fourth score kernel of the affine path (sw_affine_kernel.h): the extension stage of a seed-and-extend mapper,
+// where read k meets its own candidate window and nothing else.  Slot geometry, stream window and the slot's winner:
+// sw_wave_common.h — but the slots of a workgroup share neither sequence, and the orientation is the other one: lane l holds ROWS
+// l R .. l R + R - 1 of the query x (1..512 rows), the COLUMNS of the window of y stream, so nothing is kept per column and the
+// window may be long.  sw_affine_prof_kernel (sw_affine_prof_kernel.h) with the roles of E and F exchanged:
+//
+//   E(i,j) = max(E(i,j-1) - e, H(i,j-1) - o)     runs along the columns of y: one register per row
+//   F(i,j) = max(F(i-1,j) - e, H(i-1,j) - o)     runs along the rows of x: down the lane's R rows within a step (Frun), handed to
+//                                                the next lane by one DPP row_shr:1
+//   H(i,j) = max(0, H(i-1,j-1) + s, E, F)
+//
+// Cells are float32 scaled by 2^-k (2^k above every value: the host admits integer scores with smax (rows + 1) < 2^18 and
+// gap_open < 2^18: exact, five mantissa bits free).  Per row the lane keeps E[r] and Ho[r] = H - o; the table holds s + o:
+//     x     = v_add_f32 clamp(Ho(i-1,j-1), s + o)         = max(0, H(i-1,j-1) + s): the [0, 1] clamp is the zero floor
+//     E[r]  = max(E[r] - e, Ho[r])                        Ho[r] still holds H(i,j-1) - o
+//     H     = max3(x, E[r], Frun)
+//     Ho[r] = H - o
+//     Frun  = max(Frun - e, Ho[r])                        F of the next row
+// seven float32 ops per cell.  Borders: H = 0, i.e. Ho = -o, and E = F = -o (lemma L15 (d)); the slot's first lane takes both
+// border values from the `old` operand of its two DPP moves.
+//
+// Substitution scores: there is no per-workgroup profile, since every slot has its own query and its own window.  One small table
+// in LDS serves the workgroup: tab[code of y][class of x] = (s + o) 2^-k, classes as affine_prof_plan groups the bytes of x (5 x 5
+// entries for DNA, 25 x 21 for a 20-letter table); the last row ("outside": steps in front of and beyond the window) and the last
+// class (padding rows beyond the query) hold kPadScoreF.  A lane computes the byte offset of its R rows' classes once; per cell one
+// v_add_u32 (the step's row pointer + that offset) and one ds_read_b32.  Equal addresses broadcast; a table of at most 32 entries
+// lies in as many banks.
+//
+// Winner: the first maximum in column-major order.  Per lane one key bits(H) | (31 - row in the lane); within a step (one column) the
+// greatest key is the greatest value at its smallest row.  ACROSS steps a later column replaces the lane's key only where its VALUE
+// is greater — the compare is against the stored key with its five low bits set — so the smallest column stays, whatever its row
+// (a plain '>' on keys would let an equal value at a smaller row of a later column in).  Across the 16 lanes slot_first_max: value,
+// then smaller column, then smaller row.  Padding rows and outside positions hold max(0, neighbours - penalty), strictly below some
+// real cell: they never lead the slot.
+//
+// A slot writes only best[pid] / cell[2 pid ..]; no slot communicates with another, no workgroup waits, no atomics.  A slot whose
+// window ends early idles on `outside` codes until the longest window of its wavefront is done (wave_steps).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sw_wave_common.h"
+
+namespace mi355sw {
+
+// rows per lane of the compiled instances: 16 R rows each, 150 rows on R = 10
+constexpr int kPairR[] = {2, 5, 10, 16, 24, 32};
+
+struct AffinePairProblem {
+  const uint8_t *x;          // bytes of the query
+  const uint8_t *y;          // CODES of the window of the reference
+  int32_t m, n;              // rows (1..16 R), columns (>= 1)
+};
+
+struct AffinePairArgs {
+  const float *tab;          // [nrows][ncls]: (s + o) * 2^-k; last row and last class: kPadScoreF
+  const uint8_t *cls;        // [256] byte of x -> class
+  int32_t nrows, ncls;       // letters of the reference + 1, classes of x's bytes + 1
+  float open_s, ext_s;       // o and e * 2^-k
+  float unscale;             // 2^k
+  float *best;               // [nprob] maximum (0 when no positive cell)
+  int64_t *cell;             // [nprob][2] = row (into x), column (into the window), 1-based, of the first maximum
+};
+
+template <int R>
+__global__ __launch_bounds__(256) void sw_affine_pair_kernel(const AffinePairProblem *probs, int nprob, const AffinePairArgs sa) {
+  static_assert(R >= 1 && R <= 32, "the key holds the row within the lane in five bits");
+  extern __shared__ __attribute__((aligned(16))) uint32_t pairsmem[];
+  __shared__ __attribute__((aligned(16))) uint8_t win[16 * kWaveBuf];
+  float *tab = reinterpret_cast<float *>(pairsmem);                // [nrows][ncls]
+  const int tid = threadIdx.x;
+  const int l = tid & 15;
+  const int slot = tid >> 4;
+  const int pid = blockIdx.x * 16 + slot;
+  const bool active = pid < nprob;
+  const uint8_t *xb = nullptr, *yc = nullptr;
+  int m = 0, n = 0;
+  if (active) { xb = probs[pid].x; yc = probs[pid].y; m = probs[pid].m; n = probs[pid].n; }
+  for (int e = tid; e < sa.nrows * sa.ncls; e += 256) tab[e] = sa.tab[e];
+  // byte offset of each row's class within a table row (padding rows: the last class)
+  uint32_t boff[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = l * R + r;
+    boff[r] = 4u * (i < m ? (uint32_t)sa.cls[xb[i]] : (uint32_t)(sa.ncls - 1));
+  }
+  __syncthreads();
+
+  // stream window of CODES (in front of the first column and beyond the last: `outside`)
+  const uint32_t outside = (uint32_t)(sa.nrows - 1);
+  auto stage_load = [&](int seg) -> uint32_t {
+    return wave_stage_word(yc, n, seg * kWaveSeg + 4 * l, [&](bool in, uint32_t byte) { return in ? byte : outside; });
+  };
+  int nseg, steps4;
+  wave_steps(n, 16, nseg, steps4);
+  uint8_t *buf = win + slot * kWaveBuf;
+  uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
+  const uint8_t *buf_lane = buf + 16 - l;
+  uint32_t nextc = stage_load(0);
+  if (l < 4) buf32[l] = outside * 0x01010101u;                     // history in front of the first column
+  buf32[4 + l] = nextc;
+  nextc = stage_load(1);
+
+  float ov = sa.open_s, ev = sa.ext_s;
+  asm volatile("" : "+v"(ov), "+v"(ev));                           // (VGPR operands: v_sub_f32 then issues at the double rate)
+  const int nopen = (int)__float_as_uint(-sa.open_s);              // both border values: H = 0 is Ho = -o, and F = -o
+  float E[R], Ho[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) { E[r] = -ov; Ho[r] = -ov; }
+  float up_prev = -ov;                                             // Ho of the previous lane's last row, one column to the left
+  float fout = -ov;                                                // F this lane hands to the next one
+  float blk = 0.0f, blk31 = __uint_as_float(31u);                  // the lane's best key, and the same with its row bits set
+  int tl = 0;                                                      // the column (0-based) blk was first seen at
+  const uint32_t row_bytes = 4u * (uint32_t)sa.ncls;
+  const char *tab_b = reinterpret_cast<const char *>(tab);
+
+  for (int seg = 0; seg < nseg; ++seg) {
+    const int kq = min(kWaveSeg, steps4 - seg * kWaveSeg) >> 2;
+    for (int k4 = 0; k4 < kq; ++k4) {
+#pragma unroll
+      for (int ku = 0; ku < 4; ++ku) {
+        const int k = 4 * k4 + ku;
+        const int t = seg * kWaveSeg + k - l;                      // this lane's column of the window (0-based)
+        const uint32_t c = (uint32_t)buf_lane[k];
+        const char *rowp = tab_b + c * row_bytes;
+        // the previous lane's last row in this column: Ho and the F it hands on; the slot's first lane keeps `old`, the border
+        const float up = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(nopen, (int)__float_as_uint(Ho[R - 1]), 0x111, 0xf, 0xf, false));
+        float frun = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(nopen, (int)__float_as_uint(fout), 0x111, 0xf, 0xf, false));
+        float diag = up_prev;                                      // H(i-1, j-1) - o
+        up_prev = up;
+        float mx = 0.0f, tpend = 0.0f;
+        (void)tpend;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const float w = Ho[r];                                   // H(i, j-1) - o
+          const float s = *reinterpret_cast<const float *>(rowp + boff[r]);
+          float x, g, h, ho, fs;
+          asm("v_add_f32_e64 %0, %1, %2 clamp" : "=v"(x) : "v"(diag), "v"(s));
+          asm("v_sub_f32 %0, %1, %2" : "=v"(g) : "v"(E[r]), "v"(ev));
+          asm("v_max_f32 %0, %1, %2" : "=v"(g) : "v"(g), "v"(w));
+          asm("v_max3_f32 %0, %1, %2, %3" : "=v"(h) : "v"(x), "v"(g), "v"(frun));
+          WaveKeyFold::cell<R>(r, h, mx, tpend);
+          asm("v_sub_f32 %0, %1, %2" : "=v"(ho) : "v"(h), "v"(ov));
+          asm("v_sub_f32 %0, %1, %2" : "=v"(fs) : "v"(frun), "v"(ev));
+          asm("v_max_f32 %0, %1, %2" : "=v"(frun) : "v"(fs), "v"(ho));
+          E[r] = g;
+          Ho[r] = ho;
+          diag = w;
+        }
+        fout = frun;
+        // a later column wins only with a greater VALUE (header: Winner)
+        const bool take = mx > blk31;
+        tl = take ? t : tl;
+        blk = take ? mx : blk;
+        blk31 = __uint_as_float(__float_as_uint(blk) | 31u);
+      }
+    }
+    const uint32_t hist = buf32[kWaveSeg / 4 + (l & 3)];
+    if (l < 4) buf32[l] = hist;
+    buf32[4 + l] = nextc;
+    nextc = stage_load(seg + 2);
+  }
+
+  // the lane's winner: value, row of x, column of the window (1-based), then the slot's
+  const uint32_t kb = __float_as_uint(blk);
+  float bv = __uint_as_float(kb & ~31u) * sa.unscale;
+  long long bi = (long long)l * R + (31 - (int)(kb & 31u)) + 1;
+  long long bj = (long long)tl + 1;
+  if (!(bv > 0.0f)) { bv = 0.0f; bi = 0; bj = 0; }
+  slot_first_max(bv, bi, bj);
+  if (l == 0 && active) {
+    sa.best[pid] = bv;
+    sa.cell[2 * (size_t)pid] = bv > 0.0f ? bi : 0;
+    sa.cell[2 * (size_t)pid + 1] = bv > 0.0f ? bj : 0;
+  }
+}
+
+}  // namespace mi355sw
