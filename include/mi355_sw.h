@@ -319,7 +319,13 @@ int mi355_sw_last_counters(const mi355_sw_ctx *ctx, uint64_t out[4]);
  * strip rows its sweep saved, "saved_fallbacks" — those that took the zero-border windows instead; "wait_retries" — launches
  * repeated on a non-waiting instance after a wait between workgroups expired; "early_settled" — uint8 engine: queries settled
  * from the first and last sub-chunks without a sweep; "beyond_f16" — sequences of a many-small-alignments batch whose maximum lay
- * beyond the packed float16 pass's key range and were redone on float32 cells.  MI355_SW_EINVAL for an unknown name. */
+ * beyond the packed float16 pass's key range and were redone on float32 cells; "prefix_certified" — float engine, short-read
+ * batches against a long reference: queries settled by the prefix-row filter, i.e. without a sweep of all
+ * their rows (its offenders are swept on all rows and counted by "requeried"; when more than half of a batch offends the whole batch
+ * is swept, "whole_batch_again").  Options of the filter (mi355_sw_set_option): "no_prefix" switches it off (the A/B),
+ * "prefix_min_cols" = n moves the reference length from which it engages (default 8 Mi columns).  mi355_sw_last_kernel then names the
+ * prefix instance and its `cells` are the cells that launch swept (P rows per read), not |x| * |y|.
+ * MI355_SW_EINVAL for an unknown name. */
 int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *out);
 
 /* Which kernels and pipeline decisions the last call used: space-separated tags, each at most once, e.g.

@@ -14,8 +14,8 @@ constexpr size_t kExactLdsMax = 159 * 1024;    // dynamic part; the wide instanc
 #define MI355_SW_BOOL_OPTIONS(X) \
   X(no_f16) X(no_unsat) X(no_sample) X(no_satflag) X(no_solo) X(no_wave) X(no_comb) X(no_twin) X(no_wide) X(no_strip) \
   X(no_quant) X(no_devlist) X(no_ref_cache) X(no_strip_groups) X(u8_long_twin) X(long_twin) X(no_long) \
-  X(no_requery) X(force_f32) X(no_long_p32) X(no_opt_margin) X(no_wave_prof) X(no_wave_window) X(no_first) X(no_long_save) X(u8_sample_short) X(no_wave_pieces) X(no_u8_early) X(no_wave_f16) X(no_devlist_by_id) X(no_f16_mirror) X(no_f16m_int_diag) X(no_affine_sweep) X(no_affine_prof) X(no_affine_pairs) X(trace)
-#define MI355_SW_INT_OPTIONS(X) X(strip_r) X(slot) X(few_r) X(chunk) X(long_pipes) X(long_wgs) X(long_sub) X(long_r) X(long_groups) X(assume_cus) X(long_save_what)
+  X(no_requery) X(force_f32) X(no_long_p32) X(no_opt_margin) X(no_wave_prof) X(no_wave_window) X(no_first) X(no_long_save) X(u8_sample_short) X(no_wave_pieces) X(no_u8_early) X(no_wave_f16) X(no_devlist_by_id) X(no_f16_mirror) X(no_f16m_int_diag) X(no_affine_sweep) X(no_affine_prof) X(no_affine_pairs) X(no_prefix) X(trace)
+#define MI355_SW_INT_OPTIONS(X) X(strip_r) X(slot) X(few_r) X(chunk) X(long_pipes) X(long_wgs) X(long_sub) X(long_r) X(long_groups) X(assume_cus) X(long_save_what) X(prefix_min_cols)
 struct Options {
 #define X(n) bool n = false;
   MI355_SW_BOOL_OPTIONS(X)
@@ -23,6 +23,8 @@ struct Options {
 #define X(n) long n = 0;
   MI355_SW_INT_OPTIONS(X)
 #undef X
+  bool prefix_tiles = false;      // test hook, only through mi355_sw_set_option("prefix_tiles"), never from the environment: mi355_sw_score_ranges of ONE range
+                                  // sweeps a bucket of the prefix shape with its prefix instance (raw keys of the prefix tiles)
   int fault_inject = 0;           // test hook, only through mi355_sw_set_option("fault_inject", "strip_stall" | "long_stall"): never from the environment
 };
 inline std::string option_env_name(const char *n) {
@@ -53,6 +55,7 @@ inline int option_set(Options &o, const char *key, const char *value) {
 #define X(n) if (k == #n) { o.n = on ? std::atol(v.c_str()) : 0; return 0; }
   MI355_SW_INT_OPTIONS(X)
 #undef X
+  if (k == "prefix_tiles") { o.prefix_tiles = on; return 0; }
   if (k == "fault_inject") { o.fault_inject = v == "strip_stall" ? 1 : (v == "long_stall" ? 2 : 0); return 0; }
   return -1;
 }
@@ -61,7 +64,7 @@ inline const char *option_names() {
 #define X(n) #n ","
   MI355_SW_BOOL_OPTIONS(X) MI355_SW_INT_OPTIONS(X)
 #undef X
-  "fault_inject";
+  "prefix_tiles,fault_inject";
 }
 thread_local const Options *tl_opt = nullptr;
 inline const Options &opt() {
@@ -314,6 +317,8 @@ struct mi355_sw_ctx {
   size_t requeried = 0;           // queries of the running call that were swept a second time on the exact instances
   size_t whole_again = 0;         // ... times the whole batch was (most of it exceeded its candidate cap)
   size_t candidates = 0;          // candidate sub-chunks the sampled / saturating sweeps of the call flagged
+  bool prefix_named = false;      // last_kernel names the prefix instance of the running call: later sweeps (its offenders) add their cells to it
+  size_t prefix_certified = 0;    // queries of the running call settled by the prefix filter (lemma L19), without a sweep of all their rows
   const void *wlut_ref = nullptr; // reference (and its version) whose byte -> code tables are in `wlut` (sw_wave_prof_kernel)
   uint64_t wlut_version = 0;
   std::vector<uint8_t> h_wlut;
@@ -333,7 +338,7 @@ struct mi355_sw_ctx {
   std::vector<float> h_aprof;
   std::vector<uint8_t> h_pieces;  // host side of the piece table of the running call (host_batch.h)
   size_t saved_locates = 0, saved_traces = 0, saved_fallbacks = 0;   // finish steps of the running call that started from saved state / fell back
-  DevBuf qcnt, sel2, gcnt, wlut, ckpt, first, keys, ranges, stab, ftab, ftab_s, htab, htab8, soloblk, flags, submax, lut, probs, dirs, outs_f, outs_i, cons, walkp, hmat, brow, wprobs, scan;
+  DevBuf pkeys, pthr, psel, qcnt, sel2, gcnt, wlut, ckpt, first, keys, ranges, stab, ftab, ftab_s, htab, htab8, soloblk, flags, submax, lut, probs, dirs, outs_f, outs_i, cons, walkp, hmat, brow, wprobs, scan;
   // host sides of small per-call uploads: they must outlive the asynchronous copies, and the tables are only
   // sent again when they change
   std::vector<int64_t> h_ranges;

@@ -491,6 +491,139 @@ float elapsed_us(mi355_sw_ctx *ctx, hipEvent_t a, hipEvent_t b) {
   return ms * 1000.0f;
 }
 
+// (DESIGN.md §3.3 lemma L19.)  The prefix filter of one bucket (host_score.h prefix_ok), in front of the full sweep: a sampled sweep of
+// the first P = kPrefixLanes * R rows of every read, then all rows only where those rows allow the maximum.
+//   round 1: the sub-chunk of the read's prefix key and its right neighbours, evaluated exactly on all rows: B0, an exact alignment score;
+//   round 2: sw_prefix_filter flags every sub-chunk whose prefix value reaches B0 - smax (m - P) - slack; each flagged sub-chunk f
+//            stands for f .. f + D (D = ceil(W / sub_len): the end cell lies at most W columns right of its crossing of row P; the
+//            left neighbour is covered by the 63 columns a candidate window starts in front of its sub-chunk, locate_saturated),
+//            and what round 1 has not evaluated is evaluated now; the read's result is the first maximum over both rounds.
+// A read is an OFFENDER (appended to `offenders`, nothing written for it) when B0 cannot certify — B0 <= smax (m - P) + slack —
+// or when it flags more sub-chunks than its cap.  Everybody else: loc[] and qdone[] are final, qchunk[] / qwarm[] set.
+int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_params &p,
+                  const ScoreTable &table, const Bucket &b, std::vector<int64_t> &qchunk, std::vector<int64_t> &qwarm,
+                  std::vector<Located> &loc, std::vector<char> &qdone, std::vector<int> &offenders) {
+  HostTrace trace_("prefix_bucket");
+  const size_t nq = q.nq;
+  const int64_t n = rg.hi - rg.lo;
+  const std::vector<Range> ranges{rg};
+  int rc = score_begin(ctx, q, ranges, table);
+  if (rc) return rc;
+  if (ctx->pkeys.ensure(nq * 8 + 16) || ctx->pthr.ensure(nq * 4 + 16)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(score scratch) failed");
+  HIPCHK(ctx, hipMemsetAsync(ctx->pkeys.p, 0, nq * 8, ctx->stream));
+  // a. the prefix sweep: the bucket's own instance at kPrefixLanes lanes; keys and sub-chunk values as the sampled sweep writes them
+  Bucket pb = b;
+  pb.SL = kPrefixLanes; pb.prefix = true;
+  ScoreIO io;
+  io.range_lo = ctx->ranges.as<int64_t>(); io.range_hi = ctx->ranges.as<int64_t>() + 1; io.keys = ctx->pkeys.as<unsigned long long>();
+  rc = score_launch(ctx, ref, q, ranges, p, table, pb, &io);
+  if (rc) return rc;
+  std::vector<unsigned long long> pkeys;
+  rc = score_fetch(ctx, nq, pkeys, ctx->pkeys.p);
+  if (rc) return rc;
+  const int P = pb.SL * pb.R;
+  const int64_t E = pb.sub_len, nsub = (n + E - 1) / E;                            // sub-chunks that hold columns of the range
+  const int64_t stride = ((n + pb.chunk_len - 1) / pb.chunk_len) * (pb.chunk_len / E);   // value row of one read (whole tiles)
+  const float slack = sample_slack(table, pb), smax = (float)table.smax;
+  const int64_t W = (int64_t)(b.maxlen - P) + (int64_t)((int64_t)table.smax * (b.maxlen - P) / table.gap);
+  const int64_t D = (W + E - 1) / E;
+  static_assert(kPrefixLanes - 1 + kScoreMK - 1 <= 63, "a candidate window starts 63 columns in front of its sub-chunk: the lag of a prefix value");
+  // b. round 1
+  std::vector<float> bound(nq, 0.0f), qlow(nq, 0.0f), B0(nq, 0.0f), thr(nq, 0.0f);
+  std::vector<char> off(nq, 0), mine(nq, 0);
+  std::vector<std::pair<uint32_t, uint32_t>> f1;
+  for (int k = 0; k < b.count; ++k) {
+    const int id = q.order[b.first + k];
+    mine[id] = 1; qchunk[id] = E; qwarm[id] = b.warm;
+    // windows of both rounds only have to be exact for cells that hold a maximum above the certification bound (L3)
+    bound[id] = smax * (float)(q.len[id] - P) + slack;
+    qlow[id] = bound[id];
+    if (!(key_score(kKeyF16, (uint32_t)(pkeys[id] >> 32), 0) > 0)) { off[id] = 1; continue; }
+    const int64_t s0 = (int64_t)(0xFFFFFFFFull - (pkeys[id] & 0xFFFFFFFFull));
+    for (int64_t sc = s0; sc <= s0 + D && sc < nsub; ++sc) f1.push_back({(uint32_t)id, (uint32_t)sc});
+  }
+  std::sort(f1.begin(), f1.end());
+  std::vector<Located> loc1(nq), loc2(nq);
+  std::vector<char> done1(nq, 0), done2(nq, 0);
+  HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+  rc = locate_flagged(ctx, ref, q, rg, p, qchunk, qwarm, qlow, table, f1, loc1, done1);
+  if (rc) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+  ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+  size_t noff = 0;
+  for (int k = 0; k < b.count; ++k) {
+    const int id = q.order[b.first + k];
+    B0[id] = done1[id] ? loc1[id].score : 0.0f;
+    if (!off[id] && !(B0[id] > bound[id])) off[id] = 1;
+    if (!off[id]) thr[id] = B0[id] - smax * (float)(q.len[id] - P) - slack;      // (> 0: B0 is above the bound)
+    noff += off[id] ? 1 : 0;
+  }
+  auto give_up = [&]() {                                                         // most of the bucket offends: the full sweep for all of it
+    for (int k = 0; k < b.count; ++k) offenders.push_back(q.order[b.first + k]);
+    return 0;
+  };
+  if (2 * noff > (size_t)b.count) return give_up();
+  // c. round 2: one filter launch, per-query thresholds
+  const uint32_t qcap = query_flag_cap(nq);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->pthr.p, thr.data(), nq * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->flags.p, 0, 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->qcnt.p, 0, nq * 4, ctx->stream));
+  for (int f0 = 0; f0 < b.count; f0 += 65535) {
+    const int fc = std::min(65535, b.count - f0);
+    const dim3 fgrid((unsigned)std::min<int64_t>(64, (stride + 255) / 256), (unsigned)fc);
+    hipLaunchKernelGGL(sw_prefix_filter, fgrid, dim3(256), 0, ctx->stream, (const uint16_t *)ctx->submax.as<uint16_t>(), stride, stride,
+                       (const int32_t *)q.sel.as<int32_t>(), b.first, f0, b.count, (const float *)ctx->pthr.as<float>(),
+                       ctx->flags.as<unsigned int>(), reinterpret_cast<uint2 *>(ctx->flags.as<unsigned int>() + 2), ctx->flag_cap,
+                       ctx->qcnt.as<unsigned int>(), qcap);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  unsigned int nflag = 0;
+  std::vector<uint32_t> cnt(nq, 0);
+  HIPCHK(ctx, hipMemcpyAsync(&nflag, ctx->flags.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(cnt.data(), ctx->qcnt.p, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  nflag = std::min(nflag, ctx->flag_cap);
+  std::vector<uint32_t> raw(2 * (size_t)nflag);
+  if (nflag) HIPCHK(ctx, hipMemcpy(raw.data(), ctx->flags.as<unsigned int>() + 2, (size_t)nflag * 8, hipMemcpyDeviceToHost));
+  // d. offenders by the cap
+  for (int k = 0; k < b.count; ++k) {
+    const int id = q.order[b.first + k];
+    if (!off[id] && cnt[id] > qcap) { off[id] = 1; ++noff; }
+  }
+  if (opt().trace) std::fprintf(stderr, "[mi355_sw] prefix filter: %u flagged sub-chunks, %zu of %d reads offend (D = %lld)\n", nflag, noff, b.count, (long long)D);
+  if (2 * noff > (size_t)b.count) return give_up();
+  // e. what the flags add to round 1
+  std::vector<std::pair<uint32_t, uint32_t>> f2, f2new;
+  for (size_t f = 0; f < nflag; ++f) {
+    const uint32_t id = raw[2 * f];
+    if (id >= nq || !mine[id] || off[id]) continue;
+    for (int64_t sc = raw[2 * f + 1]; sc <= (int64_t)raw[2 * f + 1] + D && sc < nsub; ++sc) f2.push_back({id, (uint32_t)sc});
+  }
+  std::sort(f2.begin(), f2.end());
+  f2.erase(std::unique(f2.begin(), f2.end()), f2.end());
+  std::set_difference(f2.begin(), f2.end(), f1.begin(), f1.end(), std::back_inserter(f2new));
+  ctx->candidates += f1.size() + f2new.size();
+  if (!f2new.empty()) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    rc = locate_flagged(ctx, ref, q, rg, p, qchunk, qwarm, B0, table, f2new, loc2, done2);
+    if (rc) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+  }
+  for (int k = 0; k < b.count; ++k) {
+    const int id = q.order[b.first + k];
+    if (off[id]) { offenders.push_back(id); continue; }
+    Located best = loc1[id];                                                     // (done1: B0 > 0 came from it)
+    const int64_t m = q.len[id];
+    if (done2[id] && (loc2[id].score > best.score ||
+                      (loc2[id].score == best.score && host_order_key(p.semantics, loc2[id].ix, loc2[id].iy, m, n) < host_order_key(p.semantics, best.ix, best.iy, m, n))))
+      best = loc2[id];
+    loc[id] = best; qdone[id] = 1;
+    ctx->prefix_certified += 1;
+  }
+  return 0;
+}
+
 // All queries of `q` against one range of the reference: argmax cells and traceback views (into buffers the context
 // keeps until its next call), indexed by query id.
 // `pre` (mi355_sw_align_scored_range): the keys of an earlier mi355_sw_score_ranges sweep over this very range stand in
@@ -559,7 +692,8 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
       if (!(ctx->long_cert >= 0.0f) || best > ctx->long_cert) return true;
       const double m = (double)q.maxlen;
       ctx->long_margin = (int64_t)(m + std::ceil(((double)table.smax * m - (double)best) / (double)table.gap)) + 2 + 64;
-      ctx->last_kernel.cells = 0; ctx->timings[4] = 0; ctx->timings[5] = 0;
+      if (!ctx->prefix_named) ctx->last_kernel.cells = 0;          // (cells swept by a prefix filter of this call stay counted)
+      ctx->timings[4] = 0; ctx->timings[5] = 0;
       ctx->whole_again += 1;
       path_note(ctx, "margin_again");
       return false;
@@ -616,34 +750,106 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
         }
       }
     }
-    for (int attempt = 0; attempt < 4 && !pre && !all_early; ++attempt) {
+    // Prefix filter (lemma L19) in front of the sweep: the buckets it takes are settled here read by read; its offenders and the
+    // queries of every other bucket form the view `qs` that the sweep below works on (requery: they are swept on all their rows)
+    QueryBatch qrest;
+    const QueryBatch *qs = &q;
+    bool all_prefix = false;
+    if (!pre && !all_early && p.semantics == MI355_SW_F32 && !opt().no_prefix && nq >= 2 && n >= 1024 && n >= prefix_cols_min() && table.ok &&
+        rg.lo == 0 && (size_t)rg.hi == ref.n) {                        // (one range: the whole reference)
+      std::vector<Bucket> bk = make_buckets(ref, q, table, p, n, allow_sat, allow_sample);
+      std::vector<int> offenders;
+      const size_t candidates_before = ctx->candidates;
+      std::vector<char> tried(nq, 0);
+      size_t ntried = 0;
+      for (Bucket &b : bk) {
+        b.fast = bucket_fast_ok(ref, table, b, n, p);
+        if (!prefix_ok(table, b, q.len[q.order[b.first]], n, p)) continue;
+        // A large bucket is PROBED first: its first kPrefixProbe reads alone (the shortest: the hardest to certify).  When more than half
+        // of them offend — reads that differ too much from the reference for their first P rows to decide — the rest of the bucket
+        // skips the filter and is swept as ever: what such a batch pays for the filter is the probe (CHANGELOG.md: 10 % substitutions),
+        // not a prefix sweep of every read.  (A failed probe of the call's only eligible bucket ends in the rule below: whole_again.)
+        Bucket part = b;
+        if (b.count >= 8 * kPrefixProbe) {
+          part.count = kPrefixProbe;
+          const size_t before = offenders.size();
+          int rc = prefix_bucket(ctx, ref, q, rg, p, table, part, qchunk, qwarm, loc, qdone, offenders);
+          if (rc) return rc;
+          for (int k = 0; k < part.count; ++k) tried[q.order[part.first + k]] = 1;
+          ntried += (size_t)part.count;
+          if (2 * (offenders.size() - before) > (size_t)part.count) { path_note(ctx, "prefix_probe_failed"); continue; }
+          part.first = b.first + kPrefixProbe; part.count = b.count - kPrefixProbe;
+        }
+        int rc = prefix_bucket(ctx, ref, q, rg, p, table, part, qchunk, qwarm, loc, qdone, offenders);
+        if (rc) return rc;
+        for (int k = 0; k < part.count; ++k) tried[q.order[part.first + k]] = 1;
+        ntried += (size_t)part.count;
+      }
+      if (ntried && (2 * offenders.size() > ntried || (opt().no_requery && !offenders.empty()))) {
+        // most reads cannot be certified by their prefix (no hit, or a repeat family over the cap): the sweep decides for everybody
+        for (size_t k = 0; k < nq; ++k) if (tried[k]) { loc[k] = Located(); qdone[k] = 0; }
+        ctx->prefix_certified = 0; ctx->prefix_named = false; ctx->candidates = candidates_before;
+        ctx->last_kernel.cells = 0; ctx->timings[4] = 0; ctx->timings[5] = 0;
+        ctx->whole_again += 1;
+        path_note(ctx, "whole_again");
+      } else if (ntried) {
+        std::vector<int> rest;
+        std::vector<char> is_off(nq, 0);
+        for (int id : offenders) is_off[id] = 1;
+        for (size_t k = 0; k < nq; ++k) {
+          if (tried[k] && !is_off[k]) { qfast[k] = 1; qfloat[k] = kKeyF16; any_fast = true; }
+          else rest.push_back((int)k);
+        }
+        if (!offenders.empty()) { ctx->requeried += offenders.size(); path_note(ctx, "requery"); }
+        if (rest.empty()) all_prefix = true;
+        else {
+          // a view of the batch that lists only `rest` (same device bytes / offsets / lengths, own sorted id list)
+          qrest.bytes.alias(q.bytes.p); qrest.lens.alias(q.lens.p); qrest.offs.alias(q.offs.p); qrest.cum.alias(q.cum.p);
+          qrest.len = q.len; qrest.off = q.off;
+          qrest.order.assign(rest.begin(), rest.end());
+          std::stable_sort(qrest.order.begin(), qrest.order.end(), [&](int32_t a, int32_t b2) { return q.len[a] < q.len[b2]; });
+          qrest.nq = rest.size();
+          qrest.maxlen = 0;
+          for (int id : rest) qrest.maxlen = std::max(qrest.maxlen, (int)q.len[id]);
+          if (ctx->psel.ensure(qrest.nq * 4 + 16)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(score scratch) failed");
+          HIPCHK(ctx, hipMemcpy(ctx->psel.p, qrest.order.data(), qrest.nq * 4, hipMemcpyHostToDevice));
+          qrest.sel.alias(ctx->psel.p);
+          qs = &qrest;
+        }
+      }
+    }
+    if (all_prefix) keys.assign(nq, 0ull);
+    const bool prefix_kept = qs != &q || all_prefix;                   // reads settled above stay settled whatever the sweep below does
+    for (int attempt = 0; attempt < 4 && !pre && !all_early && !all_prefix; ++attempt) {
       buckets.clear();
-      if (n >= 1024) buckets = make_buckets(ref, q, table, p, n, allow_sat, allow_sample);
-      any_fast = false;
+      if (n >= 1024) buckets = make_buckets(ref, *qs, table, p, n, allow_sat, allow_sample);
+      any_fast = prefix_kept;
       bool any_sat = false;
+      bool any_sweep = false;
       for (Bucket &b : buckets) {
-        b.fast = bucket_fast_ok(ref, table, b, n, p); any_fast |= b.fast; any_sat |= b.fast && (b.satflag || b.sampled);
+        b.fast = bucket_fast_ok(ref, table, b, n, p); any_fast |= b.fast; any_sweep |= b.fast; any_sat |= b.fast && (b.satflag || b.sampled);
         // (not for the uint8 engine's unsaturated sweep: there every cell that reaches 255 must be exact, wherever it lies)
         b.opt_margin = b.longp && !b.unsat && nq == 1 && !opt().no_opt_margin;   // (certified below for a lone query only)
       }
-      if (!any_fast) break;
+      if (!any_sweep) { if (prefix_kept) keys.assign(nq, 0ull); break; }
       const std::vector<Range> ranges{rg};
       int rc = score_begin(ctx, q, ranges, table);
       if (rc) return rc;
       std::fill(qsat.begin(), qsat.end(), 0);
       for (Bucket &b : buckets) {
         if (!b.fast) continue;
-        rc = score_launch(ctx, ref, q, ranges, p, table, b);
+        rc = score_launch(ctx, ref, *qs, ranges, p, table, b);
         if (rc) return rc;
         for (int k = 0; k < b.count; ++k) {
-          const int id = q.order[b.first + k];
+          const int id = qs->order[b.first + k];
           qfast[id] = 1; qchunk[id] = b.sub_len; qwarm[id] = b.warm; qsat[id] = b.sampled ? 2 : (b.satflag ? 1 : 0);
           qfloat[id] = key_kind(b);
         }
       }
       rc = score_fetch(ctx, nq, keys);
       if (rc == kRetryNoWait) {                                       // (an expired wait between workgroups: the non-waiting layout)
-        ctx->last_kernel.cells = 0; ctx->timings[4] = 0; ctx->timings[5] = 0;
+        if (!ctx->prefix_named) ctx->last_kernel.cells = 0;        // (cells swept by a prefix filter of this call stay counted)
+        ctx->timings[4] = 0; ctx->timings[5] = 0;
         continue;
       }
       if (rc) return rc;
@@ -665,7 +871,7 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
         // saturated nearly everywhere (a background that reaches the cap): the exact sweep instead, for every query
         allow_sat = false;
         allow_sample = false;
-        ctx->last_kernel.cells = 0;                                  // the sweep that counts is the one that follows
+        if (!ctx->prefix_named) ctx->last_kernel.cells = 0;         // the sweep that counts is the one that follows
         ctx->timings[4] = 0; ctx->timings[5] = 0;                    // launches / cells: only the sweep that produced the result
                                                                      // (its device time stays in timings[0]: honest extra cost)
         ctx->whole_again += 1;
@@ -1022,6 +1228,12 @@ int range_maxima(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     if (!b.longp) b.sampled = false;                               // only sw_long_kernel lays out one value row per range
     sampled |= b.fast && b.sampled;
     b.opt_margin = winner_only && b.longp && !b.unsat && nq == 1 && !opt().no_opt_margin;
+    // test hook (option prefix_tiles, one range): a bucket of the prefix shape is swept by its PREFIX instance — the maxima are then
+    // the sampled keys of the reads' first P rows (lower bounds within sample_slack, tests/test_gpu_prefix_tiles.py)
+    if (opt().prefix_tiles && nr == 1 && !winner_only && b.fast && b.sem == kSemF16 && b.mirror && !b.strips && !b.twin && !b.satflag && !b.unsat &&
+        b.SL == 8 && b.count >= 2 && kernel_sem(b) == kSemF16M && listed(kR8M, b.R)) {
+      b.SL = kPrefixLanes; b.prefix = true; b.sampled = true;
+    }
   }
   ctx->long_margin = 0;
   if (winner_only && nq == 1 && known_best > 0.0f && table.integral)
@@ -1147,7 +1359,7 @@ void reset_timings(mi355_sw_ctx *ctx) {
   for (double &t : ctx->timings) t = 0;
   ctx->score_ev_used = 0; ctx->arenas.clear(); ctx->cons_used = 0;
   ctx->last_kernel = mi355_sw_kernel_info{};
-  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
+  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
   ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
   ctx->path.clear();
 }

@@ -41,6 +41,8 @@ struct Bucket {
   int nstrips = 0;            // ... strips (= wavefronts) per tile
   bool satflag = false;       // float engine swept on float16 cells BEYOND their exact range (the sweep saturates at 2048):
                               // sub-chunks that reach the cap are flagged and re-evaluated exactly (locate_saturated)
+  bool prefix = false;        // a PREFIX sweep (lemma L19): SL = kPrefixLanes lanes x R rows = the first P rows of queries that are longer;
+                              // its sub-chunk values stay in ctx->submax for sw_prefix_filter (host_pipeline.h prefix_bucket), no filter here
   int64_t warm = 0;           // exactness margin in columns
   bool fast = false;          // swept by the score kernel (else whole-matrix exact path)
   int64_t chunk_len = 0;      // own columns per tile
@@ -56,6 +58,7 @@ constexpr int kR16S[] = {32};                                  // 16-lane tiles 
 constexpr int kR64S[] = {20, 24, 32};                          // whole-wavefront tiles in strips
 constexpr int kR8M[] = {13, 16, 19, 26, 32};                   // sampled maximum (MK = 4) on 8-lane tiles
 constexpr int kR16M[] = {10, 12, 16, 20, 24, 32};              // ... on 16-lane and whole-wavefront tiles
+constexpr int kPrefixLanes = 2;                                // lanes of a prefix tile (lemma L19): P = kPrefixLanes * R rows, on the kR8M list
 template <size_t N> constexpr bool listed(const int (&rs)[N], long r) { for (int v : rs) if (v == r) return true; return false; }
 
 // sw_score_kernel<R, sem, strips, SL, twin, comb, mk>
@@ -86,6 +89,7 @@ constexpr ScoreShapes kScoreShapes[] = {
   {kR8M, std::size(kR8M), false, 8, false, false, 4, kCellsSampled | kCellsMirror},
   {kR16M, std::size(kR16M), false, 64, false, false, 4, kCellsSampled},
   {kR64S, std::size(kR64S), true, 64, false, false, 4, 1u << kSemF32},         // a lone long query on float32 cells
+  {kR8M, std::size(kR8M), false, kPrefixLanes, false, false, 4, 1u << kSemF16M},   // prefix tiles of the 8-lane shapes (lemma L19)
 };
 constexpr size_t score_inst_count() {
   size_t n = 0;
@@ -125,6 +129,7 @@ static_assert(score_compiled(kR8M, false, 8, false, false, 4, kCellsSampled | kC
               score_compiled(kR16M, false, 16, false, false, 4, kCellsSampled | kCellsMirror) &&
               score_compiled(kR16M, false, 64, false, false, 4, kCellsSampled) && score_compiled(kR64S, true, 64, false, false, 4, 1u << kSemF32),
               "sampled_instance");
+static_assert(score_compiled(kR8M, false, kPrefixLanes, false, false, 4, 1u << kSemF16M), "prefix_ok");
 
 typedef void (*ScoreKernel)(const ScoreArgs);
 template <size_t... I> constexpr std::array<ScoreKernel, sizeof...(I)> score_kernels(std::index_sequence<I...>) {
@@ -489,6 +494,22 @@ int launch_score(const ScoreInst &want, dim3 grid, size_t shmem, hipStream_t st,
 int kernel_sem(const Bucket &b) {
   if (b.sem == kSemF16 && b.mirror) return opt().no_f16m_int_diag ? kSemF16MF : kSemF16M;
   return b.sem;
+}
+
+// Prefix filter (DESIGN.md §3.3 lemma L19) in front of the full sweep of a bucket: float engine, integer scoring, sampled mirrored
+// 8-lane tiles in one strip (the instances compiled at kPrefixLanes lanes), one whole-reference range of at least prefix_cols_min()
+// columns, and reads long enough beyond P = kPrefixLanes * R rows that the rule can certify at all: the best score of the SHORTEST
+// read must exceed what the rows below P of the LONGEST can score, plus the sampling slack.
+constexpr int64_t kPrefixMinCols = (int64_t)8 << 20;   // range length from which the filter engages (CHANGELOG.md has what was measured)
+constexpr int kPrefixProbe = 64;                       // reads of a bucket of >= 8 x as many that take the filter first, as a probe (align_range_core)
+inline int64_t prefix_cols_min() { const long v = opt().prefix_min_cols; return v > 0 ? (int64_t)v : kPrefixMinCols; }
+bool prefix_ok(const ScoreTable &t, const Bucket &b, int minlen, int64_t n, const mi355_sw_params &p) {
+  if (opt().no_prefix || p.semantics != MI355_SW_F32 || !t.integral || t.gap <= 0 || t.smax <= 0) return false;
+  if (!(b.fast && b.sem == kSemF16 && b.mirror && b.sampled && !b.strips && !b.twin && !b.satflag && !b.unsat && b.SL == 8 && b.count >= 2)) return false;
+  if (kernel_sem(b) != kSemF16M || !listed(kR8M, b.R)) return false;
+  const int P = kPrefixLanes * b.R;
+  if (minlen <= P || n < prefix_cols_min()) return false;
+  return (float)t.smax * (float)minlen > (float)t.smax * (float)(b.maxlen - P) + sample_slack(t, b);
 }
 
 // What a score launch passes that depends on the kernel's cell type
@@ -937,7 +958,14 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   a.qcount = std::min(b.count - (int)(p0 * nqw), (int)(pn * nqw));
   size_t shmem = profile_lds_bytes(ref.ncodes, b.R, b.SL, b.twin, b.comb) + (size_t)(b.twin ? 2 : 1) * nslot * codebuf_bytes(b.SL);
   const int64_t nsub = cpr * (b.chunk_len / b.sub_len);                // sub-chunks of the range (sampled sweep: one value each)
-  if (b.sampled) {
+  if (b.prefix) {
+    // every launch's rows stay (bucket-local query position p at submax[p * nsub ..]): the filter runs after the first locate round,
+    // and before any other sweep of the call needs the buffer (prefix_bucket finishes its bucket)
+    if (p0 == 0 && ctx->submax.ensure((size_t)b.count * (size_t)nsub * cl.value_bytes + 64))
+      return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(sub-chunk values) failed");
+    a.submax_out = ctx->submax.as<uint16_t>() + p0 * (size_t)nqw * (size_t)nsub;
+    a.submax_stride = nsub;
+  } else if (b.sampled) {
     if (ctx->submax.ensure((size_t)pn * (size_t)nqw * (size_t)nsub * cl.value_bytes + 64))
       return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(sub-chunk values) failed");
     a.submax_out = ctx->submax.as<uint16_t>();
@@ -969,9 +997,10 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   const ScoreInst inst{b.R, sem, b.strips, b.SL, b.twin, b.comb, a.submax_out != nullptr ? kScoreMK : 1};
   if (launch_score(inst, grid, shmem, ctx->stream, a)) return fail(ctx, MI355_SW_ENOTSUP, "no score kernel instance for this R");
   HIPCHK(ctx, hipGetLastError());
-  path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d%s,satflag=%d,unsat=%d,pow2=%d%s]", cl.cell, b.SL, b.R, (int)b.strips,
+  if (b.prefix) path_note(ctx, "prefix[SL=%d,R=%d,P=%d]", b.SL, b.R, b.SL * b.R);
+  else path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d%s,satflag=%d,unsat=%d,pow2=%d%s]", cl.cell, b.SL, b.R, (int)b.strips,
             (int)b.twin, (int)b.comb, (int)b.sampled, rows_note, (int)b.satflag, (int)b.unsat, (int)((b.chunk_len & (b.chunk_len - 1)) == 0), cl.tag);
-  if (b.sampled) {
+  if (b.sampled && !b.prefix) {
     // grid.y = query positions of this launch, at most 65535 per filter launch
     for (int f0 = 0; f0 < a.qcount; f0 += 65535) {
       const int fc = std::min(65535, a.qcount - f0);
@@ -1006,10 +1035,12 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   }
   double cells = 0;
   for (int k = 0; k < b.count; ++k)
-    for (auto &r : ranges) cells += (double)q.len[q.order[b.first + k]] * (double)(r.hi - r.lo);
+    for (auto &r : ranges) cells += (double)(b.prefix ? std::min(b.SL * b.R, (int)q.len[q.order[b.first + k]]) : q.len[q.order[b.first + k]]) * (double)(r.hi - r.lo);
   ctx->timings[5] += cells;
-  if (cells > ctx->last_kernel.cells) {
+  if (ctx->prefix_named && !b.prefix) ctx->last_kernel.cells += cells;   // (the offenders of a prefix filter: cells actually swept)
+  else if (b.prefix || cells > ctx->last_kernel.cells) {
     mi355_sw_kernel_info &ki = ctx->last_kernel;
+    if (b.prefix) { cells += ctx->prefix_named ? ki.cells : 0.0; ctx->prefix_named = true; }
     ki.cell = b.sem; ki.lanes = b.SL; ki.rows_per_lane = b.R; ki.strips = b.strips; ki.twin = b.twin;
     ki.chunk_len = b.chunk_len; ki.sub_len = b.sub_len; ki.warm = a.warm; ki.cells = cells;
     ki.valu_ops_per_cell = valu_ops_per_cell(b);
@@ -1020,6 +1051,10 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     if (b.sampled) {
       const size_t at = std::strlen(ki.name);
       std::snprintf(ki.name + at, sizeof ki.name - at, "; maximum folded every 4th step (candidates re-evaluated), row stride %d", sample_rows(b));
+    }
+    if (b.prefix) {
+      const size_t at = std::strlen(ki.name);
+      std::snprintf(ki.name + at, sizeof ki.name - at, "; prefix rows 1..%d only (exact filter, all rows where they allow the maximum)", b.SL * b.R);
     }
   }
   return 0;
@@ -1050,9 +1085,9 @@ float key_score(int kind, uint32_t hi, int fshift) {
 
 constexpr int kRetryNoWait = 1;   // score_fetch: not an error — sweep again, tl_no_wait is set
 
-int score_fetch(mi355_sw_ctx *ctx, size_t count, std::vector<unsigned long long> &keys) {
+int score_fetch(mi355_sw_ctx *ctx, size_t count, std::vector<unsigned long long> &keys, const void *from = nullptr) {
   keys.resize(count);
-  HIPCHK(ctx, hipMemcpyAsync(keys.data(), ctx->keys.p, count * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(keys.data(), from ? from : ctx->keys.p, count * 8, hipMemcpyDeviceToHost, ctx->stream));
   int32_t long_status = 0;
   if (ctx->long_launched) HIPCHK(ctx, hipMemcpyAsync(&long_status, ctx->flags.as<unsigned int>() + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

@@ -41,7 +41,7 @@ typedef short i16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kSlotLanes = 16;         // lanes of a DPP row; a tile ("slot") takes 16 or 8 of them
+constexpr int kSlotLanes = 16;         // lanes of a DPP row; a tile ("slot") takes 16 or 8 of them (prefix tiles: 4 or 2)
 constexpr int kSeg = 64;               // steps between two refills of the code window
 // bytes of history kept in front of a segment (>= lanes per slot - 1), and the per-slot window size
 __host__ __device__ constexpr int hist_bytes(int SL) { return SL > 16 ? SL : 16; }
@@ -322,7 +322,9 @@ template <> struct Cell<kSemF32U8> : CellF<kSemF32U8> {};
 // compiled instances (host_score.h)
 template <int SEM> __host__ __device__ constexpr bool score_instance_ok(int R, bool STRIPS, int SL, bool TWIN, bool COMB, int MK) {
   typedef Cell<SEM> C;
-  return (SL == 64 || SL == 16 || SL == 8) &&                      // a slot is a whole wavefront, a DPP row or half a DPP row
+  return (SL == 64 || SL == 16 || SL == 8 ||                       // a slot is a whole wavefront, a DPP row or half a DPP row,
+          // or a PREFIX tile of 4 or 2 lanes: the first SL*R rows of longer queries on mirrored cells (lemma L19, host_score.h)
+          ((SL == 4 || SL == 2) && C::kMirror && !STRIPS && !TWIN)) &&
          !(STRIPS && SL == 8) &&                                   // the strip-mined instances use whole DPP rows or wavefronts
          (!TWIN || ((SL == 64 || SL == 16) && !C::kFloat && R % 2 == 0)) &&   // twin tiles: packed cells, 64- or 16-lane tiles
          (!COMB || (TWIN && !STRIPS)) &&                           // the code-pair profile belongs to the twin instances
@@ -339,6 +341,8 @@ __host__ __device__ constexpr int fold_row_stride(int R, int MK) { return MK == 
 
 // SL = lanes per tile ("slot"): 16 (one DPP row) or 8 (half a DPP row; the DPP shift then needs one mask op
 // per step, but 8*R rows fit the read length more tightly: 150 bp = 8 x 19 rows instead of 16 x 10).
+// SL = 4 or 2 (mirrored cells): a PREFIX tile — the profile is built for rows 0 .. SL*R - 1 of queries that are longer, so the
+// tile sweeps the matrix of x[0 : SL*R], which is the first SL*R rows of the query's own matrix; 256 / SL tiles per workgroup.
 // STRIPS = false: the whole query (<= SL*R rows) is one strip held in registers.
 // STRIPS = true : the query is swept in strips of SL*R rows; the bottom row of strip s over the tile's
 // columns goes through a per-tile global scratch row (L2-resident) and enters strip s+1 through the
@@ -501,12 +505,23 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   // first fill: history = padding; later: the last HIST bytes of the window move to its front
   auto window_init = [&]() {
     if (SL == 64) { buf[ls] = (uint8_t)pad; if (TWIN) buf2[ls] = (uint8_t)pad; }
+    else if constexpr (SL < HIST / 4) {                             // prefix tiles: fewer lanes than history dwords
+#pragma unroll
+      for (int e = 0; e < HIST / 4; e += SL) buf32[e + ls] = pad4;
+    }
     else if (ls < HIST / 4) { buf32[ls] = pad4; if (TWIN) buf2_32[ls] = pad4; }
   };
   auto window_slide = [&]() {
     if (SL == 64) {
       const uint8_t h = buf[kSeg + ls]; buf[ls] = h;
       if (TWIN) { const uint8_t h2 = buf2[kSeg + ls]; buf2[ls] = h2; }
+    }
+    else if constexpr (SL < HIST / 4) {
+      uint32_t h[HIST / 4 / SL];
+#pragma unroll
+      for (int e = 0; e < HIST / 4 / SL; ++e) h[e] = buf32[kSeg / 4 + e * SL + ls];
+#pragma unroll
+      for (int e = 0; e < HIST / 4 / SL; ++e) buf32[e * SL + ls] = h[e];
     }
     else {
       const uint32_t h = buf32[kSeg / 4 + (ls & 3)]; if (ls < HIST / 4) buf32[ls] = h;
@@ -830,6 +845,27 @@ __global__ __launch_bounds__(256) void sw_sample_filter(const void *submax, int6
       if (qcnt != nullptr && atomicAdd(&qcnt[q], 1u) > per_query_cap) continue;
       const unsigned int at = atomicAdd(flag_count, 1u);
       if (at < flag_cap) flag_list[at] = make_uint2((unsigned int)q, (unsigned int)s + sub_offset);
+    }
+  }
+}
+
+// Prefix sweep (lemma L19): every sub-chunk whose prefix value reaches ITS QUERY's threshold thr[q] (H units) is appended to the
+// flag list; a query without a positive threshold is an offender on the host and lists nothing.  grid.y = bucket-local query
+// position (the value rows of the prefix sweep), threads stride over sub-chunks; the per-query count and cap of sw_sample_filter.
+__global__ __launch_bounds__(256) void sw_prefix_filter(const uint16_t *submax, int64_t stride, int64_t nsub, const int32_t *qsel,
+                                                        int qfirst, int pos0, int qcount, const float *thr, unsigned int *flag_count,
+                                                        uint2 *flag_list, uint32_t flag_cap, unsigned int *qcnt, uint32_t per_query_cap) {
+  const int pos = pos0 + (int)blockIdx.y;
+  if (pos >= qcount) return;
+  const int q = qsel[qfirst + pos];
+  const float t = thr[q];
+  if (!(t > 0.0f)) return;
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nsub; s += (int64_t)gridDim.x * blockDim.x) {
+    const float v = (float)__builtin_bit_cast(_Float16, submax[(size_t)pos * (size_t)stride + (size_t)s]) * 2048.0f;
+    if (v >= t) {
+      if (atomicAdd(&qcnt[q], 1u) > per_query_cap) continue;
+      const unsigned int at = atomicAdd(flag_count, 1u);
+      if (at < flag_cap) flag_list[at] = make_uint2((unsigned int)q, (unsigned int)s);
     }
   }
 }
