@@ -1,7 +1,8 @@
 // host_affine.h — affine-gap score, end cell and traceback: parameter checks, the sw_affine_kernel sweep, the
 // sw_affine_exact_kernel behind it, sw_affine_trace_kernel (sw_affine_kernel.h) and, for references (ranges) of
 // at most 512 letters, sw_affine_prof_kernel (sw_affine_prof_kernel.h); for lists of (query, window) pairs, sw_affine_pair_kernel
-// (sw_affine_pair_kernel.h).
+// (sw_affine_pair_kernel.h).  The drivers affine_run (affine_prof_run, affine_sweep) and affine_pairs (affine_pair_stage) share one
+// AffineCall (affine_begin .. affine_end) and one affine_note_kernel, affine_exact_stage, affine_download and affine_class_table.
 // Part of the single translation unit mi355_sw.hip (included there, in order; not a standalone header).
 namespace {
 
@@ -65,27 +66,53 @@ int affine_table(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_affine_pa
   return 0;
 }
 
+// One affine call, as every stage below takes it: where it runs, on what, its scoring and the table of that scoring
+struct AffineCall {
+  mi355_sw_ctx *ctx;
+  const RefData &ref; const QueryBatch &q;   // the reference and the batch it runs on
+  const mi355_sw_affine_params &p;
+  AffineTable t;
+};
+
+// Opens the call: fills c.t and starts the call's interval (ev[4]).  0: go on; 1: nothing to do, the caller's zeroed outputs
+// stand; negative: the error.
+int affine_begin(AffineCall &c) {
+  { int rc = affine_table(c.ctx, c.ref, c.p, c.t); if (rc) return rc; }
+  if (c.t.smax <= 0) return 1;                                     // no positive cell: every maximum is 0
+  HIPCHK(c.ctx, hipEventRecord(c.ctx->ev[4], c.ctx->stream));
+  return 0;
+}
+
+// One launch (the sweep: one bucket) of an affine score kernel over `cells` cells: counted in timings[5] and, where it is the
+// largest of the call so far, described in last_kernel; `fmt` makes its name.
+__attribute__((format(printf, 10, 11)))
+void affine_note_kernel(mi355_sw_ctx *ctx, double cells, int cell, int lanes, int R, int64_t chunk_len, int64_t sub_len, int64_t warm,
+                        double valu_ops_per_cell, const char *fmt, ...) {
+  ctx->timings[5] += cells;
+  if (!(cells > ctx->last_kernel.cells)) return;
+  mi355_sw_kernel_info &ki = ctx->last_kernel;
+  ki.cell = cell; ki.lanes = lanes; ki.rows_per_lane = R; ki.strips = 0; ki.twin = 0;
+  ki.chunk_len = chunk_len; ki.sub_len = sub_len; ki.warm = warm; ki.cells = cells; ki.valu_ops_per_cell = valu_ops_per_cell;
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(ki.name, sizeof ki.name, fmt, ap);
+  va_end(ap);
+}
+
 typedef void (*AffineKernel)(const ScoreArgs, const uint32_t, const uint32_t);
-template <size_t... I> AffineKernel affine_kernel16(int R, std::index_sequence<I...>) {
-  AffineKernel k = nullptr;
-  ((kR16[I] == R ? (void)(k = &sw_affine_kernel<kR16[I], 16>) : (void)0), ...);
-  return k;
-}
-template <size_t... I> AffineKernel affine_kernel8(int R, std::index_sequence<I...>) {
-  AffineKernel k = nullptr;
-  ((kR8[I] == R ? (void)(k = &sw_affine_kernel<kR8[I], 8>) : (void)0), ...);
-  return k;
-}
 // the instance for a shape of pick_shape: every R of kR16 on 16 lanes, every R of kR8 on 8
 AffineKernel affine_kernel(int SL, int R) {
-  return SL == 8 ? affine_kernel8(R, std::make_index_sequence<std::size(kR8)>{}) : affine_kernel16(R, std::make_index_sequence<std::size(kR16)>{});
+  AffineKernel k = nullptr;
+  if (SL == 8) with_listed_R<kR8>(R, [&](auto r) { k = &sw_affine_kernel<decltype(r)::value, 8>; });
+  else with_listed_R<kR16>(R, [&](auto r) { k = &sw_affine_kernel<decltype(r)::value, 16>; });
+  return k;
 }
 
 size_t affine_exact_lds(int m) { return (size_t)7 * (m + 2) * 4 + (size_t)m + 16; }
 
 // Runs jobs[lo, hi) on sw_affine_exact_kernel in one launch (ExactJob: q, ylo, nw, col_offset, own_lo, target -> best, ci, cj).
-int run_affine_exact(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const mi355_sw_affine_params &p,
-                     std::vector<ExactJob> &jobs, size_t lo, size_t hi) {
+int run_affine_exact(const AffineCall &c, std::vector<ExactJob> &jobs, size_t lo, size_t hi) {
+  mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q;
   const size_t n = hi - lo;
   if (n == 0) return 0;
   size_t lds = 0;
@@ -114,7 +141,7 @@ int run_affine_exact(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
   }
   HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactProblem), hipMemcpyHostToDevice, ctx->stream));
   AffineScoring sc;
-  { int rc = affine_scoring(ctx, p, sc); if (rc) return rc; }
+  { int rc = affine_scoring(ctx, c.p, sc); if (rc) return rc; }
   launch_dyn_lds(&sw_affine_exact_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactProblem>(), sc);
   HIPCHK(ctx, hipGetLastError());
   std::vector<float> bf(n);
@@ -126,9 +153,47 @@ int run_affine_exact(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
   return 0;
 }
 
+// Query q of the batch against the n columns from `lo` as a whole problem of the exact kernel, `index` the caller's range or pair.
+// False where the kernel does not take it: too many cells, or scores beyond float32's integers (the caller words the refusal).
+bool affine_whole_job(const AffineCall &c, int q, int64_t lo, int64_t n, size_t index, ExactJob &j) {
+  const double m = (double)c.q.len[q];
+  if (m * (double)n > kAffineExactCellsMax || (double)c.t.smax * (m + 1.0) >= 16777216.0) return false;
+  j.q = q; j.ylo = lo; j.nw = (int32_t)n; j.col_offset = 0; j.full_n = n; j.own_lo = 1; j.quirk = 0;
+  j.target = -1.0f; j.want_dirs = false; j.index = index;
+  return true;
+}
+
+// The exact kernel over all of `jobs`, 65536 per launch; its interval (ev[2]..ev[3]) goes to timings[1].
+int affine_exact_stage(const AffineCall &c, std::vector<ExactJob> &jobs) {
+  mi355_sw_ctx *ctx = c.ctx;
+  if (jobs.empty()) return 0;
+  HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+  for (size_t lo = 0; lo < jobs.size(); lo += 65536) {
+    { int rc = run_affine_exact(c, jobs, lo, std::min(jobs.size(), lo + 65536)); if (rc) return rc; }
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+  ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+  return 0;
+}
+
+// (best, cell) of the np problems launched since ev[0], from outs_f / outs_i through pin_out: closes the interval (ev[1]), copies,
+// waits, adds the interval to timings[0].  h_best[np], h_cell[np][2]: views into pin_out.  `nomem`: the caller's ENOMEM message.
+int affine_download(mi355_sw_ctx *ctx, size_t np, const char *nomem, const float *&h_best, const int64_t *&h_cell) {
+  HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+  const size_t o_cell = (np * 4 + 15) & ~(size_t)15;
+  if (ctx->pin_out.ensure(o_cell + np * 16)) return fail(ctx, MI355_SW_ENOMEM, nomem);
+  uint8_t *pin = ctx->pin_out.as<uint8_t>();
+  h_best = reinterpret_cast<const float *>(pin); h_cell = reinterpret_cast<const int64_t *>(pin + o_cell);
+  HIPCHK(ctx, hipMemcpyAsync(pin, ctx->outs_f.p, np * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(pin + o_cell, ctx->outs_i.p, np * 16, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->timings[0] += elapsed_us(ctx, ctx->ev[0], ctx->ev[1]);
+  return 0;
+}
+
 // One bucket of the batch on sw_affine_kernel over `ranges` (device copies in ctx->ranges, keys in ctx->keys).
-int affine_sweep_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const std::vector<Range> &ranges,
-                        const AffineTable &t, Bucket &b) {
+int affine_sweep_launch(const AffineCall &c, const std::vector<Range> &ranges, Bucket &b) {
+  mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q; const AffineTable &t = c.t;
   const size_t nr = ranges.size();
   int64_t maxlen = 0;
   double range_cols = 0;
@@ -179,17 +244,11 @@ int affine_sweep_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch 
   path_note(ctx, "affine[cell=f16,SL=%d,R=%d]", b.SL, b.R);
   double cells = 0;
   for (int k = 0; k < b.count; ++k) cells += (double)q.len[q.order[b.first + k]] * range_cols;
-  ctx->timings[5] += cells;
-  if (cells > ctx->last_kernel.cells) {
-    mi355_sw_kernel_info &ki = ctx->last_kernel;
-    ki.cell = MI355_SW_CELL_F16; ki.lanes = b.SL; ki.rows_per_lane = b.R; ki.strips = 0; ki.twin = 0;
-    ki.chunk_len = b.chunk_len; ki.sub_len = b.sub_len; ki.warm = a.warm; ki.cells = cells;
-    // as valu_ops_per_cell (host_score.h): per step seven ops per row and a maximum3 per two rows, the overhead of the linear
-    // sweep (DPP move, profile address, code extract; border mask on 8-lane tiles) and F's DPP move (8 lanes: and its and-or),
-    // over the two cells of a register
-    ki.valu_ops_per_cell = (7.0 * b.R + (b.R + 1) / 2 + (b.SL == 8 ? 6.0 : 4.0)) / (2.0 * b.R);
-    std::snprintf(ki.name, sizeof ki.name, "sw_affine_kernel<R=%d, f16x2, SL=%d>", b.R, b.SL);
-  }
+  // as valu_ops_per_cell (host_score.h): per step seven ops per row and a maximum3 per two rows, the overhead of the linear
+  // sweep (DPP move, profile address, code extract; border mask on 8-lane tiles) and F's DPP move (8 lanes: and its and-or),
+  // over the two cells of a register
+  affine_note_kernel(ctx, cells, MI355_SW_CELL_F16, b.SL, b.R, b.chunk_len, b.sub_len, a.warm,
+                     (7.0 * b.R + (b.R + 1) / 2 + (b.SL == 8 ? 6.0 : 4.0)) / (2.0 * b.R), "sw_affine_kernel<R=%d, f16x2, SL=%d>", b.R, b.SL);
   return 0;
 }
 
@@ -232,8 +291,7 @@ void affine_byte_classes(const RefData &ref, const mi355_sw_affine_params &p, co
 
 void affine_prof_plan(const RefData &ref, const mi355_sw_affine_params &p, const AffineTable &t, AffineProfPlan &plan) {
   plan.ok = false;
-  if (opt().no_affine_prof) return;
-  affine_byte_classes(ref, p, t, plan);
+  if (!opt().no_affine_prof) affine_byte_classes(ref, p, t, plan);
 }
 
 bool affine_prof_range_ok(const AffineProfPlan &plan, const AffineTable &t, int64_t n) {
@@ -242,12 +300,34 @@ bool affine_prof_range_ok(const AffineProfPlan &plan, const AffineTable &t, int6
   return wave_prof_lds(plan.nclass, wave_prof_R((int)n)) <= kAffineProfLdsMax;
 }
 
+// The class table of sw_affine_prof_kernel / sw_affine_pair_kernel for cells of at most `side` + 1 steps of smax, built and sent to
+// ctx->aprof: tab_floats floats, (s + o) 2^-k of class cl against letter l at [cl * cstride + l * lstride] and kPadScoreF elsewhere,
+// then plan.cls.  Sets `tab` and sa's cls, open_s, ext_s, unscale.  `nomem`: the caller's ENOMEM message.
+template <class Args>
+int affine_class_table(const AffineCall &c, const AffineProfPlan &plan, int64_t side, size_t tab_floats, size_t cstride, size_t lstride,
+                       const char *nomem, const float *&tab, Args &sa) {
+  mi355_sw_ctx *ctx = c.ctx;
+  // cells hold H * 2^-k, 2^k above every value of the call (as wave_prof_launch)
+  const int k = std::max(1, std::ilogb((double)c.t.smax * ((double)side + 1.0) + 1.0) + 2);
+  ctx->h_aprof.assign(tab_floats + 64, kPadScoreF);                // (outlives the asynchronous copy)
+  for (int cl = 0; cl + 1 < plan.nclass; ++cl)
+    for (int l = 0; l < c.ref.ncodes - 1; ++l)
+      ctx->h_aprof[cl * cstride + l * lstride] = std::ldexp(affine_score(c.ref, c.p, plan.rep[cl], l) + (float)c.t.open, -k);
+  memcpy(ctx->h_aprof.data() + tab_floats, plan.cls, 256);
+  if (ctx->aprof.ensure((tab_floats + 64) * 4)) return fail(ctx, MI355_SW_ENOMEM, nomem);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->aprof.p, ctx->h_aprof.data(), (tab_floats + 64) * 4, hipMemcpyHostToDevice, ctx->stream));
+  tab = ctx->aprof.as<float>();
+  sa.cls = reinterpret_cast<const uint8_t *>(ctx->aprof.as<float>() + tab_floats);
+  sa.open_s = std::ldexp((float)c.t.open, -k); sa.ext_s = std::ldexp((float)c.t.ext, -k); sa.unscale = std::ldexp(1.0f, k);
+  return 0;
+}
+
 // Every non-empty query of the batch against each range of `which` (indices into `ranges`, all affine_prof_range_ok): one launch
 // of sw_affine_prof_kernel per range over descriptors that batch_wave_setup builds on the device, longest sequence first; (best,
 // cell) of a group of ranges come down in one copy.  maxima / ends as affine_run.
-int affine_prof_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const std::vector<Range> &ranges,
-                    const std::vector<size_t> &which, const mi355_sw_affine_params &p, const AffineTable &t,
-                    const AffineProfPlan &plan, float *maxima, int64_t *ends) {
+int affine_prof_run(const AffineCall &c, const std::vector<Range> &ranges, const std::vector<size_t> &which, const AffineProfPlan &plan,
+                    float *maxima, int64_t *ends) {
+  mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q;
   const size_t nq = q.nq;
   size_t first = 0;
   while (first < nq && q.len[q.order[first]] < 1) ++first;          // (sorted by length: the empty queries lead)
@@ -256,24 +336,12 @@ int affine_prof_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, 
   if (count > ((size_t)1 << 30)) return fail(ctx, MI355_SW_ENOTSUP, "affine: more than 2^30 queries");
   int64_t nmax = 0;
   for (size_t r : which) nmax = std::max(nmax, ranges[r].hi - ranges[r].lo);
-  // cells hold H * 2^-k, 2^k above every value of the call (as wave_prof_launch)
-  const int k = std::max(1, std::ilogb((double)t.smax * ((double)nmax + 1.0) + 1.0) + 2);
   const int nl = ref.ncodes - 1;
   // class scores and the byte -> class table: [nclass][nl] floats, then 256 bytes
-  const size_t tab_floats = (size_t)plan.nclass * nl;
-  ctx->h_aprof.assign(tab_floats + 64, 0.0f);                      // (outlives the asynchronous copy)
-  for (int c = 0; c < plan.nclass; ++c)
-    for (int l = 0; l < nl; ++l)
-      ctx->h_aprof[(size_t)c * nl + l] = c + 1 < plan.nclass ? std::ldexp(affine_score(ref, p, plan.rep[c], l) + (float)t.open, -k) : kPadScoreF;
-  memcpy(ctx->h_aprof.data() + tab_floats, plan.cls, 256);
-  if (ctx->aprof.ensure((tab_floats + 64) * 4)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine profile classes) failed");
-  HIPCHK(ctx, hipMemcpyAsync(ctx->aprof.p, ctx->h_aprof.data(), (tab_floats + 64) * 4, hipMemcpyHostToDevice, ctx->stream));
   AffineProfArgs sa;
-  sa.ctab = ctx->aprof.as<float>();
-  sa.cls = reinterpret_cast<const uint8_t *>(ctx->aprof.as<float>() + tab_floats);
   sa.nclass = plan.nclass; sa.nletters = nl;
-  sa.open_s = std::ldexp((float)t.open, -k); sa.ext_s = std::ldexp((float)t.ext, -k);
-  sa.unscale = std::ldexp(1.0f, k);
+  int rc = affine_class_table(c, plan, nmax, (size_t)plan.nclass * nl, nl, 1, "hipMalloc(affine profile classes) failed", sa.ctab, sa);
+  if (rc) return rc;
 
   const size_t per_group = std::max<size_t>(1, kAffineProfGroupProblems / count);
   const unsigned blocks = (unsigned)((count + 15) / 16);
@@ -281,10 +349,9 @@ int affine_prof_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, 
   for (size_t s = first; s < nq; ++s) row_sum += (double)q.len[q.order[s]];
   for (size_t g0 = 0; g0 < which.size(); g0 += per_group) {
     const size_t ng = std::min(per_group, which.size() - g0), np = ng * count;
-    const size_t o_cell = (np * 4 + 15) & ~(size_t)15;
-    if (ctx->wprobs.ensure(np * sizeof(WaveProblem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16) ||
-        ctx->pin_out.ensure(o_cell + np * 16))
-      return fail(ctx, MI355_SW_ENOMEM, "affine: allocation of the batch scratch failed");
+    const char *nomem = "affine: allocation of the batch scratch failed";
+    if (ctx->wprobs.ensure(np * sizeof(WaveProblem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16))
+      return fail(ctx, MI355_SW_ENOMEM, nomem);
     BatchWaveArgs a;
     memset(&a, 0, sizeof a);
     a.qbytes = q.bytes.as<uint8_t>(); a.qoff = q.offs.as<int64_t>(); a.qlen = q.lens.as<int32_t>();
@@ -311,26 +378,13 @@ int affine_prof_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, 
       HIPCHK(ctx, hipGetLastError());
       path_note(ctx, "affine_prof[R=%d]", R);
       ctx->timings[4] += 1;
-      const double cells = row_sum * (double)n;
-      ctx->timings[5] += cells;
-      if (cells > ctx->last_kernel.cells) {
-        mi355_sw_kernel_info &ki = ctx->last_kernel;
-        ki.cell = MI355_SW_CELL_F32; ki.lanes = 16; ki.rows_per_lane = R; ki.strips = 0; ki.twin = 0;
-        ki.chunk_len = n; ki.sub_len = n; ki.warm = 0; ki.cells = cells;
-        // per step and lane: seven ops and the key's v_or per cell, a maximum3 per two cells for the lane's best key, and seven of
-        // overhead (two DPP moves, the profile address: multiply-add and shift, and compare, select, maximum for the first row)
-        ki.valu_ops_per_cell = (8.0 * R + (R + 1) / 2 + 7.0) / (double)R;
-        std::snprintf(ki.name, sizeof ki.name, "sw_affine_prof_kernel<R=%d, f32>", R);
-      }
+      // per step and lane: seven ops and the key's v_or per cell, a maximum3 per two cells for the lane's best key, and seven of
+      // overhead (two DPP moves, the profile address: multiply-add and shift, and compare, select, maximum for the first row)
+      affine_note_kernel(ctx, row_sum * (double)n, MI355_SW_CELL_F32, 16, R, n, n, 0, (8.0 * R + (R + 1) / 2 + 7.0) / (double)R,
+                         "sw_affine_prof_kernel<R=%d, f32>", R);
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    uint8_t *pin = ctx->pin_out.as<uint8_t>();
-    const float *h_best = reinterpret_cast<const float *>(pin);
-    const int64_t *h_cell = reinterpret_cast<const int64_t *>(pin + o_cell);
-    HIPCHK(ctx, hipMemcpyAsync(pin, ctx->outs_f.p, np * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(pin + o_cell, ctx->outs_i.p, np * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->timings[0] += elapsed_us(ctx, ctx->ev[0], ctx->ev[1]);
+    const float *h_best = nullptr; const int64_t *h_cell = nullptr;
+    rc = affine_download(ctx, np, nomem, h_best, h_cell); if (rc) return rc;
     for (size_t g = 0; g < ng; ++g) {
       const size_t r = which[g0 + g];
       for (size_t kk = 0; kk < count; ++kk) {
@@ -352,8 +406,8 @@ struct AffineTraceItem { int q; int64_t lo; float score; int64_t ex, ey; };
 // cell — the L17 window of columns and the L18 window of rows, each where it is shorter than the matrix, clamped
 // at the item's own left border and at row 1 — in launch groups of at most kAffineTraceDirsMax decision bytes.
 // tout[items.size()]: views into ctx->arenas.
-int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const std::vector<AffineTraceItem> &items,
-                 const mi355_sw_affine_params &p, const AffineTable &t, std::vector<TraceOut> &tout) {
+int affine_trace(const AffineCall &c, const std::vector<AffineTraceItem> &items, std::vector<TraceOut> &tout) {
+  mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q; const AffineTable &t = c.t;
   struct Job { size_t item; int32_t m, nw; int64_t wl, row_lo; bool clamped, row_clamped; size_t dirs_off, cons_off; };
   std::vector<Job> jobs;
   for (size_t k = 0; k < items.size(); ++k) {
@@ -393,7 +447,7 @@ int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   if (jobs.empty()) return 0;
   path_note(ctx, "affine_trace");
   AffineScoring sc;
-  { int rc = affine_scoring(ctx, p, sc); if (rc) return rc; }
+  { int rc = affine_scoring(ctx, c.p, sc); if (rc) return rc; }
   for (size_t lo = 0; lo < jobs.size();) {
     size_t hi = lo, dirs_total = 0, cons_total = 0, lds = 0;
     while (hi < jobs.size() && hi - lo < 65536) {
@@ -458,111 +512,65 @@ int affine_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   return 0;
 }
 
-// Affine score (and, for one range, end cell) of every query of `q` over each range of `ref`, each range an independent
-// problem.  maxima: [nranges][nq].  ends (may be null; one range only): [nq][2] = row, column relative to the range start.
-// tout (may be null; needs ends): the traceback of every query, [nq] (affine_trace).
-int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const std::vector<Range> &ranges,
-               const mi355_sw_affine_params &p, float *maxima, int64_t *ends, std::vector<TraceOut> *tout = nullptr) {
-  const size_t nq = q.nq, nr = ranges.size();
-  if (nq == 0 || nr == 0) return 0;
-  for (size_t k = 0; k < nq * nr; ++k) maxima[k] = 0.0f;
-  if (ends) for (size_t k = 0; k < 2 * nq; ++k) ends[k] = 0;
-  if (tout) tout->assign(nq, TraceOut());
-  AffineTable t;
-  int rc = affine_table(ctx, ref, p, t);
-  if (rc) return rc;
-  if (t.smax <= 0) return 0;                                       // no positive cell: every maximum is 0
-  HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-  const Margin mg = make_margin((double)t.smax, (double)t.ext, true, 0.0);   // lemma L15: L1-L4 with g := gap_extend
-
-  // ---- ranges of at most 512 columns: every non-empty query is a problem of sw_affine_prof_kernel, whatever its length ---------
-  // (a range whose problems hold fewer than kAffineProfMinCells cells in all, every one within the exact kernel's LDS, is so
-  // little work that it stays where it was: one launch of the exact kernel)
-  std::vector<char> rprof(nr, 0);
-  std::vector<size_t> prof_ranges;
-  AffineProfPlan plan;
-  bool any_short = false;
-  for (size_t r = 0; r < nr; ++r) any_short |= ranges[r].hi - ranges[r].lo >= 1 && ranges[r].hi - ranges[r].lo <= kWaveMaxLanesSide;
-  if (any_short) affine_prof_plan(ref, p, t, plan);
-  double batch_rows = 0;
-  for (size_t k = 0; k < nq; ++k) batch_rows += (double)q.len[k];
-  const bool exact_holds_all = affine_exact_lds(q.maxlen) <= kExactLdsMax;
-  for (size_t r = 0; r < nr; ++r) {
-    const int64_t n = ranges[r].hi - ranges[r].lo;
-    if (!affine_prof_range_ok(plan, t, n) || (exact_holds_all && batch_rows * (double)n < kAffineProfMinCells)) continue;
-    rprof[r] = 1; prof_ranges.push_back(r);
+// Closes the call: the traceback of `items` (tout may be null: none), whose scores and end cells are score[k] and ends[k][2], then
+// the end of the call's interval (ev[5]), which goes to timings[3].
+int affine_end(const AffineCall &c, std::vector<AffineTraceItem> &items, const float *score, const int64_t *ends, std::vector<TraceOut> *tout) {
+  if (tout) {
+    for (size_t k = 0; k < items.size(); ++k) { items[k].score = score[k]; items[k].ex = ends[2 * k]; items[k].ey = ends[2 * k + 1]; }
+    { int rc = affine_trace(c, items, *tout); if (rc) return rc; }
   }
-  if (!prof_ranges.empty()) {
-    rc = affine_prof_run(ctx, ref, q, ranges, prof_ranges, p, t, plan, maxima, ends);
-    if (rc) return rc;
-  }
+  HIPCHK(c.ctx, hipEventRecord(c.ctx->ev[5], c.ctx->stream));
+  c.ctx->timings[3] += elapsed_us(c.ctx, c.ctx->ev[4], c.ctx->ev[5]);
+  return 0;
+}
 
-  // ---- which (query, range) the sweep takes -----------------------------------------------------------------------------
-  std::vector<char> rsweep(nr, 0), qfast(nq, 0);
-  std::vector<size_t> sweep_ranges;
-  for (size_t r = 0; r < nr; ++r)
-    if (!opt().no_affine_sweep && ranges[r].hi - ranges[r].lo >= kAffineSweepMinCols) { rsweep[r] = 1; sweep_ranges.push_back(r); }
+// The sweep's buckets: the non-empty queries of at most 512 rows by tile shape, and for each whether its float16 cells hold the
+// call (fast).  qfast[id] = 1 for the queries of the fast ones; why_slow: what keeps a query or a bucket out, for the refusal.
+std::vector<Bucket> affine_sweep_buckets(const AffineCall &c, const Margin &mg, std::vector<char> &qfast, std::string &why_slow) {
+  const QueryBatch &q = c.q; const AffineTable &t = c.t;
   std::vector<Bucket> buckets;
-  std::string why_slow;
-  if (!sweep_ranges.empty()) {
-    for (size_t pos = 0; pos < nq; ++pos) {
-      const int len = q.len[q.order[pos]];
-      if (len < 1) continue;
-      if (len > kMaxRowsFast) { why_slow = "query longer than 512 rows"; break; }   // (sorted by length: all further ones too)
-      int SL = 16, R = 2;
-      pick_shape(len, SL, R);
-      if (buckets.empty() || buckets.back().R != R || buckets.back().SL != SL) {
-        Bucket b;
-        b.first = (int)pos; b.R = R; b.SL = SL; b.sem = kSemF16;
-        buckets.push_back(b);
-      }
-      buckets.back().count++;
-      buckets.back().maxlen = std::max(buckets.back().maxlen, len);
+  for (size_t pos = 0; pos < q.nq; ++pos) {
+    const int len = q.len[q.order[pos]];
+    if (len < 1) continue;
+    if (len > kMaxRowsFast) { why_slow = "query longer than 512 rows"; break; }   // (sorted by length: all further ones too)
+    int SL = 16, R = 2;
+    pick_shape(len, SL, R);
+    if (buckets.empty() || buckets.back().R != R || buckets.back().SL != SL) {
+      Bucket b;
+      b.first = (int)pos; b.R = R; b.SL = SL; b.sem = kSemF16;
+      buckets.push_back(b);
     }
-    for (Bucket &b : buckets) {
-      b.warm = std::min(kColsMax, (mg.cols(b.maxlen) + 63) / 64 * 64);
-      char msg[160];
-      msg[0] = 0;
-      if ((int64_t)t.smax * (b.maxlen + 1) > kAffineF16Bound)
-        std::snprintf(msg, sizeof msg, "smax * (rows + 1) = %lld exceeds %d", (long long)t.smax * (b.maxlen + 1), kAffineF16Bound);
-      else if (t.open > kAffineF16Bound) std::snprintf(msg, sizeof msg, "gap_open = %d exceeds %d", t.open, kAffineF16Bound);
-      else if (profile_lds_bytes(ref.ncodes, b.R, b.SL) > kProfileLdsMax || ref.ncodes > 256)
-        std::snprintf(msg, sizeof msg, "%d reference letters: the query profile of %d rows per lane does not fit LDS", ref.ncodes - 1, b.R);
-      b.fast = msg[0] == 0;
-      if (!b.fast) why_slow = msg;
-      if (b.fast) for (int k = 0; k < b.count; ++k) qfast[q.order[b.first + k]] = 1;
-    }
+    buckets.back().count++;
+    buckets.back().maxlen = std::max(buckets.back().maxlen, len);
   }
-
-  // ---- whole problems of the exact kernel: everything the sweep does not take ---------------------------------------------
-  std::vector<ExactJob> jobs;
-  for (size_t r = 0; r < nr; ++r) {
-    const int64_t n = ranges[r].hi - ranges[r].lo;
-    for (size_t k = 0; k < nq; ++k) {
-      if (rprof[r] || (rsweep[r] && qfast[k]) || q.len[k] < 1 || n < 1) continue;
-      if ((double)q.len[k] * (double)n > kAffineExactCellsMax || (double)t.smax * ((double)q.len[k] + 1.0) >= 16777216.0) {
-        if (opt().no_affine_sweep) return fail(ctx, MI355_SW_ENOTSUP, "affine, option no_affine_sweep: a problem of more than 2^26 cells");
-        return fail(ctx, MI355_SW_ENOTSUP, "affine: " + (why_slow.empty() ? std::string("problem outside the sweep") : why_slow) +
-                                               " (beyond the sweep's float16 cells), and more than 2^26 cells for the exact kernel");
-      }
-      ExactJob j;
-      j.q = (int)k; j.ylo = ranges[r].lo; j.nw = (int32_t)n; j.col_offset = 0; j.full_n = n; j.own_lo = 1; j.quirk = 0;
-      j.target = -1.0f; j.want_dirs = false;
-      j.dirs_off = r;                                             // (no decisions here: the job's range)
-      jobs.push_back(j);
-    }
+  for (Bucket &b : buckets) {
+    b.warm = std::min(kColsMax, (mg.cols(b.maxlen) + 63) / 64 * 64);
+    char msg[160];
+    msg[0] = 0;
+    if ((int64_t)t.smax * (b.maxlen + 1) > kAffineF16Bound)
+      std::snprintf(msg, sizeof msg, "smax * (rows + 1) = %lld exceeds %d", (long long)t.smax * (b.maxlen + 1), kAffineF16Bound);
+    else if (t.open > kAffineF16Bound) std::snprintf(msg, sizeof msg, "gap_open = %d exceeds %d", t.open, kAffineF16Bound);
+    else if (profile_lds_bytes(c.ref.ncodes, b.R, b.SL) > kProfileLdsMax || c.ref.ncodes > 256)
+      std::snprintf(msg, sizeof msg, "%d reference letters: the query profile of %d rows per lane does not fit LDS", c.ref.ncodes - 1, b.R);
+    b.fast = msg[0] == 0;
+    if (!b.fast) why_slow = msg;
+    if (b.fast) for (int k = 0; k < b.count; ++k) qfast[q.order[b.first + k]] = 1;
   }
-  const size_t nwhole = jobs.size();
+  return buckets;
+}
 
-  // ---- the sweep, 32768 ranges per launch group ------------------------------------------------------------------------------
+// The sweep over `sweep_ranges` (indices into `ranges`), 32768 ranges per launch group: the maxima of the fast queries, and with
+// want_ends (one range) their end-cell windows behind `jobs`.
+int affine_sweep(const AffineCall &c, const std::vector<Range> &ranges, const std::vector<size_t> &sweep_ranges, std::vector<Bucket> &buckets,
+                 const std::vector<char> &qfast, const Margin &mg, float *maxima, bool want_ends, std::vector<ExactJob> &jobs) {
+  mi355_sw_ctx *ctx = c.ctx; const QueryBatch &q = c.q; const size_t nq = q.nq;
   bool any_fast = false;
   for (const Bucket &b : buckets) any_fast |= b.fast;
-  if (any_fast) {
-    if (ctx->atab.ensure(t.htab.size() * 2 + 16)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine score table) failed");
-    ctx->h_atab = t.htab;                                          // (outlives the asynchronous copy)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->atab.p, ctx->h_atab.data(), ctx->h_atab.size() * 2, hipMemcpyHostToDevice, ctx->stream));
-  }
-  for (size_t g0 = 0; any_fast && g0 < sweep_ranges.size(); g0 += 32768) {
+  if (!any_fast) return 0;
+  if (ctx->atab.ensure(c.t.htab.size() * 2 + 16)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine score table) failed");
+  ctx->h_atab = c.t.htab;                                          // (outlives the asynchronous copy)
+  HIPCHK(ctx, hipMemcpyAsync(ctx->atab.p, ctx->h_atab.data(), ctx->h_atab.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+  for (size_t g0 = 0; g0 < sweep_ranges.size(); g0 += 32768) {
     const size_t g1 = std::min(sweep_ranges.size(), g0 + 32768), ng = g1 - g0;
     std::vector<Range> sub(ng);
     std::vector<int64_t> &rl = ctx->h_ranges;
@@ -574,7 +582,7 @@ int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     for (Bucket &b : buckets) {
       if (!b.fast) continue;
-      rc = affine_sweep_launch(ctx, ref, q, sub, t, b);
+      int rc = affine_sweep_launch(c, sub, b);
       if (rc) return rc;
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
@@ -585,7 +593,7 @@ int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const
     for (size_t k = 0; k < ng; ++k)
       for (size_t i = 0; i < nq; ++i)
         if (qfast[i]) maxima[sweep_ranges[g0 + k] * nq + i] = key_score(kKeyF16, (uint32_t)(keys[k * nq + i] >> 32), 0);
-    if (!ends) continue;
+    if (!want_ends) continue;
     // (one range.)  The end cell: the first sub-chunk that reached the maximum holds the first maximum in column-major order —
     // or the up to SL - 1 trailing columns of the sub-chunk before it, reported with it — so one window per query, as the
     // linear float engine's locate_fast.  Only cells equal to the maximum compete: lemma L3 with g := gap_extend.
@@ -604,41 +612,89 @@ int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const
         ExactJob j;
         j.q = id; j.ylo = ranges[0].lo + wl; j.nw = (int32_t)(own_hi - wl); j.col_offset = wl; j.full_n = n;
         j.own_lo = (int32_t)(own_lo - wl + 1); j.quirk = 0; j.target = score; j.want_dirs = false;
-        j.dirs_off = 0;
         jobs.push_back(j);
       }
     }
   }
-
-  // ---- exact kernel: whole problems and end-cell windows ----------------------------------------------------------------------
-  if (!jobs.empty()) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    for (size_t lo = 0; lo < jobs.size(); lo += 65536) {
-      rc = run_affine_exact(ctx, ref, q, p, jobs, lo, std::min(jobs.size(), lo + 65536));
-      if (rc) return rc;
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
-    for (size_t k = 0; k < jobs.size(); ++k) {
-      const ExactJob &j = jobs[k];
-      if (k < nwhole) {
-        maxima[j.dirs_off * nq + (size_t)j.q] = j.best > 0 ? j.best : 0.0f;
-        if (ends && j.best > 0) { ends[2 * j.q] = j.ci; ends[2 * j.q + 1] = j.cj; }
-      } else {
-        if (j.best != j.target) return fail(ctx, MI355_SW_ENODEV, "internal: maximum of the affine sweep not found again by the exact kernel");
-        ends[2 * j.q] = j.ci; ends[2 * j.q + 1] = j.cj;
-      }
-    }
-  }
-  if (tout && ends) {
-    std::vector<AffineTraceItem> items(nq);                          // every query of the batch against the one range
-    for (size_t k = 0; k < nq; ++k) items[k] = AffineTraceItem{(int)k, ranges[0].lo, maxima[k], ends[2 * k], ends[2 * k + 1]};
-    rc = affine_trace(ctx, ref, q, items, p, t, *tout);
-    if (rc) return rc;
-  }
-  HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-  ctx->timings[3] += elapsed_us(ctx, ctx->ev[4], ctx->ev[5]);
   return 0;
+}
+
+// Affine score (and, for one range, end cell) of every query of `q` over each range of `ref`, each range an independent
+// problem.  maxima: [nranges][nq].  ends (may be null; one range only): [nq][2] = row, column relative to the range start.
+// tout (may be null; needs ends): the traceback of every query, [nq] (affine_trace).
+int affine_run(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const std::vector<Range> &ranges,
+               const mi355_sw_affine_params &p, float *maxima, int64_t *ends, std::vector<TraceOut> *tout = nullptr) {
+  const size_t nq = q.nq, nr = ranges.size();
+  if (nq == 0 || nr == 0) return 0;
+  for (size_t k = 0; k < nq * nr; ++k) maxima[k] = 0.0f;
+  if (ends) for (size_t k = 0; k < 2 * nq; ++k) ends[k] = 0;
+  if (tout) tout->assign(nq, TraceOut());
+  AffineCall c{ctx, ref, q, p, AffineTable()};
+  int rc = affine_begin(c);
+  if (rc) return rc > 0 ? 0 : rc;
+  const Margin mg = make_margin((double)c.t.smax, (double)c.t.ext, true, 0.0);   // lemma L15: L1-L4 with g := gap_extend
+
+  // ---- ranges of at most 512 columns: every non-empty query is a problem of sw_affine_prof_kernel, whatever its length ---------
+  // (a range whose problems hold fewer than kAffineProfMinCells cells in all, every one within the exact kernel's LDS, is so
+  // little work that it stays where it was: one launch of the exact kernel)
+  std::vector<char> rprof(nr, 0);
+  std::vector<size_t> prof_ranges;
+  AffineProfPlan plan;
+  bool any_short = false;
+  for (size_t r = 0; r < nr; ++r) any_short |= ranges[r].hi - ranges[r].lo >= 1 && ranges[r].hi - ranges[r].lo <= kWaveMaxLanesSide;
+  if (any_short) affine_prof_plan(ref, p, c.t, plan);
+  double batch_rows = 0;
+  for (size_t k = 0; k < nq; ++k) batch_rows += (double)q.len[k];
+  const bool exact_holds_all = affine_exact_lds(q.maxlen) <= kExactLdsMax;
+  for (size_t r = 0; r < nr; ++r) {
+    const int64_t n = ranges[r].hi - ranges[r].lo;
+    if (!affine_prof_range_ok(plan, c.t, n) || (exact_holds_all && batch_rows * (double)n < kAffineProfMinCells)) continue;
+    rprof[r] = 1; prof_ranges.push_back(r);
+  }
+  if (!prof_ranges.empty()) { rc = affine_prof_run(c, ranges, prof_ranges, plan, maxima, ends); if (rc) return rc; }
+
+  // ---- which (query, range) the sweep takes -----------------------------------------------------------------------------
+  std::vector<char> rsweep(nr, 0), qfast(nq, 0);
+  std::vector<size_t> sweep_ranges;
+  for (size_t r = 0; r < nr; ++r)
+    if (!opt().no_affine_sweep && ranges[r].hi - ranges[r].lo >= kAffineSweepMinCols) { rsweep[r] = 1; sweep_ranges.push_back(r); }
+  std::vector<Bucket> buckets; std::string why_slow;
+  if (!sweep_ranges.empty()) buckets = affine_sweep_buckets(c, mg, qfast, why_slow);
+
+  // ---- whole problems of the exact kernel: everything the sweep does not take (ExactJob::index: the range) --------------------
+  std::vector<ExactJob> jobs;
+  for (size_t r = 0; r < nr; ++r) {
+    const int64_t n = ranges[r].hi - ranges[r].lo;
+    for (size_t k = 0; k < nq; ++k) {
+      if (rprof[r] || (rsweep[r] && qfast[k]) || q.len[k] < 1 || n < 1) continue;
+      ExactJob j;
+      if (!affine_whole_job(c, (int)k, ranges[r].lo, n, r, j)) {
+        if (opt().no_affine_sweep) return fail(ctx, MI355_SW_ENOTSUP, "affine, option no_affine_sweep: a problem of more than 2^26 cells");
+        return fail(ctx, MI355_SW_ENOTSUP, "affine: " + (why_slow.empty() ? std::string("problem outside the sweep") : why_slow) +
+                                               " (beyond the sweep's float16 cells), and more than 2^26 cells for the exact kernel");
+      }
+      jobs.push_back(j);
+    }
+  }
+  const size_t nwhole = jobs.size();
+
+  // ---- the sweep with its end-cell windows, then the exact kernel: whole problems and end-cell windows ------------------------
+  rc = affine_sweep(c, ranges, sweep_ranges, buckets, qfast, mg, maxima, ends != nullptr, jobs);
+  if (!rc) rc = affine_exact_stage(c, jobs);
+  if (rc) return rc;
+  for (size_t k = 0; k < jobs.size(); ++k) {
+    const ExactJob &j = jobs[k];
+    if (k < nwhole) {
+      maxima[j.index * nq + (size_t)j.q] = j.best > 0 ? j.best : 0.0f;
+      if (ends && j.best > 0) { ends[2 * j.q] = j.ci; ends[2 * j.q + 1] = j.cj; }
+    } else {
+      if (j.best != j.target) return fail(ctx, MI355_SW_ENODEV, "internal: maximum of the affine sweep not found again by the exact kernel");
+      ends[2 * j.q] = j.ci; ends[2 * j.q + 1] = j.cj;
+    }
+  }
+  std::vector<AffineTraceItem> items(tout && ends ? nq : 0);        // every query of the batch against the one range
+  for (size_t k = 0; k < items.size(); ++k) items[k] = AffineTraceItem{(int)k, ranges[0].lo, 0.0f, 0, 0};
+  return affine_end(c, items, maxima, ends, ends ? tout : nullptr);
 }
 
 // ---- sw_affine_pair_kernel (sw_affine_pair_kernel.h): a list of (query, window of the resident reference) pairs -----------------
@@ -656,10 +712,72 @@ int affine_pair_R(int rows) {
   return 0;
 }
 typedef void (*AffinePairKernel)(const AffinePairProblem *, int, const AffinePairArgs);
-template <size_t... I> AffinePairKernel affine_pair_kernel(int R, std::index_sequence<I...>) {
-  AffinePairKernel k = nullptr;
-  ((kPairR[I] == R ? (void)(k = &sw_affine_pair_kernel<kPairR[I]>) : (void)0), ...);
-  return k;
+
+// sw_affine_pair_kernel over the pairs of `fast`: by instance, longest window first, so that the slots of a wavefront run similar
+// step counts; score / ends of the pairs with a positive maximum.
+int affine_pair_stage(const AffineCall &c, const int32_t *qid, const int64_t *lefts, const int64_t *rights, const AffineProfPlan &plan,
+                      std::vector<uint32_t> &fast, int mmax, float *score, int64_t *ends) {
+  mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q;
+  if (fast.empty()) return 0;
+  std::sort(fast.begin(), fast.end(), [&](uint32_t a, uint32_t b) {
+    const int Ra = affine_pair_R(q.len[qid[a]]), Rb = affine_pair_R(q.len[qid[b]]);
+    if (Ra != Rb) return Ra < Rb;
+    const int64_t na = rights[a] - lefts[a], nb = rights[b] - lefts[b];
+    return na != nb ? na > nb : a < b;
+  });
+  const int nl = ref.ncodes - 1, nrows = nl + 1, ncls = plan.nclass;
+  const size_t tab_floats = (size_t)nrows * ncls;
+  AffinePairArgs sa;
+  sa.nrows = nrows; sa.ncls = ncls;
+  int rc = affine_class_table(c, plan, mmax, tab_floats, 1, ncls, "hipMalloc(affine pair table) failed", sa.tab, sa);
+  if (rc) return rc;
+  for (size_t g0 = 0; g0 < fast.size(); g0 += kAffinePairGroupProblems) {
+    const size_t np = std::min(kAffinePairGroupProblems, fast.size() - g0);
+    const char *nomem = "affine pairs: allocation of the pair scratch failed";
+    if (ctx->wprobs.ensure(np * sizeof(AffinePairProblem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16) ||
+        ctx->pin_probs.ensure(np * sizeof(AffinePairProblem)))
+      return fail(ctx, MI355_SW_ENOMEM, nomem);
+    AffinePairProblem *pr = ctx->pin_probs.as<AffinePairProblem>();
+    for (size_t i = 0; i < np; ++i) {                              // one upload of the pair list
+      const uint32_t id = fast[g0 + i];
+      pr[i].x = q.bytes.as<uint8_t>() + q.off[qid[id]];
+      pr[i].y = ref.codes.as<uint8_t>() + lefts[id];
+      pr[i].m = q.len[qid[id]];
+      pr[i].n = (int32_t)(rights[id] - lefts[id]);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr, np * sizeof(AffinePairProblem), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    for (size_t i0 = 0; i0 < np;) {                                // one launch per instance
+      const int R = affine_pair_R(pr[i0].m);
+      size_t i1 = i0;
+      double cells = 0;
+      while (i1 < np && affine_pair_R(pr[i1].m) == R) { cells += (double)pr[i1].m * (double)pr[i1].n; ++i1; }
+      AffinePairKernel kern = nullptr;
+      with_listed_R<kPairR>(R, [&](auto r) { kern = &sw_affine_pair_kernel<decltype(r)::value>; });
+      if (!kern) return fail(ctx, MI355_SW_ENODEV, "internal: no sw_affine_pair_kernel instance for this query");
+      sa.best = ctx->outs_f.as<float>() + i0;
+      sa.cell = ctx->outs_i.as<int64_t>() + 2 * i0;
+      launch_dyn_lds(kern, dim3((unsigned)((i1 - i0 + 15) / 16)), dim3(256), tab_floats * 4, ctx->stream,
+                     ctx->wprobs.as<AffinePairProblem>() + i0, (int)(i1 - i0), sa);
+      HIPCHK(ctx, hipGetLastError());
+      path_note(ctx, "affine_pair[R=%d]", R);
+      ctx->timings[4] += 1;
+      // per step and lane: seven ops, the table address' v_add and the key's v_or per cell, a maximum3 per two cells for the
+      // step's best key, and twelve of overhead as compiled (two DPP moves and their two copies, the row pointer's multiply
+      // and add, the column, the code's address, and compare, two selects and the v_or of the value-only key update)
+      affine_note_kernel(ctx, cells, MI355_SW_CELL_F32, 16, R, pr[i0].n, pr[i0].n, 0, (9.0 * R + (R + 1) / 2 + 12.0) / (double)R,
+                         "sw_affine_pair_kernel<R=%d>", R);
+      i0 = i1;
+    }
+    const float *h_best = nullptr; const int64_t *h_cell = nullptr;
+    rc = affine_download(ctx, np, nomem, h_best, h_cell); if (rc) return rc;
+    for (size_t i = 0; i < np; ++i) {
+      const uint32_t id = fast[g0 + i];
+      if (!(h_best[i] > 0)) continue;
+      score[id] = h_best[i]; ends[2 * (size_t)id] = h_cell[2 * i]; ends[2 * (size_t)id + 1] = h_cell[2 * i + 1];
+    }
+  }
+  return 0;
 }
 
 // npairs independent problems: query qid[k] of `q` against [lefts[k], rights[k]) of `ref` (validated by the caller), each with
@@ -670,15 +788,13 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, siz
                  const int64_t *rights, const mi355_sw_affine_params &p, float *score, int64_t *ends, std::vector<TraceOut> *tout) {
   for (size_t k = 0; k < npairs; ++k) { score[k] = 0.0f; ends[2 * k] = 0; ends[2 * k + 1] = 0; }
   if (tout) tout->assign(npairs, TraceOut());
-  AffineTable t;
-  int rc = affine_table(ctx, ref, p, t);
-  if (rc) return rc;
-  if (t.smax <= 0) return 0;                                       // no positive cell: every maximum is 0
-  HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+  AffineCall c{ctx, ref, q, p, AffineTable()};
+  int rc = affine_begin(c);
+  if (rc) return rc > 0 ? 0 : rc;
   AffineProfPlan plan;
   if (!opt().no_affine_pairs) {
-    affine_byte_classes(ref, p, t, plan);
-    if (!plan.ok && ref.ncodes >= 2 && ref.ncodes <= 256 && (double)t.open < kAffineProfBound) {
+    affine_byte_classes(ref, p, c.t, plan);
+    if (!plan.ok && ref.ncodes >= 2 && ref.ncodes <= 256 && (double)c.t.open < kAffineProfBound) {
       // a table that scores all 256 bytes differently: every byte is its own class
       plan.rep.resize(256);
       for (int a = 0; a < 256; ++a) { plan.cls[a] = (uint8_t)a; plan.rep[a] = a; }
@@ -688,7 +804,7 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, siz
   }
   const bool table_ok = plan.ok && affine_pair_lds(ref, plan) <= kAffinePairLdsMax;
 
-  // ---- which kernel a pair takes ---------------------------------------------------------------------------------------------------
+  // ---- which kernel a pair takes (ExactJob::index: the pair) ------------------------------------------------------------------------
   if (npairs > 0xFFFFFFFFull) return fail(ctx, MI355_SW_ENOTSUP, "affine pairs: more than 2^32 pairs");
   std::vector<uint32_t> fast;                                      // pair indices of sw_affine_pair_kernel
   std::vector<ExactJob> jobs;
@@ -697,132 +813,33 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, siz
     const int m = q.len[qid[k]];
     const int64_t n = rights[k] - lefts[k];
     if (m < 1 || n < 1) continue;
-    if (table_ok && m <= kMaxRowsFast && n <= kAffinePairColsMax && (double)t.smax * ((double)m + 1.0) < kAffineProfBound) {
+    if (table_ok && m <= kMaxRowsFast && n <= kAffinePairColsMax && (double)c.t.smax * ((double)m + 1.0) < kAffineProfBound) {
       fast.push_back((uint32_t)k);
       mmax = std::max(mmax, m);
       continue;
     }
-    if ((double)m * (double)n > kAffineExactCellsMax || (double)t.smax * ((double)m + 1.0) >= 16777216.0) {
+    ExactJob j;
+    if (!affine_whole_job(c, qid[k], lefts[k], n, k, j)) {
       char msg[240];
       std::snprintf(msg, sizeof msg, "affine pairs: pair %zu (%d rows x %lld columns) is outside the pair kernel (1..512 rows, 1..2^20 columns, "
                     "smax * (rows + 1) < 2^18, gap_open < 2^18) and has more than 2^26 cells for the exact kernel", k, m, (long long)n);
       return fail(ctx, MI355_SW_ENOTSUP, msg);
     }
     if (affine_exact_lds(m) > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine pairs: query longer than the exact kernel's LDS diagonals hold");
-    ExactJob j;
-    j.q = qid[k]; j.ylo = lefts[k]; j.nw = (int32_t)n; j.col_offset = 0; j.full_n = n; j.own_lo = 1; j.quirk = 0;
-    j.target = -1.0f; j.want_dirs = false;
-    j.dirs_off = k;                                                // (no decisions here: the job's pair)
     jobs.push_back(j);
   }
 
-  // ---- sw_affine_pair_kernel: by instance, longest window first, so that the slots of a wavefront run similar step counts ---------
-  if (!fast.empty()) {
-    std::sort(fast.begin(), fast.end(), [&](uint32_t a, uint32_t b) {
-      const int Ra = affine_pair_R(q.len[qid[a]]), Rb = affine_pair_R(q.len[qid[b]]);
-      if (Ra != Rb) return Ra < Rb;
-      const int64_t na = rights[a] - lefts[a], nb = rights[b] - lefts[b];
-      return na != nb ? na > nb : a < b;
-    });
-    // cells hold H * 2^-k, 2^k above every value of the call (as affine_prof_run)
-    const int k = std::max(1, std::ilogb((double)t.smax * ((double)mmax + 1.0) + 1.0) + 2);
-    const int nl = ref.ncodes - 1, nrows = nl + 1, ncls = plan.nclass;
-    const size_t tab_floats = (size_t)nrows * ncls;
-    ctx->h_aprof.assign(tab_floats + 64, kPadScoreF);               // (outlives the asynchronous copy)
-    for (int l = 0; l < nl; ++l)
-      for (int c = 0; c + 1 < ncls; ++c)
-        ctx->h_aprof[(size_t)l * ncls + c] = std::ldexp(affine_score(ref, p, plan.rep[c], l) + (float)t.open, -k);
-    memcpy(ctx->h_aprof.data() + tab_floats, plan.cls, 256);
-    if (ctx->aprof.ensure((tab_floats + 64) * 4)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine pair table) failed");
-    HIPCHK(ctx, hipMemcpyAsync(ctx->aprof.p, ctx->h_aprof.data(), (tab_floats + 64) * 4, hipMemcpyHostToDevice, ctx->stream));
-    AffinePairArgs sa;
-    sa.tab = ctx->aprof.as<float>();
-    sa.cls = reinterpret_cast<const uint8_t *>(ctx->aprof.as<float>() + tab_floats);
-    sa.nrows = nrows; sa.ncls = ncls;
-    sa.open_s = std::ldexp((float)t.open, -k); sa.ext_s = std::ldexp((float)t.ext, -k);
-    sa.unscale = std::ldexp(1.0f, k);
-    for (size_t g0 = 0; g0 < fast.size(); g0 += kAffinePairGroupProblems) {
-      const size_t np = std::min(kAffinePairGroupProblems, fast.size() - g0);
-      const size_t o_cell = (np * 4 + 15) & ~(size_t)15;
-      if (ctx->wprobs.ensure(np * sizeof(AffinePairProblem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16) ||
-          ctx->pin_probs.ensure(np * sizeof(AffinePairProblem)) || ctx->pin_out.ensure(o_cell + np * 16))
-        return fail(ctx, MI355_SW_ENOMEM, "affine pairs: allocation of the pair scratch failed");
-      AffinePairProblem *pr = ctx->pin_probs.as<AffinePairProblem>();
-      for (size_t i = 0; i < np; ++i) {                              // one upload of the pair list
-        const uint32_t id = fast[g0 + i];
-        pr[i].x = q.bytes.as<uint8_t>() + q.off[qid[id]];
-        pr[i].y = ref.codes.as<uint8_t>() + lefts[id];
-        pr[i].m = q.len[qid[id]];
-        pr[i].n = (int32_t)(rights[id] - lefts[id]);
-      }
-      HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr, np * sizeof(AffinePairProblem), hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-      for (size_t i0 = 0; i0 < np;) {                                // one launch per instance
-        const int R = affine_pair_R(pr[i0].m);
-        size_t i1 = i0;
-        double cells = 0;
-        while (i1 < np && affine_pair_R(pr[i1].m) == R) { cells += (double)pr[i1].m * (double)pr[i1].n; ++i1; }
-        AffinePairKernel kern = affine_pair_kernel(R, std::make_index_sequence<std::size(kPairR)>{});
-        if (!kern) return fail(ctx, MI355_SW_ENODEV, "internal: no sw_affine_pair_kernel instance for this query");
-        sa.best = ctx->outs_f.as<float>() + i0;
-        sa.cell = ctx->outs_i.as<int64_t>() + 2 * i0;
-        launch_dyn_lds(kern, dim3((unsigned)((i1 - i0 + 15) / 16)), dim3(256), tab_floats * 4, ctx->stream,
-                       ctx->wprobs.as<AffinePairProblem>() + i0, (int)(i1 - i0), sa);
-        HIPCHK(ctx, hipGetLastError());
-        path_note(ctx, "affine_pair[R=%d]", R);
-        ctx->timings[4] += 1;
-        ctx->timings[5] += cells;
-        if (cells > ctx->last_kernel.cells) {
-          mi355_sw_kernel_info &ki = ctx->last_kernel;
-          ki.cell = MI355_SW_CELL_F32; ki.lanes = 16; ki.rows_per_lane = R; ki.strips = 0; ki.twin = 0;
-          ki.chunk_len = pr[i0].n; ki.sub_len = pr[i0].n; ki.warm = 0; ki.cells = cells;
-          // per step and lane: seven ops, the table address' v_add and the key's v_or per cell, a maximum3 per two cells for the
-          // step's best key, and twelve of overhead as compiled (two DPP moves and their two copies, the row pointer's multiply
-          // and add, the column, the code's address, and compare, two selects and the v_or of the value-only key update)
-          ki.valu_ops_per_cell = (9.0 * R + (R + 1) / 2 + 12.0) / (double)R;
-          std::snprintf(ki.name, sizeof ki.name, "sw_affine_pair_kernel<R=%d>", R);
-        }
-        i0 = i1;
-      }
-      HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-      uint8_t *pin = ctx->pin_out.as<uint8_t>();
-      const float *h_best = reinterpret_cast<const float *>(pin);
-      const int64_t *h_cell = reinterpret_cast<const int64_t *>(pin + o_cell);
-      HIPCHK(ctx, hipMemcpyAsync(pin, ctx->outs_f.p, np * 4, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(pin + o_cell, ctx->outs_i.p, np * 16, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      ctx->timings[0] += elapsed_us(ctx, ctx->ev[0], ctx->ev[1]);
-      for (size_t i = 0; i < np; ++i) {
-        const uint32_t id = fast[g0 + i];
-        if (!(h_best[i] > 0)) continue;
-        score[id] = h_best[i]; ends[2 * (size_t)id] = h_cell[2 * i]; ends[2 * (size_t)id + 1] = h_cell[2 * i + 1];
-      }
-    }
+  // ---- sw_affine_pair_kernel, then the exact kernel: every other pair as a whole problem ------------------------------------------
+  rc = affine_pair_stage(c, qid, lefts, rights, plan, fast, mmax, score, ends);
+  if (!rc) rc = affine_exact_stage(c, jobs);
+  if (rc) return rc;
+  for (const ExactJob &j : jobs) {
+    if (!(j.best > 0)) continue;
+    score[j.index] = j.best; ends[2 * j.index] = j.ci; ends[2 * j.index + 1] = j.cj;
   }
-
-  // ---- exact kernel: every other pair as a whole problem ---------------------------------------------------------------------------
-  if (!jobs.empty()) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    for (size_t lo = 0; lo < jobs.size(); lo += 65536) {
-      rc = run_affine_exact(ctx, ref, q, p, jobs, lo, std::min(jobs.size(), lo + 65536));
-      if (rc) return rc;
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
-    for (const ExactJob &j : jobs) {
-      if (!(j.best > 0)) continue;
-      score[j.dirs_off] = j.best; ends[2 * j.dirs_off] = j.ci; ends[2 * j.dirs_off + 1] = j.cj;
-    }
-  }
-  if (tout) {
-    std::vector<AffineTraceItem> items(npairs);
-    for (size_t k = 0; k < npairs; ++k) items[k] = AffineTraceItem{qid[k], lefts[k], score[k], ends[2 * k], ends[2 * k + 1]};
-    rc = affine_trace(ctx, ref, q, items, p, t, *tout);
-    if (rc) return rc;
-  }
-  HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-  ctx->timings[3] += elapsed_us(ctx, ctx->ev[4], ctx->ev[5]);
-  return 0;
+  std::vector<AffineTraceItem> items(tout ? npairs : 0);
+  for (size_t k = 0; k < items.size(); ++k) items[k] = AffineTraceItem{qid[k], lefts[k], 0.0f, 0, 0};
+  return affine_end(c, items, score, ends, tout);
 }
 
 }  // namespace

@@ -17,6 +17,7 @@ struct ExactJob {
   float best = -1;
   int64_t ci = 0, cj = 0;
   size_t dirs_off = 0;
+  size_t index = 0;      // affine whole problems: the caller's range or pair (host_affine.h)
 };
 
 // bytes of the diagonal-major decision array of an (m x nw) window (sw_exact_kernel.h)

@@ -46,6 +46,12 @@ void with_wave_R(int R, F f) {
   else f(std::integral_constant<int, 32>{});
 }
 
+// ... and for the kernels whose instances are a constexpr list: f(std::integral_constant<int, Rs[i]>) for the Rs[i] equal to R,
+// no call where none is
+template <const auto &Rs, size_t I = 0, class F> void with_listed_R(int R, F f) {
+  if constexpr (I < std::size(Rs)) { if (Rs[I] == R) f(std::integral_constant<int, Rs[I]>{}); else with_listed_R<Rs, I + 1>(R, f); }
+}
+
 // The sw_wave_kernel instance of a launch: tracking, decisions or both; keyed tracking (lanes = rows of x).  Null for nine rows per
 // lane, which wave_R never picks: the kernel has no such instance.
 typedef void (*WaveKernel)(const WaveProblem *, int, const WaveScoring);

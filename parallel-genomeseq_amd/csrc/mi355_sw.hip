@@ -11,6 +11,7 @@
 //   affine gaps (score, end cell, traceback): sw_affine_kernel sweep + sw_affine_exact / _trace_kernel, and
 //                      sw_affine_prof_kernel for references (ranges) of at most 512 letters,
 //                      sw_affine_pair_kernel for lists of (query, window) pairs                      host_affine.h
+//                      (entry points: affine_align_any, affine_batch_any, affine_pairs_any — one body per run / trace twin)
 // Problems the score kernel does not cover (see bucket_fast_ok) run 2+3 on the whole matrix.
 // The host code is one translation unit; the fragments below are included in order.
 #include "../../include/mi355_sw.h"
@@ -374,90 +375,81 @@ void mi355_sw_default_affine_params(mi355_sw_affine_params *p) {
   p->lut = nullptr; p->match = 3.0f; p->mismatch = -3.0f; p->gap_open = 5.0f; p->gap_extend = 1.0f;
 }
 
-int mi355_sw_affine_align(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, size_t ny,
-                          const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y) {
-  OptScope opt_scope_(ctx);
-  int rc = affine_check(ctx, params);
-  if (rc) return rc;
-  if (!score || !end_x || !end_y || (!x && nx) || (!y && ny)) return fail(ctx, MI355_SW_EINVAL, "null argument");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  reset_timings(ctx);
-  *score = 0.0f; *end_x = 0; *end_y = 0;
-  if (nx == 0 || ny == 0) return 0;
-  const RefData *ref = nullptr;
-  rc = adhoc_reference(ctx, y, ny, &ref);
-  if (!rc) rc = upload_queries(ctx, ctx->one, 1, &x, &nx);
-  int64_t end[2] = {0, 0};
-  if (!rc) rc = affine_run(ctx, *ref, ctx->one, std::vector<Range>{Range{0, (int64_t)ny}}, *params, score, end);
-  if (rc) return rc;
-  *end_x = end[0]; *end_y = end[1];
-  return 0;
+// (score, end cell, traceback) of n alignments as results; every one carries the call's sweep time
+static void affine_results(mi355_sw_ctx *ctx, size_t n, const float *score, const int64_t *ends, const std::vector<TraceOut> &tout, mi355_sw_result *outs) {
+  for (size_t k = 0; k < n; ++k) {
+    set_result(outs[k], score[k], ends[2 * k], ends[2 * k + 1], &tout[k]);
+    outs[k].timings_us[0] = outs[k].timings_us[1] = (float)ctx->timings[0];
+  }
 }
 
-int mi355_sw_affine_batch_run(mi355_sw_ctx *ctx, const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y) {
+// mi355_sw_affine_align (score, end_x, end_y) and, with `trace`, mi355_sw_affine_align_trace (out)
+static int affine_align_any(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, size_t ny, const mi355_sw_affine_params *params,
+                            bool trace, float *score, int64_t *end_x, int64_t *end_y, mi355_sw_result *out) {
   OptScope opt_scope_(ctx);
   int rc = affine_check(ctx, params);
   if (rc) return rc;
-  const size_t nq = ctx->batch.nq;
-  if (nq && (!score || !end_x || !end_y)) return fail(ctx, MI355_SW_EINVAL, "null argument");
+  if ((trace ? !out : !score || !end_x || !end_y) || (!x && nx) || (!y && ny)) return fail(ctx, MI355_SW_EINVAL, "null argument");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   reset_timings(ctx);
-  if (nq == 0) return 0;
-  for (size_t k = 0; k < nq; ++k) { score[k] = 0.0f; end_x[k] = 0; end_y[k] = 0; }
-  if (ctx->ref.n == 0) return 0;
-  std::vector<int64_t> ends(2 * nq, 0);
-  rc = affine_run(ctx, ctx->ref, ctx->batch, std::vector<Range>{Range{0, (int64_t)ctx->ref.n}}, *params, score, ends.data());
-  if (rc) return rc;
-  for (size_t k = 0; k < nq; ++k) { end_x[k] = ends[2 * k]; end_y[k] = ends[2 * k + 1]; }
-  return 0;
-}
-
-int mi355_sw_affine_align_trace(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, size_t ny,
-                                const mi355_sw_affine_params *params, mi355_sw_result *out) {
-  OptScope opt_scope_(ctx);
-  int rc = affine_check(ctx, params);
-  if (rc) return rc;
-  if (!out || (!x && nx) || (!y && ny)) return fail(ctx, MI355_SW_EINVAL, "null argument");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  reset_timings(ctx);
-  memset(out, 0, sizeof *out);
-  float score = 0.0f;
+  float own = 0.0f;
   int64_t end[2] = {0, 0};
   std::vector<TraceOut> tout(1);
+  if (trace) { memset(out, 0, sizeof *out); score = &own; }
+  else { *score = 0.0f; *end_x = 0; *end_y = 0; }
   if (nx != 0 && ny != 0) {
     const RefData *ref = nullptr;
     rc = adhoc_reference(ctx, y, ny, &ref);
     if (!rc) rc = upload_queries(ctx, ctx->one, 1, &x, &nx);
-    if (!rc) rc = affine_run(ctx, *ref, ctx->one, std::vector<Range>{Range{0, (int64_t)ny}}, *params, &score, end, &tout);
+    if (!rc) rc = affine_run(ctx, *ref, ctx->one, std::vector<Range>{Range{0, (int64_t)ny}}, *params, score, end, trace ? &tout : nullptr);
     if (rc) return rc;
   }
-  set_result(*out, score, end[0], end[1], &tout[0]);
-  out->timings_us[0] = out->timings_us[1] = (float)ctx->timings[0];
+  if (trace) affine_results(ctx, 1, score, end, tout, out);
+  else { *end_x = end[0]; *end_y = end[1]; }
   return 0;
 }
 
-int mi355_sw_affine_batch_trace(mi355_sw_ctx *ctx, const mi355_sw_affine_params *params, mi355_sw_result *outs) {
+int mi355_sw_affine_align(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, size_t ny,
+                          const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y) {
+  return affine_align_any(ctx, x, nx, y, ny, params, false, score, end_x, end_y, nullptr);
+}
+
+int mi355_sw_affine_align_trace(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, size_t ny,
+                                const mi355_sw_affine_params *params, mi355_sw_result *out) {
+  return affine_align_any(ctx, x, nx, y, ny, params, true, nullptr, nullptr, nullptr, out);
+}
+
+// mi355_sw_affine_batch_run (score, end_x, end_y) and, with `trace`, mi355_sw_affine_batch_trace (outs)
+static int affine_batch_any(mi355_sw_ctx *ctx, const mi355_sw_affine_params *params, bool trace, float *score, int64_t *end_x, int64_t *end_y,
+                            mi355_sw_result *outs) {
   OptScope opt_scope_(ctx);
   int rc = affine_check(ctx, params);
   if (rc) return rc;
   const size_t nq = ctx->batch.nq;
-  if (!outs) return fail(ctx, MI355_SW_EINVAL, "outs is NULL");
+  if (trace ? !outs : nq && (!score || !end_x || !end_y)) return fail(ctx, MI355_SW_EINVAL, trace ? "outs is NULL" : "null argument");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   reset_timings(ctx);
   if (nq == 0) return 0;
-  memset(outs, 0, nq * sizeof *outs);
-  std::vector<float> score(nq, 0.0f);
+  std::vector<float> own(trace ? nq : 0, 0.0f);
   std::vector<int64_t> ends(2 * nq, 0);
-  std::vector<TraceOut> tout(nq);
+  std::vector<TraceOut> tout(trace ? nq : 0);
+  if (trace) { memset(outs, 0, nq * sizeof *outs); score = own.data(); }
+  else for (size_t k = 0; k < nq; ++k) { score[k] = 0.0f; end_x[k] = 0; end_y[k] = 0; }
   if (ctx->ref.n != 0) {
-    rc = affine_run(ctx, ctx->ref, ctx->batch, std::vector<Range>{Range{0, (int64_t)ctx->ref.n}}, *params, score.data(), ends.data(), &tout);
+    rc = affine_run(ctx, ctx->ref, ctx->batch, std::vector<Range>{Range{0, (int64_t)ctx->ref.n}}, *params, score, ends.data(), trace ? &tout : nullptr);
     if (rc) return rc;
   }
-  for (size_t k = 0; k < nq; ++k) {
-    set_result(outs[k], score[k], ends[2 * k], ends[2 * k + 1], &tout[k]);
-    outs[k].timings_us[0] = outs[k].timings_us[1] = (float)ctx->timings[0];
-  }
+  if (trace) affine_results(ctx, nq, score, ends.data(), tout, outs);
+  else for (size_t k = 0; k < nq; ++k) { end_x[k] = ends[2 * k]; end_y[k] = ends[2 * k + 1]; }
   return 0;
+}
+
+int mi355_sw_affine_batch_run(mi355_sw_ctx *ctx, const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y) {
+  return affine_batch_any(ctx, params, false, score, end_x, end_y, nullptr);
+}
+
+int mi355_sw_affine_batch_trace(mi355_sw_ctx *ctx, const mi355_sw_affine_params *params, mi355_sw_result *outs) {
+  return affine_batch_any(ctx, params, true, nullptr, nullptr, nullptr, outs);
 }
 
 int mi355_sw_affine_score_ranges(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,
@@ -477,57 +469,39 @@ int mi355_sw_affine_score_ranges(mi355_sw_ctx *ctx, size_t nranges, const int64_
   return affine_run(ctx, ctx->ref, ctx->batch, ranges, *params, maxima, nullptr);
 }
 
-// the arguments of the two pairs calls: 0, or MI355_SW_EINVAL with the message set
-static int affine_pairs_check(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights) {
-  if (!query || !lefts || !rights) return fail(ctx, MI355_SW_EINVAL, "null argument");
+// mi355_sw_affine_pairs_run (score, end_x, end_y) and, with `trace`, mi355_sw_affine_pairs_trace (outs), written only after success
+static int affine_pairs_any(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
+                            const mi355_sw_affine_params *params, bool trace, float *score, int64_t *end_x, int64_t *end_y, mi355_sw_result *outs) {
+  OptScope opt_scope_(ctx);
+  int rc = affine_check(ctx, params);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  reset_timings(ctx);
+  if (npairs == 0) return 0;
+  if (trace && !outs) return fail(ctx, MI355_SW_EINVAL, "outs is NULL");
+  if ((!trace && (!score || !end_x || !end_y)) || !query || !lefts || !rights) return fail(ctx, MI355_SW_EINVAL, "null argument");
   for (size_t k = 0; k < npairs; ++k) {
     if (query[k] < 0 || (size_t)query[k] >= ctx->batch.nq) return fail(ctx, MI355_SW_EINVAL, "pair: query index outside the resident batch");
     if (lefts[k] < 0 || rights[k] < lefts[k] || rights[k] > (int64_t)ctx->ref.n) return fail(ctx, MI355_SW_EINVAL, "pair: window outside the resident reference");
   }
+  std::vector<float> sc(npairs, 0.0f);
+  std::vector<int64_t> ends(2 * npairs, 0);
+  std::vector<TraceOut> tout(trace ? npairs : 0);
+  rc = affine_pairs(ctx, ctx->ref, ctx->batch, npairs, query, lefts, rights, *params, sc.data(), ends.data(), trace ? &tout : nullptr);
+  if (rc) return rc;
+  if (trace) { memset(outs, 0, npairs * sizeof *outs); affine_results(ctx, npairs, sc.data(), ends.data(), tout, outs); }
+  else for (size_t k = 0; k < npairs; ++k) { score[k] = sc[k]; end_x[k] = ends[2 * k]; end_y[k] = ends[2 * k + 1]; }
   return 0;
 }
 
 int mi355_sw_affine_pairs_run(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
                               const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y) {
-  OptScope opt_scope_(ctx);
-  int rc = affine_check(ctx, params);
-  if (rc) return rc;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  reset_timings(ctx);
-  if (npairs == 0) return 0;
-  if (!score || !end_x || !end_y) return fail(ctx, MI355_SW_EINVAL, "null argument");
-  rc = affine_pairs_check(ctx, npairs, query, lefts, rights);
-  if (rc) return rc;
-  std::vector<float> sc(npairs, 0.0f);
-  std::vector<int64_t> ends(2 * npairs, 0);
-  rc = affine_pairs(ctx, ctx->ref, ctx->batch, npairs, query, lefts, rights, *params, sc.data(), ends.data(), nullptr);
-  if (rc) return rc;
-  for (size_t k = 0; k < npairs; ++k) { score[k] = sc[k]; end_x[k] = ends[2 * k]; end_y[k] = ends[2 * k + 1]; }
-  return 0;
+  return affine_pairs_any(ctx, npairs, query, lefts, rights, params, false, score, end_x, end_y, nullptr);
 }
 
 int mi355_sw_affine_pairs_trace(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
                                 const mi355_sw_affine_params *params, mi355_sw_result *outs) {
-  OptScope opt_scope_(ctx);
-  int rc = affine_check(ctx, params);
-  if (rc) return rc;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  reset_timings(ctx);
-  if (npairs == 0) return 0;
-  if (!outs) return fail(ctx, MI355_SW_EINVAL, "outs is NULL");
-  rc = affine_pairs_check(ctx, npairs, query, lefts, rights);
-  if (rc) return rc;
-  std::vector<float> sc(npairs, 0.0f);
-  std::vector<int64_t> ends(2 * npairs, 0);
-  std::vector<TraceOut> tout(npairs);
-  rc = affine_pairs(ctx, ctx->ref, ctx->batch, npairs, query, lefts, rights, *params, sc.data(), ends.data(), &tout);
-  if (rc) return rc;
-  memset(outs, 0, npairs * sizeof *outs);
-  for (size_t k = 0; k < npairs; ++k) {
-    set_result(outs[k], sc[k], ends[2 * k], ends[2 * k + 1], &tout[k]);
-    outs[k].timings_us[0] = outs[k].timings_us[1] = (float)ctx->timings[0];
-  }
-  return 0;
+  return affine_pairs_any(ctx, npairs, query, lefts, rights, params, true, nullptr, nullptr, nullptr, outs);
 }
 
 int mi355_sw_best_range(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,

@@ -419,6 +419,35 @@ def test_score_ranges_short_and_long(ctx):
     assert np.array_equal(old, mx)
 
 
+def test_score_ranges_all_three_stages_write_one_array(ctx):
+    """One call in which sw_affine_prof_kernel, the sweep and the exact kernel each write part of one `maxima` array: ranges on both
+    sides of the sweep's 1 024 columns and a query beyond its 512 rows.  The 700-column range is the exact kernel's for every query,
+    the 600-row query on the 2 000-column range as well."""
+    rng = np.random.default_rng(9901)
+    ref = bytearray(rand(rng, 4200))
+    xs = [rand(rng, int(m)) for m in rng.integers(1, 400, 24)] + [b"", rand(rng, 600)]
+    ranges = [(3, 147), (500, 1012), (1300, 1600), (1801, 3801), (3400, 4100)]   # 144, 512 and 300 columns, 2 000 and 700
+    for q, (lo, hi) in zip((0, 5, 9, 13, 25), ranges):
+        ref[lo + 20:lo + 20 + min(len(xs[q]), hi - lo - 40)] = xs[q][:hi - lo - 40]
+    ref = bytes(ref)
+    assert sum(len(x) for x in xs) * 144 >= MIN_CELLS
+    exp = np.array([affine_ref.locate_batch(xs, ref[lo:hi])[0] for lo, hi in ranges])
+    assert exp.max(axis=1).tolist() == [315, 975, 348, 1143, 1800] and not exp[:, 24].any()
+    ctx.set_reference(ref)
+    ctx.batch_upload(xs)
+    mx = ctx.affine_score_ranges(ranges)
+    path = ctx.last_path()
+    assert np.array_equal(mx.astype(np.float64), exp), (mx.tolist(), exp.tolist())
+    assert prof_tags(path) == ["affine_prof[R=9]", "affine_prof[R=32]", "affine_prof[R=20]"], path
+    assert any(t.startswith("affine[cell=f16") for t in path) and "affine_exact" in path, path
+    ctx.set_option("no_affine_prof", 1)
+    try:
+        old = ctx.affine_score_ranges(ranges)
+    finally:
+        ctx.set_option("no_affine_prof", 0)
+    assert np.array_equal(old.astype(np.float64), exp), (old.tolist(), exp.tolist())
+
+
 # ---- traceback: the row window ----------------------------------------------------------------------------------------------------
 def _row_window_case():
     x6, y = _long_x()
