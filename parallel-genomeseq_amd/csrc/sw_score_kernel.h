@@ -46,6 +46,8 @@ constexpr int kSeg = 64;               // steps between two refills of the code 
 // bytes of history kept in front of a segment (>= lanes per slot - 1), and the per-slot window size
 __host__ __device__ constexpr int hist_bytes(int SL) { return SL > 16 ? SL : 16; }
 __host__ __device__ constexpr int codebuf_bytes(int SL) { return hist_bytes(SL) + kSeg; }
+constexpr int kWideCPL = 16;           // a lane that stages at least this many codes per segment loads them 16 bytes at a time (stage_load)
+static_assert(kWideCPL % 16 == 0 && kSeg % kWideCPL == 0, "wide staging moves whole 16-byte vectors");
 constexpr int kBrowFront = 64;         // dwords of front padding of a strip boundary row (>= lanes per slot)
 constexpr int kPadScore = -16384;      // substitution score of padding rows / columns
 constexpr int kSemI16 = 0;             // Similarity_Matrix semantics on integer scores, two queries per register
@@ -454,12 +456,54 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   // codes of stream positions seg*64 + CPL*ls .. +CPL-1 (pad outside [rlo, own_hi)): CPL/4 dwords, or one
   // byte per lane when the slot is a whole wavefront
   struct Codes { uint32_t w[CPL >= 4 ? CPL / 4 : 1]; };
+  // Wide staging (CPL >= kWideCPL): the lane's CPL codes come in as whole dwords, 16 bytes per load where there are that many.
+  //   * the load is unconditional: its address is clamped into the allocation, [0, ref_len + 64) — the reference is allocated with
+  //     64 bytes of (uninitialised) slack at its end (host_common.h upload_reference), and a load takes CPL + 4 <= 36 bytes.  A span
+  //     with a column inside [rlo, hi) is never moved by the clamp: it starts at or behind rlo (below) and in front of hi <= ref_len;
+  //   * chunk_len and warm are multiples of 64, so s0 = rlo (mod 64) and a lane's first column c0 = s0 + 64 seg + CPL ls = rlo
+  //     (mod CPL): a span never straddles rlo, only hi — and c0 & 3 == rlo & 3 is uniform for the range.  The load starts at the
+  //     dword below c0 and takes one dword more where rlo & 3 != 0; v_alignbyte_b32 by that uniform count puts the bytes in place;
+  //   * what lies outside [rlo, hi), and every byte of an inactive tile, becomes `pad` through a byte mask per dword on the loaded
+  //     registers, all under one branch that interior lanes do not take.
+  const int64_t wide_last = (a.ref_len + 64 - (CPL + 4)) & ~(int64_t)3;   // last dword-aligned offset a wide load may start at
   auto stage_load = [&](int seg, bool second = false) -> Codes {
     Codes out;
     const bool act = second ? active2 : active;
     const int64_t hi = second ? own_hi2 : own_hi;
     const int64_t c0 = s0 + (second ? a.chunk_len : 0) + (int64_t)seg * kSeg + CPL * ls;
-    if (CPL >= 4) {
+    if constexpr (CPL >= kWideCPL) {
+      constexpr int ND = CPL / 4;
+      const uint32_t sh = (uint32_t)rlo & 3u;
+      int64_t at = c0 - (int64_t)sh;
+      at = at < 0 ? 0 : (at > wide_last ? wide_last : at);
+      // refcodes comes from hipMalloc and `at` is a multiple of 4; a multi-dword global load needs no more than dword alignment
+      const uint32_t *src = static_cast<const uint32_t *>(__builtin_assume_aligned(a.refcodes + at, 4));
+      uint32_t w[ND + 1];
+#pragma unroll
+      for (int q = 0; q < ND / 4; ++q) {
+        u32x4 v;
+        __builtin_memcpy(&v, src + 4 * q, 16);
+        w[4 * q + 0] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+      }
+      if (sh != 0u) {                                                // (uniform)
+        w[ND] = src[ND];
+#pragma unroll
+        for (int d = 0; d < ND; ++d) w[d] = __builtin_amdgcn_alignbyte(w[d + 1], w[d], sh);
+      }
+      if (!act || c0 < rlo || c0 + CPL > hi) {
+        // the span's first vhi bytes are columns of [rlo, hi): none in front of rlo (all of the span is, then), hi - c0 otherwise
+        const int64_t left = hi - c0;
+        const int vhi = (!act || c0 < rlo || left < 0) ? 0 : (left > CPL ? CPL : (int)left);
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+          const int t = vhi - 4 * d < 0 ? 0 : (vhi - 4 * d > 4 ? 4 : vhi - 4 * d);   // the dword keeps its bytes b < t
+          const uint32_t keep = (0xFFFFFFFFu >> (16 - 4 * t)) >> (16 - 4 * t);
+          w[d] = (w[d] & keep) | (pad4 & ~keep);
+        }
+      }
+#pragma unroll
+      for (int d = 0; d < ND; ++d) out.w[d] = w[d];
+    } else if (CPL >= 4) {
 #pragma unroll
       for (int d = 0; d < CPL / 4; ++d) {
         uint32_t w = 0;
