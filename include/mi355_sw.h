@@ -325,8 +325,17 @@ int mi355_sw_last_counters(const mi355_sw_ctx *ctx, uint64_t out[4]);
  * is swept, "whole_batch_again").  Options of the filter (mi355_sw_set_option): "no_prefix" switches it off (the A/B),
  * "prefix_min_cols" = n moves the reference length from which it engages (default 8 Mi columns).  mi355_sw_last_kernel then names the
  * prefix instance and its `cells` are the cells that launch swept (P rows per read), not |x| * |y|.
+ * A bucket of at least 512 reads is probed with its first 64, at the next lower prefix height on tiles that fold row P alone; the
+ * probe decides the height of the rest.  "no_prefix_low" keeps such a bucket at its own height with the fold over
+ * all prefix rows (the A/B).
  * MI355_SW_EINVAL for an unknown name. */
 int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *out);
+
+/* Test hook.  After a mi355_sw_score_ranges call of ONE range under mi355_sw_set_option("prefix_rowp", R) — the bucket of the prefix
+ * shape swept by the instance of R rows per lane that folds row P = 2 R alone — the value of every sub-chunk of the range as the tiles
+ * published it, in score units: values[q * *n_sub + s] for resident query q, -1 for queries the hook did not sweep.  *n_sub = 0 (and
+ * nothing written) when the last call left no such values; values may be NULL to ask for *n_sub alone. */
+int mi355_sw_prefix_values(mi355_sw_ctx *ctx, float *values, size_t capacity, size_t *n_sub);
 
 /* Which kernels and pipeline decisions the last call used: space-separated tags, each at most once, e.g.
  * "score[cell=f16,SL=8,R=19,...,sampled=1,...] strip[R=3,mode=max,...] wave[orient=0,...,dirs=1,...] walk_wave" — what the parity

@@ -24,6 +24,7 @@ EXPORTS = [
     "mi355_sw_set_option", "mi355_sw_option_names", "mi355_sw_multi_set_option", "mi355_sw_last_counters", "mi355_sw_last_counter", "mi355_sw_batch_upload_packed", "mi355_sw_best_range", "mi355_sw_last_path",
     "mi355_sw_default_affine_params", "mi355_sw_affine_align", "mi355_sw_affine_batch_run", "mi355_sw_affine_score_ranges",
     "mi355_sw_affine_align_trace", "mi355_sw_affine_batch_trace", "mi355_sw_affine_pairs_run", "mi355_sw_affine_pairs_trace",
+    "mi355_sw_prefix_values",
 ]
 MULTI_RCCL = 1
 
@@ -465,6 +466,17 @@ class Context:
             if rc:
                 raise MI355Error(rc, "mi355_sw_last_counter(%s)" % name)
             out[name] = int(v.value)
+        return out
+
+    def prefix_values(self):
+        """Test hook (set_option("prefix_rowp", R), then score_ranges of one range): the sub-chunk values the row-P prefix tiles
+        published, array [n_queries, n_sub] in score units, -1 in the rows of queries the hook did not sweep; None without such values."""
+        nsub = C.c_size_t(0)
+        self._chk(self._L.mi355_sw_prefix_values(self._ctx, None, C.c_size_t(0), C.byref(nsub)))
+        if nsub.value == 0:
+            return None
+        out = np.zeros((self._nbatch, nsub.value), dtype=np.float32)
+        self._chk(self._L.mi355_sw_prefix_values(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size), C.byref(nsub)))
         return out
 
     def last_path(self):

@@ -14,7 +14,8 @@ constexpr size_t kExactLdsMax = 159 * 1024;    // dynamic part; the wide instanc
 #define MI355_SW_BOOL_OPTIONS(X) \
   X(no_f16) X(no_unsat) X(no_sample) X(no_satflag) X(no_solo) X(no_wave) X(no_comb) X(no_twin) X(no_wide) X(no_strip) \
   X(no_quant) X(no_devlist) X(no_ref_cache) X(no_strip_groups) X(u8_long_twin) X(long_twin) X(no_long) \
-  X(no_requery) X(force_f32) X(no_long_p32) X(no_opt_margin) X(no_wave_prof) X(no_wave_window) X(no_first) X(no_long_save) X(u8_sample_short) X(no_wave_pieces) X(no_u8_early) X(no_wave_f16) X(no_devlist_by_id) X(no_f16_mirror) X(no_f16m_int_diag) X(no_affine_sweep) X(no_affine_prof) X(no_affine_pairs) X(no_prefix) X(trace)
+  X(no_requery) X(force_f32) X(no_long_p32) X(no_opt_margin) X(no_wave_prof) X(no_wave_window) X(no_first) X(no_long_save) X(u8_sample_short) X(no_wave_pieces) X(no_u8_early) X(no_wave_f16) X(no_devlist_by_id) X(no_f16_mirror) X(no_f16m_int_diag) X(no_affine_sweep) X(no_affine_prof) X(no_affine_pairs) X(no_prefix) X(trace) \
+  X(no_prefix_low)
 #define MI355_SW_INT_OPTIONS(X) X(strip_r) X(slot) X(few_r) X(chunk) X(long_pipes) X(long_wgs) X(long_sub) X(long_r) X(long_groups) X(assume_cus) X(long_save_what) X(prefix_min_cols)
 struct Options {
 #define X(n) bool n = false;
@@ -25,6 +26,9 @@ struct Options {
 #undef X
   bool prefix_tiles = false;      // test hook, only through mi355_sw_set_option("prefix_tiles"), never from the environment: mi355_sw_score_ranges of ONE range
                                   // sweeps a bucket of the prefix shape with its prefix instance (raw keys of the prefix tiles)
+  long prefix_rowp = 0;           // test hook, only through mi355_sw_set_option("prefix_rowp", R), never from the environment: as prefix_tiles, with the instance of
+                                  // R rows per lane that folds row P = 2 R alone (R on the list of sampled 8-lane shapes); the sub-chunk values stay for
+                                  // mi355_sw_prefix_values
   int fault_inject = 0;           // test hook, only through mi355_sw_set_option("fault_inject", "strip_stall" | "long_stall"): never from the environment
 };
 inline std::string option_env_name(const char *n) {
@@ -56,6 +60,7 @@ inline int option_set(Options &o, const char *key, const char *value) {
   MI355_SW_INT_OPTIONS(X)
 #undef X
   if (k == "prefix_tiles") { o.prefix_tiles = on; return 0; }
+  if (k == "prefix_rowp") { o.prefix_rowp = on ? std::atol(v.c_str()) : 0; return 0; }
   if (k == "fault_inject") { o.fault_inject = v == "strip_stall" ? 1 : (v == "long_stall" ? 2 : 0); return 0; }
   return -1;
 }
@@ -64,7 +69,7 @@ inline const char *option_names() {
 #define X(n) #n ","
   MI355_SW_BOOL_OPTIONS(X) MI355_SW_INT_OPTIONS(X)
 #undef X
-  "prefix_tiles,fault_inject";
+  "prefix_tiles,prefix_rowp,fault_inject";
 }
 thread_local const Options *tl_opt = nullptr;
 inline const Options &opt() {
@@ -318,6 +323,8 @@ struct mi355_sw_ctx {
   size_t whole_again = 0;         // ... times the whole batch was (most of it exceeded its candidate cap)
   size_t candidates = 0;          // candidate sub-chunks the sampled / saturating sweeps of the call flagged
   bool prefix_named = false;      // last_kernel names the prefix instance of the running call: later sweeps (its offenders) add their cells to it
+  std::vector<int32_t> hook_ids;  // test hook prefix_rowp: query id of every value row the last mi355_sw_score_ranges left in `submax` ...
+  int64_t hook_nsub = 0;          // ... and the sub-chunks per row (0: nothing to read, mi355_sw_prefix_values)
   size_t prefix_certified = 0;    // queries of the running call settled by the prefix filter (lemma L19), without a sweep of all their rows
   const void *wlut_ref = nullptr; // reference (and its version) whose byte -> code tables are in `wlut` (sw_wave_prof_kernel)
   uint64_t wlut_version = 0;
@@ -338,7 +345,7 @@ struct mi355_sw_ctx {
   std::vector<float> h_aprof;
   std::vector<uint8_t> h_pieces;  // host side of the piece table of the running call (host_batch.h)
   size_t saved_locates = 0, saved_traces = 0, saved_fallbacks = 0;   // finish steps of the running call that started from saved state / fell back
-  DevBuf pkeys, pthr, psel, qcnt, sel2, gcnt, wlut, ckpt, first, keys, ranges, stab, ftab, ftab_s, htab, htab8, soloblk, flags, submax, lut, probs, dirs, outs_f, outs_i, cons, walkp, hmat, brow, wprobs, scan;
+  DevBuf pkeys, pthr, psel, psel2, qcnt, sel2, gcnt, wlut, ckpt, first, keys, ranges, stab, ftab, ftab_s, htab, htab8, soloblk, flags, submax, lut, probs, dirs, outs_f, outs_i, cons, walkp, hmat, brow, wprobs, scan;
   // host sides of small per-call uploads: they must outlive the asynchronous copies, and the tables are only
   // sent again when they change
   std::vector<int64_t> h_ranges;

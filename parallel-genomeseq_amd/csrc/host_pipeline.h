@@ -500,9 +500,16 @@ float elapsed_us(mi355_sw_ctx *ctx, hipEvent_t a, hipEvent_t b) {
 //            and what round 1 has not evaluated is evaluated now; the read's result is the first maximum over both rounds.
 // A read is an OFFENDER (appended to `offenders`, nothing written for it) when B0 cannot certify — B0 <= smax (m - P) + slack —
 // or when it flags more sub-chunks than its cap.  Everybody else: loc[] and qdone[] are final, qchunk[] / qwarm[] set.
+// The prefix is P = kPrefixLanes * prefR rows, which need not be the bucket's own R (a probed bucket tries a lower height first,
+// align_range_core).  rowp: the tiles fold row P alone — slack = rowp_slack, and a read also offends unless B0 > smax P (prefix_bound).
+// vote (by query id, may be null; a probe at a lower height asks): could a row-P pass of voteR rows per lane certify the read?  1 when
+// B0 is above that height's bound AND that height's threshold, B0 - smax (m - 2 voteR) - slack, applied to the values of THIS sweep
+// stays within the cap.  The second part is a forecast, not a proof: row 2 voteR reads no lower than the row swept here against a
+// random background, so a threshold that drowns here drowns there (10 % substitutions: B0 is about 360, above the bound 342 of
+// R = 19, with a threshold of 18 that most sub-chunks reach).  It only steers the choice of the height; every result stays exact.
 int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_params &p,
-                  const ScoreTable &table, const Bucket &b, std::vector<int64_t> &qchunk, std::vector<int64_t> &qwarm,
-                  std::vector<Located> &loc, std::vector<char> &qdone, std::vector<int> &offenders) {
+                  const ScoreTable &table, const Bucket &b, int prefR, bool rowp, std::vector<int64_t> &qchunk, std::vector<int64_t> &qwarm,
+                  std::vector<Located> &loc, std::vector<char> &qdone, std::vector<int> &offenders, int voteR = 0, std::vector<char> *vote = nullptr) {
   HostTrace trace_("prefix_bucket");
   const size_t nq = q.nq;
   const int64_t n = rg.hi - rg.lo;
@@ -511,9 +518,9 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   if (rc) return rc;
   if (ctx->pkeys.ensure(nq * 8 + 16) || ctx->pthr.ensure(nq * 4 + 16)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(score scratch) failed");
   HIPCHK(ctx, hipMemsetAsync(ctx->pkeys.p, 0, nq * 8, ctx->stream));
-  // a. the prefix sweep: the bucket's own instance at kPrefixLanes lanes; keys and sub-chunk values as the sampled sweep writes them
+  // a. the prefix sweep: the instance of prefR rows at kPrefixLanes lanes; keys and sub-chunk values as the sampled sweep writes them
   Bucket pb = b;
-  pb.SL = kPrefixLanes; pb.prefix = true;
+  pb.SL = kPrefixLanes; pb.R = prefR; pb.prefix = true; pb.rowp = rowp;
   ScoreIO io;
   io.range_lo = ctx->ranges.as<int64_t>(); io.range_hi = ctx->ranges.as<int64_t>() + 1; io.keys = ctx->pkeys.as<unsigned long long>();
   rc = score_launch(ctx, ref, q, ranges, p, table, pb, &io);
@@ -524,7 +531,7 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   const int P = pb.SL * pb.R;
   const int64_t E = pb.sub_len, nsub = (n + E - 1) / E;                            // sub-chunks that hold columns of the range
   const int64_t stride = ((n + pb.chunk_len - 1) / pb.chunk_len) * (pb.chunk_len / E);   // value row of one read (whole tiles)
-  const float slack = sample_slack(table, pb), smax = (float)table.smax;
+  const float slack = rowp ? rowp_slack(table) : sample_slack(table, pb), smax = (float)table.smax;
   const int64_t W = (int64_t)(b.maxlen - P) + (int64_t)((int64_t)table.smax * (b.maxlen - P) / table.gap);
   const int64_t D = (W + E - 1) / E;
   static_assert(kPrefixLanes - 1 + kScoreMK - 1 <= 63, "a candidate window starts 63 columns in front of its sub-chunk: the lag of a prefix value");
@@ -536,7 +543,7 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     const int id = q.order[b.first + k];
     mine[id] = 1; qchunk[id] = E; qwarm[id] = b.warm;
     // windows of both rounds only have to be exact for cells that hold a maximum above the certification bound (L3)
-    bound[id] = smax * (float)(q.len[id] - P) + slack;
+    bound[id] = prefix_bound(table, q.len[id], P, slack, rowp);
     qlow[id] = bound[id];
     if (!(key_score(kKeyF16, (uint32_t)(pkeys[id] >> 32), 0) > 0)) { off[id] = 1; continue; }
     const int64_t s0 = (int64_t)(0xFFFFFFFFull - (pkeys[id] & 0xFFFFFFFFull));
@@ -562,27 +569,47 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     for (int k = 0; k < b.count; ++k) offenders.push_back(q.order[b.first + k]);
     return 0;
   };
-  if (2 * noff > (size_t)b.count) return give_up();
-  // c. round 2: one filter launch, per-query thresholds
+  // one filter launch over the bucket's value rows with per-query thresholds: flags in ctx->flags, their number and the per-query counts
   const uint32_t qcap = query_flag_cap(nq);
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pthr.p, thr.data(), nq * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(ctx->flags.p, 0, 8, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(ctx->qcnt.p, 0, nq * 4, ctx->stream));
-  for (int f0 = 0; f0 < b.count; f0 += 65535) {
-    const int fc = std::min(65535, b.count - f0);
-    const dim3 fgrid((unsigned)std::min<int64_t>(64, (stride + 255) / 256), (unsigned)fc);
-    hipLaunchKernelGGL(sw_prefix_filter, fgrid, dim3(256), 0, ctx->stream, (const uint16_t *)ctx->submax.as<uint16_t>(), stride, stride,
-                       (const int32_t *)q.sel.as<int32_t>(), b.first, f0, b.count, (const float *)ctx->pthr.as<float>(),
-                       ctx->flags.as<unsigned int>(), reinterpret_cast<uint2 *>(ctx->flags.as<unsigned int>() + 2), ctx->flag_cap,
-                       ctx->qcnt.as<unsigned int>(), qcap);
-  }
-  HIPCHK(ctx, hipGetLastError());
   unsigned int nflag = 0;
   std::vector<uint32_t> cnt(nq, 0);
-  HIPCHK(ctx, hipMemcpyAsync(&nflag, ctx->flags.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(cnt.data(), ctx->qcnt.p, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  nflag = std::min(nflag, ctx->flag_cap);
+  auto run_filter = [&](const std::vector<float> &t) -> int {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pthr.p, t.data(), nq * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->flags.p, 0, 8, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->qcnt.p, 0, nq * 4, ctx->stream));
+    for (int f0 = 0; f0 < b.count; f0 += 65535) {
+      const int fc = std::min(65535, b.count - f0);
+      const dim3 fgrid((unsigned)std::min<int64_t>(64, (stride + 255) / 256), (unsigned)fc);
+      hipLaunchKernelGGL(sw_prefix_filter, fgrid, dim3(256), 0, ctx->stream, (const uint16_t *)ctx->submax.as<uint16_t>(), stride, stride,
+                         (const int32_t *)q.sel.as<int32_t>(), b.first, f0, b.count, (const float *)ctx->pthr.as<float>(),
+                         ctx->flags.as<unsigned int>(), reinterpret_cast<uint2 *>(ctx->flags.as<unsigned int>() + 2), ctx->flag_cap,
+                         ctx->qcnt.as<unsigned int>(), qcap);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(&nflag, ctx->flags.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cnt.data(), ctx->qcnt.p, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    nflag = std::min(nflag, ctx->flag_cap);
+    return 0;
+  };
+  if (vote) {
+    const int vP = kPrefixLanes * voteR;
+    std::vector<float> vthr(nq, 0.0f);
+    for (int k = 0; k < b.count; ++k) {
+      const int id = q.order[b.first + k];
+      if (B0[id] > prefix_bound(table, q.len[id], vP, rowp_slack(table), true)) vthr[id] = B0[id] - smax * (float)(q.len[id] - vP) - rowp_slack(table);
+    }
+    rc = run_filter(vthr);
+    if (rc) return rc;
+    for (int k = 0; k < b.count; ++k) {
+      const int id = q.order[b.first + k];
+      (*vote)[id] = vthr[id] > 0.0f && cnt[id] <= qcap;
+    }
+  }
+  if (2 * noff > (size_t)b.count) return give_up();
+  // c. round 2: the filter with the thresholds of this height
+  rc = run_filter(thr);
+  if (rc) return rc;
   std::vector<uint32_t> raw(2 * (size_t)nflag);
   if (nflag) HIPCHK(ctx, hipMemcpy(raw.data(), ctx->flags.as<unsigned int>() + 2, (size_t)nflag * 8, hipMemcpyDeviceToHost));
   // d. offenders by the cap
@@ -769,18 +796,64 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
         // of them offend — reads that differ too much from the reference for their first P rows to decide — the rest of the bucket
         // skips the filter and is swept as ever: what such a batch pays for the filter is the probe (CHANGELOG.md: 10 % substitutions),
         // not a prefix sweep of every read.  (A failed probe of the call's only eligible bucket ends in the rule below: whole_again.)
+        // The probe also picks the HEIGHT (option no_prefix_low: not): it runs at the next lower listed R that is still eligible, on tiles
+        // that fold row P alone (rowp_slack instead of sample_slack: a lower prefix certifies what the bucket's own certifies with
+        // the fold over all rows).  B0 is an exact alignment score, whatever the height that found its window:
+        //   * at most kPrefixProbe / 16 of the probe offend: the rest of the bucket runs at the low height;
+        //   * more than half cannot be certified at the bucket's own R under the row-P fold either — B0 is not above that bound, or
+        //     that threshold already draws more flags than the cap on the rows of the probe (prefix_bucket: vote): the probe has
+        //     failed, as above;
+        //   * else the rest runs at the bucket's own R with the row-P fold, and with it the probe's offenders that this height can
+        //     certify (the others stay offenders).
         Bucket part = b;
+        int restR = b.R;
+        bool rest_rowp = false;
+        std::vector<int> riders;
         if (b.count >= 8 * kPrefixProbe) {
           part.count = kPrefixProbe;
+          const int lowR = opt().no_prefix_low ? 0 : prefix_low_R(table, b, q.len[q.order[b.first]]);
           const size_t before = offenders.size();
-          int rc = prefix_bucket(ctx, ref, q, rg, p, table, part, qchunk, qwarm, loc, qdone, offenders);
+          std::vector<char> own_ok(lowR ? nq : 0, 0);                  // could the bucket's own height certify the read?  (prefix_bucket: vote)
+          int rc = prefix_bucket(ctx, ref, q, rg, p, table, part, lowR ? lowR : b.R, lowR != 0, qchunk, qwarm, loc, qdone, offenders, b.R, lowR ? &own_ok : nullptr);
           if (rc) return rc;
           for (int k = 0; k < part.count; ++k) tried[q.order[part.first + k]] = 1;
           ntried += (size_t)part.count;
-          if (2 * (offenders.size() - before) > (size_t)part.count) { path_note(ctx, "prefix_probe_failed"); continue; }
+          if (!lowR) {
+            if (2 * (offenders.size() - before) > (size_t)part.count) { path_note(ctx, "prefix_probe_failed"); continue; }
+          } else if (16 * (offenders.size() - before) <= (size_t)kPrefixProbe) {
+            restR = lowR; rest_rowp = true;
+            path_note(ctx, "prefix_height[R=%d,low]", restR);
+          } else {
+            size_t hopeless = 0;
+            for (int k = 0; k < part.count; ++k) hopeless += own_ok[q.order[part.first + k]] ? 0 : 1;
+            if (2 * hopeless > (size_t)part.count) { path_note(ctx, "prefix_probe_failed"); continue; }
+            rest_rowp = true;
+            for (size_t o = before; o < offenders.size(); ++o)
+              if (own_ok[offenders[o]]) riders.push_back(offenders[o]);
+            offenders.erase(std::remove_if(offenders.begin() + before, offenders.end(),
+                                           [&](int id) { return std::find(riders.begin(), riders.end(), id) != riders.end(); }), offenders.end());
+            path_note(ctx, "prefix_height[R=%d,own,riders=%zu]", restR, riders.size());
+          }
           part.first = b.first + kPrefixProbe; part.count = b.count - kPrefixProbe;
         }
-        int rc = prefix_bucket(ctx, ref, q, rg, p, table, part, qchunk, qwarm, loc, qdone, offenders);
+        int rc;
+        if (riders.empty()) {
+          rc = prefix_bucket(ctx, ref, q, rg, p, table, part, restR, rest_rowp, qchunk, qwarm, loc, qdone, offenders);
+        } else {
+          // the rest of the bucket with the riders in front: a view of the batch with its own sorted id list (ids index everything else)
+          QueryBatch qv;
+          qv.bytes.alias(q.bytes.p); qv.lens.alias(q.lens.p); qv.offs.alias(q.offs.p); qv.cum.alias(q.cum.p);
+          qv.len = q.len; qv.off = q.off; qv.nq = q.nq; qv.maxlen = q.maxlen;
+          qv.order.assign(riders.begin(), riders.end());
+          for (int k = 0; k < part.count; ++k) qv.order.push_back(q.order[part.first + k]);
+          std::stable_sort(qv.order.begin(), qv.order.end(), [&](int32_t a, int32_t b2) { return q.len[a] < q.len[b2]; });
+          if (ctx->psel2.ensure(qv.order.size() * 4 + 16)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(score scratch) failed");
+          HIPCHK(ctx, hipMemcpy(ctx->psel2.p, qv.order.data(), qv.order.size() * 4, hipMemcpyHostToDevice));
+          qv.sel.alias(ctx->psel2.p);
+          Bucket vb = part;
+          vb.first = 0; vb.count = (int)qv.order.size();
+          rc = prefix_bucket(ctx, ref, qv, rg, p, table, vb, restR, rest_rowp, qchunk, qwarm, loc, qdone, offenders);
+        }
         if (rc) return rc;
         for (int k = 0; k < part.count; ++k) tried[q.order[part.first + k]] = 1;
         ntried += (size_t)part.count;
@@ -1234,6 +1307,13 @@ int range_maxima(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
         b.SL == 8 && b.count >= 2 && kernel_sem(b) == kSemF16M && listed(kR8M, b.R)) {
       b.SL = kPrefixLanes; b.prefix = true; b.sampled = true;
     }
+    // ... (option prefix_rowp = R, a listed R whose prefix is shorter than the bucket's reads) by the instance of R rows per lane that
+    // folds row P = 2 R alone; the value rows stay readable (mi355_sw_prefix_values, tests/test_gpu_prefix_rowp_tiles.py)
+    if (listed(kR8M, opt().prefix_rowp) && nr == 1 && !winner_only && b.fast && b.sem == kSemF16 && b.mirror && !b.strips && !b.twin && !b.satflag &&
+        !b.unsat && b.SL == 8 && b.count >= 2 && kernel_sem(b) == kSemF16M && kPrefixLanes * opt().prefix_rowp < q.len[q.order[b.first]] && ctx->hook_ids.empty()) {
+      b.SL = kPrefixLanes; b.R = (int)opt().prefix_rowp; b.prefix = true; b.sampled = true; b.rowp = true;
+      for (int k = 0; k < b.count; ++k) ctx->hook_ids.push_back(q.order[b.first + k]);
+    }
   }
   ctx->long_margin = 0;
   if (winner_only && nq == 1 && known_best > 0.0f && table.integral)
@@ -1360,6 +1440,7 @@ void reset_timings(mi355_sw_ctx *ctx) {
   ctx->score_ev_used = 0; ctx->arenas.clear(); ctx->cons_used = 0;
   ctx->last_kernel = mi355_sw_kernel_info{};
   ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
+  ctx->hook_ids.clear(); ctx->hook_nsub = 0;
   ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
   ctx->path.clear();
 }

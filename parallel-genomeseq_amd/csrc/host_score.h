@@ -43,6 +43,7 @@ struct Bucket {
                               // sub-chunks that reach the cap are flagged and re-evaluated exactly (locate_saturated)
   bool prefix = false;        // a PREFIX sweep (lemma L19): SL = kPrefixLanes lanes x R rows = the first P rows of queries that are longer;
                               // its sub-chunk values stay in ctx->submax for sw_prefix_filter (host_pipeline.h prefix_bucket), no filter here
+  bool rowp = false;          // ... whose tiles fold row P alone (sw_score_kernel ROWP): values within rowp_slack of row P's maximum per sub-chunk
   int64_t warm = 0;           // exactness margin in columns
   bool fast = false;          // swept by the score kernel (else whole-matrix exact path)
   int64_t chunk_len = 0;      // own columns per tile
@@ -61,15 +62,15 @@ constexpr int kR16M[] = {10, 12, 16, 20, 24, 32};              // ... on 16-lane
 constexpr int kPrefixLanes = 2;                                // lanes of a prefix tile (lemma L19): P = kPrefixLanes * R rows, on the kR8M list
 template <size_t N> constexpr bool listed(const int (&rs)[N], long r) { for (int v : rs) if (v == r) return true; return false; }
 
-// sw_score_kernel<R, sem, strips, SL, twin, comb, mk>
+// sw_score_kernel<R, sem, strips, SL, twin, comb, mk, rowp>
 struct ScoreInst {
-  int R, sem; bool strips; int SL; bool twin, comb; int mk;
+  int R, sem; bool strips; int SL; bool twin, comb; int mk; bool rowp = false;
   constexpr bool operator==(const ScoreInst &o) const {
-    return R == o.R && sem == o.sem && strips == o.strips && SL == o.SL && twin == o.twin && comb == o.comb && mk == o.mk;
+    return R == o.R && sem == o.sem && strips == o.strips && SL == o.SL && twin == o.twin && comb == o.comb && mk == o.mk && rowp == o.rowp;
   }
 };
-// One row per shape: the rows-per-lane list, the shape, and the cells (bit SEM) compiled on it
-struct ScoreShapes { const int *rs; size_t n; bool strips; int SL; bool twin, comb; int mk; unsigned sems; };
+// One row per shape: the rows-per-lane list, the shape, the cells (bit SEM) compiled on it, and the fold of a prefix tile
+struct ScoreShapes { const int *rs; size_t n; bool strips; int SL; bool twin, comb; int mk; unsigned sems; bool rowp = false; };
 constexpr unsigned kCellsPlain = 0x3Fu;                              // kSemI16 .. kSemU8H
 constexpr unsigned kCellsMirror = 1u << kSemF16M | 1u << kSemF16MF;
 constexpr unsigned kCellsTwin = 1u << kSemI16 | 1u << kSemU8 | 1u << kSemF16 | 1u << kSemU8H;
@@ -90,6 +91,7 @@ constexpr ScoreShapes kScoreShapes[] = {
   {kR16M, std::size(kR16M), false, 64, false, false, 4, kCellsSampled},
   {kR64S, std::size(kR64S), true, 64, false, false, 4, 1u << kSemF32},         // a lone long query on float32 cells
   {kR8M, std::size(kR8M), false, kPrefixLanes, false, false, 4, 1u << kSemF16M},   // prefix tiles of the 8-lane shapes (lemma L19)
+  {kR8M, std::size(kR8M), false, kPrefixLanes, false, false, 4, 1u << kSemF16M, true},   // ... that fold row P alone
 };
 constexpr size_t score_inst_count() {
   size_t n = 0;
@@ -103,7 +105,7 @@ constexpr std::array<ScoreInst, score_inst_count()> score_insts() {
   for (const ScoreShapes &g : kScoreShapes)
     for (int sem = 0; sem < 8; ++sem)
       if (g.sems >> sem & 1u)
-        for (size_t j = 0; j < g.n; ++j) out[k++] = ScoreInst{g.rs[j], sem, g.strips, g.SL, g.twin, g.comb, g.mk};
+        for (size_t j = 0; j < g.n; ++j) out[k++] = ScoreInst{g.rs[j], sem, g.strips, g.SL, g.twin, g.comb, g.mk, g.rowp};
   return out;
 }
 constexpr auto kScoreInsts = score_insts();
@@ -113,10 +115,10 @@ constexpr bool score_compiled(const ScoreInst &want) {
 }
 // every shape a chooser below can name is compiled for the cells make_buckets may give it (mirror_ok: 8- and 16-lane tiles, one
 // strip; sampled_instance; the lone float32 query's sampled strips; twin_shape: 16-lane twins of the float16 cell)
-template <size_t N> constexpr bool score_compiled(const int (&rs)[N], bool strips, int SL, bool twin, bool comb, int mk, unsigned sems) {
+template <size_t N> constexpr bool score_compiled(const int (&rs)[N], bool strips, int SL, bool twin, bool comb, int mk, unsigned sems, bool rowp = false) {
   for (int r : rs)
     for (int sem = 0; sem < 8; ++sem)
-      if ((sems >> sem & 1u) && !score_compiled(ScoreInst{r, sem, strips, SL, twin, comb, mk})) return false;
+      if ((sems >> sem & 1u) && !score_compiled(ScoreInst{r, sem, strips, SL, twin, comb, mk, rowp})) return false;
   return true;
 }
 static_assert(score_compiled(kR16, false, 16, false, false, 1, kCellsPlain | kCellsMirror) &&
@@ -129,14 +131,15 @@ static_assert(score_compiled(kR8M, false, 8, false, false, 4, kCellsSampled | kC
               score_compiled(kR16M, false, 16, false, false, 4, kCellsSampled | kCellsMirror) &&
               score_compiled(kR16M, false, 64, false, false, 4, kCellsSampled) && score_compiled(kR64S, true, 64, false, false, 4, 1u << kSemF32),
               "sampled_instance");
-static_assert(score_compiled(kR8M, false, kPrefixLanes, false, false, 4, 1u << kSemF16M), "prefix_ok");
+static_assert(score_compiled(kR8M, false, kPrefixLanes, false, false, 4, 1u << kSemF16M) &&
+              score_compiled(kR8M, false, kPrefixLanes, false, false, 4, 1u << kSemF16M, true), "prefix_ok, prefix_low_R");
 
 typedef void (*ScoreKernel)(const ScoreArgs);
 template <size_t... I> constexpr std::array<ScoreKernel, sizeof...(I)> score_kernels(std::index_sequence<I...>) {
   static_assert((score_instance_ok<kScoreInsts[I].sem>(kScoreInsts[I].R, kScoreInsts[I].strips, kScoreInsts[I].SL, kScoreInsts[I].twin,
-                                                      kScoreInsts[I].comb, kScoreInsts[I].mk) && ...), "an illegal instance in the table");
+                                                      kScoreInsts[I].comb, kScoreInsts[I].mk, kScoreInsts[I].rowp) && ...), "an illegal instance in the table");
   return {&sw_score_kernel<kScoreInsts[I].R, kScoreInsts[I].sem, kScoreInsts[I].strips, kScoreInsts[I].SL, kScoreInsts[I].twin,
-                           kScoreInsts[I].comb, kScoreInsts[I].mk>...};
+                           kScoreInsts[I].comb, kScoreInsts[I].mk, kScoreInsts[I].rowp>...};
 }
 constexpr std::array<ScoreKernel, kScoreInsts.size()> kScoreKernels = score_kernels(std::make_index_sequence<kScoreInsts.size()>{});
 
@@ -291,6 +294,10 @@ float sample_slack(const ScoreTable &t, const Bucket &b) {
   if (b.sem != kSemF32) return subs * (float)t.gap;
   return subs * t.gapf + (t.integral ? 0.0f : subs / 3.0f * std::ldexp(t.smaxf * (float)(b.maxlen + 1), -20));
 }
+
+// The slack of a prefix sweep that folds row P alone (sw_score_kernel ROWP; lemma L19, row-P variant): the last cell of the optimal
+// path in row P is seen at the next folded step of that very row, at most kScoreMK - 1 gaps along it — no row term.
+float rowp_slack(const ScoreTable &t) { return (float)(kScoreMK - 1) * (float)t.gap; }
 
 // Mirrored float16 cells (kSemF16M, lemma L14) for a kSemF16 bucket of two-query tiles: every value of the sweep stays within
 // 1024 (smax * maxlen + smax: a cell's value and its diagonal term), where N = 1 - H / 2048 keeps to one float16 binade; 8- and
@@ -503,6 +510,19 @@ int kernel_sem(const Bucket &b) {
 constexpr int64_t kPrefixMinCols = (int64_t)8 << 20;   // range length from which the filter engages (CHANGELOG.md has what was measured)
 constexpr int kPrefixProbe = 64;                       // reads of a bucket of >= 8 x as many that take the filter first, as a probe (align_range_core)
 inline int64_t prefix_cols_min() { const long v = opt().prefix_min_cols; return v > 0 ? (int64_t)v : kPrefixMinCols; }
+// What a read of m rows must score ABOVE to be certified by a prefix of P rows: the rows below P cannot make up the difference.  A
+// row-P pass also needs the alignment to end below row P (an alignment that ends inside the prefix never shows in row P): B0 > smax P,
+// which the first term implies for m >= 2 P.
+float prefix_bound(const ScoreTable &t, int m, int P, float slack, bool rowp) {
+  const float b = (float)t.smax * (float)(m - P) + slack;
+  return rowp ? std::max(b, (float)t.smax * (float)P) : b;
+}
+// ... on R rows per lane (the bucket's own R, or a lower listed one), with either fold
+bool prefix_height_ok(const ScoreTable &t, const Bucket &b, int minlen, int R, bool rowp) {
+  const int P = kPrefixLanes * R;
+  if (!listed(kR8M, R) || minlen <= P) return false;
+  return (float)t.smax * (float)minlen > prefix_bound(t, b.maxlen, P, rowp ? rowp_slack(t) : sample_slack(t, b), rowp);
+}
 bool prefix_ok(const ScoreTable &t, const Bucket &b, int minlen, int64_t n, const mi355_sw_params &p) {
   if (opt().no_prefix || p.semantics != MI355_SW_F32 || !t.integral || t.gap <= 0 || t.smax <= 0) return false;
   if (!(b.fast && b.sem == kSemF16 && b.mirror && b.sampled && !b.strips && !b.twin && !b.satflag && !b.unsat && b.SL == 8 && b.count >= 2)) return false;
@@ -510,6 +530,12 @@ bool prefix_ok(const ScoreTable &t, const Bucket &b, int minlen, int64_t n, cons
   const int P = kPrefixLanes * b.R;
   if (minlen <= P || n < prefix_cols_min()) return false;
   return (float)t.smax * (float)minlen > (float)t.smax * (float)(b.maxlen - P) + sample_slack(t, b);
+}
+// The height a PROBED bucket tries first: the next lower listed R that is still eligible under the row-P fold; 0: there is none
+int prefix_low_R(const ScoreTable &t, const Bucket &b, int minlen) {
+  int low = 0;
+  for (int r : kR8M) if (r < b.R && r > low) low = r;
+  return low && prefix_height_ok(t, b, minlen, low, true) ? low : 0;
 }
 
 // What a score launch passes that depends on the kernel's cell type
@@ -965,6 +991,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
       return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(sub-chunk values) failed");
     a.submax_out = ctx->submax.as<uint16_t>() + p0 * (size_t)nqw * (size_t)nsub;
     a.submax_stride = nsub;
+    if (!ctx->hook_ids.empty()) ctx->hook_nsub = nsub;               // (test hook prefix_rowp: the rows stay for mi355_sw_prefix_values)
   } else if (b.sampled) {
     if (ctx->submax.ensure((size_t)pn * (size_t)nqw * (size_t)nsub * cl.value_bytes + 64))
       return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(sub-chunk values) failed");
@@ -994,10 +1021,10 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   HIPCHK(ctx, hipEventRecord(ctx->score_ev[ctx->score_ev_used], ctx->stream));
   char rows_note[16] = "";                                           // sampled launches: the row stride of the fold
   if (b.sampled) std::snprintf(rows_note, sizeof rows_note, ",rows=%d", sample_rows(b));
-  const ScoreInst inst{b.R, sem, b.strips, b.SL, b.twin, b.comb, a.submax_out != nullptr ? kScoreMK : 1};
+  const ScoreInst inst{b.R, sem, b.strips, b.SL, b.twin, b.comb, a.submax_out != nullptr ? kScoreMK : 1, b.prefix && b.rowp};
   if (launch_score(inst, grid, shmem, ctx->stream, a)) return fail(ctx, MI355_SW_ENOTSUP, "no score kernel instance for this R");
   HIPCHK(ctx, hipGetLastError());
-  if (b.prefix) path_note(ctx, "prefix[SL=%d,R=%d,P=%d]", b.SL, b.R, b.SL * b.R);
+  if (b.prefix) path_note(ctx, "prefix[SL=%d,R=%d,P=%d%s]", b.SL, b.R, b.SL * b.R, b.rowp ? ",fold=rowP" : "");
   else path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d%s,satflag=%d,unsat=%d,pow2=%d%s]", cl.cell, b.SL, b.R, (int)b.strips,
             (int)b.twin, (int)b.comb, (int)b.sampled, rows_note, (int)b.satflag, (int)b.unsat, (int)((b.chunk_len & (b.chunk_len - 1)) == 0), cl.tag);
   if (b.sampled && !b.prefix) {
@@ -1048,7 +1075,10 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
                   b.strips ? ", strips" : "", b.twin ? (b.comb ? ", twin, code-pair profile" : ", twin") : "",
                   b.unsat ? " uint8 engine swept unsaturated, maxima clamped at 255"
                   : b.satflag ? (b.sampled ? " float engine swept saturating at 2048" : " float engine swept saturating at 2048, saturated sub-chunks re-evaluated exactly") : "");
-    if (b.sampled) {
+    if (b.sampled && b.rowp) {
+      const size_t at = std::strlen(ki.name);
+      std::snprintf(ki.name + at, sizeof ki.name - at, "; maximum of row P folded every 4th step");
+    } else if (b.sampled) {
       const size_t at = std::strlen(ki.name);
       std::snprintf(ki.name + at, sizeof ki.name - at, "; maximum folded every 4th step (candidates re-evaluated), row stride %d", sample_rows(b));
     }

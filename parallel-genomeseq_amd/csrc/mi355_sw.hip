@@ -104,7 +104,7 @@ void mi355_sw_destroy(mi355_sw_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   DevBuf *bufs[] = {&c->qcnt, &c->sel2, &c->gcnt, &c->wlut, &c->ref.bytes, &c->ref.codes, &c->batch.bytes, &c->batch.lens, &c->keys, &c->ranges, &c->stab,
-                    &c->batch.offs, &c->batch.sel, &c->colsave, &c->rowsave, &c->pieces, &c->ftab, &c->ftab_s, &c->htab, &c->htab8, &c->soloblk, &c->flags, &c->submax, &c->lut, &c->probs, &c->dirs, &c->outs_f, &c->outs_i, &c->cons, &c->walkp, &c->hmat, &c->brow, &c->wprobs, &c->scan, &c->batch.cum, &c->ckpt, &c->first, &c->recs, &c->atab, &c->aprof, &c->pkeys, &c->pthr, &c->psel};
+                    &c->batch.offs, &c->batch.sel, &c->colsave, &c->rowsave, &c->pieces, &c->ftab, &c->ftab_s, &c->htab, &c->htab8, &c->soloblk, &c->flags, &c->submax, &c->lut, &c->probs, &c->dirs, &c->outs_f, &c->outs_i, &c->cons, &c->walkp, &c->hmat, &c->brow, &c->wprobs, &c->scan, &c->batch.cum, &c->ckpt, &c->first, &c->recs, &c->atab, &c->aprof, &c->pkeys, &c->pthr, &c->psel, &c->psel2};
   for (DevBuf *b : bufs) b->release();
   c->adhoc.release(); c->one.release();
   c->pin_probs.release(); c->pin_walk.release(); c->pin_out.release(); c->pin_solo_up.release(); c->pin_solo_down.release();
@@ -633,6 +633,22 @@ int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *o
   else if (k == "saved_traces") *out = ctx->saved_traces;
   else if (k == "saved_fallbacks") *out = ctx->saved_fallbacks;
   else return MI355_SW_EINVAL;
+  return 0;
+}
+
+int mi355_sw_prefix_values(mi355_sw_ctx *ctx, float *values, size_t capacity, size_t *n_sub) {
+  if (!ctx || !n_sub) return MI355_SW_EINVAL;
+  OptScope opt_scope_(ctx);
+  const size_t nsub = (size_t)ctx->hook_nsub, nq = ctx->batch.nq;
+  *n_sub = nsub;
+  if (nsub == 0 || !values) return 0;
+  if (capacity < nq * nsub) return fail(ctx, MI355_SW_EINVAL, "mi355_sw_prefix_values: capacity below n_queries * n_sub");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<uint16_t> raw(ctx->hook_ids.size() * nsub);
+  HIPCHK(ctx, hipMemcpy(raw.data(), ctx->submax.p, raw.size() * 2, hipMemcpyDeviceToHost));
+  std::fill(values, values + nq * nsub, -1.0f);
+  for (size_t r = 0; r < ctx->hook_ids.size(); ++r)
+    for (size_t s = 0; s < nsub; ++s) values[(size_t)ctx->hook_ids[r] * nsub + s] = half_value(raw[r * nsub + s]) * kF16Scale;
   return 0;
 }
 

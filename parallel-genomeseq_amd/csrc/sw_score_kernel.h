@@ -320,9 +320,9 @@ template <> struct Cell<kSemF32> : CellF<kSemF32> {
 };
 template <> struct Cell<kSemF32U8> : CellF<kSemF32U8> {};
 
-// The legal instances sw_score_kernel<R, SEM, STRIPS, SL, TWIN, COMB, MK>: the kernel asserts it, and so does the host's table of
+// The legal instances sw_score_kernel<R, SEM, STRIPS, SL, TWIN, COMB, MK, ROWP>: the kernel asserts it, and so does the host's table of
 // compiled instances (host_score.h)
-template <int SEM> __host__ __device__ constexpr bool score_instance_ok(int R, bool STRIPS, int SL, bool TWIN, bool COMB, int MK) {
+template <int SEM> __host__ __device__ constexpr bool score_instance_ok(int R, bool STRIPS, int SL, bool TWIN, bool COMB, int MK, bool ROWP = false) {
   typedef Cell<SEM> C;
   return (SL == 64 || SL == 16 || SL == 8 ||                       // a slot is a whole wavefront, a DPP row or half a DPP row,
           // or a PREFIX tile of 4 or 2 lanes: the first SL*R rows of longer queries on mirrored cells (lemma L19, host_score.h)
@@ -332,7 +332,8 @@ template <int SEM> __host__ __device__ constexpr bool score_instance_ok(int R, b
          (!COMB || (TWIN && !STRIPS)) &&                           // the code-pair profile belongs to the twin instances
          (!C::kMirror || (!TWIN && !STRIPS && SL != 64)) &&        // mirrored cells: two-query 8- or 16-lane tiles, one strip
          // sampled maximum: packed float16 two-query tiles in one strip, or float32 cells (one query per tile)
-         (MK == 1 || (MK == 4 && !TWIN && C::kKeepsHg && (C::kFloat || !STRIPS)));
+         (MK == 1 || (MK == 4 && !TWIN && C::kKeepsHg && (C::kFloat || !STRIPS))) &&
+         (!ROWP || (SL == 2 && C::kMirror && MK == 4));           // the row-P fold belongs to the sampled 2-lane prefix tiles
 }
 // Row stride of the sampled running maximum (lemma L5): a one-strip MK > 1 instance folds, at a folded step, only the rows r of a
 // lane with r % RK == RK - 1, and the lane's last.  A cell holding M passes M - g to the row below it in the same column and step
@@ -361,9 +362,12 @@ __host__ __device__ constexpr int fold_row_stride(int R, int MK) { return MK == 
 // sub-chunk within the slack of the query's final key is re-evaluated exactly (host_pipeline.h), and the cell costs
 // 3 + 1/(2 MK) instead of 3.5 ops.  In one strip the folded step takes only every RK-th row of the lane (fold_row_stride):
 // the same cell also decays by one gap per row down its column, within the lane and within the step.
-template <int R, int SEM, bool STRIPS = false, int SL = 16, bool TWIN = false, bool COMB = false, int MK = 1>
+// ROWP (prefix tiles, MK = 4): the folded step takes row P = SL * R ALONE — the last row of the tile's last lane — and a sub-chunk
+// value is the maximum of that row's cells at the folded steps: within (MK - 1) g of the row's maximum over the sub-chunk's
+// columns, whatever the rows above it hold (DESIGN.md §3.3 L19, row-P variant; host_score.h rowp_slack).
+template <int R, int SEM, bool STRIPS = false, int SL = 16, bool TWIN = false, bool COMB = false, int MK = 1, bool ROWP = false>
 __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
-  static_assert(score_instance_ok<SEM>(R, STRIPS, SL, TWIN, COMB, MK), "no such sw_score_kernel instance (score_instance_ok)");
+  static_assert(score_instance_ok<SEM>(R, STRIPS, SL, TWIN, COMB, MK, ROWP), "no such sw_score_kernel instance (score_instance_ok)");
   constexpr bool HALF = TWIN && !COMB;                             // the profile holds 16-bit entries, two rows per dword
   constexpr int LS = HALF ? lane_stride(R / 2) : lane_stride(R);   // dwords between the profile rows of adjacent lanes
   constexpr int NQ4 = HALF ? (R / 2 + 3) / 4 : (R + 3) / 4;
@@ -604,6 +608,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   uint32_t best_a = C::kPubZero, best_b = best_a;
   auto slot_max = [&]() -> uint32_t {                              // maximum of mx over the slot's lanes
     uint32_t m32 = C::bits(mx);
+    if constexpr (ROWP) { if (ls != SL - 1) m32 = C::kZero; }        // only the last lane's row R - 1 is row P
 #pragma unroll
     for (int off = SL / 2; off >= 1; off >>= 1) {
       const uint32_t o = (uint32_t)__shfl_xor((int)m32, off, SL);
@@ -780,8 +785,10 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
             else w = H[r];
             const T x = C::add(diag, C::from_bits(p[r]), a.clamp2);
             const T h = C::cell_h(x, Hg[r], ng);
-            if ((MK == 1 || (k & (MK - 1)) == MK - 1) &&           // (compile-time per unrolled step and row)
-                (r % RK == RK - 1 || r == R - 1)) {
+            if constexpr (ROWP) {                                  // row P alone: one maximum per folded step
+              if ((k & (MK - 1)) == MK - 1 && r == R - 1) mx = C::vmax(mx, h);
+            } else if ((MK == 1 || (k & (MK - 1)) == MK - 1) &&    // (compile-time per unrolled step and row)
+                       (r % RK == RK - 1 || r == R - 1)) {
               constexpr int NF = (R + RK - 1) / RK;                // folded rows of a lane; this one is number r / RK
               if ((r / RK) & 1) mx = C::vmax3(mx, tpend, h);
               else if (r / RK + 1 < NF) tpend = h;
