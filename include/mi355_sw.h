@@ -316,7 +316,10 @@ int mi355_sw_last_counters(const mi355_sw_ctx *ctx, uint64_t out[4]);
 /* One counter of the last call by name: "requeried", "whole_batch_again", "candidates", "left_window" (= [0..3] above) and
  * "first_settled" — uint8 engine: queries over their candidate cap whose first candidates, evaluated in order, settled them
  * without a second sweep; "saved_locates" / "saved_traces" — finish steps of a lone long query that started from the columns and
- * strip rows its sweep saved, "saved_fallbacks" — those that took the zero-border windows instead; "wait_retries" — launches
+ * strip rows its sweep saved, "saved_fallbacks" — those that took the zero-border windows instead; "walk_widened" — times a
+ * traceback walk reported that its decision window was too small (the greedy walk left what the window makes exact, DESIGN.md
+ * §3.3 L2) and the alignment was run again with four times the column budget: one count per alignment and round;
+ * "wait_retries" — launches
  * repeated on a non-waiting instance after a wait between workgroups expired; "early_settled" — uint8 engine: queries settled
  * from the first and last sub-chunks without a sweep; "beyond_f16" — sequences of a many-small-alignments batch whose maximum lay
  * beyond the packed float16 pass's key range and were redone on float32 cells; "prefix_certified" — float engine, short-read
@@ -339,7 +342,9 @@ int mi355_sw_prefix_values(mi355_sw_ctx *ctx, float *values, size_t capacity, si
 
 /* Which kernels and pipeline decisions the last call used: space-separated tags, each at most once, e.g.
  * "score[cell=f16,SL=8,R=19,...,sampled=1,...] strip[R=3,mode=max,...] wave[orient=0,...,dirs=1,...] walk_wave" — what the parity
- * tests assert a switch of mi355_sw_set_option ENGAGED with.  Valid until the next call on the context; never NULL. */
+ * tests assert a switch of mi355_sw_set_option ENGAGED with.  A call whose single-alignment chain declined after its launches
+ * ("solo[...]") and went on to the general path keeps that tag beside the general path's.  Valid until the next call on the
+ * context; never NULL. */
 const char *mi355_sw_last_path(const mi355_sw_ctx *ctx);
 
 /* Which sw_score_kernel instance swept the most cells in the last call (what the `iterate` of

@@ -345,6 +345,7 @@ struct mi355_sw_ctx {
   std::vector<float> h_aprof;
   std::vector<uint8_t> h_pieces;  // host side of the piece table of the running call (host_batch.h)
   size_t saved_locates = 0, saved_traces = 0, saved_fallbacks = 0;   // finish steps of the running call that started from saved state / fell back
+  size_t walk_widened = 0;        // times a traceback window's budget was multiplied by 4 in the running call (walk status 1)
   DevBuf pkeys, pthr, psel, psel2, qcnt, sel2, gcnt, wlut, ckpt, first, keys, ranges, stab, ftab, ftab_s, htab, htab8, soloblk, flags, submax, lut, probs, dirs, outs_f, outs_i, cons, walkp, hmat, brow, wprobs, scan;
   // host sides of small per-call uploads: they must outlive the asynchronous copies, and the tables are only
   // sent again when they change

@@ -106,7 +106,7 @@ int trace_located(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
       for (size_t t = 0; t < jobs.size(); ++t) {
         const size_t k = owner[t];
         if (st[t] == 0) tout[k] = std::move(outs[t]);
-        else if (st[t] == 1) { budget[k] *= 4; next.push_back(k); }
+        else if (st[t] == 1) { budget[k] *= 4; ctx->walk_widened += 1; next.push_back(k); }
         else return fail(ctx, MI355_SW_ENOTSUP, "consensus longer than |x| + window");
       }
     }
@@ -1441,8 +1441,16 @@ void reset_timings(mi355_sw_ctx *ctx) {
   ctx->last_kernel = mi355_sw_kernel_info{};
   ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
   ctx->hook_ids.clear(); ctx->hook_nsub = 0;
-  ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
+  ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->walk_widened = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
   ctx->path.clear();
+}
+
+// The single-alignment chain (host_solo.h) declined: the call starts over on the general path.  What the declined attempt
+// launched did run, so its tags stay in the call's path (mi355_sw_last_path: "solo[...]" beside the general path's tags).
+void reset_after_decline(mi355_sw_ctx *ctx) {
+  const std::string ran = ctx->path;
+  reset_timings(ctx);
+  ctx->path = ran;
 }
 
 }  // namespace

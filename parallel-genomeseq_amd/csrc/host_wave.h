@@ -591,7 +591,7 @@ int wave_trace(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const
       });
       for (size_t t = 0; t < n; ++t) {                              // the rare ones that need a wider window
         const int st = (int)wo[3 * t + 2];
-        if (st == 1) { budget[owner[t]] *= 4; next.push_back(owner[t]); }
+        if (st == 1) { budget[owner[t]] *= 4; ctx->walk_widened += 1; next.push_back(owner[t]); }
         else if (st != 0) return fail(ctx, MI355_SW_ENOTSUP, "consensus longer than |x| + |y|");
       }
     }

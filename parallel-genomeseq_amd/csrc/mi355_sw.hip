@@ -197,7 +197,7 @@ int mi355_sw_align(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, s
   auto work = [&]() -> int {
     int r = solo_align(ctx, *ref, x, nx, std::vector<Range>{Range{0, (int64_t)ny}}, *params, true, out);
     if (r <= 0) return r;
-    reset_timings(ctx);
+    reset_after_decline(ctx);
     r = upload_queries(ctx, ctx->one, 1, &x, &nx);
     if (!r) r = align_range(ctx, *ref, ctx->one, Range{0, (int64_t)ny}, *params, 0, out);
     return r;
@@ -228,7 +228,7 @@ int mi355_sw_argmax(mi355_sw_ctx *ctx, const char *x, size_t nx, const char *y, 
   auto work = [&]() -> int {
     int r2 = solo_align(ctx, *ref, x, nx, std::vector<Range>{Range{0, (int64_t)ny}}, *params, false, &r);
     if (r2 <= 0) return r2;
-    reset_timings(ctx);
+    reset_after_decline(ctx);
     r2 = upload_queries(ctx, ctx->one, 1, &x, &nx);
     if (!r2) r2 = align_range(ctx, *ref, ctx->one, Range{0, (int64_t)ny}, *params, MI355_SW_SCORE_ONLY, &r);
     return r2;
@@ -306,7 +306,7 @@ int mi355_sw_align_split(mi355_sw_ctx *ctx, const char *x, size_t nx, const char
         out->timings_us[1] = out->timings_us[0];
         return 0;
       }
-      reset_timings(ctx);
+      reset_after_decline(ctx);
     }
     int r = upload_queries(ctx, q, 1, &x, &nx);
     if (r) return r;
@@ -632,6 +632,7 @@ int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *o
   else if (k == "saved_locates") *out = ctx->saved_locates;
   else if (k == "saved_traces") *out = ctx->saved_traces;
   else if (k == "saved_fallbacks") *out = ctx->saved_fallbacks;
+  else if (k == "walk_widened") *out = ctx->walk_widened;
   else return MI355_SW_EINVAL;
   return 0;
 }
