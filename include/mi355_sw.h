@@ -331,13 +331,19 @@ int mi355_sw_last_counters(const mi355_sw_ctx *ctx, uint64_t out[4]);
  * A bucket of at least 512 reads is probed with its first 64, at the next lower prefix height on tiles that fold row P alone; the
  * probe decides the height of the rest.  "no_prefix_low" keeps such a bucket at its own height with the fold over
  * all prefix rows (the A/B).
+ * A probed bucket of at least 1024 reads takes its heights as a chain: the probe runs at the lowest eligible height on tiles that fold
+ * row P at every step (no slack), the rest of the bucket starts at the lowest height the probe's offender count pays for, and the
+ * offenders of that pass take ONE prefix pass at the next height before the sweep of all rows; "prefix_second_pass" counts the reads
+ * that took it.  "no_prefix_cascade" gives such buckets the flow of the smaller ones, "no_prefix_step" keeps the chain on the tiles
+ * that fold every 4th step (both A/Bs).
  * MI355_SW_EINVAL for an unknown name. */
 int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *out);
 
 /* Test hook.  After a mi355_sw_score_ranges call of ONE range under mi355_sw_set_option("prefix_rowp", R) — the bucket of the prefix
  * shape swept by the instance of R rows per lane that folds row P = 2 R alone — the value of every sub-chunk of the range as the tiles
  * published it, in score units: values[q * *n_sub + s] for resident query q, -1 for queries the hook did not sweep.  *n_sub = 0 (and
- * nothing written) when the last call left no such values; values may be NULL to ask for *n_sub alone. */
+ * nothing written) when the last call left no such values; values may be NULL to ask for *n_sub alone.
+ * mi355_sw_set_option("prefix_rowp_step", R) works the same way on the instance that folds row P at every step. */
 int mi355_sw_prefix_values(mi355_sw_ctx *ctx, float *values, size_t capacity, size_t *n_sub);
 
 /* Which kernels and pipeline decisions the last call used: space-separated tags, each at most once, e.g.

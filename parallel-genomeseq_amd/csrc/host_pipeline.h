@@ -507,9 +507,19 @@ float elapsed_us(mi355_sw_ctx *ctx, hipEvent_t a, hipEvent_t b) {
 // stays within the cap.  The second part is a forecast, not a proof: row 2 voteR reads no lower than the row swept here against a
 // random background, so a threshold that drowns here drowns there (10 % substitutions: B0 is about 360, above the bound 342 of
 // R = 19, with a threshold of 18 that most sub-chunks reach).  It only steers the choice of the height; every result stays exact.
+// ask: what a caller wants beyond the pass itself.  step: the tiles fold row P at EVERY step (rowp only) — rowp_slack is then 0, here and in
+// the votes; one vote per height of voteR (votes[k][query id]); B0 (by query id) receives the exact round-1 score of every read of the
+// pass, offenders included; gave_up is set when most of the pass offended and everybody was handed back.
+struct PrefixAsk {
+  bool step = false, second = false;
+  std::vector<int> voteR;
+  std::vector<std::vector<char>> *votes = nullptr;
+  std::vector<float> *B0 = nullptr;
+  bool *gave_up = nullptr;
+};
 int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_params &p,
                   const ScoreTable &table, const Bucket &b, int prefR, bool rowp, std::vector<int64_t> &qchunk, std::vector<int64_t> &qwarm,
-                  std::vector<Located> &loc, std::vector<char> &qdone, std::vector<int> &offenders, int voteR = 0, std::vector<char> *vote = nullptr) {
+                  std::vector<Located> &loc, std::vector<char> &qdone, std::vector<int> &offenders, const PrefixAsk &ask = PrefixAsk()) {
   HostTrace trace_("prefix_bucket");
   const size_t nq = q.nq;
   const int64_t n = rg.hi - rg.lo;
@@ -520,7 +530,7 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   HIPCHK(ctx, hipMemsetAsync(ctx->pkeys.p, 0, nq * 8, ctx->stream));
   // a. the prefix sweep: the instance of prefR rows at kPrefixLanes lanes; keys and sub-chunk values as the sampled sweep writes them
   Bucket pb = b;
-  pb.SL = kPrefixLanes; pb.R = prefR; pb.prefix = true; pb.rowp = rowp;
+  pb.SL = kPrefixLanes; pb.R = prefR; pb.prefix = true; pb.rowp = rowp; pb.step = rowp && ask.step; pb.second = ask.second;
   ScoreIO io;
   io.range_lo = ctx->ranges.as<int64_t>(); io.range_hi = ctx->ranges.as<int64_t>() + 1; io.keys = ctx->pkeys.as<unsigned long long>();
   rc = score_launch(ctx, ref, q, ranges, p, table, pb, &io);
@@ -531,7 +541,8 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   const int P = pb.SL * pb.R;
   const int64_t E = pb.sub_len, nsub = (n + E - 1) / E;                            // sub-chunks that hold columns of the range
   const int64_t stride = ((n + pb.chunk_len - 1) / pb.chunk_len) * (pb.chunk_len / E);   // value row of one read (whole tiles)
-  const float slack = rowp ? rowp_slack(table) : sample_slack(table, pb), smax = (float)table.smax;
+  const float vslack = rowp_slack(table, rowp_mk(ask.step));                       // of a row-P pass on the same kind of tile
+  const float slack = rowp ? vslack : sample_slack(table, pb), smax = (float)table.smax;
   const int64_t W = (int64_t)(b.maxlen - P) + (int64_t)((int64_t)table.smax * (b.maxlen - P) / table.gap);
   const int64_t D = (W + E - 1) / E;
   static_assert(kPrefixLanes - 1 + kScoreMK - 1 <= 63, "a candidate window starts 63 columns in front of its sub-chunk: the lag of a prefix value");
@@ -564,9 +575,11 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     if (!off[id] && !(B0[id] > bound[id])) off[id] = 1;
     if (!off[id]) thr[id] = B0[id] - smax * (float)(q.len[id] - P) - slack;      // (> 0: B0 is above the bound)
     noff += off[id] ? 1 : 0;
+    if (ask.B0) (*ask.B0)[id] = B0[id];
   }
   auto give_up = [&]() {                                                         // most of the bucket offends: the full sweep for all of it
     for (int k = 0; k < b.count; ++k) offenders.push_back(q.order[b.first + k]);
+    if (ask.gave_up) *ask.gave_up = true;
     return 0;
   };
   // one filter launch over the bucket's value rows with per-query thresholds: flags in ctx->flags, their number and the per-query counts
@@ -592,18 +605,19 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     nflag = std::min(nflag, ctx->flag_cap);
     return 0;
   };
-  if (vote) {
-    const int vP = kPrefixLanes * voteR;
+  if (ask.votes) ask.votes->assign(ask.voteR.size(), std::vector<char>(nq, 0));
+  for (size_t v = 0; ask.votes && v < ask.voteR.size(); ++v) {
+    const int vP = kPrefixLanes * ask.voteR[v];
     std::vector<float> vthr(nq, 0.0f);
     for (int k = 0; k < b.count; ++k) {
       const int id = q.order[b.first + k];
-      if (B0[id] > prefix_bound(table, q.len[id], vP, rowp_slack(table), true)) vthr[id] = B0[id] - smax * (float)(q.len[id] - vP) - rowp_slack(table);
+      if (B0[id] > prefix_bound(table, q.len[id], vP, vslack, true)) vthr[id] = B0[id] - smax * (float)(q.len[id] - vP) - vslack;
     }
     rc = run_filter(vthr);
     if (rc) return rc;
     for (int k = 0; k < b.count; ++k) {
       const int id = q.order[b.first + k];
-      (*vote)[id] = vthr[id] > 0.0f && cnt[id] <= qcap;
+      (*ask.votes)[v][id] = vthr[id] > 0.0f && cnt[id] <= qcap;
     }
   }
   if (2 * noff > (size_t)b.count) return give_up();
@@ -649,6 +663,103 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     ctx->prefix_certified += 1;
   }
   return 0;
+}
+
+// A view of the batch that lists only `ids` (same device bytes / offsets / lengths; its own id list, sorted by length, in `sel`) and
+// the bucket that spans it
+int prefix_view(mi355_sw_ctx *ctx, const QueryBatch &q, const std::vector<int> &ids, DevBuf &sel, QueryBatch &qv, const Bucket &like, Bucket &vb) {
+  qv.bytes.alias(q.bytes.p); qv.lens.alias(q.lens.p); qv.offs.alias(q.offs.p); qv.cum.alias(q.cum.p);
+  qv.len = q.len; qv.off = q.off; qv.nq = q.nq; qv.maxlen = q.maxlen;
+  qv.order.assign(ids.begin(), ids.end());
+  std::stable_sort(qv.order.begin(), qv.order.end(), [&](int32_t a, int32_t b2) { return q.len[a] < q.len[b2]; });
+  if (sel.ensure(qv.order.size() * 4 + 16)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(score scratch) failed");
+  HIPCHK(ctx, hipMemcpy(sel.p, qv.order.data(), qv.order.size() * 4, hipMemcpyHostToDevice));
+  qv.sel.alias(sel.p);
+  vb = like;
+  vb.first = 0; vb.count = (int)qv.order.size();
+  return 0;
+}
+
+// The prefix filter of a probed bucket of at least kPrefixChain reads: its heights as a chain (host_score.h prefix_heights), every pass
+// on tiles that fold row P alone — at every step (no slack) unless option no_prefix_step.
+//   probe:  the first kPrefixProbe reads at the LOWEST height h0.  B0 is exact whatever the height; o[0] = the probe's offenders, and
+//           o[i] of a taller height = the reads that height's vote does not certify (prefix_bucket: a forecast on the probe's values);
+//   start:  the lowest height whose offenders pay less at the next height than everybody pays for starting there (prefix_start_height);
+//           none: `failed`, the rest of the bucket skips the filter (prefix_probe_failed);
+//   rest:   the rest of the bucket at the start height, with the probe's offenders that this height's vote certifies (riders);
+//   second: ONE pass at the next height for the offenders of the rest — only those whose B0 is above that height's bound: a read
+//           without a hit does not pay for a pass that cannot certify it — and for the probe's offenders with that height's vote.
+// Whoever offends the second pass, and everybody it was not worth trying on, is an offender of the bucket (swept on all rows).
+int prefix_chain(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_params &p,
+                 const ScoreTable &table, const Bucket &b, std::vector<int64_t> &qchunk, std::vector<int64_t> &qwarm,
+                 std::vector<Located> &loc, std::vector<char> &qdone, std::vector<int> &offenders, bool &failed) {
+  const size_t nq = q.nq;
+  const bool step = !opt().no_prefix_step;
+  const std::vector<int> hs = prefix_heights(table, b, q.len[q.order[b.first]], step);
+  const size_t nh = hs.size();
+  failed = false;
+  Bucket part = b;
+  part.count = kPrefixProbe;
+  std::vector<std::vector<char>> votes;                              // votes[i - 1]: height i
+  std::vector<float> B0(nq, 0.0f);
+  std::vector<int> poff;
+  PrefixAsk ask;
+  ask.step = step; ask.voteR.assign(hs.begin() + 1, hs.end()); ask.votes = &votes; ask.B0 = &B0;
+  int rc = prefix_bucket(ctx, ref, q, rg, p, table, part, hs[0], true, qchunk, qwarm, loc, qdone, poff, ask);
+  if (rc) return rc;
+  std::vector<int> P(nh), o(nh, 0);
+  for (size_t i = 0; i < nh; ++i) P[i] = kPrefixLanes * hs[i];
+  o[0] = (int)poff.size();
+  for (size_t i = 1; i < nh; ++i)
+    for (int k = 0; k < part.count; ++k) o[i] += votes[i - 1][q.order[part.first + k]] ? 0 : 1;
+  const int start = prefix_start_height(P, o);
+  if (start < 0) {
+    offenders.insert(offenders.end(), poff.begin(), poff.end());
+    path_note(ctx, "prefix_probe_failed");
+    failed = true;
+    return 0;
+  }
+  const bool taller = (size_t)start + 1 < nh;                        // there is a height for a second pass
+  std::vector<int> riders, pend;
+  for (int id : poff) {
+    if (start > 0 && votes[start - 1][id]) riders.push_back(id);
+    else if (taller && votes[start][id]) pend.push_back(id);
+    else offenders.push_back(id);
+  }
+  if (riders.empty()) path_note(ctx, "prefix_height[R=%d,start]", hs[start]);
+  else path_note(ctx, "prefix_height[R=%d,start,riders=%zu]", hs[start], riders.size());
+  part.first = b.first + kPrefixProbe; part.count = b.count - kPrefixProbe;
+  std::vector<int> roff;
+  bool gave_up = false;
+  PrefixAsk rask;
+  rask.step = step; rask.B0 = &B0; rask.gave_up = &gave_up;
+  if (riders.empty()) {
+    rc = prefix_bucket(ctx, ref, q, rg, p, table, part, hs[start], true, qchunk, qwarm, loc, qdone, roff, rask);
+  } else {
+    std::vector<int> ids(riders);
+    for (int k = 0; k < part.count; ++k) ids.push_back(q.order[part.first + k]);
+    QueryBatch qv;
+    Bucket vb;
+    rc = prefix_view(ctx, q, ids, ctx->psel2, qv, part, vb);
+    if (!rc) rc = prefix_bucket(ctx, ref, qv, rg, p, table, vb, hs[start], true, qchunk, qwarm, loc, qdone, roff, rask);
+  }
+  if (rc) return rc;
+  // (a pass that gave up handed everybody back: most of the bucket has no hit its prefix could show, at any height)
+  const float slack = rowp_slack(table, rowp_mk(step));
+  for (int id : roff) {
+    if (taller && !gave_up && B0[id] > prefix_bound(table, q.len[id], P[start + 1], slack, true)) pend.push_back(id);
+    else offenders.push_back(id);
+  }
+  if (pend.empty()) return 0;
+  QueryBatch qv;
+  Bucket vb;
+  rc = prefix_view(ctx, q, pend, ctx->psel2, qv, part, vb);
+  if (rc) return rc;
+  path_note(ctx, "prefix_second[R=%d,n=%zu]", hs[start + 1], pend.size());
+  ctx->prefix_second_pass += pend.size();
+  PrefixAsk sask;
+  sask.step = step; sask.second = true;
+  return prefix_bucket(ctx, ref, qv, rg, p, table, vb, hs[start + 1], true, qchunk, qwarm, loc, qdone, offenders, sask);
 }
 
 // All queries of `q` against one range of the reference: argmax cells and traceback views (into buffers the context
@@ -805,6 +916,17 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
         //     failed, as above;
         //   * else the rest runs at the bucket's own R with the row-P fold, and with it the probe's offenders that this height can
         //     certify (the others stay offenders).
+        // A probed bucket of at least kPrefixChain reads takes its heights as a chain, with one taller pass for the offenders of the
+        // height it starts at (prefix_chain; options no_prefix_cascade, no_prefix_low: the flow below, as for the smaller buckets)
+        if (b.count >= kPrefixChain && !opt().no_prefix_cascade && !opt().no_prefix_low) {
+          bool failed = false;
+          int rc = prefix_chain(ctx, ref, q, rg, p, table, b, qchunk, qwarm, loc, qdone, offenders, failed);
+          if (rc) return rc;
+          const int ndone = failed ? kPrefixProbe : b.count;
+          for (int k = 0; k < ndone; ++k) tried[q.order[b.first + k]] = 1;
+          ntried += (size_t)ndone;
+          continue;
+        }
         Bucket part = b;
         int restR = b.R;
         bool rest_rowp = false;
@@ -813,9 +935,12 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
           part.count = kPrefixProbe;
           const int lowR = opt().no_prefix_low ? 0 : prefix_low_R(table, b, q.len[q.order[b.first]]);
           const size_t before = offenders.size();
-          std::vector<char> own_ok(lowR ? nq : 0, 0);                  // could the bucket's own height certify the read?  (prefix_bucket: vote)
-          int rc = prefix_bucket(ctx, ref, q, rg, p, table, part, lowR ? lowR : b.R, lowR != 0, qchunk, qwarm, loc, qdone, offenders, b.R, lowR ? &own_ok : nullptr);
+          std::vector<std::vector<char>> votes;                        // could the bucket's own height certify the read?  (prefix_bucket: vote)
+          PrefixAsk ask;
+          if (lowR) { ask.voteR.push_back(b.R); ask.votes = &votes; }
+          int rc = prefix_bucket(ctx, ref, q, rg, p, table, part, lowR ? lowR : b.R, lowR != 0, qchunk, qwarm, loc, qdone, offenders, ask);
           if (rc) return rc;
+          const std::vector<char> own_ok = lowR ? votes[0] : std::vector<char>();
           for (int k = 0; k < part.count; ++k) tried[q.order[part.first + k]] = 1;
           ntried += (size_t)part.count;
           if (!lowR) {
@@ -861,7 +986,7 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
       if (ntried && (2 * offenders.size() > ntried || (opt().no_requery && !offenders.empty()))) {
         // most reads cannot be certified by their prefix (no hit, or a repeat family over the cap): the sweep decides for everybody
         for (size_t k = 0; k < nq; ++k) if (tried[k]) { loc[k] = Located(); qdone[k] = 0; }
-        ctx->prefix_certified = 0; ctx->prefix_named = false; ctx->candidates = candidates_before;
+        ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_named = false; ctx->candidates = candidates_before;
         ctx->last_kernel.cells = 0; ctx->timings[4] = 0; ctx->timings[5] = 0;
         ctx->whole_again += 1;
         path_note(ctx, "whole_again");
@@ -1309,9 +1434,12 @@ int range_maxima(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     }
     // ... (option prefix_rowp = R, a listed R whose prefix is shorter than the bucket's reads) by the instance of R rows per lane that
     // folds row P = 2 R alone; the value rows stay readable (mi355_sw_prefix_values, tests/test_gpu_prefix_rowp_tiles.py)
-    if (listed(kR8M, opt().prefix_rowp) && nr == 1 && !winner_only && b.fast && b.sem == kSemF16 && b.mirror && !b.strips && !b.twin && !b.satflag &&
-        !b.unsat && b.SL == 8 && b.count >= 2 && kernel_sem(b) == kSemF16M && kPrefixLanes * opt().prefix_rowp < q.len[q.order[b.first]] && ctx->hook_ids.empty()) {
-      b.SL = kPrefixLanes; b.R = (int)opt().prefix_rowp; b.prefix = true; b.sampled = true; b.rowp = true;
+    // (option prefix_rowp_step = R: the instance that folds row P at every step, tests/test_gpu_prefix_step_tiles.py)
+    const bool hook_step = listed(kR8M, opt().prefix_rowp_step);
+    const long hook_R = hook_step ? opt().prefix_rowp_step : opt().prefix_rowp;
+    if (listed(kR8M, hook_R) && nr == 1 && !winner_only && b.fast && b.sem == kSemF16 && b.mirror && !b.strips && !b.twin && !b.satflag &&
+        !b.unsat && b.SL == 8 && b.count >= 2 && kernel_sem(b) == kSemF16M && kPrefixLanes * hook_R < q.len[q.order[b.first]] && ctx->hook_ids.empty()) {
+      b.SL = kPrefixLanes; b.R = (int)hook_R; b.prefix = true; b.sampled = true; b.rowp = true; b.step = hook_step;
       for (int k = 0; k < b.count; ++k) ctx->hook_ids.push_back(q.order[b.first + k]);
     }
   }
@@ -1439,7 +1567,7 @@ void reset_timings(mi355_sw_ctx *ctx) {
   for (double &t : ctx->timings) t = 0;
   ctx->score_ev_used = 0; ctx->arenas.clear(); ctx->cons_used = 0;
   ctx->last_kernel = mi355_sw_kernel_info{};
-  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
+  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
   ctx->hook_ids.clear(); ctx->hook_nsub = 0;
   ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->walk_widened = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
   ctx->path.clear();

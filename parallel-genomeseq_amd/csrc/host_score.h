@@ -44,6 +44,9 @@ struct Bucket {
   bool prefix = false;        // a PREFIX sweep (lemma L19): SL = kPrefixLanes lanes x R rows = the first P rows of queries that are longer;
                               // its sub-chunk values stay in ctx->submax for sw_prefix_filter (host_pipeline.h prefix_bucket), no filter here
   bool rowp = false;          // ... whose tiles fold row P alone (sw_score_kernel ROWP): values within rowp_slack of row P's maximum per sub-chunk
+  bool step = false;          // ... at EVERY step (the MK = 1 instances): the values are row P's maxima, rowp_slack is 0
+  bool second = false;        // ... the taller second pass over the offenders of a lower one (host_pipeline.h prefix_chain): its cells are
+                              // counted, the call's kernel_info keeps describing the pass that swept the bucket
   int64_t warm = 0;           // exactness margin in columns
   bool fast = false;          // swept by the score kernel (else whole-matrix exact path)
   int64_t chunk_len = 0;      // own columns per tile
@@ -92,6 +95,7 @@ constexpr ScoreShapes kScoreShapes[] = {
   {kR64S, std::size(kR64S), true, 64, false, false, 4, 1u << kSemF32},         // a lone long query on float32 cells
   {kR8M, std::size(kR8M), false, kPrefixLanes, false, false, 4, 1u << kSemF16M},   // prefix tiles of the 8-lane shapes (lemma L19)
   {kR8M, std::size(kR8M), false, kPrefixLanes, false, false, 4, 1u << kSemF16M, true},   // ... that fold row P alone
+  {kR8M, std::size(kR8M), false, kPrefixLanes, false, false, 1, 1u << kSemF16M, true},   // ... at every step
 };
 constexpr size_t score_inst_count() {
   size_t n = 0;
@@ -132,7 +136,8 @@ static_assert(score_compiled(kR8M, false, 8, false, false, 4, kCellsSampled | kC
               score_compiled(kR16M, false, 64, false, false, 4, kCellsSampled) && score_compiled(kR64S, true, 64, false, false, 4, 1u << kSemF32),
               "sampled_instance");
 static_assert(score_compiled(kR8M, false, kPrefixLanes, false, false, 4, 1u << kSemF16M) &&
-              score_compiled(kR8M, false, kPrefixLanes, false, false, 4, 1u << kSemF16M, true), "prefix_ok, prefix_low_R");
+              score_compiled(kR8M, false, kPrefixLanes, false, false, 4, 1u << kSemF16M, true) &&
+              score_compiled(kR8M, false, kPrefixLanes, false, false, 1, 1u << kSemF16M, true), "prefix_ok, prefix_low_R, prefix_heights");
 
 typedef void (*ScoreKernel)(const ScoreArgs);
 template <size_t... I> constexpr std::array<ScoreKernel, sizeof...(I)> score_kernels(std::index_sequence<I...>) {
@@ -296,8 +301,10 @@ float sample_slack(const ScoreTable &t, const Bucket &b) {
 }
 
 // The slack of a prefix sweep that folds row P alone (sw_score_kernel ROWP; lemma L19, row-P variant): the last cell of the optimal
-// path in row P is seen at the next folded step of that very row, at most kScoreMK - 1 gaps along it — no row term.
-float rowp_slack(const ScoreTable &t) { return (float)(kScoreMK - 1) * (float)t.gap; }
+// path in row P is seen at the next folded step of that very row, at most mk - 1 gaps along it — no row term.  mk is the instance's
+// fold stride: kScoreMK, or 1 for the tiles that fold at every step (no slack at all).
+float rowp_slack(const ScoreTable &t, int mk = kScoreMK) { return (float)(mk - 1) * (float)t.gap; }
+inline int rowp_mk(bool step) { return step ? 1 : kScoreMK; }
 
 // Mirrored float16 cells (kSemF16M, lemma L14) for a kSemF16 bucket of two-query tiles: every value of the sweep stays within
 // 1024 (smax * maxlen + smax: a cell's value and its diagonal term), where N = 1 - H / 2048 keeps to one float16 binade; 8- and
@@ -471,7 +478,8 @@ double valu_ops_per_cell(const Bucket &b) {
   int cells_per_row = 2;
   // sw_score_kernel's cells that keep H - g: one maximum3 per two folded rows, on a sampled sweep every kScoreMK-th step only
   const int folded = b.sampled ? (R + sample_rows(b) - 1) / sample_rows(b) : R;
-  const double fold = (b.sampled ? 1.0 / kScoreMK : 1.0) * ((folded + 1) / 2);
+  double fold = (b.sampled ? 1.0 / kScoreMK : 1.0) * ((folded + 1) / 2);
+  if (b.prefix && b.rowp && b.step) fold = 1.0;                      // row P alone, at every step: one packed minimum per step
   switch (b.sem) {
     case kSemF32:   per_step = 3.0 * R + (b.longp ? (b.sampled ? 1.0 / kLongMK : 1.0) * ((R + 1) / 2) : fold) + 1 + over; cells_per_row = 1; break;   // add clamp, max3, sub; max3 per two cells
     case kSemF32U8: per_step = 6.0 * R + (R + 1) / 2 + over; cells_per_row = 1; break;          // add, min, max, sub, max, max
@@ -518,10 +526,10 @@ float prefix_bound(const ScoreTable &t, int m, int P, float slack, bool rowp) {
   return rowp ? std::max(b, (float)t.smax * (float)P) : b;
 }
 // ... on R rows per lane (the bucket's own R, or a lower listed one), with either fold
-bool prefix_height_ok(const ScoreTable &t, const Bucket &b, int minlen, int R, bool rowp) {
+bool prefix_height_ok(const ScoreTable &t, const Bucket &b, int minlen, int R, bool rowp, bool step = false) {
   const int P = kPrefixLanes * R;
   if (!listed(kR8M, R) || minlen <= P) return false;
-  return (float)t.smax * (float)minlen > prefix_bound(t, b.maxlen, P, rowp ? rowp_slack(t) : sample_slack(t, b), rowp);
+  return (float)t.smax * (float)minlen > prefix_bound(t, b.maxlen, P, rowp ? rowp_slack(t, rowp_mk(step)) : sample_slack(t, b), rowp);
 }
 bool prefix_ok(const ScoreTable &t, const Bucket &b, int minlen, int64_t n, const mi355_sw_params &p) {
   if (opt().no_prefix || p.semantics != MI355_SW_F32 || !t.integral || t.gap <= 0 || t.smax <= 0) return false;
@@ -536,6 +544,26 @@ int prefix_low_R(const ScoreTable &t, const Bucket &b, int minlen) {
   int low = 0;
   for (int r : kR8M) if (r < b.R && r > low) low = r;
   return low && prefix_height_ok(t, b, minlen, low, true) ? low : 0;
+}
+// The heights a bucket of at least kPrefixChain reads may run at, as a chain (host_pipeline.h prefix_chain): the listed R below the
+// bucket's own that are eligible under the row-P fold, ascending, then the bucket's own.
+constexpr int kPrefixChain = 16 * kPrefixProbe;
+std::vector<int> prefix_heights(const ScoreTable &t, const Bucket &b, int minlen, bool step) {
+  std::vector<int> hs;
+  for (int r : kR8M) if (r < b.R && prefix_height_ok(t, b, minlen, r, true, step)) hs.push_back(r);
+  hs.push_back(b.R);
+  return hs;
+}
+// The height the rest of a chained bucket starts at.  P[i] are the heights' prefix rows; o[i] of the kPrefixProbe probe reads cannot be
+// certified at height i (measured for the probe's own height, forecast for the taller ones).  Starting at height i costs P[i] rows for
+// everybody and P[i+1] more for the offenders, against P[i+1] for everybody one height up: P[i] + f P[i+1] < P[i+1] with f = o / 64
+// biased up by two reads (about one standard deviation at a few per cent), i.e. (o[i] + 2) P[i+1] <= 64 (P[i+1] - P[i]).  The lowest
+// such height wins; the last height is what remains, or nothing (-1) when more than half of the probe is hopeless there too.
+int prefix_start_height(const std::vector<int> &P, const std::vector<int> &o) {
+  const size_t last = P.size() - 1;
+  for (size_t i = 0; i < last; ++i)
+    if ((o[i] + 2) * P[i + 1] <= kPrefixProbe * (P[i + 1] - P[i])) return (int)i;
+  return 2 * o[last] > kPrefixProbe ? -1 : (int)last;
 }
 
 // What a score launch passes that depends on the kernel's cell type
@@ -1021,10 +1049,11 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   HIPCHK(ctx, hipEventRecord(ctx->score_ev[ctx->score_ev_used], ctx->stream));
   char rows_note[16] = "";                                           // sampled launches: the row stride of the fold
   if (b.sampled) std::snprintf(rows_note, sizeof rows_note, ",rows=%d", sample_rows(b));
-  const ScoreInst inst{b.R, sem, b.strips, b.SL, b.twin, b.comb, a.submax_out != nullptr ? kScoreMK : 1, b.prefix && b.rowp};
+  const bool step = b.prefix && b.rowp && b.step;                    // (its values are written all the same: sw_score_kernel ROWP)
+  const ScoreInst inst{b.R, sem, b.strips, b.SL, b.twin, b.comb, a.submax_out != nullptr && !step ? kScoreMK : 1, b.prefix && b.rowp};
   if (launch_score(inst, grid, shmem, ctx->stream, a)) return fail(ctx, MI355_SW_ENOTSUP, "no score kernel instance for this R");
   HIPCHK(ctx, hipGetLastError());
-  if (b.prefix) path_note(ctx, "prefix[SL=%d,R=%d,P=%d%s]", b.SL, b.R, b.SL * b.R, b.rowp ? ",fold=rowP" : "");
+  if (b.prefix) path_note(ctx, "prefix[SL=%d,R=%d,P=%d%s]", b.SL, b.R, b.SL * b.R, step ? ",fold=rowP,step=1" : (b.rowp ? ",fold=rowP" : ""));
   else path_note(ctx, "score[cell=%s,SL=%d,R=%d,strips=%d,twin=%d,comb=%d,sampled=%d%s,satflag=%d,unsat=%d,pow2=%d%s]", cl.cell, b.SL, b.R, (int)b.strips,
             (int)b.twin, (int)b.comb, (int)b.sampled, rows_note, (int)b.satflag, (int)b.unsat, (int)((b.chunk_len & (b.chunk_len - 1)) == 0), cl.tag);
   if (b.sampled && !b.prefix) {
@@ -1064,7 +1093,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   for (int k = 0; k < b.count; ++k)
     for (auto &r : ranges) cells += (double)(b.prefix ? std::min(b.SL * b.R, (int)q.len[q.order[b.first + k]]) : q.len[q.order[b.first + k]]) * (double)(r.hi - r.lo);
   ctx->timings[5] += cells;
-  if (ctx->prefix_named && !b.prefix) ctx->last_kernel.cells += cells;   // (the offenders of a prefix filter: cells actually swept)
+  if (ctx->prefix_named && (!b.prefix || b.second)) ctx->last_kernel.cells += cells;   // (the offenders of a prefix filter: cells actually swept)
   else if (b.prefix || cells > ctx->last_kernel.cells) {
     mi355_sw_kernel_info &ki = ctx->last_kernel;
     if (b.prefix) { cells += ctx->prefix_named ? ki.cells : 0.0; ctx->prefix_named = true; }
@@ -1077,7 +1106,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
                   : b.satflag ? (b.sampled ? " float engine swept saturating at 2048" : " float engine swept saturating at 2048, saturated sub-chunks re-evaluated exactly") : "");
     if (b.sampled && b.rowp) {
       const size_t at = std::strlen(ki.name);
-      std::snprintf(ki.name + at, sizeof ki.name - at, "; maximum of row P folded every 4th step");
+      std::snprintf(ki.name + at, sizeof ki.name - at, b.step ? "; maximum of row P folded every step" : "; maximum of row P folded every 4th step");
     } else if (b.sampled) {
       const size_t at = std::strlen(ki.name);
       std::snprintf(ki.name + at, sizeof ki.name - at, "; maximum folded every 4th step (candidates re-evaluated), row stride %d", sample_rows(b));

@@ -333,7 +333,8 @@ template <int SEM> __host__ __device__ constexpr bool score_instance_ok(int R, b
          (!C::kMirror || (!TWIN && !STRIPS && SL != 64)) &&        // mirrored cells: two-query 8- or 16-lane tiles, one strip
          // sampled maximum: packed float16 two-query tiles in one strip, or float32 cells (one query per tile)
          (MK == 1 || (MK == 4 && !TWIN && C::kKeepsHg && (C::kFloat || !STRIPS))) &&
-         (!ROWP || (SL == 2 && C::kMirror && MK == 4));           // the row-P fold belongs to the sampled 2-lane prefix tiles
+         // the row-P fold belongs to the 2-lane prefix tiles: every 4th step, or every step (the sub-chunk values carry no slack then)
+         (!ROWP || (SL == 2 && C::kMirror && (MK == 4 || MK == 1)));
 }
 // Row stride of the sampled running maximum (lemma L5): a one-strip MK > 1 instance folds, at a folded step, only the rows r of a
 // lane with r % RK == RK - 1, and the lane's last.  A cell holding M passes M - g to the row below it in the same column and step
@@ -365,6 +366,8 @@ __host__ __device__ constexpr int fold_row_stride(int R, int MK) { return MK == 
 // ROWP (prefix tiles, MK = 4): the folded step takes row P = SL * R ALONE — the last row of the tile's last lane — and a sub-chunk
 // value is the maximum of that row's cells at the folded steps: within (MK - 1) g of the row's maximum over the sub-chunk's
 // columns, whatever the rows above it hold (DESIGN.md §3.3 L19, row-P variant; host_score.h rowp_slack).
+// ROWP with MK = 1: row P is folded at EVERY step — one packed minimum more per step — and a sub-chunk value IS the row's maximum
+// over the sub-chunk's columns (shifted by the lane lag): no slack, so the same threshold is met by a prefix two rows lower.
 template <int R, int SEM, bool STRIPS = false, int SL = 16, bool TWIN = false, bool COMB = false, int MK = 1, bool ROWP = false>
 __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
   static_assert(score_instance_ok<SEM>(R, STRIPS, SL, TWIN, COMB, MK, ROWP), "no such sw_score_kernel instance (score_instance_ok)");
@@ -646,7 +649,7 @@ __global__ __launch_bounds__(256) void sw_score_kernel(const ScoreArgs a) {
             if (at < a.flag_cap) a.flag_list[at] = make_uint2((unsigned int)qA, gsub + (unsigned int)subs_per_tile);
           }
         }
-        if (MK > 1 && a.submax_out != nullptr) {
+        if ((MK > 1 || ROWP) && a.submax_out != nullptr) {
           const size_t at = (size_t)(2 * pair) * (size_t)a.submax_stride + (size_t)(chunk * subs_per_tile + sub);
           a.submax_out[at] = (uint16_t)va;
           if (hasB) a.submax_out[at + (size_t)a.submax_stride] = (uint16_t)vb;

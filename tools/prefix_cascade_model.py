@@ -1,0 +1,106 @@
+"""CPU model of the prefix filter's heights (prefix_chain): how many reads of a batch a row-P pass of P rows cannot
+certify, for each listed start height and both folds (slack 0: row P folded at every step; slack (MK - 1) g = 6: every 4th step).
+
+Two parts, numpy only (one maximum.accumulate per matrix row):
+  * background flags: `--prefixes` random `--prefix-len`-letter prefixes against `--bg-len` columns of uniform DNA.  For every
+    P and every x, the sub-chunks (E = 256 columns) whose row-P maximum reaches smax P - x, scaled to the reference length, as a
+    mean per read.  x = deficit + slack with deficit = smax m - B0: the threshold of a read is T = smax P - x;
+  * deficits of a batch: every read of the bench batch (synth.reads_from_ref(dna(3, ref), 4, reads, m)) scored exactly against the
+    window at its origin.
+A read is predicted to offend at (P, slack) when its threshold is not positive above the bound (x >= smax P, or the alignment cannot
+end below row P) or when the expected number of background flags at its x exceeds the per-query cap (64).  Prints ONE JSON line.
+
+    python tools/prefix_cascade_model.py [--bg-len 5000000 --prefixes 10 --ref-len 50000000 --reads 2048 --read-len 150]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SUB = 256
+CAP = 64
+MATCH, MISMATCH, GAP = 3.0, -3.0, 2.0
+HEIGHTS = (11, 12, 13, 14, 16, 19)                                   # rows per lane: P = 2 R (13, 16, 19 are compiled)
+
+
+def rows(x, y, keep):
+    """Rows `keep` (1-based) of the local-alignment matrix of x against y, linear gaps: {row: values by column}."""
+    ys = np.frombuffer(y, dtype=np.uint8) if isinstance(y, bytes) else y
+    n = len(ys)
+    jg = GAP * np.arange(n + 1, dtype=np.float32)
+    prev = np.zeros(n + 1, dtype=np.float32)
+    out = {}
+    for i in range(1, max(keep) + 1):
+        a = np.empty(n + 1, dtype=np.float32)
+        a[0] = 0.0
+        np.maximum(prev[1:] - GAP, prev[:-1] + np.where(ys == x[i - 1], MATCH, MISMATCH).astype(np.float32), out=a[1:])
+        np.maximum(a, 0.0, out=a)
+        prev = np.maximum.accumulate(a + jg) - jg
+        if i in keep:
+            out[i] = prev
+    return out
+
+
+def background(pgs, bg_len, prefixes, prefix_len, scale):
+    """flags[P][x] = mean number of sub-chunks per read whose row-P maximum reaches smax P - x, x = 0 .. smax P, scaled by `scale`."""
+    y = pgs.synth.dna(77, bg_len)
+    nsub = bg_len // SUB
+    flags = {}
+    for k in range(prefixes):
+        x = pgs.synth.dna(7700 + k, prefix_len)
+        got = rows(x, y, {2 * R for R in HEIGHTS if 2 * R <= prefix_len})
+        for P, row in got.items():
+            top = row[1:nsub * SUB + 1].reshape(nsub, SUB).max(axis=1)
+            hist = np.bincount(top.astype(np.int64), minlength=int(MATCH) * P + 1)
+            reach = np.cumsum(hist[::-1])                             # reach[x] = sub-chunks with maximum >= smax P - x
+            flags.setdefault(P, np.zeros(int(MATCH) * P + 1))
+            flags[P] += reach[:int(MATCH) * P + 1] * (scale / prefixes)
+    return flags
+
+
+def deficits(pgs, ref_len, reads, m):
+    ref = pgs.synth.dna(3, ref_len)
+    batch, offs = pgs.synth.reads_from_ref(ref, 4, reads, m)
+    out = np.empty(reads, dtype=np.int64)
+    for k in range(reads):
+        lo, hi = max(0, int(offs[k]) - 32), min(ref_len, int(offs[k]) + m + 48)
+        H = rows(batch[k], ref[lo:hi], set(range(1, m + 1)))
+        out[k] = int(MATCH * m - max(float(r.max()) for r in H.values()))
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--bg-len", type=int, default=5_000_000)
+    ap.add_argument("--prefixes", type=int, default=10)
+    ap.add_argument("--prefix-len", type=int, default=38)
+    ap.add_argument("--ref-len", type=int, default=50_000_000)
+    ap.add_argument("--reads", type=int, default=2048)
+    ap.add_argument("--read-len", type=int, default=150)
+    args = ap.parse_args(argv)
+    import __graft_entry__ as entry
+    pgs = entry._load_package()
+    m = args.read_len
+    flags = background(pgs, args.bg_len, args.prefixes, args.prefix_len, args.ref_len / args.bg_len)
+    d = deficits(pgs, args.ref_len, args.reads, m)
+    line = dict(tool="prefix_cascade_model", bg_len=args.bg_len, prefixes=args.prefixes, ref_len=args.ref_len, reads=args.reads, read_len=m,
+                cap=CAP, flags_per_read={str(P): {str(x): round(float(f[x]), 1) for x in (18, 24, 30, 36, 42) if x < len(f)} for P, f in sorted(flags.items())},
+                deficit_above={str(t): int((d > t).sum()) for t in (12, 20, 26, 30, 36, 42)}, offenders={})
+    for P, f in sorted(flags.items()):
+        for slack in (0, 6):
+            x = d + slack
+            hopeless = (x >= MATCH * P) | (MATCH * m - d <= MATCH * P)
+            over = np.zeros(len(d), dtype=bool)
+            ok = ~hopeless
+            over[ok] = f[np.minimum(x[ok], len(f) - 1)] > CAP
+            line["offenders"]["P=%d,slack=%d" % (P, slack)] = dict(bound=int(hopeless.sum()), cap=int(over.sum()), total=int((hopeless | over).sum()))
+    print(json.dumps(line))
+
+
+if __name__ == "__main__":
+    main()
