@@ -609,7 +609,7 @@ int64_t score_sub_len(int semantics, const Bucket &b) {
 }
 
 int64_t pick_chunk_len(int64_t max_range_len, size_t npairs, int64_t warm, int SL = 16, bool twin = false, int maxlen = 0,
-                       int64_t sub_len = 0, int64_t quant = 0) {
+                       int64_t sub_len = 0, int64_t quant = 0, bool chain_main = false) {
   int64_t cl = 65536;
   while (cl < 8 * warm) cl *= 2;                 // long queries: keep the warm-up redundancy bounded
   // fill the chip: CUs x 32 waves x 4 slots (65 536 tiles on 256 CUs); shrink tiles while they stay >> warm-up
@@ -630,6 +630,16 @@ int64_t pick_chunk_len(int64_t max_range_len, size_t npairs, int64_t warm, int S
                                                                                        // 0.30 ms per 150 bp x 1 Mbp call at 128 columns, 0.33 at 256)
   const double per_wg = 256.0 / SL * (twin ? 2.0 : 1.0);
   while (cl / 2 >= floor_cl && (double)npairs * (double)((max_range_len + cl - 1) / cl) / per_wg < cus) cl /= 2;
+  // chain_main: the pass of a chained prefix bucket that sweeps its bulk (>= kPrefixChain - kPrefixProbe reads on the two-lane tiles
+  // that fold row P at every step, score_launch).  The rule above leaves the bench's (992 read pairs x 50 Mbp, R = 13) with
+  // 65536-column tiles: 5952 workgroups of 128 tiles, 4.65 rounds of the 1280 resident ones (5 per CU), each a fifth of the launch
+  // long — while the last round drains, the SIMDs hold 4.4 wavefronts of 5 on average (SQ_WAVE_CYCLES).  Tiles halve while the
+  // launch has fewer than 8192 tiles per CU and a tile stays >= 32 warm-ups: 16384 columns there, 23 808 workgroups, 18.6 rounds.
+  // Measured on that pass through the hook prefix_rowp_step: 99.6 -> 94.4 ms (32768 columns were not measured on these tiles).
+  // Every other prefix pass — probe, second pass, smaller buckets, the tiles that fold every 4th step — keeps the rule above.
+  if (chain_main)
+    while (cl / 2 >= std::max<int64_t>({32 * warm, 2048, floor_cl}) &&
+           (double)npairs * (double)((max_range_len + cl - 1) / cl) < 8192.0 * cus) cl /= 2;
   // Few workgroups per CU: the launch's duration is (workgroups per CU, rounded UP) x (one tile's sweep), so a tile length
   // that lets the workgroup count land just under a multiple of the 256 CUs beats the power of two next to it
   // (50 Mbp, one 400 bp read: 763 workgroups of 2048-column tiles = 3 per CU, 509 of 3072-column tiles = 2 per CU:
@@ -960,7 +970,8 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     const int64_t cl0 = pick_chunk_len(maxlen, npairs * nr, b.warm, b.SL, b.twin, b.maxlen, b.sub_len, 0);
     while (2 * cl0 / b.sub_len > 64) b.sub_len *= 2;
   }
-  b.chunk_len = pick_chunk_len(maxlen, npairs * nr, b.warm, b.SL, b.twin, b.maxlen, b.sub_len, free_sub ? 64 * kSeg : b.sub_len);
+  const bool chain_main = b.prefix && b.rowp && b.step && !b.second && b.SL == kPrefixLanes && b.count >= kPrefixChain - kPrefixProbe;
+  b.chunk_len = pick_chunk_len(maxlen, npairs * nr, b.warm, b.SL, b.twin, b.maxlen, b.sub_len, free_sub ? 64 * kSeg : b.sub_len, chain_main);
   if (free_sub && b.chunk_len % (64 * kSeg) == 0) b.sub_len = b.chunk_len / 64;
   if (b.strips) while (b.chunk_len / b.sub_len > 64) b.sub_len *= 2;      // the strip-mined instances keep <= 64 sub-chunk maxima in LDS
   if (b.sub_len > b.chunk_len || b.chunk_len % b.sub_len != 0) b.sub_len = b.chunk_len;

@@ -11,6 +11,10 @@ A read is predicted to offend at (P, slack) when its threshold is not positive a
 end below row P) or when the expected number of background flags at its x exceeds the per-query cap (64).  Prints ONE JSON line.
 
     python tools/prefix_cascade_model.py [--bg-len 5000000 --prefixes 10 --ref-len 50000000 --reads 2048 --read-len 150]
+
+--heights takes the prefix rows P to model (default: twice the rows per lane above); with it the line also carries `flows`: the rows
+swept per batch, a full sweep counted as read-len rows, by a chain that starts at P[i] with one second pass at P[j]
+(sw_prefix_kernel's heights: --heights 18,20,22,24,26,28,30,32,38, slack 0).
 """
 import argparse
 import json
@@ -46,14 +50,14 @@ def rows(x, y, keep):
     return out
 
 
-def background(pgs, bg_len, prefixes, prefix_len, scale):
+def background(pgs, bg_len, prefixes, prefix_len, scale, heights=None):
     """flags[P][x] = mean number of sub-chunks per read whose row-P maximum reaches smax P - x, x = 0 .. smax P, scaled by `scale`."""
     y = pgs.synth.dna(77, bg_len)
     nsub = bg_len // SUB
     flags = {}
     for k in range(prefixes):
         x = pgs.synth.dna(7700 + k, prefix_len)
-        got = rows(x, y, {2 * R for R in HEIGHTS if 2 * R <= prefix_len})
+        got = rows(x, y, {P for P in (heights or [2 * R for R in HEIGHTS]) if P <= prefix_len})
         for P, row in got.items():
             top = row[1:nsub * SUB + 1].reshape(nsub, SUB).max(axis=1)
             hist = np.bincount(top.astype(np.int64), minlength=int(MATCH) * P + 1)
@@ -82,11 +86,12 @@ def main(argv=None):
     ap.add_argument("--ref-len", type=int, default=50_000_000)
     ap.add_argument("--reads", type=int, default=2048)
     ap.add_argument("--read-len", type=int, default=150)
+    ap.add_argument("--heights", type=lambda v: [int(t) for t in v.split(",")], default=None, help="prefix rows P to model, comma separated")
     args = ap.parse_args(argv)
     import __graft_entry__ as entry
     pgs = entry._load_package()
     m = args.read_len
-    flags = background(pgs, args.bg_len, args.prefixes, args.prefix_len, args.ref_len / args.bg_len)
+    flags = background(pgs, args.bg_len, args.prefixes, max([args.prefix_len] + (args.heights or [])), args.ref_len / args.bg_len, args.heights)
     d = deficits(pgs, args.ref_len, args.reads, m)
     line = dict(tool="prefix_cascade_model", bg_len=args.bg_len, prefixes=args.prefixes, ref_len=args.ref_len, reads=args.reads, read_len=m,
                 cap=CAP, flags_per_read={str(P): {str(x): round(float(f[x]), 1) for x in (18, 24, 30, 36, 42) if x < len(f)} for P, f in sorted(flags.items())},
@@ -99,6 +104,12 @@ def main(argv=None):
             ok = ~hopeless
             over[ok] = f[np.minimum(x[ok], len(f) - 1)] > CAP
             line["offenders"]["P=%d,slack=%d" % (P, slack)] = dict(bound=int(hopeless.sum()), cap=int(over.sum()), total=int((hopeless | over).sum()))
+    if args.heights:
+        # rows swept by start -> second with slack 0: everybody at P[i], the start's offenders at P[j], the second pass's on all rows
+        off = {P: line["offenders"]["P=%d,slack=0" % P]["total"] for P in sorted(flags)}
+        line["heights"] = sorted(flags)
+        line["flows"] = {"%d->%d" % (a, b): args.reads * a + off[a] * b + off[b] * m for a in sorted(flags) for b in sorted(flags) if a < b}
+        line["flows"].update({"%d" % a: args.reads * a + off[a] * m for a in sorted(flags)})
     print(json.dumps(line))
 
 
