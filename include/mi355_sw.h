@@ -283,6 +283,53 @@ int mi355_sw_affine_pairs_run(mi355_sw_ctx *ctx, size_t npairs, const int32_t *q
 int mi355_sw_affine_pairs_trace(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
                                 const mi355_sw_affine_params *params, mi355_sw_result *outs);
 
+/* ---- lists of pairs, end-to-end mode ("fit", "glocal": a mapper's extension stage that must not clip the read) --------
+ * Every letter of the query x (m rows) is aligned, the flanks of the window y (n columns) are free, and the score may be
+ * negative.  With s = f(x[i], y[j]), o = gap_open, e = gap_extend, o >= e > 0:
+ *
+ *   E(i,j) = max(E(i,j-1) - e, H(i,j-1) - o)
+ *   F(i,j) = max(F(i-1,j) - e, H(i-1,j) - o)
+ *   H(i,j) = max(H(i-1,j-1) + s, E(i,j), F(i,j))                       no zero floor
+ *   H(0,j) = 0, E(0,j) = F(0,j) = -infinity   for j = 0..n             the window's flanks are free
+ *   H(i,0) = F(i,0) = -(o + (i-1) e), E(i,0) = -infinity   for i >= 1  (column 0: the same recurrence with only its F term)
+ *
+ * Score = max over 1 <= j <= n of H(m, j); it may be negative or 0.  end_x = m; end_y = the smallest such j, 1-based and
+ * relative to the window start.  An empty query or an empty window has no alignment: score 0, end 0 / 0, empty strings.
+ *
+ * Traceback: the priorities of the local rule (diagonal over E over F, opening wins a tie with extending).
+ *
+ *   state M at (i,j):  i == 0                         stop
+ *                      j == 0                         go to state F at (i, 0)
+ *                      H(i,j) == H(i-1,j-1) + s       emit (x[i], y[j]), go to M at (i-1, j-1)
+ *                      H(i,j) == E(i,j)               go to state E at (i, j)
+ *                      else                           go to state F at (i, j)
+ *   states E and F: as in the local rule; in column 0 only F moves happen, until row 0.
+ *
+ * So cons_x without its '-' is all of x, reversed, and begin_x = 1; pos = begin_y is the column of the last emitted pair
+ * that carries a letter of y, 0 if there is none; the value of the two strings under (f, o, e) is the score.
+ *
+ * mode: MI355_SW_AFFINE_LOCAL is mi355_sw_affine_pairs_run / _trace themselves (same code path, same bytes, same
+ * mi355_sw_last_path); MI355_SW_AFFINE_END_TO_END is the model above; any other value: MI355_SW_EINVAL.  Arguments, their
+ * checks and their order, ownership of the results, timings, mi355_sw_last_kernel and "the context stays usable after any
+ * error" are those of the two calls above.  Dispatch is theirs as well: the pair kernel for 1..512 rows and 1..2^20 columns
+ * while the score table fits 32 KiB of LDS, the exact kernel (2^26 cells, about 5 600 rows) for every other pair, else
+ * MI355_SW_ENOTSUP; option no_affine_pairs sends every pair to the exact kernel.  End-to-end mode reserves no mantissa bits
+ * and floors nothing, so its admission test is that every value formed is an integer below 2^24 in magnitude — with smin
+ * (smax) the least (greatest) substitution score, both taken with 0:
+ *     2 gap_open + (rows + 1) gap_extend - smin < 2^24     and     smax (rows + 1) + gap_open < 2^24
+ * (H >= -(o + (m-1) e) by the all-F path from row 0; H - o, E, F >= -(2o + m e), and one e lower before their maximum; the
+ * diagonal term >= -(2o + m e) + (smin + o), which the first inequality covers as well; upwards H <= smax m and the table
+ * holds s + o).  A pair outside it goes to the exact kernel, which forms no s + o and holds a pair while
+ * 2 gap_open + (rows + 1) gap_extend < 2^24, gap_open + rows gap_extend - smin < 2^24 and smax (rows + 1) < 2^24; a pair
+ * beyond that is MI355_SW_ENOTSUP.  mi355_sw_last_path: "affine_pair_e2e[R=..]" once per instance of the pair kernel that ran, "affine_exact" and
+ * "affine_trace" as above.  The traceback window: DESIGN.md §3.8, L19. */
+enum { MI355_SW_AFFINE_LOCAL = 0, MI355_SW_AFFINE_END_TO_END = 1 };
+int mi355_sw_affine_pairs_run_mode(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts,
+                                   const int64_t *rights, const mi355_sw_affine_params *params, float *score, int64_t *end_x,
+                                   int64_t *end_y);
+int mi355_sw_affine_pairs_trace_mode(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts,
+                                     const int64_t *rights, const mi355_sw_affine_params *params, mi355_sw_result *outs);
+
 /* Host-only helper: piece ranges [left,right). Returns MI355_SW_ERANGE where the reference asserts. */
 int mi355_sw_make_string_range(int npiece, int64_t shortlen, int64_t longlen, float overlap_ratio,
                                int64_t *lefts, int64_t *rights);

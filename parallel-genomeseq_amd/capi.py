@@ -24,8 +24,10 @@ EXPORTS = [
     "mi355_sw_set_option", "mi355_sw_option_names", "mi355_sw_multi_set_option", "mi355_sw_last_counters", "mi355_sw_last_counter", "mi355_sw_batch_upload_packed", "mi355_sw_best_range", "mi355_sw_last_path",
     "mi355_sw_default_affine_params", "mi355_sw_affine_align", "mi355_sw_affine_batch_run", "mi355_sw_affine_score_ranges",
     "mi355_sw_affine_align_trace", "mi355_sw_affine_batch_trace", "mi355_sw_affine_pairs_run", "mi355_sw_affine_pairs_trace",
-    "mi355_sw_prefix_values",
+    "mi355_sw_prefix_values", "mi355_sw_affine_pairs_run_mode", "mi355_sw_affine_pairs_trace_mode",
 ]
+AFFINE_LOCAL, AFFINE_END_TO_END = 0, 1                 # mode of the affine pairs calls (include/mi355_sw.h)
+AFFINE_MODES = {"local": AFFINE_LOCAL, "end_to_end": AFFINE_END_TO_END}
 MULTI_RCCL = 1
 
 
@@ -147,11 +149,13 @@ def cigar(cons_x, cons_y):
     return "".join(out)
 
 
-def _take_affine(r):
+def _take_affine(r, end_to_end=False):
+    """end_to_end: an alignment exists wherever there is an end cell, whatever the sign of its score."""
     cx = C.string_at(r.cons_x, r.cons_len).decode("latin-1") if r.cons_len else ""
     cy = C.string_at(r.cons_y, r.cons_len).decode("latin-1") if r.cons_len else ""
     ex, score = int(r.end_x), float(r.score)
-    return dict(score=score, end_x=ex, end_y=int(r.end_y), begin_x=(ex + 1 - (len(cx) - cx.count("-"))) if score > 0 else 0,
+    aligned = ex > 0 if end_to_end else score > 0
+    return dict(score=score, end_x=ex, end_y=int(r.end_y), begin_x=(ex + 1 - (len(cx) - cx.count("-"))) if aligned else 0,
                 begin_y=int(r.pos), pos=int(r.pos), cons_x=cx, cons_y=cy, cigar=cigar(cx, cy))
 
 
@@ -408,33 +412,49 @@ class Context:
             raise ValueError("query, lefts and rights must have the same length")
         return q, lo, hi
 
-    def affine_pairs_run(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
+    @staticmethod
+    def _pair_mode(mode):
+        if mode not in AFFINE_MODES:
+            raise ValueError("mode must be one of %s" % ", ".join(repr(k) for k in AFFINE_MODES))
+        return AFFINE_MODES[mode]
+
+    def affine_pairs_run(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None, mode="local"):
         """Pair k = resident query query[k] against the window [lefts[k], rights[k]) of the resident reference, each a stand-alone
         problem (mi355_sw_affine_pairs_run): dict of arrays score, end_x, end_y in the caller's order; end_y is relative to the
-        window start.  query, lefts, rights: numpy int arrays or lists."""
+        window start.  query, lefts, rights: numpy int arrays or lists.  mode="end_to_end" (mi355_sw_affine_pairs_run_mode): the
+        whole query against its window, free flanks of the window, a score of any sign; end_x is the query's length."""
         p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
         q, lo, hi = self._pair_arrays(query, lefts, rights)
         n = len(q)
         score = np.zeros(n, dtype=np.float32)
         ex = np.zeros(n, dtype=np.int64)
         ey = np.zeros(n, dtype=np.int64)
-        self._chk(self._L.mi355_sw_affine_pairs_run(self._ctx, C.c_size_t(n), q.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                    lo.ctypes.data_as(C.POINTER(C.c_int64)), hi.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                    C.byref(p), score.ctypes.data_as(C.POINTER(C.c_float)),
-                                                    ex.ctypes.data_as(C.POINTER(C.c_int64)), ey.ctypes.data_as(C.POINTER(C.c_int64))))
+        args = (C.c_size_t(n), q.ctypes.data_as(C.POINTER(C.c_int32)), lo.ctypes.data_as(C.POINTER(C.c_int64)),
+                hi.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p), score.ctypes.data_as(C.POINTER(C.c_float)),
+                ex.ctypes.data_as(C.POINTER(C.c_int64)), ey.ctypes.data_as(C.POINTER(C.c_int64)))
+        m = self._pair_mode(mode)
+        if m == AFFINE_LOCAL:
+            self._chk(self._L.mi355_sw_affine_pairs_run(self._ctx, *args))
+        else:
+            self._chk(self._L.mi355_sw_affine_pairs_run_mode(self._ctx, C.c_int(m), *args))
         return dict(score=score, end_x=ex, end_y=ey)
 
-    def affine_pairs_trace(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None):
+    def affine_pairs_trace(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None, mode="local"):
         """affine_pairs_run with the traceback (mi355_sw_affine_pairs_trace): the dict shape of affine_batch_trace, one entry per pair;
-        begin_y / pos are relative to the window start."""
+        begin_y / pos are relative to the window start.  mode="end_to_end" (mi355_sw_affine_pairs_trace_mode): begin_x is 1 for
+        every pair that has an alignment, whatever the sign of its score."""
         p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
         q, lo, hi = self._pair_arrays(query, lefts, rights)
         n = len(q)
         res = (Result * max(1, n))()
-        self._chk(self._L.mi355_sw_affine_pairs_trace(self._ctx, C.c_size_t(n), q.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                      lo.ctypes.data_as(C.POINTER(C.c_int64)), hi.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                      C.byref(p), res))
-        rows = [_take_affine(res[k]) for k in range(n)]
+        args = (C.c_size_t(n), q.ctypes.data_as(C.POINTER(C.c_int32)), lo.ctypes.data_as(C.POINTER(C.c_int64)),
+                hi.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p), res)
+        m = self._pair_mode(mode)
+        if m == AFFINE_LOCAL:
+            self._chk(self._L.mi355_sw_affine_pairs_trace(self._ctx, *args))
+        else:
+            self._chk(self._L.mi355_sw_affine_pairs_trace_mode(self._ctx, C.c_int(m), *args))
+        rows = [_take_affine(res[k], m == AFFINE_END_TO_END) for k in range(n)]
         self._L.mi355_sw_free_results(res, C.c_size_t(n))
         out = dict(score=np.array([r["score"] for r in rows], dtype=np.float32))
         for k in ("end_x", "end_y", "begin_x", "begin_y", "pos"):

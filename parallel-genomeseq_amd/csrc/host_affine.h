@@ -1,7 +1,8 @@
 // host_affine.h — affine-gap score, end cell and traceback: parameter checks, the sw_affine_kernel sweep, the
 // sw_affine_exact_kernel behind it, sw_affine_trace_kernel (sw_affine_kernel.h) and, for references (ranges) of
 // at most 512 letters, sw_affine_prof_kernel (sw_affine_prof_kernel.h); for lists of (query, window) pairs, sw_affine_pair_kernel
-// (sw_affine_pair_kernel.h).  The drivers affine_run (affine_prof_run, affine_sweep) and affine_pairs (affine_pair_stage) share one
+// (sw_affine_pair_kernel.h; end-to-end mode of the pairs calls: sw_affine_pair_e2e_kernel and the E2E instances of the exact and the
+// trace kernel, AffineCall::mode).  The drivers affine_run (affine_prof_run, affine_sweep) and affine_pairs (affine_pair_stage) share one
 // AffineCall (affine_begin .. affine_end) and one affine_note_kernel, affine_exact_stage, affine_download and affine_class_table.
 // Part of the single translation unit mi355_sw.hip (included there, in order; not a standalone header).
 namespace {
@@ -16,6 +17,7 @@ struct AffineTable {
   std::vector<uint16_t> htab;     // [256][ncodes] float16 bits of s / 2048, scores below -2048 raised to it (the clamped
                                   // diagonal term is 0 either way: H <= 2040); pad column last
   int smax = 0, open = 0, ext = 0;
+  int smin = 0;                   // the least substitution score (end-to-end mode: the low end of the diagonal term)
 };
 
 int affine_check(mi355_sw_ctx *ctx, const mi355_sw_affine_params *p) {
@@ -52,7 +54,7 @@ int affine_table(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_affine_pa
   if (p.gap_open > 16777216.0f) return fail(ctx, MI355_SW_ENOTSUP, "affine scoring: gap_open beyond 2^24");
   t.open = (int)p.gap_open; t.ext = (int)p.gap_extend;
   t.htab.assign((size_t)256 * nc, half_bits(-8.0f));
-  float smax = 0;
+  float smax = 0, smin = 0;
   for (int a = 0; a < 256; ++a)
     for (int c = 0; c < nc - 1; ++c) {
       const float s = affine_score(ref, p, a, c);
@@ -60,9 +62,11 @@ int affine_table(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_affine_pa
       if (s != std::floor(s)) return fail(ctx, MI355_SW_ENOTSUP, "affine scoring: substitution scores must be integers");
       if (std::fabs(s) > 1.0e6f) return fail(ctx, MI355_SW_ENOTSUP, "affine scoring: substitution score beyond +-10^6");
       smax = std::max(smax, s);
+      smin = std::min(smin, s);
       t.htab[(size_t)a * nc + c] = half_bits(std::min(2048.0f, std::max(-2048.0f, s)) / kF16Scale);
     }
   t.smax = (int)smax;
+  t.smin = (int)smin;
   return 0;
 }
 
@@ -72,13 +76,28 @@ struct AffineCall {
   const RefData &ref; const QueryBatch &q;   // the reference and the batch it runs on
   const mi355_sw_affine_params &p;
   AffineTable t;
+  int mode = MI355_SW_AFFINE_LOCAL;          // pairs calls: MI355_SW_AFFINE_END_TO_END (no floor, row m wins; include/mi355_sw.h)
+  bool e2e() const { return mode == MI355_SW_AFFINE_END_TO_END; }
 };
+
+// End-to-end mode: are all values of a problem of m rows integers below 2^24 in magnitude (exact in float32, no bit reserved)?
+// H >= -(o + (m-1) e) by the all-F path from the free row 0, so Ho, E, F >= -(2o + m e), E - e and F - e one e lower, and the
+// diagonal term H + s >= -(o + (m-1) e) + smin; upwards H <= smax m.  (t.smin <= 0 <= t.smax.)
+// The pair kernel also forms the table's s + o in [smin + o, smax + o] and the diagonal term as Ho + (s + o); one inequality covers
+// its low side, 2o + (m+1) e - smin < 2^24.  The exact kernel forms neither: each of its values has its own inequality.
+bool affine_e2e_exact(const AffineTable &t, double m) {
+  const double low = 2.0 * t.open + (m + 1.0) * t.ext - t.smin, high = (double)t.smax * (m + 1.0) + t.open;
+  return low < 16777216.0 && high < 16777216.0;
+}
+bool affine_e2e_whole_exact(const AffineTable &t, double m) {
+  return 2.0 * t.open + (m + 1.0) * t.ext < 16777216.0 && t.open + m * t.ext - t.smin < 16777216.0 && (double)t.smax * (m + 1.0) < 16777216.0;
+}
 
 // Opens the call: fills c.t and starts the call's interval (ev[4]).  0: go on; 1: nothing to do, the caller's zeroed outputs
 // stand; negative: the error.
 int affine_begin(AffineCall &c) {
   { int rc = affine_table(c.ctx, c.ref, c.p, c.t); if (rc) return rc; }
-  if (c.t.smax <= 0) return 1;                                     // no positive cell: every maximum is 0
+  if (c.t.smax <= 0 && !c.e2e()) return 1;                         // no positive cell: every maximum is 0 (end-to-end: no floor)
   HIPCHK(c.ctx, hipEventRecord(c.ctx->ev[4], c.ctx->stream));
   return 0;
 }
@@ -142,7 +161,8 @@ int run_affine_exact(const AffineCall &c, std::vector<ExactJob> &jobs, size_t lo
   HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactProblem), hipMemcpyHostToDevice, ctx->stream));
   AffineScoring sc;
   { int rc = affine_scoring(ctx, c.p, sc); if (rc) return rc; }
-  launch_dyn_lds(&sw_affine_exact_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactProblem>(), sc);
+  launch_dyn_lds(c.e2e() ? &sw_affine_exact_kernel<true> : &sw_affine_exact_kernel<false>, dim3((unsigned)n), dim3(64), lds, ctx->stream,
+                 ctx->probs.as<ExactProblem>(), sc);
   HIPCHK(ctx, hipGetLastError());
   std::vector<float> bf(n);
   std::vector<int64_t> ci(2 * n);
@@ -158,6 +178,7 @@ int run_affine_exact(const AffineCall &c, std::vector<ExactJob> &jobs, size_t lo
 bool affine_whole_job(const AffineCall &c, int q, int64_t lo, int64_t n, size_t index, ExactJob &j) {
   const double m = (double)c.q.len[q];
   if (m * (double)n > kAffineExactCellsMax || (double)c.t.smax * (m + 1.0) >= 16777216.0) return false;
+  if (c.e2e() && !affine_e2e_whole_exact(c.t, m)) return false;
   j.q = q; j.ylo = lo; j.nw = (int32_t)n; j.col_offset = 0; j.full_n = n; j.own_lo = 1; j.quirk = 0;
   j.target = -1.0f; j.want_dirs = false; j.index = index;
   return true;
@@ -267,10 +288,12 @@ struct AffineProfPlan {
 };
 
 // the classes alone (sw_affine_prof_kernel and sw_affine_pair_kernel)
-void affine_byte_classes(const RefData &ref, const mi355_sw_affine_params &p, const AffineTable &t, AffineProfPlan &plan) {
+// (open_bound: the key's five bits need gap_open < 2^18; the end-to-end pair instance has no key: affine_e2e_exact bounds gap_open)
+void affine_byte_classes(const RefData &ref, const mi355_sw_affine_params &p, const AffineTable &t, AffineProfPlan &plan,
+                         double open_bound = kAffineProfBound) {
   plan.ok = false;
   const int nl = ref.ncodes - 1;
-  if (nl < 1 || nl > 255 || (double)t.open >= kAffineProfBound) return;
+  if (nl < 1 || nl > 255 || (double)t.open >= open_bound) return;
   plan.rep.clear();
   for (int a = 0; a < 256; ++a) {
     int c = 0;
@@ -303,6 +326,7 @@ bool affine_prof_range_ok(const AffineProfPlan &plan, const AffineTable &t, int6
 // The class table of sw_affine_prof_kernel / sw_affine_pair_kernel for cells of at most `side` + 1 steps of smax, built and sent to
 // ctx->aprof: tab_floats floats, (s + o) 2^-k of class cl against letter l at [cl * cstride + l * lstride] and kPadScoreF elsewhere,
 // then plan.cls.  Sets `tab` and sa's cls, open_s, ext_s, unscale.  `nomem`: the caller's ENOMEM message.
+// (End-to-end mode has no clamp, so the scale decides nothing there: a power of two moves no mantissa bit.  It stays the same one.)
 template <class Args>
 int affine_class_table(const AffineCall &c, const AffineProfPlan &plan, int64_t side, size_t tab_floats, size_t cstride, size_t lstride,
                        const char *nomem, const float *&tab, Args &sa) {
@@ -412,16 +436,17 @@ int affine_trace(const AffineCall &c, const std::vector<AffineTraceItem> &items,
   std::vector<Job> jobs;
   for (size_t k = 0; k < items.size(); ++k) {
     const float score = items[k].score;
-    if (!(score > 0)) continue;
     const int64_t ex = items[k].ex, ey = items[k].ey;
-    const double spare = std::max(0.0, (double)t.smax * (double)ex - (double)score);
+    // end-to-end: every pair with an end cell (a non-empty query and window), whatever the sign of its score
+    if (c.e2e() ? ex < 1 || ey < 1 : !(score > 0)) continue;
+    const double spare = std::max(0.0, (double)t.smax * (double)ex - (double)score);   // (t.smax is max(smax, 0))
     const double W = (double)ex + std::ceil(spare / (double)t.ext) + 2.0;
     // lemma L18, the mirror image of L17: at most end_y diagonal or horizontal steps, hence at most (smax end_y - score) / e rows of gaps
     const double spare_r = std::max(0.0, (double)t.smax * (double)ey - (double)score);
     const double Wr = (double)ey + std::ceil(spare_r / (double)t.ext) + 2.0;
     Job j;
     j.item = k;
-    j.row_clamped = Wr >= (double)ex;
+    j.row_clamped = c.e2e() || Wr >= (double)ex;                    // end-to-end (L19): all m rows belong to the alignment, no row window
     const int64_t mw = j.row_clamped ? ex : (int64_t)Wr;
     j.row_lo = ex - mw;
     j.clamped = W >= (double)ey;
@@ -484,7 +509,8 @@ int affine_trace(const AffineCall &c, const std::vector<AffineTraceItem> &items,
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr.data(), n * sizeof(AffineTraceProblem), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-    launch_dyn_lds(&sw_affine_trace_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<AffineTraceProblem>(), sc);
+    launch_dyn_lds(c.e2e() ? &sw_affine_trace_kernel<true> : &sw_affine_trace_kernel<false>, dim3((unsigned)n), dim3(64), lds, ctx->stream,
+                   ctx->wprobs.as<AffineTraceProblem>(), sc);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     std::vector<int64_t> wo(3 * n);
@@ -753,15 +779,26 @@ int affine_pair_stage(const AffineCall &c, const int32_t *qid, const int64_t *le
       double cells = 0;
       while (i1 < np && affine_pair_R(pr[i1].m) == R) { cells += (double)pr[i1].m * (double)pr[i1].n; ++i1; }
       AffinePairKernel kern = nullptr;
-      with_listed_R<kPairR>(R, [&](auto r) { kern = &sw_affine_pair_kernel<decltype(r)::value>; });
+      with_listed_R<kPairR>(R, [&](auto r) {
+        kern = c.e2e() ? &sw_affine_pair_e2e_kernel<decltype(r)::value> : &sw_affine_pair_kernel<decltype(r)::value>;
+      });
       if (!kern) return fail(ctx, MI355_SW_ENODEV, "internal: no sw_affine_pair_kernel instance for this query");
       sa.best = ctx->outs_f.as<float>() + i0;
       sa.cell = ctx->outs_i.as<int64_t>() + 2 * i0;
       launch_dyn_lds(kern, dim3((unsigned)((i1 - i0 + 15) / 16)), dim3(256), tab_floats * 4, ctx->stream,
                      ctx->wprobs.as<AffinePairProblem>() + i0, (int)(i1 - i0), sa);
       HIPCHK(ctx, hipGetLastError());
-      path_note(ctx, "affine_pair[R=%d]", R);
       ctx->timings[4] += 1;
+      if (c.e2e()) {
+        // per step and lane: seven ops, the table address' v_add and the winner row's select per cell, and eleven of overhead (the
+        // local instance's twelve without the key's v_or); no key, no maximum3 fold.  The 16 border steps of a slot are not counted
+        path_note(ctx, "affine_pair_e2e[R=%d]", R);
+        affine_note_kernel(ctx, cells, MI355_SW_CELL_F32, 16, R, pr[i0].n, pr[i0].n, 0, (9.0 * R + 11.0) / (double)R,
+                           "sw_affine_pair_e2e_kernel<R=%d>", R);
+        i0 = i1;
+        continue;
+      }
+      path_note(ctx, "affine_pair[R=%d]", R);
       // per step and lane: seven ops, the table address' v_add and the key's v_or per cell, a maximum3 per two cells for the
       // step's best key, and twelve of overhead as compiled (two DPP moves and their two copies, the row pointer's multiply
       // and add, the column, the code's address, and compare, two selects and the v_or of the value-only key update)
@@ -773,7 +810,7 @@ int affine_pair_stage(const AffineCall &c, const int32_t *qid, const int64_t *le
     rc = affine_download(ctx, np, nomem, h_best, h_cell); if (rc) return rc;
     for (size_t i = 0; i < np; ++i) {
       const uint32_t id = fast[g0 + i];
-      if (!(h_best[i] > 0)) continue;
+      if (!c.e2e() && !(h_best[i] > 0)) continue;
       score[id] = h_best[i]; ends[2 * (size_t)id] = h_cell[2 * i]; ends[2 * (size_t)id + 1] = h_cell[2 * i + 1];
     }
   }
@@ -784,17 +821,20 @@ int affine_pair_stage(const AffineCall &c, const int32_t *qid, const int64_t *le
 // zero borders.  score[npairs]; ends[npairs][2] = row, column relative to the window start; tout (may be null): the traceback of
 // every pair (affine_trace).  A pair of 1..512 rows and 1..2^20 columns under the bounds of the header takes sw_affine_pair_kernel,
 // every other one is a whole problem of the exact kernel; results come back in the caller's order.
-int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, size_t npairs, const int32_t *qid, const int64_t *lefts,
+// mode MI355_SW_AFFINE_END_TO_END: the end-to-end model of the header on the E2E instances of the same kernels; the pair kernel's
+// bounds are then those of affine_e2e_exact, and only an empty query or an empty window leaves the zeros (a score may be <= 0).
+int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, int mode, size_t npairs, const int32_t *qid, const int64_t *lefts,
                  const int64_t *rights, const mi355_sw_affine_params &p, float *score, int64_t *ends, std::vector<TraceOut> *tout) {
   for (size_t k = 0; k < npairs; ++k) { score[k] = 0.0f; ends[2 * k] = 0; ends[2 * k + 1] = 0; }
   if (tout) tout->assign(npairs, TraceOut());
-  AffineCall c{ctx, ref, q, p, AffineTable()};
+  AffineCall c{ctx, ref, q, p, AffineTable(), mode};
   int rc = affine_begin(c);
   if (rc) return rc > 0 ? 0 : rc;
+  const double open_bound = c.e2e() ? 16777216.0 : kAffineProfBound;
   AffineProfPlan plan;
   if (!opt().no_affine_pairs) {
-    affine_byte_classes(ref, p, c.t, plan);
-    if (!plan.ok && ref.ncodes >= 2 && ref.ncodes <= 256 && (double)c.t.open < kAffineProfBound) {
+    affine_byte_classes(ref, p, c.t, plan, open_bound);
+    if (!plan.ok && ref.ncodes >= 2 && ref.ncodes <= 256 && (double)c.t.open < open_bound) {
       // a table that scores all 256 bytes differently: every byte is its own class
       plan.rep.resize(256);
       for (int a = 0; a < 256; ++a) { plan.cls[a] = (uint8_t)a; plan.rep[a] = a; }
@@ -813,16 +853,19 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, siz
     const int m = q.len[qid[k]];
     const int64_t n = rights[k] - lefts[k];
     if (m < 1 || n < 1) continue;
-    if (table_ok && m <= kMaxRowsFast && n <= kAffinePairColsMax && (double)c.t.smax * ((double)m + 1.0) < kAffineProfBound) {
+    const bool exact_f32 = c.e2e() ? affine_e2e_exact(c.t, (double)m) : (double)c.t.smax * ((double)m + 1.0) < kAffineProfBound;
+    if (table_ok && m <= kMaxRowsFast && n <= kAffinePairColsMax && exact_f32) {
       fast.push_back((uint32_t)k);
       mmax = std::max(mmax, m);
       continue;
     }
     ExactJob j;
     if (!affine_whole_job(c, qid[k], lefts[k], n, k, j)) {
-      char msg[240];
+      char msg[360];
       std::snprintf(msg, sizeof msg, "affine pairs: pair %zu (%d rows x %lld columns) is outside the pair kernel (1..512 rows, 1..2^20 columns, "
-                    "smax * (rows + 1) < 2^18, gap_open < 2^18) and has more than 2^26 cells for the exact kernel", k, m, (long long)n);
+                    "%s) and has more than 2^26 cells for the exact kernel", k, m, (long long)n,
+                    c.e2e() ? "end-to-end: 2 gap_open + (rows + 1) gap_extend - min(smin, 0) < 2^24, smax * (rows + 1) + gap_open < 2^24"
+                            : "smax * (rows + 1) < 2^18, gap_open < 2^18");
       return fail(ctx, MI355_SW_ENOTSUP, msg);
     }
     if (affine_exact_lds(m) > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine pairs: query longer than the exact kernel's LDS diagonals hold");
@@ -834,7 +877,7 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, siz
   if (!rc) rc = affine_exact_stage(c, jobs);
   if (rc) return rc;
   for (const ExactJob &j : jobs) {
-    if (!(j.best > 0)) continue;
+    if (!c.e2e() && !(j.best > 0)) continue;
     score[j.index] = j.best; ends[2 * j.index] = j.ci; ends[2 * j.index + 1] = j.cj;
   }
   std::vector<AffineTraceItem> items(tout ? npairs : 0);

@@ -470,11 +470,13 @@ int mi355_sw_affine_score_ranges(mi355_sw_ctx *ctx, size_t nranges, const int64_
 }
 
 // mi355_sw_affine_pairs_run (score, end_x, end_y) and, with `trace`, mi355_sw_affine_pairs_trace (outs), written only after success
-static int affine_pairs_any(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
+// (and their _mode twins: MI355_SW_AFFINE_LOCAL is the same call)
+static int affine_pairs_any(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
                             const mi355_sw_affine_params *params, bool trace, float *score, int64_t *end_x, int64_t *end_y, mi355_sw_result *outs) {
   OptScope opt_scope_(ctx);
   int rc = affine_check(ctx, params);
   if (rc) return rc;
+  if (mode != MI355_SW_AFFINE_LOCAL && mode != MI355_SW_AFFINE_END_TO_END) return fail(ctx, MI355_SW_EINVAL, "affine pairs: no such mode");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   reset_timings(ctx);
   if (npairs == 0) return 0;
@@ -487,21 +489,36 @@ static int affine_pairs_any(mi355_sw_ctx *ctx, size_t npairs, const int32_t *que
   std::vector<float> sc(npairs, 0.0f);
   std::vector<int64_t> ends(2 * npairs, 0);
   std::vector<TraceOut> tout(trace ? npairs : 0);
-  rc = affine_pairs(ctx, ctx->ref, ctx->batch, npairs, query, lefts, rights, *params, sc.data(), ends.data(), trace ? &tout : nullptr);
+  rc = affine_pairs(ctx, ctx->ref, ctx->batch, mode, npairs, query, lefts, rights, *params, sc.data(), ends.data(), trace ? &tout : nullptr);
   if (rc) return rc;
-  if (trace) { memset(outs, 0, npairs * sizeof *outs); affine_results(ctx, npairs, sc.data(), ends.data(), tout, outs); }
+  if (trace) {
+    memset(outs, 0, npairs * sizeof *outs);
+    affine_results(ctx, npairs, sc.data(), ends.data(), tout, outs);
+    // end-to-end: the end cell stands whatever the sign of the score (set_result keeps it for positive scores only)
+    if (mode == MI355_SW_AFFINE_END_TO_END) for (size_t k = 0; k < npairs; ++k) { outs[k].end_x = ends[2 * k]; outs[k].end_y = ends[2 * k + 1]; }
+  }
   else for (size_t k = 0; k < npairs; ++k) { score[k] = sc[k]; end_x[k] = ends[2 * k]; end_y[k] = ends[2 * k + 1]; }
   return 0;
 }
 
 int mi355_sw_affine_pairs_run(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
                               const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y) {
-  return affine_pairs_any(ctx, npairs, query, lefts, rights, params, false, score, end_x, end_y, nullptr);
+  return affine_pairs_any(ctx, MI355_SW_AFFINE_LOCAL, npairs, query, lefts, rights, params, false, score, end_x, end_y, nullptr);
 }
 
 int mi355_sw_affine_pairs_trace(mi355_sw_ctx *ctx, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
                                 const mi355_sw_affine_params *params, mi355_sw_result *outs) {
-  return affine_pairs_any(ctx, npairs, query, lefts, rights, params, true, nullptr, nullptr, nullptr, outs);
+  return affine_pairs_any(ctx, MI355_SW_AFFINE_LOCAL, npairs, query, lefts, rights, params, true, nullptr, nullptr, nullptr, outs);
+}
+
+int mi355_sw_affine_pairs_run_mode(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
+                                   const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y) {
+  return affine_pairs_any(ctx, mode, npairs, query, lefts, rights, params, false, score, end_x, end_y, nullptr);
+}
+
+int mi355_sw_affine_pairs_trace_mode(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
+                                     const mi355_sw_affine_params *params, mi355_sw_result *outs) {
+  return affine_pairs_any(ctx, mode, npairs, query, lefts, rights, params, true, nullptr, nullptr, nullptr, outs);
 }
 
 int mi355_sw_best_range(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,

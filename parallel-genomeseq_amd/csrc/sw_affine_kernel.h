@@ -238,8 +238,10 @@ enum : int { kAffStop = 0, kAffDiag = 1, kAffE = 2, kAffF = 3, kAffEExt = 4, kAf
 // indexed by the row: cell (i, jl) of diagonal d = i + jl sits at index i.  A wavefront executes its LDS operations in order,
 // so no barrier is needed between diagonals.  TRACE: every cell also stores its decision byte to P.dirs and nothing competes
 // for the maximum; the value of the corner cell (m, nw) comes back in `best` of every lane.
+// E2E: the end-to-end model of include/mi355_sw.h — no floor, column 0 holds H = F = -(o + (i-1) e) and E = -inf (row 0 stays 0),
+// only row m competes and the first column wins (own_lo as before); a decision byte never holds kAffStop.
 struct AffineBest { float best; int64_t i, j; };
-template <bool TRACE>
+template <bool TRACE, bool E2E = false>
 __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, const AffineScoring sc, uint8_t *smem_raw) {
   const int lane = threadIdx.x;
   const int m = P.m, nw = P.nw;
@@ -252,8 +254,9 @@ __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, co
   for (int k = lane; k < 3 * plen; k += 64) Hb[k] = 0.0f;
   for (int k = lane; k < 4 * plen; k += 64) E0[k] = ninf;
   for (int k = lane; k < m; k += 64) xs[k] = P.x[k];
+  if (E2E && lane == 0 && m >= 1) { H0[1] = -sc.gap_open; F0[1] = -sc.gap_open; }   // diagonal 1: cell (1, 0)
 
-  float best = -1.0f;
+  float best = E2E ? ninf : -1.0f;
   unsigned long long bkey = ~0ull;
   int64_t bi = 0, bj = 0;
   const float go = sc.gap_open, ge = sc.gap_extend;
@@ -268,7 +271,10 @@ __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, co
     // border cells of this diagonal: row 0 (index 0) and column 0 (index d)
     if (lane == 0) {
       Hc[0] = 0.0f; Fc[0] = ninf; Ec[0] = ninf;
-      if (d <= m) { Hc[d] = 0.0f; Ec[d] = ninf; Fc[d] = ninf; }
+      if (d <= m) {
+        const float b0 = E2E ? -(sc.gap_open + (float)(d - 1) * sc.gap_extend) : 0.0f;   // (integers below 2^24: exact)
+        Hc[d] = b0; Ec[d] = ninf; Fc[d] = E2E ? b0 : ninf;
+      }
     }
     const int ilo = d - nw > 1 ? d - nw : 1;
     const int ihi = d - 1 < m ? d - 1 : m;
@@ -280,12 +286,15 @@ __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, co
       const float e = fmaxf(Ep[i] - ge, eo);
       const float f = fmaxf(Fp[i - 1] - ge, fo);
       const float x = Hpp[i - 1] + s;
-      const float h = fmaxf(fmaxf(x, 0.0f), fmaxf(e, f));
+      const float h = E2E ? fmaxf(x, fmaxf(e, f)) : fmaxf(fmaxf(x, 0.0f), fmaxf(e, f));
       Hc[i] = h; Ec[i] = e; Fc[i] = f;
       if (TRACE) {
-        const int src = h == 0.0f ? kAffStop : h == x ? kAffDiag : h == e ? kAffE : kAffF;
+        const int src = (!E2E && h == 0.0f) ? kAffStop : h == x ? kAffDiag : h == e ? kAffE : kAffF;
         P.dirs[(size_t)d * (size_t)dstride + (size_t)(i - ilo)] = (uint8_t)(src | (e != eo ? kAffEExt : 0) | (f != fo ? kAffFExt : 0));
         if (d == m + nw) best = h;                                 // (one cell, one lane)
+      } else if (E2E) {
+        // row m, own columns; a lane meets its columns in rising order, so '>' keeps its first, and the key orders the lanes
+        if (i == m && jl >= P.own_lo && h > best) { best = h; bkey = (unsigned long long)(P.col_offset + jl); bi = i; bj = P.col_offset + jl; }
       } else if (jl >= P.own_lo && h > 0.0f) {
         const bool cand = (P.target >= 0.0f) ? (h == P.target) : (h >= best);
         if (cand) {
@@ -308,15 +317,16 @@ __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, co
   return AffineBest{best, bi, bj};
 }
 
+template <bool E2E = false>
 __global__ __launch_bounds__(64) void sw_affine_exact_kernel(const ExactProblem *probs, const AffineScoring sc) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   const ExactProblem P = probs[blockIdx.x];
-  const AffineBest r = affine_exact_fill<false>(P, sc, smem_raw);
+  const AffineBest r = affine_exact_fill<false, E2E>(P, sc, smem_raw);
   const float best = r.best;
   const int64_t bi = r.i, bj = r.j;
   if (threadIdx.x == 0) {
     if (P.best) *P.best = best;
-    if (P.cell) { P.cell[0] = best > 0.0f ? bi : 0; P.cell[1] = best > 0.0f ? bj : 0; }
+    if (P.cell) { P.cell[0] = (E2E || best > 0.0f) ? bi : 0; P.cell[1] = (E2E || best > 0.0f) ? bj : 0; }
   }
 }
 
@@ -338,11 +348,14 @@ struct AffineTraceProblem {
 // Fills the window as sw_affine_exact_kernel does (the same cells: affine_exact_fill), one decision byte per cell, then lane 0
 // walks them from the corner by the rule of include/mi355_sw.h: state M follows bits 0-1, states E / F emit one gap letter and
 // close the gap unless their extension bit is set (the opening wins a tie: the shortest gap).
+// E2E: the walk ends in row 0 and nowhere else.  Local column 0 of a clamped window is the model's column 0: the rest of x is one run
+// of F moves (x[i], '-') up to row 0; of an unclamped window it is status 1 as before (lemma L19).  There is no row window.
+template <bool E2E = false>
 __global__ __launch_bounds__(64) void sw_affine_trace_kernel(const AffineTraceProblem *probs, const AffineScoring sc) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   const AffineTraceProblem T = probs[blockIdx.x];
   const ExactProblem &P = T.e;
-  const float corner = affine_exact_fill<true>(P, sc, smem_raw).best;
+  const float corner = affine_exact_fill<true, E2E>(P, sc, smem_raw).best;
   // the walk reads what other lanes of this wavefront stored: wait for the stores, then keep the loads behind the barrier
   __threadfence();
   __syncthreads();
@@ -352,7 +365,16 @@ __global__ __launch_bounds__(64) void sw_affine_trace_kernel(const AffineTracePr
   int i = m, jl = nw, len = 0, state = kAffDiag;                   // kAffDiag stands for state M
   int64_t status = corner == P.target ? 0 : 3, pos = 0;
   while (status == 0) {
-    if (i <= 0 || jl <= 0) {                                       // border: H = 0, stop
+    if (E2E) {
+      if (i <= 0) break;
+      if (jl <= 0) {
+        if (!T.clamped) { status = 1; break; }
+        if (len >= T.cap) { status = 2; break; }
+        T.cons_x[len] = (char)P.x[i - 1]; T.cons_y[len] = '-'; ++len;
+        --i;
+        continue;
+      }
+    } else if (i <= 0 || jl <= 0) {                                       // border: H = 0, stop
       if ((jl <= 0 && !T.clamped) || (i <= 0 && !T.row_clamped)) status = 1;
       break;
     }

@@ -42,6 +42,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "sw_wave_common.h"
 
 namespace mi355sw {
@@ -175,6 +177,161 @@ __global__ __launch_bounds__(256) void sw_affine_pair_kernel(const AffinePairPro
     sa.best[pid] = bv;
     sa.cell[2 * (size_t)pid] = bv > 0.0f ? bi : 0;
     sa.cell[2 * (size_t)pid + 1] = bv > 0.0f ? bj : 0;
+  }
+}
+
+// sw_affine_pair_e2e_kernel — the END-TO-END sibling (include/mi355_sw.h "end-to-end mode", DESIGN.md §3.8 lemma L19): every row of
+// x is aligned, the window's flanks are free, the score may be negative.  A sibling and not a flag of the kernel above, so that the
+// local instances stay the code they were; slots, stream window, table and the per-cell chain are copies of the kernel above, which a
+// change of the scaffold must visit as well.  What differs:
+//   * no floor: the diagonal term is a plain v_add_f32;
+//   * left border H(i,0) = F(i,0) = -(o + (i-1) e), E(i,0) = -inf.  Lane l stands on column 0 at its step with t == -1 (step l - 1;
+//     lane 0: in front of the loop).  There its rows take Ho[r] = E[r] = H(i,0) - o: E(i,1) = max(E[r] - e, Ho[r]) = H(i,0) - o, the
+//     value -inf gives.  What the lane computed on `outside` codes before that step is overwritten.  At the same step the lane's DPP
+//     move reads the previous lane's Ho[R - 1] as that lane left it at ITS border step, one step earlier: Ho(i0 - 1, 0), which
+//     becomes up_prev; one step later it reads Ho(i0 - 1, 1) and the real F(i0, 1).  The chain needs no further change, and the
+//     slot's first lane keeps `old` = -o (H(0,j) = 0, F(1,j) = -o).  The selects live in a prologue of the first 16 steps (every
+//     border step is one of steps 0..14); the steady-state loop has none of them;
+//   * winner: only row m competes — lane (m-1)/R, row (m-1)%R: one select per cell under masks fixed before the loop — and only a
+//     strictly greater value replaces the lane's best, so the smallest column stays.  The best restarts at the border step: nothing
+//     left of column 1 competes.  No key, no WaveKeyFold; at the end the slot takes value and column from that one lane.
+// Columns beyond n and rows beyond m keep the `outside` code and the last class.  A padding row never feeds a real one (F and the
+// diagonal run downwards).  A padding column has E and F only: H(m, j > n) <= max over j <= n of H(m, j), with equality only for the
+// all-F path from the free row 0, and the strict compare keeps the real column (L19 (c)).  kPadScoreF enters one sum per cell, whose
+// other operand is an Ho = max(.., E, F) - o, and E and F never hold such a sum alone: every register stays finite (L19 (d)).
+// Exactness: nothing is floored and no mantissa bit is reserved; the host admits integer scores whose every value is below 2^24 in
+// magnitude (host_affine.h: affine_e2e_exact); the scale 2^-k moves no mantissa bit.
+// best[pid] = max over j of H(m, j), of any sign; cell[2 pid ..] = m and the smallest such column (1-based).
+template <int R>
+__global__ __launch_bounds__(256) void sw_affine_pair_e2e_kernel(const AffinePairProblem *probs, int nprob, const AffinePairArgs sa) {
+  static_assert(R >= 1 && R <= 32, "instances of kPairR");
+  extern __shared__ __attribute__((aligned(16))) uint32_t pairsmem[];
+  __shared__ __attribute__((aligned(16))) uint8_t win[16 * kWaveBuf];
+  float *tab = reinterpret_cast<float *>(pairsmem);                // [nrows][ncls]
+  const int tid = threadIdx.x;
+  const int l = tid & 15;
+  const int slot = tid >> 4;
+  const int pid = blockIdx.x * 16 + slot;
+  const bool active = pid < nprob;
+  const uint8_t *xb = nullptr, *yc = nullptr;
+  int m = 0, n = 0;
+  if (active) { xb = probs[pid].x; yc = probs[pid].y; m = probs[pid].m; n = probs[pid].n; }
+  for (int e = tid; e < sa.nrows * sa.ncls; e += 256) tab[e] = sa.tab[e];
+  uint32_t boff[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = l * R + r;
+    boff[r] = 4u * (i < m ? (uint32_t)sa.cls[xb[i]] : (uint32_t)(sa.ncls - 1));
+  }
+  __syncthreads();
+
+  const uint32_t outside = (uint32_t)(sa.nrows - 1);
+  auto stage_load = [&](int seg) -> uint32_t {
+    return wave_stage_word(yc, n, seg * kWaveSeg + 4 * l, [&](bool in, uint32_t byte) { return in ? byte : outside; });
+  };
+  int nseg, steps4;
+  wave_steps(n, 16, nseg, steps4);
+  uint8_t *buf = win + slot * kWaveBuf;
+  uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
+  const uint8_t *buf_lane = buf + 16 - l;
+  uint32_t nextc = stage_load(0);
+  if (l < 4) buf32[l] = outside * 0x01010101u;
+  buf32[4 + l] = nextc;
+  nextc = stage_load(1);
+
+  float ov = sa.open_s, ev = sa.ext_s;
+  asm volatile("" : "+v"(ov), "+v"(ev));
+  const int nopen = (int)__float_as_uint(-sa.open_s);              // row 0: H = 0 is Ho = -o, and F(1, j) = -o
+  // Ho = E = H(i,0) - o = -(2 o + (i - 1) e) of the lane's first row, i - 1 = l R (integers below 2^24 units: exact)
+  const float bord0 = -(2.0f * sa.open_s + (float)(l * R) * sa.ext_s);
+  float E[R], Ho[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) { E[r] = bord0 - (float)r * sa.ext_s; Ho[r] = E[r]; }   // lane 0 stands on column 0 here
+  float up_prev = -ov;                                             // Ho(i0 - 1, 0) of lane 0: row 0
+  float fout = -ov;
+  const float ninf = -__builtin_inff();
+  float best = ninf;                                               // the greatest H(m, j) so far, first seen at column tl (0-based)
+  int tl = 0;
+  const uint32_t row_bytes = 4u * (uint32_t)sa.ncls;
+  const char *tab_b = reinterpret_cast<const char *>(tab);
+  // the one cell of a column that competes, row m: lane (m - 1) / R, row (m - 1) % R (no lane of an idle slot)
+  const int wrow = (m > 0 && (m - 1) / R == l) ? (m - 1) % R : -1;
+  bool wsel[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) wsel[r] = wrow == r;
+
+  // one step of the lane: column t = gstep - l of the window, code at buf_lane[k].  BORDER (the first 16 steps): the lane whose t is
+  // -1 stands on column 0 and takes the border instead of what it computed
+  auto step = [&](auto border, const int gstep, const int k) {
+    constexpr bool BORDER = decltype(border)::value;
+    const int t = gstep - l;
+    const uint32_t c = (uint32_t)buf_lane[k];
+    const char *rowp = tab_b + c * row_bytes;
+    const float up = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(nopen, (int)__float_as_uint(Ho[R - 1]), 0x111, 0xf, 0xf, false));
+    float frun = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(nopen, (int)__float_as_uint(fout), 0x111, 0xf, 0xf, false));
+    float diag = up_prev;                                          // H(i-1, j-1) - o
+    up_prev = up;
+    float hm = ninf;                                               // H(m, t + 1) in the lane that holds row m
+    const bool on_border = BORDER && t == -1;
+    float bord = bord0;
+    // the step's R table values, all requested in front of the row loop: left to itself the scheduler issued each ds_read_b32 next to
+    // its use and waited for it (lgkmcnt(0) after nearly every load at R >= 16: twice the local instance's time at R = 32)
+    float sv[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) sv[r] = *reinterpret_cast<const float *>(rowp + boff[r]);
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float w = Ho[r];                                       // H(i, j-1) - o
+      const float s = sv[r];
+      float x, g, h, ho, fs;
+      asm("v_add_f32 %0, %1, %2" : "=v"(x) : "v"(diag), "v"(s));   // no clamp: no floor
+      asm("v_sub_f32 %0, %1, %2" : "=v"(g) : "v"(E[r]), "v"(ev));
+      asm("v_max_f32 %0, %1, %2" : "=v"(g) : "v"(g), "v"(w));
+      asm("v_max3_f32 %0, %1, %2, %3" : "=v"(h) : "v"(x), "v"(g), "v"(frun));
+      hm = wsel[r] ? h : hm;
+      asm("v_sub_f32 %0, %1, %2" : "=v"(ho) : "v"(h), "v"(ov));
+      asm("v_sub_f32 %0, %1, %2" : "=v"(fs) : "v"(frun), "v"(ev));
+      asm("v_max_f32 %0, %1, %2" : "=v"(frun) : "v"(fs), "v"(ho));
+      if constexpr (BORDER) { g = on_border ? bord : g; ho = on_border ? bord : ho; bord -= ev; }
+      E[r] = g;
+      Ho[r] = ho;
+      diag = w;
+    }
+    fout = frun;
+    // only a strictly greater value: the smallest column stays; at the border step the best restarts
+    const bool take = hm > best;
+    tl = take ? t : tl;
+    best = take ? hm : best;
+    if constexpr (BORDER) best = on_border ? ninf : best;
+  };
+
+  for (int seg = 0; seg < nseg; ++seg) {
+    const int kq = min(kWaveSeg, steps4 - seg * kWaveSeg) >> 2;
+    int k4 = 0;
+    if (seg == 0) {                                                // the 16 steps that hold every lane's border step (steps4 >= 16)
+#pragma unroll 1
+      for (int k = 0; k < 16; ++k) step(std::true_type(), k, k);
+      k4 = 4;
+    }
+    for (; k4 < kq; ++k4) {
+#pragma unroll
+      for (int ku = 0; ku < 4; ++ku) step(std::false_type(), seg * kWaveSeg + 4 * k4 + ku, 4 * k4 + ku);
+    }
+    const uint32_t hist = buf32[kWaveSeg / 4 + (l & 3)];
+    if (l < 4) buf32[l] = hist;
+    buf32[4 + l] = nextc;
+    nextc = stage_load(seg + 2);
+  }
+
+  // the slot's result: value and column of the lane that holds row m
+  const int wl = m > 0 ? (m - 1) / R : 0;
+  const float bv = __shfl(best, wl, 16) * sa.unscale;
+  const int bt = __shfl(tl, wl, 16);
+  if (l == 0 && active) {
+    sa.best[pid] = bv;
+    sa.cell[2 * (size_t)pid] = m;
+    sa.cell[2 * (size_t)pid + 1] = (long long)bt + 1;
   }
 }
 
