@@ -330,6 +330,46 @@ int mi355_sw_affine_pairs_run_mode(mi355_sw_ctx *ctx, int mode, size_t npairs, c
 int mi355_sw_affine_pairs_trace_mode(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts,
                                      const int64_t *rights, const mi355_sw_affine_params *params, mi355_sw_result *outs);
 
+/* ---- lists of pairs, banded pairs (a mapper extends inside a band around its seed's diagonal: BWA-MEM -w, minimap2 -r) ----
+ * Pair k is query x (m rows) against window y (n columns) as in mi355_sw_affine_pairs_run, and has a band
+ *
+ *     band_lo[k] <= j - i <= band_hi[k]          i the 1-based row, j the 1-based column relative to the window start; signed
+ *
+ * (a seed at read offset p and window offset q with half width w: [q - p - w, q - p + w]).  Cells outside the band are not part
+ * of the matrix: H = E = F = -infinity there.  Inside the band the local recurrence above holds unchanged, the zero floor
+ * included, and the borders keep H = 0 where they lie in the band.  For the local model this is the same as saying that an
+ * out-of-band neighbour holds H = 0 and E = F = -infinity: it then contributes at most -gap_open < 0 and never wins.
+ *
+ * Score: the maximum of H over the in-band cells.  End cell: the first maximum in column-major order among the in-band cells.
+ * No positive in-band cell, or a band that misses the matrix: score 0, end 0 / 0, empty strings.  Traceback: the rule above,
+ * unchanged; an equality with -infinity never holds, so the walk never leaves the band: every emitted pair and gap letter lies
+ * on an in-band cell, and the value of the strings is the score.  A band changes answers: an alignment that leaves it does
+ * not count.
+ *
+ * Effective band: lo_e = max(band_lo, 1 - m), hi_e = min(band_hi, n - 1), W = hi_e - lo_e + 1 diagonals.  lo_e > hi_e: zeros.
+ * lo_e == 1 - m and hi_e == n - 1 (the band covers the matrix): the pair IS the unbanded pair, on today's code path with
+ * today's bytes.  Every other pair is computed by the band kernel when it has 1..512 rows and W <= 256, under the pair kernel's
+ * bounds (integer scores, smax * (rows + 1) < 2^18, gap_open < 2^18, the score table within 32 KiB of LDS) — work in
+ * proportion to rows x W — and else by the exact kernel under a band, within that kernel's limits (2^26 cells of rows x
+ * columns, about 5 600 rows); one pair beyond those fails the whole call with MI355_SW_ENOTSUP, naming the pair.  A banded
+ * pair never falls back to an unbanded kernel.  Option no_affine_band (A/B, tests): every banded pair on the exact kernel.
+ *
+ * Arguments, their checks and the order of those checks, ownership of the results and "the context stays usable after any
+ * error" are those of the _mode calls.  band_lo == NULL and band_hi == NULL: the _mode call itself (same code path, same
+ * bytes, same mi355_sw_last_path).  Exactly one of the two NULL, or band_hi[k] < band_lo[k]: MI355_SW_EINVAL.
+ * MI355_SW_AFFINE_END_TO_END with bands is not supported yet (the column-0 border inside a band, and pairs whose band reaches
+ * no cell of row m, need decisions of their own): MI355_SW_ENOTSUP after the argument checks.
+ * mi355_sw_last_timings: [0] includes the band kernel, [4] / [5] count its launches and its cells, rows x W per pair.
+ * mi355_sw_last_path: "affine_band[R=..]" once per instance of the band kernel that ran (R registers per lane, 16 R
+ * diagonals; R is one of kBandR in csrc/sw_affine_band_kernel.h: 1, 2, 3, 5, 7, 9, 12, 16), "affine_exact_band" when the exact kernel ran under a band, beside the tags above.
+ * mi355_sw_last_kernel names the instance ("sw_affine_band_kernel<R=..>") and its ops per cell.  DESIGN.md §3.8, L20. */
+int mi355_sw_affine_pairs_run_band(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts,
+                                   const int64_t *rights, const int64_t *band_lo, const int64_t *band_hi,
+                                   const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y);
+int mi355_sw_affine_pairs_trace_band(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts,
+                                     const int64_t *rights, const int64_t *band_lo, const int64_t *band_hi,
+                                     const mi355_sw_affine_params *params, mi355_sw_result *outs);
+
 /* Host-only helper: piece ranges [left,right). Returns MI355_SW_ERANGE where the reference asserts. */
 int mi355_sw_make_string_range(int npiece, int64_t shortlen, int64_t longlen, float overlap_ratio,
                                int64_t *lefts, int64_t *rights);

@@ -162,18 +162,21 @@ class AffineSWAligner:
 
     @staticmethod
     def align_pairs(query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, scoring=None, context=None,
-                    traceback=False, end_to_end=False):
+                    traceback=False, end_to_end=False, band=None):
         """The extension stage of a mapper: pair k = query[k] of the context's resident batch against the window
         [lefts[k], rights[k]) of its resident reference, each a stand-alone problem (Context.affine_pairs_run, or
         affine_pairs_trace with traceback=True).  Returns that call's dict of per-pair arrays.  end_to_end=True aligns every
-        letter of the query (free flanks of the window, no soft clips, a score of any sign) instead of the best local piece."""
+        letter of the query (free flanks of the window, no soft clips, a score of any sign) instead of the best local piece.
+        band=(lo, hi), each an int or an array per pair: only cells with lo <= j - i <= hi count (row i, column j relative to the
+        window start, 1-based) — the band around a seed's diagonal."""
         ctx = context if context is not None else default_context()
         lut = None
         if scoring is not None:
             lut = _lut_from_function(scoring) if callable(scoring) else np.asarray(scoring, dtype=np.float32)
         call = ctx.affine_pairs_trace if traceback else ctx.affine_pairs_run
+        band_lo, band_hi = (None, None) if band is None else band
         return call(query, lefts, rights, match=float(match), mismatch=float(mismatch), gap_open=float(gap_open),
-                    gap_extend=float(gap_extend), lut=lut, mode="end_to_end" if end_to_end else "local")
+                    gap_extend=float(gap_extend), lut=lut, mode="end_to_end" if end_to_end else "local", band_lo=band_lo, band_hi=band_hi)
 
 
 class ParallelLocalAligner:

@@ -25,6 +25,7 @@ EXPORTS = [
     "mi355_sw_default_affine_params", "mi355_sw_affine_align", "mi355_sw_affine_batch_run", "mi355_sw_affine_score_ranges",
     "mi355_sw_affine_align_trace", "mi355_sw_affine_batch_trace", "mi355_sw_affine_pairs_run", "mi355_sw_affine_pairs_trace",
     "mi355_sw_prefix_values", "mi355_sw_affine_pairs_run_mode", "mi355_sw_affine_pairs_trace_mode",
+    "mi355_sw_affine_pairs_run_band", "mi355_sw_affine_pairs_trace_band",
 ]
 AFFINE_LOCAL, AFFINE_END_TO_END = 0, 1                 # mode of the affine pairs calls (include/mi355_sw.h)
 AFFINE_MODES = {"local": AFFINE_LOCAL, "end_to_end": AFFINE_END_TO_END}
@@ -418,14 +419,35 @@ class Context:
             raise ValueError("mode must be one of %s" % ", ".join(repr(k) for k in AFFINE_MODES))
         return AFFINE_MODES[mode]
 
-    def affine_pairs_run(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None, mode="local"):
+    @staticmethod
+    def _pair_bands(band_lo, band_hi, n):
+        """(lo, hi) int64 arrays of n bands, or (None, None): each of band_lo / band_hi is an int (every pair) or an array per pair."""
+        if band_lo is None and band_hi is None:
+            return None, None
+        if band_lo is None or band_hi is None:
+            raise ValueError("band_lo and band_hi must both be given, or neither")
+        out = []
+        for b in (band_lo, band_hi):
+            a = np.ascontiguousarray(b, dtype=np.int64).reshape(-1)
+            if np.ndim(b) == 0:
+                a = np.full(n, int(b), dtype=np.int64)
+            if len(a) != n:
+                raise ValueError("band_lo and band_hi must be ints or hold one value per pair")
+            out.append(a)
+        return out[0], out[1]
+
+    def affine_pairs_run(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None, mode="local",
+                         band_lo=None, band_hi=None):
         """Pair k = resident query query[k] against the window [lefts[k], rights[k]) of the resident reference, each a stand-alone
         problem (mi355_sw_affine_pairs_run): dict of arrays score, end_x, end_y in the caller's order; end_y is relative to the
         window start.  query, lefts, rights: numpy int arrays or lists.  mode="end_to_end" (mi355_sw_affine_pairs_run_mode): the
-        whole query against its window, free flanks of the window, a score of any sign; end_x is the query's length."""
+        whole query against its window, free flanks of the window, a score of any sign; end_x is the query's length.
+        band_lo / band_hi (mi355_sw_affine_pairs_run_band; an int or an array per pair): only cells with band_lo <= j - i <= band_hi
+        count, i the row and j the column relative to the window start, both 1-based."""
         p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
         q, lo, hi = self._pair_arrays(query, lefts, rights)
         n = len(q)
+        blo, bhi = self._pair_bands(band_lo, band_hi, n)
         score = np.zeros(n, dtype=np.float32)
         ex = np.zeros(n, dtype=np.int64)
         ey = np.zeros(n, dtype=np.int64)
@@ -433,24 +455,35 @@ class Context:
                 hi.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p), score.ctypes.data_as(C.POINTER(C.c_float)),
                 ex.ctypes.data_as(C.POINTER(C.c_int64)), ey.ctypes.data_as(C.POINTER(C.c_int64)))
         m = self._pair_mode(mode)
-        if m == AFFINE_LOCAL:
+        if blo is not None:
+            i64 = C.POINTER(C.c_int64)
+            self._chk(self._L.mi355_sw_affine_pairs_run_band(self._ctx, C.c_int(m), *args[:4], blo.ctypes.data_as(i64), bhi.ctypes.data_as(i64),
+                                                             *args[4:]))
+        elif m == AFFINE_LOCAL:
             self._chk(self._L.mi355_sw_affine_pairs_run(self._ctx, *args))
         else:
             self._chk(self._L.mi355_sw_affine_pairs_run_mode(self._ctx, C.c_int(m), *args))
         return dict(score=score, end_x=ex, end_y=ey)
 
-    def affine_pairs_trace(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None, mode="local"):
+    def affine_pairs_trace(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None, mode="local",
+                           band_lo=None, band_hi=None):
         """affine_pairs_run with the traceback (mi355_sw_affine_pairs_trace): the dict shape of affine_batch_trace, one entry per pair;
         begin_y / pos are relative to the window start.  mode="end_to_end" (mi355_sw_affine_pairs_trace_mode): begin_x is 1 for
-        every pair that has an alignment, whatever the sign of its score."""
+        every pair that has an alignment, whatever the sign of its score.  band_lo / band_hi (mi355_sw_affine_pairs_trace_band): as
+        affine_pairs_run; every emitted cell lies in the band."""
         p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
         q, lo, hi = self._pair_arrays(query, lefts, rights)
         n = len(q)
+        blo, bhi = self._pair_bands(band_lo, band_hi, n)
         res = (Result * max(1, n))()
         args = (C.c_size_t(n), q.ctypes.data_as(C.POINTER(C.c_int32)), lo.ctypes.data_as(C.POINTER(C.c_int64)),
                 hi.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p), res)
         m = self._pair_mode(mode)
-        if m == AFFINE_LOCAL:
+        if blo is not None:
+            i64 = C.POINTER(C.c_int64)
+            self._chk(self._L.mi355_sw_affine_pairs_trace_band(self._ctx, C.c_int(m), *args[:4], blo.ctypes.data_as(i64), bhi.ctypes.data_as(i64),
+                                                               *args[4:]))
+        elif m == AFFINE_LOCAL:
             self._chk(self._L.mi355_sw_affine_pairs_trace(self._ctx, *args))
         else:
             self._chk(self._L.mi355_sw_affine_pairs_trace_mode(self._ctx, C.c_int(m), *args))

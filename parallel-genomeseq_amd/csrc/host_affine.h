@@ -2,7 +2,8 @@
 // sw_affine_exact_kernel behind it, sw_affine_trace_kernel (sw_affine_kernel.h) and, for references (ranges) of
 // at most 512 letters, sw_affine_prof_kernel (sw_affine_prof_kernel.h); for lists of (query, window) pairs, sw_affine_pair_kernel
 // (sw_affine_pair_kernel.h; end-to-end mode of the pairs calls: sw_affine_pair_e2e_kernel and the E2E instances of the exact and the
-// trace kernel, AffineCall::mode).  The drivers affine_run (affine_prof_run, affine_sweep) and affine_pairs (affine_pair_stage) share one
+// trace kernel, AffineCall::mode; pairs with a diagonal band: sw_affine_band_kernel, sw_affine_band_kernel.h, affine_band_stage, and the
+// BAND instances of the exact and the trace kernel).  The drivers affine_run (affine_prof_run, affine_sweep) and affine_pairs (affine_pair_stage) share one
 // AffineCall (affine_begin .. affine_end) and one affine_note_kernel, affine_exact_stage, affine_download and affine_class_table.
 // Part of the single translation unit mi355_sw.hip (included there, in order; not a standalone header).
 namespace {
@@ -130,17 +131,19 @@ AffineKernel affine_kernel(int SL, int R) {
 size_t affine_exact_lds(int m) { return (size_t)7 * (m + 2) * 4 + (size_t)m + 16; }
 
 // Runs jobs[lo, hi) on sw_affine_exact_kernel in one launch (ExactJob: q, ylo, nw, col_offset, own_lo, target -> best, ci, cj).
-int run_affine_exact(const AffineCall &c, std::vector<ExactJob> &jobs, size_t lo, size_t hi) {
+// bands (may be null): [jobs.size()][2], the band of every job in its window's local coordinates — the BAND instance.
+int run_affine_exact(const AffineCall &c, std::vector<ExactJob> &jobs, size_t lo, size_t hi, const int32_t *bands = nullptr) {
   mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q;
   const size_t n = hi - lo;
   if (n == 0) return 0;
   size_t lds = 0;
   for (size_t k = lo; k < hi; ++k) lds = std::max(lds, affine_exact_lds(q.len[jobs[k].q]));
   if (lds > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine: query longer than the exact kernel's LDS diagonals hold");
-  path_note(ctx, "affine_exact");
-  if (ctx->probs.ensure(n * sizeof(ExactProblem)) || ctx->outs_f.ensure(n * 4) || ctx->outs_i.ensure(n * 16))
+  path_note(ctx, bands ? "affine_exact_band" : "affine_exact");
+  if (ctx->probs.ensure(n * (bands ? sizeof(ExactBandProblem) : sizeof(ExactProblem))) || ctx->outs_f.ensure(n * 4) || ctx->outs_i.ensure(n * 16))
     return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(exact scratch) failed");
   std::vector<ExactProblem> pr(n);
+  std::vector<ExactBandProblem> bpr(bands ? n : 0);
   for (size_t k = 0; k < n; ++k) {
     const ExactJob &j = jobs[lo + k];
     ExactProblem &e = pr[k];
@@ -157,12 +160,21 @@ int run_affine_exact(const AffineCall &c, std::vector<ExactJob> &jobs, size_t lo
     e.hout = nullptr;
     e.best = ctx->outs_f.as<float>() + k;
     e.cell = ctx->outs_i.as<int64_t>() + 2 * k;
+    if (bands) { bpr[k].e = e; bpr[k].blo = bands[2 * (lo + k)]; bpr[k].bhi = bands[2 * (lo + k) + 1]; }
   }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactProblem), hipMemcpyHostToDevice, ctx->stream));
+  if (bands) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, bpr.data(), n * sizeof(ExactBandProblem), hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactProblem), hipMemcpyHostToDevice, ctx->stream));
+  }
   AffineScoring sc;
   { int rc = affine_scoring(ctx, c.p, sc); if (rc) return rc; }
-  launch_dyn_lds(c.e2e() ? &sw_affine_exact_kernel<true> : &sw_affine_exact_kernel<false>, dim3((unsigned)n), dim3(64), lds, ctx->stream,
-                 ctx->probs.as<ExactProblem>(), sc);
+  if (bands) {
+    launch_dyn_lds(&sw_affine_exact_kernel<false, true>, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactBandProblem>(), sc);
+  } else {
+    launch_dyn_lds(c.e2e() ? &sw_affine_exact_kernel<true> : &sw_affine_exact_kernel<false>, dim3((unsigned)n), dim3(64), lds, ctx->stream,
+                   ctx->probs.as<ExactProblem>(), sc);
+  }
   HIPCHK(ctx, hipGetLastError());
   std::vector<float> bf(n);
   std::vector<int64_t> ci(2 * n);
@@ -185,12 +197,13 @@ bool affine_whole_job(const AffineCall &c, int q, int64_t lo, int64_t n, size_t 
 }
 
 // The exact kernel over all of `jobs`, 65536 per launch; its interval (ev[2]..ev[3]) goes to timings[1].
-int affine_exact_stage(const AffineCall &c, std::vector<ExactJob> &jobs) {
+// bands (may be null): as run_affine_exact.
+int affine_exact_stage(const AffineCall &c, std::vector<ExactJob> &jobs, const int32_t *bands = nullptr) {
   mi355_sw_ctx *ctx = c.ctx;
   if (jobs.empty()) return 0;
   HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
   for (size_t lo = 0; lo < jobs.size(); lo += 65536) {
-    { int rc = run_affine_exact(c, jobs, lo, std::min(jobs.size(), lo + 65536)); if (rc) return rc; }
+    { int rc = run_affine_exact(c, jobs, lo, std::min(jobs.size(), lo + 65536), bands); if (rc) return rc; }
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
   ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
@@ -424,17 +437,24 @@ int affine_prof_run(const AffineCall &c, const std::vector<Range> &ranges, const
 
 // One alignment to trace back: query q of the batch against the range of the reference that starts at column lo, with the score
 // and the end cell (row, column relative to lo, 1-based) its score pass found.
-struct AffineTraceItem { int q; int64_t lo; float score; int64_t ex, ey; };
+// banded: the alignment lies inside blo <= j - i <= bhi of the pair's own coordinates (the window of the traceback gets it shifted).
+struct AffineTraceItem { int q; int64_t lo; float score; int64_t ex, ey; bool banded = false; int64_t blo = 0, bhi = 0; };
 
 // Traceback of every item with a positive score: one sw_affine_trace_kernel problem per item over the window behind the end
 // cell — the L17 window of columns and the L18 window of rows, each where it is shorter than the matrix, clamped
 // at the item's own left border and at row 1 — in launch groups of at most kAffineTraceDirsMax decision bytes.
 // tout[items.size()]: views into ctx->arenas.
+// BAND: the banded items on the BAND instance of the kernel, the others on today's — one pass each (affine_end).  A banded alignment
+// is an alignment, so the windows of L17 and L18 hold every banded path of value `score` into the end cell as well; the window's band
+// is the pair's, shifted: delta_local = delta - wl + row_lo.
+template <bool BAND = false>
 int affine_trace(const AffineCall &c, const std::vector<AffineTraceItem> &items, std::vector<TraceOut> &tout) {
   mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q; const AffineTable &t = c.t;
+  typedef typename AffineTraceProblemOf<BAND>::type Problem;
   struct Job { size_t item; int32_t m, nw; int64_t wl, row_lo; bool clamped, row_clamped; size_t dirs_off, cons_off; };
   std::vector<Job> jobs;
   for (size_t k = 0; k < items.size(); ++k) {
+    if (items[k].banded != BAND) continue;
     const float score = items[k].score;
     const int64_t ex = items[k].ex, ey = items[k].ey;
     // end-to-end: every pair with an end cell (a non-empty query and window), whatever the sign of its score
@@ -485,14 +505,22 @@ int affine_trace(const AffineCall &c, const std::vector<AffineTraceItem> &items,
       ++hi;
     }
     const size_t n = hi - lo;
-    if (ctx->wprobs.ensure(n * sizeof(AffineTraceProblem)) || ctx->walkp.ensure(n * 24) || ctx->dirs.ensure(dirs_total) ||
+    if (ctx->wprobs.ensure(n * sizeof(Problem)) || ctx->walkp.ensure(n * 24) || ctx->dirs.ensure(dirs_total) ||
         ctx->cons.ensure(cons_total + 16))
       return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine traceback scratch) failed");
-    std::vector<AffineTraceProblem> pr(n);
+    std::vector<Problem> pr(n);
     for (size_t k = 0; k < n; ++k) {
       const Job &j = jobs[lo + k];
-      AffineTraceProblem &a = pr[k];
-      memset(&a, 0, sizeof a);
+      memset(&pr[k], 0, sizeof pr[k]);
+      AffineTraceProblem *ap;
+      if constexpr (BAND) {
+        ap = &pr[k].t;
+        // (a window lies within 2^30 rows and columns of its end cell: the clamps keep the shifted band in int32 and lose nothing)
+        const int64_t shift = j.row_lo - j.wl, big = (int64_t)1 << 30;
+        pr[k].blo = (int32_t)std::max(-big, std::min(big, items[j.item].blo + shift));
+        pr[k].bhi = (int32_t)std::max(-big, std::min(big, items[j.item].bhi + shift));
+      } else ap = &pr[k];
+      AffineTraceProblem &a = *ap;
       a.e.x = q.bytes.as<uint8_t>() + q.off[items[j.item].q] + j.row_lo;
       a.e.y = ref.bytes.as<uint8_t>() + items[j.item].lo + j.wl;
       a.e.m = j.m; a.e.nw = j.nw;
@@ -507,10 +535,14 @@ int affine_trace(const AffineCall &c, const std::vector<AffineTraceItem> &items,
       a.row_clamped = j.row_clamped ? 1 : 0;
       a.out = ctx->walkp.as<int64_t>() + 3 * k;
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr.data(), n * sizeof(AffineTraceProblem), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr.data(), n * sizeof(Problem), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-    launch_dyn_lds(c.e2e() ? &sw_affine_trace_kernel<true> : &sw_affine_trace_kernel<false>, dim3((unsigned)n), dim3(64), lds, ctx->stream,
-                   ctx->wprobs.as<AffineTraceProblem>(), sc);
+    if constexpr (BAND) {
+      launch_dyn_lds(&sw_affine_trace_kernel<false, true>, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<Problem>(), sc);
+    } else {
+      launch_dyn_lds(c.e2e() ? &sw_affine_trace_kernel<true> : &sw_affine_trace_kernel<false>, dim3((unsigned)n), dim3(64), lds, ctx->stream,
+                     ctx->wprobs.as<AffineTraceProblem>(), sc);
+    }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     std::vector<int64_t> wo(3 * n);
@@ -544,6 +576,9 @@ int affine_end(const AffineCall &c, std::vector<AffineTraceItem> &items, const f
   if (tout) {
     for (size_t k = 0; k < items.size(); ++k) { items[k].score = score[k]; items[k].ex = ends[2 * k]; items[k].ey = ends[2 * k + 1]; }
     { int rc = affine_trace(c, items, *tout); if (rc) return rc; }
+    bool any_banded = false;
+    for (const AffineTraceItem &it : items) any_banded |= it.banded;
+    if (any_banded) { int rc = affine_trace<true>(c, items, *tout); if (rc) return rc; }
   }
   HIPCHK(c.ctx, hipEventRecord(c.ctx->ev[5], c.ctx->stream));
   c.ctx->timings[3] += elapsed_us(c.ctx, c.ctx->ev[4], c.ctx->ev[5]);
@@ -817,14 +852,101 @@ int affine_pair_stage(const AffineCall &c, const int32_t *qid, const int64_t *le
   return 0;
 }
 
+// ---- sw_affine_band_kernel (sw_affine_band_kernel.h): pairs with a diagonal band ----------------------------------------------------
+// the instance of the least R of kBandR with 16 R >= W diagonals (0: none)
+int affine_band_R(int64_t W) {
+  for (int R : kBandR) if (16 * (int64_t)R >= W) return R;
+  return 0;
+}
+typedef void (*AffineBandKernel)(const AffineBandProblem *, int, const AffinePairArgs);
+
+// One banded pair as the band kernel and the banded exact job take it: the band clipped to the matrix.
+struct AffineBandPair { uint32_t id; int32_t lo, W; };
+
+// sw_affine_band_kernel over the pairs of `band`: by instance, then longest query first, so that the slots of a wavefront leave
+// the row loop at similar steps; score / ends of the pairs with a positive maximum.  The table is affine_pair_stage's.
+int affine_band_stage(const AffineCall &c, const int32_t *qid, const int64_t *lefts, const int64_t *rights, const AffineProfPlan &plan,
+                      std::vector<AffineBandPair> &band, int mmax, float *score, int64_t *ends) {
+  mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q;
+  if (band.empty()) return 0;
+  std::sort(band.begin(), band.end(), [&](const AffineBandPair &a, const AffineBandPair &b) {
+    const int Ra = affine_band_R(a.W), Rb = affine_band_R(b.W);
+    if (Ra != Rb) return Ra < Rb;
+    const int ma = q.len[qid[a.id]], mb = q.len[qid[b.id]];
+    return ma != mb ? ma > mb : a.id < b.id;
+  });
+  const int nl = ref.ncodes - 1, nrows = nl + 1, ncls = plan.nclass;
+  const size_t tab_floats = (size_t)nrows * ncls;
+  AffinePairArgs sa;
+  sa.nrows = nrows; sa.ncls = ncls;
+  int rc = affine_class_table(c, plan, mmax, tab_floats, 1, ncls, "hipMalloc(affine pair table) failed", sa.tab, sa);
+  if (rc) return rc;
+  for (size_t g0 = 0; g0 < band.size(); g0 += kAffinePairGroupProblems) {
+    const size_t np = std::min(kAffinePairGroupProblems, band.size() - g0);
+    const char *nomem = "affine pairs: allocation of the pair scratch failed";
+    if (ctx->wprobs.ensure(np * sizeof(AffineBandProblem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16) ||
+        ctx->pin_probs.ensure(np * sizeof(AffineBandProblem)))
+      return fail(ctx, MI355_SW_ENOMEM, nomem);
+    AffineBandProblem *pr = ctx->pin_probs.as<AffineBandProblem>();
+    for (size_t i = 0; i < np; ++i) {                              // one upload of the pair list
+      const AffineBandPair &b = band[g0 + i];
+      pr[i].x = q.bytes.as<uint8_t>() + q.off[qid[b.id]];
+      pr[i].y = ref.codes.as<uint8_t>() + lefts[b.id];
+      pr[i].m = q.len[qid[b.id]];
+      pr[i].n = (int32_t)(rights[b.id] - lefts[b.id]);
+      pr[i].lo = b.lo; pr[i].W = b.W;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr, np * sizeof(AffineBandProblem), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    for (size_t i0 = 0; i0 < np;) {                                // one launch per instance
+      const int R = affine_band_R(pr[i0].W);
+      size_t i1 = i0;
+      double cells = 0;
+      while (i1 < np && affine_band_R(pr[i1].W) == R) { cells += (double)pr[i1].m * (double)pr[i1].W; ++i1; }
+      AffineBandKernel kern = nullptr;
+      with_listed_R<kBandR>(R, [&](auto r) { kern = &sw_affine_band_kernel<decltype(r)::value>; });
+      if (!kern) return fail(ctx, MI355_SW_ENODEV, "internal: no sw_affine_band_kernel instance for this band");
+      sa.best = ctx->outs_f.as<float>() + i0;
+      sa.cell = ctx->outs_i.as<int64_t>() + 2 * i0;
+      launch_dyn_lds(kern, dim3((unsigned)((i1 - i0 + 15) / 16)), dim3(256), tab_floats * 4, ctx->stream,
+                     ctx->wprobs.as<AffineBandProblem>() + i0, (int)(i1 - i0), sa);
+      HIPCHK(ctx, hipGetLastError());
+      ctx->timings[4] += 1;
+      path_note(ctx, "affine_band[R=%d]", R);
+      // per step and lane, as compiled: fourteen ops per register — the table address' multiply-add, the clamped add,
+      // sub / max for F, max for Ht, Ht - o, sub / max of the lane's scan, maximum3 for H, the cap's min, the key's v_or, H - o, the
+      // carry's sub and one move — a maximum3 per two registers for the step's key, and 29 of overhead: two DPP moves for F, five DPP
+      // moves (each with the move of its `old`) and four sub / max pairs for the lanes' scan, the explicit (value, column) compare
+      // with its selects, the window addresses.  All 16 R registers of a lane row work whatever W is: the model's time is rows x 16 R
+      affine_note_kernel(ctx, cells, MI355_SW_CELL_F32, 16, R, 16 * R, 16 * R, 0, (14.0 * R + (R + 1) / 2 + 29.0) / (double)R,
+                         "sw_affine_band_kernel<R=%d>", R);
+      i0 = i1;
+    }
+    const float *h_best = nullptr; const int64_t *h_cell = nullptr;
+    rc = affine_download(ctx, np, nomem, h_best, h_cell); if (rc) return rc;
+    for (size_t i = 0; i < np; ++i) {
+      const uint32_t id = band[g0 + i].id;
+      if (!(h_best[i] > 0)) continue;
+      score[id] = h_best[i]; ends[2 * (size_t)id] = h_cell[2 * i]; ends[2 * (size_t)id + 1] = h_cell[2 * i + 1];
+    }
+  }
+  return 0;
+}
+
 // npairs independent problems: query qid[k] of `q` against [lefts[k], rights[k]) of `ref` (validated by the caller), each with
 // zero borders.  score[npairs]; ends[npairs][2] = row, column relative to the window start; tout (may be null): the traceback of
 // every pair (affine_trace).  A pair of 1..512 rows and 1..2^20 columns under the bounds of the header takes sw_affine_pair_kernel,
 // every other one is a whole problem of the exact kernel; results come back in the caller's order.
 // mode MI355_SW_AFFINE_END_TO_END: the end-to-end model of the header on the E2E instances of the same kernels; the pair kernel's
 // bounds are then those of affine_e2e_exact, and only an empty query or an empty window leaves the zeros (a score may be <= 0).
+// band_lo / band_hi (both null: none; local mode only, validated by the caller): pair k counts only cells with band_lo[k] <= j - i <=
+// band_hi[k] (include/mi355_sw.h, "banded pairs").  With the band clipped to the matrix, lo_e .. hi_e, a pair is one of four kinds:
+// zeros (the band misses the matrix), the unbanded pair (the band covers the matrix: the two paths above, untouched), a problem of
+// sw_affine_band_kernel (affine_band_stage: 1..512 rows, at most 256 diagonals, the pair kernel's table and float32 bounds), or a
+// banded job of the exact kernel.  A banded pair never runs on an unbanded kernel.
 int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, int mode, size_t npairs, const int32_t *qid, const int64_t *lefts,
-                 const int64_t *rights, const mi355_sw_affine_params &p, float *score, int64_t *ends, std::vector<TraceOut> *tout) {
+                 const int64_t *rights, const mi355_sw_affine_params &p, float *score, int64_t *ends, std::vector<TraceOut> *tout,
+                 const int64_t *band_lo = nullptr, const int64_t *band_hi = nullptr) {
   for (size_t k = 0; k < npairs; ++k) { score[k] = 0.0f; ends[2 * k] = 0; ends[2 * k + 1] = 0; }
   if (tout) tout->assign(npairs, TraceOut());
   AffineCall c{ctx, ref, q, p, AffineTable(), mode};
@@ -848,12 +970,42 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, int
   if (npairs > 0xFFFFFFFFull) return fail(ctx, MI355_SW_ENOTSUP, "affine pairs: more than 2^32 pairs");
   std::vector<uint32_t> fast;                                      // pair indices of sw_affine_pair_kernel
   std::vector<ExactJob> jobs;
-  int mmax = 0;
+  std::vector<AffineBandPair> band;                                // pairs of sw_affine_band_kernel
+  std::vector<ExactJob> bjobs;                                     // banded jobs of the exact kernel, their bands in bbands
+  std::vector<int32_t> bbands;
+  std::vector<char> banded(band_lo ? npairs : 0, 0);               // the pair's alignment is confined to its band (the traceback)
+  int mmax = 0, band_mmax = 0;
   for (size_t k = 0; k < npairs; ++k) {
     const int m = q.len[qid[k]];
     const int64_t n = rights[k] - lefts[k];
     if (m < 1 || n < 1) continue;
     const bool exact_f32 = c.e2e() ? affine_e2e_exact(c.t, (double)m) : (double)c.t.smax * ((double)m + 1.0) < kAffineProfBound;
+    if (band_lo) {
+      const int64_t lo_e = std::max<int64_t>(band_lo[k], 1 - (int64_t)m), hi_e = std::min<int64_t>(band_hi[k], n - 1);
+      if (lo_e > hi_e) continue;                                   // the band misses the matrix: zeros
+      if (lo_e != 1 - (int64_t)m || hi_e != n - 1) {               // (else the band covers the matrix: the unbanded pair, below)
+        const int64_t W = hi_e - lo_e + 1;
+        banded[k] = 1;
+        if (table_ok && !opt().no_affine_band && m <= kBandRowsMax && affine_band_R(W) != 0 && n <= 0x7fff0000 && exact_f32) {
+          band.push_back(AffineBandPair{(uint32_t)k, (int32_t)lo_e, (int32_t)W});
+          band_mmax = std::max(band_mmax, m);
+          continue;
+        }
+        ExactJob j;
+        if (!affine_whole_job(c, qid[k], lefts[k], n, k, j)) {
+          char msg[360];
+          std::snprintf(msg, sizeof msg, "affine pairs: banded pair %zu (%d rows x %lld columns, %lld diagonals) is outside the band kernel "
+                        "(1..512 rows, at most 256 diagonals, smax * (rows + 1) < 2^18, gap_open < 2^18, a score table within 32 KiB%s) and has "
+                        "more than 2^26 cells for the exact kernel", k, m, (long long)n, (long long)W,
+                        opt().no_affine_band ? "; option no_affine_band is set" : "");
+          return fail(ctx, MI355_SW_ENOTSUP, msg);
+        }
+        if (affine_exact_lds(m) > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine pairs: query longer than the exact kernel's LDS diagonals hold");
+        bjobs.push_back(j);
+        bbands.push_back((int32_t)lo_e); bbands.push_back((int32_t)hi_e);   // (|lo_e|, |hi_e| < 2^26 cells: int32)
+        continue;
+      }
+    }
     if (table_ok && m <= kMaxRowsFast && n <= kAffinePairColsMax && exact_f32) {
       fast.push_back((uint32_t)k);
       mmax = std::max(mmax, m);
@@ -874,14 +1026,27 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, int
 
   // ---- sw_affine_pair_kernel, then the exact kernel: every other pair as a whole problem ------------------------------------------
   rc = affine_pair_stage(c, qid, lefts, rights, plan, fast, mmax, score, ends);
+  if (!rc) rc = affine_band_stage(c, qid, lefts, rights, plan, band, band_mmax, score, ends);
   if (!rc) rc = affine_exact_stage(c, jobs);
+  if (!rc) rc = affine_exact_stage(c, bjobs, bbands.data());
   if (rc) return rc;
   for (const ExactJob &j : jobs) {
     if (!c.e2e() && !(j.best > 0)) continue;
     score[j.index] = j.best; ends[2 * j.index] = j.ci; ends[2 * j.index + 1] = j.cj;
   }
+  for (const ExactJob &j : bjobs) {
+    if (!(j.best > 0)) continue;
+    score[j.index] = j.best; ends[2 * j.index] = j.ci; ends[2 * j.index + 1] = j.cj;
+  }
   std::vector<AffineTraceItem> items(tout ? npairs : 0);
-  for (size_t k = 0; k < items.size(); ++k) items[k] = AffineTraceItem{qid[k], lefts[k], 0.0f, 0, 0};
+  for (size_t k = 0; k < items.size(); ++k) {
+    items[k] = AffineTraceItem{qid[k], lefts[k], 0.0f, 0, 0};
+    if (band_lo && banded[k]) {                                    // (clipped to the matrix: the same cells, and no overflow when shifted)
+      items[k].banded = true;
+      items[k].blo = std::max<int64_t>(band_lo[k], 1 - (int64_t)q.len[qid[k]]);
+      items[k].bhi = std::min<int64_t>(band_hi[k], rights[k] - lefts[k] - 1);
+    }
+  }
   return affine_end(c, items, score, ends, tout);
 }
 

@@ -48,6 +48,7 @@
 #include "sw_affine_kernel.h"
 #include "sw_affine_prof_kernel.h"
 #include "sw_affine_pair_kernel.h"
+#include "sw_affine_band_kernel.h"
 
 using namespace mi355sw;
 
@@ -470,9 +471,10 @@ int mi355_sw_affine_score_ranges(mi355_sw_ctx *ctx, size_t nranges, const int64_
 }
 
 // mi355_sw_affine_pairs_run (score, end_x, end_y) and, with `trace`, mi355_sw_affine_pairs_trace (outs), written only after success
-// (and their _mode twins: MI355_SW_AFFINE_LOCAL is the same call)
+// (and their _mode twins: MI355_SW_AFFINE_LOCAL is the same call; and their _band twins: without bands the _mode call)
 static int affine_pairs_any(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
-                            const mi355_sw_affine_params *params, bool trace, float *score, int64_t *end_x, int64_t *end_y, mi355_sw_result *outs) {
+                            const mi355_sw_affine_params *params, bool trace, float *score, int64_t *end_x, int64_t *end_y, mi355_sw_result *outs,
+                            const int64_t *band_lo = nullptr, const int64_t *band_hi = nullptr) {
   OptScope opt_scope_(ctx);
   int rc = affine_check(ctx, params);
   if (rc) return rc;
@@ -482,14 +484,19 @@ static int affine_pairs_any(mi355_sw_ctx *ctx, int mode, size_t npairs, const in
   if (npairs == 0) return 0;
   if (trace && !outs) return fail(ctx, MI355_SW_EINVAL, "outs is NULL");
   if ((!trace && (!score || !end_x || !end_y)) || !query || !lefts || !rights) return fail(ctx, MI355_SW_EINVAL, "null argument");
+  if ((band_lo == nullptr) != (band_hi == nullptr)) return fail(ctx, MI355_SW_EINVAL, "banded pairs: band_lo and band_hi must both be given, or neither");
   for (size_t k = 0; k < npairs; ++k) {
     if (query[k] < 0 || (size_t)query[k] >= ctx->batch.nq) return fail(ctx, MI355_SW_EINVAL, "pair: query index outside the resident batch");
     if (lefts[k] < 0 || rights[k] < lefts[k] || rights[k] > (int64_t)ctx->ref.n) return fail(ctx, MI355_SW_EINVAL, "pair: window outside the resident reference");
+    if (band_lo && band_hi[k] < band_lo[k]) return fail(ctx, MI355_SW_EINVAL, "banded pairs: band_hi below band_lo");
   }
+  if (band_lo && mode == MI355_SW_AFFINE_END_TO_END)
+    return fail(ctx, MI355_SW_ENOTSUP, "banded pairs: end-to-end mode with bands is not supported (the banded end-to-end model is not defined yet)");
   std::vector<float> sc(npairs, 0.0f);
   std::vector<int64_t> ends(2 * npairs, 0);
   std::vector<TraceOut> tout(trace ? npairs : 0);
-  rc = affine_pairs(ctx, ctx->ref, ctx->batch, mode, npairs, query, lefts, rights, *params, sc.data(), ends.data(), trace ? &tout : nullptr);
+  rc = affine_pairs(ctx, ctx->ref, ctx->batch, mode, npairs, query, lefts, rights, *params, sc.data(), ends.data(), trace ? &tout : nullptr,
+                    band_lo, band_hi);
   if (rc) return rc;
   if (trace) {
     memset(outs, 0, npairs * sizeof *outs);
@@ -519,6 +526,17 @@ int mi355_sw_affine_pairs_run_mode(mi355_sw_ctx *ctx, int mode, size_t npairs, c
 int mi355_sw_affine_pairs_trace_mode(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
                                      const mi355_sw_affine_params *params, mi355_sw_result *outs) {
   return affine_pairs_any(ctx, mode, npairs, query, lefts, rights, params, true, nullptr, nullptr, nullptr, outs);
+}
+
+int mi355_sw_affine_pairs_run_band(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
+                                   const int64_t *band_lo, const int64_t *band_hi, const mi355_sw_affine_params *params, float *score,
+                                   int64_t *end_x, int64_t *end_y) {
+  return affine_pairs_any(ctx, mode, npairs, query, lefts, rights, params, false, score, end_x, end_y, nullptr, band_lo, band_hi);
+}
+
+int mi355_sw_affine_pairs_trace_band(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
+                                     const int64_t *band_lo, const int64_t *band_hi, const mi355_sw_affine_params *params, mi355_sw_result *outs) {
+  return affine_pairs_any(ctx, mode, npairs, query, lefts, rights, params, true, nullptr, nullptr, nullptr, outs, band_lo, band_hi);
 }
 
 int mi355_sw_best_range(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,

@@ -1,0 +1,176 @@
+// sw_affine_band_kernel.h — affine-gap (Gotoh) score and end cell of a LIST OF PAIRS inside a DIAGONAL BAND per pair, hand-written
+// HIP for gfx950.
+//
+// The banded sibling of sw_affine_pair_kernel (sw_affine_pair_kernel.h): pair k is a query x (m rows) against a
+// window of y (n columns) restricted to the cells lo <= j - i <= hi (include/mi355_sw.h, "banded pairs").  Work must be proportional
+// to rows x band width, so the geometry is the other one: the 16 lanes of a slot lie ACROSS the diagonals of the band and the ROWS
+// are the time axis.  With lo_e the band's first diagonal inside the matrix and W its width (the host clips the band to the matrix),
+// lane l, register r holds diagonal D = l R + r, i.e. delta = lo_e + D; step i computes the cells (i, i + delta) of row i:
+//
+//   diagonal   H(i-1,j-1) is the same register one row earlier: no move.  x = v_add_f32 clamp(Ho, s + o) = max(0, H(i-1,j-1) + s),
+//              Ho = H - o and a table of s + o as in the pair kernel: the [0, 1] clamp is the zero floor
+//   F          F(i,j) = max(F(i-1,j) - e, H(i-1,j) - o) reads diagonal D + 1 of the previous row: the next register of the lane, or
+//              register 0 of the next lane through one DPP row_shl:1 (two moves per step: Ho and F); the slot's last lane keeps
+//              `old`, the value of a cell outside the band
+//   E          runs along the row, a serial chain across all lanes.  It is broken up: first Ht = max(x, F) for every cell, then
+//                  E(i,j) = max over the row's cells k < j of (Ht(i,k) - o - (j-1-k) e),          H = max(Ht, E)
+//              — the scan runs over Ht and not over H, which is exact because o >= e: re-opening out of an E never beats extending
+//              it.  A max-plus prefix scan with decay e: R serial sub / max pairs in the lane (q), then the lanes' totals through
+//              four DPP steps row_shr:1/2/4/8 with decays R e, 2R e, 4R e, 8R e, and one row_shr:1 for the exclusive carry C;
+//              E of register r is max(q[r-1], C - r e).  DPP rows are the 16-lane slots: no move crosses a slot.
+//
+// What lies outside.  A cell outside the band holds H = 0, E = F = -inf — here -o for E and F, which gives the same cells (L15 (d)):
+// it contributes at most -o < 0 to a neighbour and never wins (the header's second statement of the model).  Three kinds:
+//   * columns j < 1 and j > n (the band sticks out of the matrix in later or earlier rows) and rows beyond m (the slots of a
+//     wavefront run to the longest query of the four): the `outside` code of y and the last class of x, kPadScoreF, as in the pair
+//     kernel.  Left of column 1 and above row 1 nothing positive ever arrives, so those cells stay 0; right of column n and below row m
+//     a cell holds max(0, E, F), strictly below a real cell, feeds only cells of its own kind (F runs down a column, the diagonal
+//     stays on its diagonal, E runs to the right) and never leads the slot;
+//   * registers D >= W of a band narrower than the instance's 16 R diagonals: real cells of the matrix to the right of the band.  E
+//     flows into them and the diagonal term can score there, and their F would flow back into diagonal W - 1.  One v_min_f32 per cell
+//     against cap[r] (1 in the band, 0 beyond) makes their H 0 — the model's value — before it is stored, folded or handed on;
+//   * beyond the slot's last lane: the `old` operand of the two row_shl moves, Ho = F = -o.
+//
+// y reaches the cells through LDS: the slot stages the codes of columns lo_e + 1 .. lo_e + steps + 16 R once, and the class offsets
+// of its rows of x; cell (i, D) reads entry i - 1 + D — per cell one ds_read_u8 at an immediate offset, one v_mad_u32_u24 (code *
+// bytes of a table row + the row's class offset) and the ds_read_b32 of the table.  Static LDS: 16 x (512 + 16 R) + 16 KiB, at most
+// 28 KiB, so that a 32 KiB table keeps the workgroup within 64 KiB.  The table is that kernel's: tab[code of y][class of x] = (s + o) 2^-k.
+//
+// Winner: the first maximum in column-major order.  The sweep is by ROWS, so "a later step only wins with a greater value" is wrong
+// here: a later row can hold the same value in a smaller column.  Per step the lane's greatest key bits(H) | (31 - r) is the
+// greatest value at its smallest column (columns rise with r); the lane replaces its best where the step's value is greater, or
+// equal in a smaller column (equal in the same column: the earlier row stays).  Across lanes slot_first_max: value, then smaller
+// column, then smaller row.  Exactness (float32 scaled by 2^-k, five mantissa bits free, decayed carries): DESIGN.md §3.8, L20.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sw_affine_pair_kernel.h"
+
+namespace mi355sw {
+
+// registers per lane of the compiled instances: a band of at most 16 R diagonals each.  A step costs all 16 R diagonals whatever W is, so
+// the list is dense where a mapper's bands lie: half widths 8, 16, 32, 64 are 17, 33, 65, 129 diagonals, on R = 2, 3, 5, 9
+constexpr int kBandR[] = {1, 2, 3, 5, 7, 9, 12, 16};
+constexpr int kBandRowsMax = 512;                                  // rows of a pair: what a slot's windows in LDS hold
+
+struct AffineBandProblem {
+  const uint8_t *x;          // bytes of the query
+  const uint8_t *y;          // CODES of the window of the reference
+  int32_t m, n;              // rows (1..kBandRowsMax), columns (>= 1)
+  int32_t lo, W;             // first diagonal j - i of the band inside the matrix, and its width (1..16 R)
+};
+
+template <int CTRL>
+__device__ __forceinline__ float band_dpp(float old, float v) {
+  return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp((int)__float_as_uint(old), (int)__float_as_uint(v), CTRL, 0xf, 0xf, false));
+}
+
+// sa: as for sw_affine_pair_kernel
+template <int R>
+__global__ __launch_bounds__(256) void sw_affine_band_kernel(const AffineBandProblem *probs, int nprob, const AffinePairArgs sa) {
+  static_assert(R >= 1 && R <= 32, "the key holds the register within the lane in five bits");
+  constexpr int YW = kBandRowsMax + 16 * R;                        // entries of a slot's window of y: cell (i, D) reads i - 1 + D
+  extern __shared__ __attribute__((aligned(16))) uint32_t bandsmem[];
+  __shared__ uint8_t ywin[16 * YW];                                // codes of y
+  __shared__ uint16_t xwin[16 * kBandRowsMax];                     // 4 * class of x[i]
+  float *tab = reinterpret_cast<float *>(bandsmem);                // [nrows][ncls]
+  const int tid = threadIdx.x;
+  const int l = tid & 15;
+  const int slot = tid >> 4;
+  const int pid = blockIdx.x * 16 + slot;
+  const bool active = pid < nprob;
+  const uint8_t *xb = nullptr, *yc = nullptr;
+  int m = 0, n = 0, lo = 0, W = 0;
+  if (active) { xb = probs[pid].x; yc = probs[pid].y; m = probs[pid].m; n = probs[pid].n; lo = probs[pid].lo; W = probs[pid].W; }
+  m = min(m, kBandRowsMax);                                        // (the host admits no more: the windows below hold no more)
+  for (int e = tid; e < sa.nrows * sa.ncls; e += 256) tab[e] = sa.tab[e];
+  // rows the wavefront runs: the longest query of its four slots
+  int steps = m;
+  steps = max(steps, __shfl_xor(steps, 16));
+  steps = max(steps, __shfl_xor(steps, 32));
+  const uint32_t row_bytes = 4u * (uint32_t)sa.ncls;
+  const uint32_t outside = (uint32_t)(sa.nrows - 1);
+  uint8_t *yw = ywin + slot * YW;
+  uint16_t *xw = xwin + slot * kBandRowsMax;
+  for (int p = l; p < steps + 16 * R; p += 16) {                   // entry p: column lo + 1 + p
+    const long long j = (long long)lo + 1 + p;
+    const uint32_t c = (j >= 1 && j <= (long long)n) ? (uint32_t)yc[j - 1] : outside;
+    yw[p] = (uint8_t)c;
+  }
+  for (int i = l; i < steps; i += 16) xw[i] = (uint16_t)(4u * (i < m ? (uint32_t)sa.cls[xb[i]] : (uint32_t)(sa.ncls - 1)));
+  __syncthreads();
+
+  const float ov = sa.open_s, ev = sa.ext_s;
+  const float nopen = -sa.open_s;                                  // outside the band: H = 0 is Ho = -o, and F = -o
+  const float ninf = -__builtin_inff();                            // in front of the slot's first lane: no carry
+  const float dec1 = (float)R * sa.ext_s, dec2 = 2.0f * dec1, dec4 = 4.0f * dec1, dec8 = 8.0f * dec1;
+  float Ho[R], F[R], cap[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) { Ho[r] = nopen; F[r] = nopen; cap[r] = (l * R + r < W) ? 1.0f : 0.0f; }
+  float bval = 0.0f;                                               // the lane's best value, first seen at (brow, bcol)
+  int brow = 0, bcol = 0x7fffffff;
+  const char *tab_b = reinterpret_cast<const char *>(tab);
+  const uint8_t *yl = yw + l * R;
+  const int col0 = lo + l * R + 1;                                 // column of register 0 in row 0 (it = 0 is row 1: + it)
+
+  for (int it = 0; it < steps; ++it) {
+    const uint32_t xo = xw[it];
+    const uint8_t *yp = yl + it;
+    // diagonal D + 1 of the previous row for the lane's last register: register 0 of the next lane
+    const float hnext = band_dpp<0x101>(nopen, Ho[0]);
+    const float fnext = band_dpp<0x101>(nopen, F[0]);
+    float Ht[R], q[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float hon = r + 1 < R ? Ho[r + 1] : hnext;             // H(i-1, j) - o
+      const float fpn = r + 1 < R ? F[r + 1] : fnext;              // F(i-1, j)
+      const float s = *reinterpret_cast<const float *>(tab_b + (__umul24((uint32_t)yp[r], row_bytes) + xo));
+      // plain C++ (an inline-asm definition costs a wait state in front of the VALU op that reads it on gfx950): the median with 0
+      // and 1 folds into the add's clamp, the maxima of results of arithmetic need no canonicalisation
+      const float x = __builtin_amdgcn_fmed3f(Ho[r] + s, 0.0f, 1.0f);
+      const float f = fmaxf(fpn - ev, hon);
+      const float ht = fmaxf(x, f);
+      const float a = ht - ov;
+      F[r] = f;
+      Ht[r] = ht;
+      q[r] = r == 0 ? a : fmaxf(q[r - 1] - ev, a);
+    }
+    // the lanes' totals: inclusive max-plus scan with decay R e per lane, then the exclusive carry
+    float G = q[R - 1];
+    G = fmaxf(G, band_dpp<0x111>(ninf, G) - dec1);
+    G = fmaxf(G, band_dpp<0x112>(ninf, G) - dec2);
+    G = fmaxf(G, band_dpp<0x114>(ninf, G) - dec4);
+    G = fmaxf(G, band_dpp<0x118>(ninf, G) - dec8);
+    float ce = band_dpp<0x111>(ninf, G);                           // E of register 0: everything left of the lane
+    float mx = 0.0f, tpend = 0.0f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float h = r == 0 ? fmaxf(Ht[0], ce) : fmaxf(fmaxf(Ht[r], q[r - 1]), ce);
+      h = fminf(h, cap[r]);
+      WaveKeyFold::cell<R>(r, h, mx, tpend);
+      Ho[r] = h - ov;
+      if (r + 1 < R) ce = ce - ev;
+    }
+    // the step's best against the lane's: greater value, or the same value in a smaller column (header: Winner)
+    const uint32_t kb = __float_as_uint(mx);
+    const float v = __uint_as_float(kb & ~31u);
+    const int col = col0 + it + (31 - (int)(kb & 31u));
+    const bool take = v > bval || (v == bval && col < bcol);
+    bval = take ? v : bval;
+    bcol = take ? col : bcol;
+    brow = take ? it + 1 : brow;
+  }
+
+  float bv = bval * sa.unscale;
+  long long bi = brow, bj = bcol;
+  if (!(bv > 0.0f)) { bv = 0.0f; bi = 0; bj = 0; }
+  slot_first_max(bv, bi, bj);
+  if (l == 0 && active) {
+    sa.best[pid] = bv;
+    sa.cell[2 * (size_t)pid] = bv > 0.0f ? bi : 0;
+    sa.cell[2 * (size_t)pid + 1] = bv > 0.0f ? bj : 0;
+  }
+}
+
+}  // namespace mi355sw

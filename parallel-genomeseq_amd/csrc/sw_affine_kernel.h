@@ -240,9 +240,17 @@ enum : int { kAffStop = 0, kAffDiag = 1, kAffE = 2, kAffF = 3, kAffEExt = 4, kAf
 // for the maximum; the value of the corner cell (m, nw) comes back in `best` of every lane.
 // E2E: the end-to-end model of include/mi355_sw.h — no floor, column 0 holds H = F = -(o + (i-1) e) and E = -inf (row 0 stays 0),
 // only row m competes and the first column wins (own_lo as before); a decision byte never holds kAffStop.
+// BAND (local model only): the banded model of include/mi355_sw.h in the window's LOCAL coordinates — only cells with
+// blo <= jl - i <= bhi are part of the matrix.  An out-of-band cell is written as H = 0, E = F = -inf (the header's second statement of
+// the model) wherever a later diagonal can read it: on diagonal d the in-band rows are ceil((d - bhi) / 2) .. floor((d - blo) / 2), the
+// two later diagonals read at most one row beyond them on either side, and the three rotating buffers hold nothing older; so the loop
+// runs over the in-band rows and one more on each side, work in proportion to the band.  Such a cell competes for nothing and gets no
+// decision byte: the walk never reaches it (its E and F never equal a positive H).  The layout of dirs is the unbanded one.
 struct AffineBest { float best; int64_t i, j; };
-template <bool TRACE, bool E2E = false>
-__device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, const AffineScoring sc, uint8_t *smem_raw) {
+template <bool TRACE, bool E2E = false, bool BAND = false>
+__device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, const AffineScoring sc, uint8_t *smem_raw, const int blo = 0,
+                                                        const int bhi = 0) {
+  static_assert(!(BAND && E2E), "the banded end-to-end model is not defined");
   const int lane = threadIdx.x;
   const int m = P.m, nw = P.nw;
   const int plen = m + 2;
@@ -278,8 +286,15 @@ __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, co
     }
     const int ilo = d - nw > 1 ? d - nw : 1;
     const int ihi = d - 1 < m ? d - 1 : m;
-    for (int i = ilo + lane; i <= ihi; i += 64) {
+    int i0 = ilo, i1 = ihi;
+    if (BAND) {                                                    // (floor division of possibly negative numbers: shifts)
+      const int b0 = ((d - bhi + 1) >> 1) - 1, b1 = ((d - blo) >> 1) + 1;
+      i0 = b0 > ilo ? b0 : ilo;
+      i1 = b1 < ihi ? b1 : ihi;
+    }
+    for (int i = i0 + lane; i <= i1; i += 64) {
       const int jl = d - i;
+      if (BAND && (jl - i < blo || jl - i > bhi)) { Hc[i] = 0.0f; Ec[i] = ninf; Fc[i] = ninf; continue; }
       const uint8_t xa = xs[i - 1], yb = P.y[jl - 1];
       const float s = sc.lut ? sc.lut[(int)xa * 256 + yb] : (xa == yb ? sc.match : sc.mismatch);
       const float eo = Hp[i] - go, fo = Hp[i - 1] - go;            // a gap opened from (i, jl-1) / (i-1, jl) on d-1
@@ -317,11 +332,22 @@ __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, co
   return AffineBest{best, bi, bj};
 }
 
-template <bool E2E = false>
-__global__ __launch_bounds__(64) void sw_affine_exact_kernel(const ExactProblem *probs, const AffineScoring sc) {
+// BAND: the problems carry their band (ExactBandProblem), in the window's local coordinates
+struct ExactBandProblem { ExactProblem e; int32_t blo, bhi; };
+template <bool BAND> struct AffineExactProblemOf { typedef ExactProblem type; };
+template <> struct AffineExactProblemOf<true> { typedef ExactBandProblem type; };
+__device__ __forceinline__ const ExactProblem &affine_problem(const ExactProblem &p) { return p; }
+__device__ __forceinline__ const ExactProblem &affine_problem(const ExactBandProblem &p) { return p.e; }
+__device__ __forceinline__ int affine_band_lo(const ExactProblem &) { return 0; }
+__device__ __forceinline__ int affine_band_hi(const ExactProblem &) { return 0; }
+__device__ __forceinline__ int affine_band_lo(const ExactBandProblem &p) { return p.blo; }
+__device__ __forceinline__ int affine_band_hi(const ExactBandProblem &p) { return p.bhi; }
+
+template <bool E2E = false, bool BAND = false>
+__global__ __launch_bounds__(64) void sw_affine_exact_kernel(const typename AffineExactProblemOf<BAND>::type *probs, const AffineScoring sc) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
-  const ExactProblem P = probs[blockIdx.x];
-  const AffineBest r = affine_exact_fill<false, E2E>(P, sc, smem_raw);
+  const ExactProblem P = affine_problem(probs[blockIdx.x]);
+  const AffineBest r = affine_exact_fill<false, E2E, BAND>(P, sc, smem_raw, affine_band_lo(probs[blockIdx.x]), affine_band_hi(probs[blockIdx.x]));
   const float best = r.best;
   const int64_t bi = r.i, bj = r.j;
   if (threadIdx.x == 0) {
@@ -350,12 +376,24 @@ struct AffineTraceProblem {
 // close the gap unless their extension bit is set (the opening wins a tie: the shortest gap).
 // E2E: the walk ends in row 0 and nowhere else.  Local column 0 of a clamped window is the model's column 0: the rest of x is one run
 // of F moves (x[i], '-') up to row 0; of an unclamped window it is status 1 as before (lemma L19).  There is no row window.
-template <bool E2E = false>
-__global__ __launch_bounds__(64) void sw_affine_trace_kernel(const AffineTraceProblem *probs, const AffineScoring sc) {
+// BAND: the window's band in its local coordinates (AffineTraceBandProblem); the walk is the same one, it never reaches a cell
+// outside the band (affine_exact_fill), and status 3 stays the guard of the window (L17 / L18 under a band: DESIGN.md §3.8).
+struct AffineTraceBandProblem { AffineTraceProblem t; int32_t blo, bhi; };
+template <bool BAND> struct AffineTraceProblemOf { typedef AffineTraceProblem type; };
+template <> struct AffineTraceProblemOf<true> { typedef AffineTraceBandProblem type; };
+__device__ __forceinline__ const AffineTraceProblem &affine_problem(const AffineTraceProblem &p) { return p; }
+__device__ __forceinline__ const AffineTraceProblem &affine_problem(const AffineTraceBandProblem &p) { return p.t; }
+__device__ __forceinline__ int affine_band_lo(const AffineTraceProblem &) { return 0; }
+__device__ __forceinline__ int affine_band_hi(const AffineTraceProblem &) { return 0; }
+__device__ __forceinline__ int affine_band_lo(const AffineTraceBandProblem &p) { return p.blo; }
+__device__ __forceinline__ int affine_band_hi(const AffineTraceBandProblem &p) { return p.bhi; }
+
+template <bool E2E = false, bool BAND = false>
+__global__ __launch_bounds__(64) void sw_affine_trace_kernel(const typename AffineTraceProblemOf<BAND>::type *probs, const AffineScoring sc) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
-  const AffineTraceProblem T = probs[blockIdx.x];
+  const AffineTraceProblem T = affine_problem(probs[blockIdx.x]);
   const ExactProblem &P = T.e;
-  const float corner = affine_exact_fill<true, E2E>(P, sc, smem_raw).best;
+  const float corner = affine_exact_fill<true, E2E, BAND>(P, sc, smem_raw, affine_band_lo(probs[blockIdx.x]), affine_band_hi(probs[blockIdx.x])).best;
   // the walk reads what other lanes of this wavefront stored: wait for the stores, then keep the loads behind the barrier
   __threadfence();
   __syncthreads();

@@ -11,11 +11,18 @@
     op-count model of both comes from mi355_sw_last_kernel, and the end-to-end result is checked once against the same call on the
     exact kernel (option no_affine_pairs).  Default --out: profiles/affine_pairs_e2e_n1.json.
 
+  * --band W_HALF[,W_HALF..]: the same pairs with the band [flank - w, flank + w] around the diagonal of the read's true locus (flank:
+    the columns the window starts in front of it), Context.affine_pairs_run(band_lo=, band_hi=) on sw_affine_band_kernel, against the
+    unbanded local instance on the same pairs, alternating in one process, medians.  A band is a different answer, so the check is
+    the banded exact kernel (option no_affine_band), once per width; kernel time, ratio and the op-count model (ops per cell x cells
+    of both kernels, from mi355_sw_last_kernel) come side by side.  Default --out: profiles/affine_pairs_band_n1.json.
+
 Prints ONE JSON line and writes it to --out; kernel times are those of mi355_sw_last_timings (device events), call times are wall
 clock around the call.
 
     python tools/affine_pairs_bench.py [--pairs 100000 --ref-len 5000000 --steps 5 --warmup 1 --out profiles/affine_pairs_n1.json]
     python tools/affine_pairs_bench.py --mode end_to_end
+    python tools/affine_pairs_bench.py --band 8,16,32,64
 """
 import argparse
 import json
@@ -40,25 +47,33 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mode", choices=("local", "end_to_end"), default="local")
+    ap.add_argument("--band", default=None, help="half widths of the band around the read's diagonal, comma separated")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.band is not None and args.mode != "local":
+        ap.error("--band needs the local mode")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "affine_pairs_e2e_n1.json" if args.mode == "end_to_end" else "affine_pairs_n1.json")
+        name = "affine_pairs_band_n1.json" if args.band is not None else "affine_pairs_e2e_n1.json" if args.mode == "end_to_end" else "affine_pairs_n1.json"
+        args.out = os.path.join(ROOT, "profiles", name)
     import __graft_entry__ as entry
     pgs = entry._load_package()
     ref = pgs.synth.dna(31, args.ref_len)
     reads, lefts, rights = [], np.zeros(args.pairs, dtype=np.int64), np.zeros(args.pairs, dtype=np.int64)
+    diag = np.zeros(args.pairs, dtype=np.int64)                       # the diagonal j - i of the read's true locus in its window
     for k in range(args.pairs):
         read, at = pgs.synth.read_from_ref(ref, 1000 + k, READ_LEN, sub_rate=0.03, indel_rate=0.02)[:2]
         reads.append(read.tobytes())
         lefts[k] = max(0, int(at) - FLANK)
         rights[k] = min(args.ref_len, int(at) + READ_LEN + FLANK)
+        diag[k] = int(at) - lefts[k]
     query = np.arange(args.pairs, dtype=np.int32)
     ctx = pgs.Context(0)
     ctx.set_reference(ref.tobytes())
     ctx.batch_upload(reads)
     if args.mode == "end_to_end":
         return e2e_against_local(args, ctx, reads, query, lefts, rights)
+    if args.band is not None:
+        return banded_against_local(args, ctx, reads, query, lefts, rights, diag)
     sides = {"pair_kernel": 0, "exact_kernel": 1}
     t = {s: dict(kernel_us=[], call_ms=[]) for s in sides}
     info, results = {}, {}
@@ -136,6 +151,60 @@ def e2e_against_local(args, ctx, reads, query, lefts, rights):
         f.write(text + "\n")
     print(text)
     return 0 if equal and line["not_above_local"] else 1
+
+
+def banded_against_local(args, ctx, reads, query, lefts, rights, diag):
+    """The unbanded local instance and the band kernel at every half width of --band on the same pairs, alternating; one JSON line."""
+    widths = [int(w) for w in str(args.band).split(",")]
+    sides = ["local"] + ["band_w%d" % w for w in widths]
+    bands = {"band_w%d" % w: (diag - w, diag + w) for w in widths}
+    t = {s: dict(kernel_us=[], call_ms=[]) for s in sides}
+    info, results = {}, {}
+    for step in range(args.warmup + args.steps):
+        for side in sides:                                          # alternating: all sides see the same clocks
+            kw = dict(band_lo=bands[side][0], band_hi=bands[side][1]) if side in bands else {}
+            t0 = time.perf_counter()
+            got = ctx.affine_pairs_run(query, lefts, rights, **kw, **SCORING)
+            wall = time.perf_counter() - t0
+            lt, ki = ctx.last_timings(), ctx.last_kernel()
+            info[side] = dict(path=ctx.last_path(), kernel=ki["name"], launches=lt["score_launches"], valu_ops_per_cell=ki["valu_ops_per_cell"],
+                              rows_per_lane=ki["rows_per_lane"], cells=lt["cells"])
+            results[side] = got
+            if step >= args.warmup:
+                t[side]["kernel_us"].append(lt["score_us"])
+                t[side]["call_ms"].append(wall * 1e3)
+    equal = {}
+    ctx.set_option("no_affine_band", 1)
+    try:
+        for side in bands:
+            exact = ctx.affine_pairs_run(query, lefts, rights, band_lo=bands[side][0], band_hi=bands[side][1], **SCORING)
+            equal[side] = all(np.array_equal(results[side][f], exact[f]) for f in ("score", "end_x", "end_y"))
+    finally:
+        ctx.set_option("no_affine_band", 0)
+    line = dict(bench="affine_pairs_bench", band_half_widths=widths, pairs=args.pairs, read_len=READ_LEN, window=READ_LEN + 2 * FLANK,
+                ref_len=args.ref_len, scoring="3/-3/5/1", steps=args.steps, results_equal_exact_kernel=equal)
+    for side in sides:
+        k_us, c_ms = statistics.median(t[side]["kernel_us"]), statistics.median(t[side]["call_ms"])
+        line[side] = dict(info[side], kernel_ms=k_us / 1e3, call_ms=c_ms, gcups_kernel=info[side]["cells"] / max(k_us, 1e-9) / 1e3,
+                          mean_score=float(results[side]["score"].mean()))
+    base = line["local"]
+    steps_local, steps_band = float((rights - lefts + 15).sum()), float(sum(len(r) for r in reads))
+    for side in bands:
+        b = line[side]
+        b["same_score_as_unbanded"] = float((results[side]["score"] == results["local"]["score"]).mean())
+        b["kernel_ratio_local_over_band"] = base["kernel_ms"] / max(b["kernel_ms"], 1e-9)
+        b["call_ratio_local_over_band"] = base["call_ms"] / max(b["call_ms"], 1e-9)
+        # ops of a lane per pair: steps x registers x ops per register — the local instance streams the window's columns + 15 of
+        # skew past its rows, the band kernel steps through the rows over all 16 R diagonals of its instance, whatever W is
+        b["model_ratio_local_over_band"] = (steps_local * base["rows_per_lane"] * base["valu_ops_per_cell"]) / \
+                                           (steps_band * b["rows_per_lane"] * b["valu_ops_per_cell"])
+    ctx.close()
+    text = json.dumps(line)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    print(text)
+    return 0 if all(equal.values()) else 1
 
 
 if __name__ == "__main__":
