@@ -436,6 +436,18 @@ class Context:
             out.append(a)
         return out[0], out[1]
 
+    def _pairs_call(self, name, m, blo, bhi, args):
+        """The entry point of a pairs call (name: mi355_sw_affine_pairs_run or _trace; args: npairs, query, lefts, rights, params,
+        outputs): `name`_band where bands are given, `name` itself in local mode, `name`_mode otherwise."""
+        if blo is not None:
+            i64 = C.POINTER(C.c_int64)
+            rc = getattr(self._L, name + "_band")(self._ctx, C.c_int(m), *args[:4], blo.ctypes.data_as(i64), bhi.ctypes.data_as(i64), *args[4:])
+        elif m == AFFINE_LOCAL:
+            rc = getattr(self._L, name)(self._ctx, *args)
+        else:
+            rc = getattr(self._L, name + "_mode")(self._ctx, C.c_int(m), *args)
+        self._chk(rc)
+
     def affine_pairs_run(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None, mode="local",
                          band_lo=None, band_hi=None):
         """Pair k = resident query query[k] against the window [lefts[k], rights[k]) of the resident reference, each a stand-alone
@@ -454,15 +466,7 @@ class Context:
         args = (C.c_size_t(n), q.ctypes.data_as(C.POINTER(C.c_int32)), lo.ctypes.data_as(C.POINTER(C.c_int64)),
                 hi.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p), score.ctypes.data_as(C.POINTER(C.c_float)),
                 ex.ctypes.data_as(C.POINTER(C.c_int64)), ey.ctypes.data_as(C.POINTER(C.c_int64)))
-        m = self._pair_mode(mode)
-        if blo is not None:
-            i64 = C.POINTER(C.c_int64)
-            self._chk(self._L.mi355_sw_affine_pairs_run_band(self._ctx, C.c_int(m), *args[:4], blo.ctypes.data_as(i64), bhi.ctypes.data_as(i64),
-                                                             *args[4:]))
-        elif m == AFFINE_LOCAL:
-            self._chk(self._L.mi355_sw_affine_pairs_run(self._ctx, *args))
-        else:
-            self._chk(self._L.mi355_sw_affine_pairs_run_mode(self._ctx, C.c_int(m), *args))
+        self._pairs_call("mi355_sw_affine_pairs_run", self._pair_mode(mode), blo, bhi, args)
         return dict(score=score, end_x=ex, end_y=ey)
 
     def affine_pairs_trace(self, query, lefts, rights, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0, lut=None, mode="local",
@@ -479,14 +483,7 @@ class Context:
         args = (C.c_size_t(n), q.ctypes.data_as(C.POINTER(C.c_int32)), lo.ctypes.data_as(C.POINTER(C.c_int64)),
                 hi.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p), res)
         m = self._pair_mode(mode)
-        if blo is not None:
-            i64 = C.POINTER(C.c_int64)
-            self._chk(self._L.mi355_sw_affine_pairs_trace_band(self._ctx, C.c_int(m), *args[:4], blo.ctypes.data_as(i64), bhi.ctypes.data_as(i64),
-                                                               *args[4:]))
-        elif m == AFFINE_LOCAL:
-            self._chk(self._L.mi355_sw_affine_pairs_trace(self._ctx, *args))
-        else:
-            self._chk(self._L.mi355_sw_affine_pairs_trace_mode(self._ctx, C.c_int(m), *args))
+        self._pairs_call("mi355_sw_affine_pairs_trace", m, blo, bhi, args)
         rows = [_take_affine(res[k], m == AFFINE_END_TO_END) for k in range(n)]
         self._L.mi355_sw_free_results(res, C.c_size_t(n))
         out = dict(score=np.array([r["score"] for r in rows], dtype=np.float32))

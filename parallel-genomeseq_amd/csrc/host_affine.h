@@ -1,11 +1,12 @@
-// host_affine.h — affine-gap score, end cell and traceback: parameter checks, the sw_affine_kernel sweep, the
-// sw_affine_exact_kernel behind it, sw_affine_trace_kernel (sw_affine_kernel.h) and, for references (ranges) of
-// at most 512 letters, sw_affine_prof_kernel (sw_affine_prof_kernel.h); for lists of (query, window) pairs, sw_affine_pair_kernel
-// (sw_affine_pair_kernel.h; end-to-end mode of the pairs calls: sw_affine_pair_e2e_kernel and the E2E instances of the exact and the
-// trace kernel, AffineCall::mode; pairs with a diagonal band: sw_affine_band_kernel, sw_affine_band_kernel.h, affine_band_stage, and the
-// BAND instances of the exact and the trace kernel).  The drivers affine_run (affine_prof_run, affine_sweep) and affine_pairs (affine_pair_stage) share one
-// AffineCall (affine_begin .. affine_end) and one affine_note_kernel, affine_exact_stage, affine_download and affine_class_table.
-// Part of the single translation unit mi355_sw.hip (included there, in order; not a standalone header).
+// host_affine.h — affine-gap score, end cell and traceback.  Part of the single translation unit mi355_sw.hip
+// (included there, in order; not a standalone header).  Two drivers:
+//   affine_run    every query of the batch against ranges of the reference: affine_prof_run (sw_affine_prof_kernel, ranges of at most
+//                 512 letters), affine_sweep (sw_affine_kernel) and the exact kernel behind both
+//   affine_pairs  a list of (query, window) pairs, local or end-to-end (AffineCall::mode), with or without a diagonal band per pair:
+//                 affine_pair_route sends each pair to affine_list_stage (sw_affine_pair_kernel, sw_affine_pair_e2e_kernel or
+//                 sw_affine_band_kernel) or to the exact kernel (its E2E or BAND instance)
+// Both share one AffineCall (affine_begin .. affine_end, the latter with affine_trace: sw_affine_trace_kernel), affine_exact_stage
+// (sw_affine_exact_kernel), affine_class_table, affine_download and affine_note_kernel.
 namespace {
 
 constexpr int64_t kAffineSweepMinCols = 1024;        // shorter references (ranges) are whole problems of the exact kernel
@@ -130,23 +131,35 @@ AffineKernel affine_kernel(int SL, int R) {
 
 size_t affine_exact_lds(int m) { return (size_t)7 * (m + 2) * 4 + (size_t)m + 16; }
 
+// A job of the exact kernel under a band, blo <= j - i <= bhi in its window's local coordinates: the BAND instance takes it.
+struct ExactBandJob : ExactJob { int32_t blo = 0, bhi = 0; };
+
+// The instance of the exact kernel for problems of either type: under a band, else by the call's mode.  (Plain overloads, the banded
+// one first: kernels stand in the code object in the order of their first mention; inside a template, or reordered, they would move.)
+inline auto affine_exact_instance(const AffineCall &, const ExactBandProblem *) { return &sw_affine_exact_kernel<false, true>; }
+inline auto affine_exact_instance(const AffineCall &c, const ExactProblem *) { return c.e2e() ? &sw_affine_exact_kernel<true> : &sw_affine_exact_kernel<false>; }
+
 // Runs jobs[lo, hi) on sw_affine_exact_kernel in one launch (ExactJob: q, ylo, nw, col_offset, own_lo, target -> best, ci, cj).
-// bands (may be null): [jobs.size()][2], the band of every job in its window's local coordinates — the BAND instance.
-int run_affine_exact(const AffineCall &c, std::vector<ExactJob> &jobs, size_t lo, size_t hi, const int32_t *bands = nullptr) {
+// Job: ExactJob, or ExactBandJob for the BAND instance, whose problem wraps the same ExactProblem (as affine_trace).
+template <class Job>
+int run_affine_exact(const AffineCall &c, std::vector<Job> &jobs, size_t lo, size_t hi) {
+  constexpr bool BAND = std::is_same<Job, ExactBandJob>::value;
+  typedef typename AffineExactProblemOf<BAND>::type Problem;
   mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q;
   const size_t n = hi - lo;
   if (n == 0) return 0;
   size_t lds = 0;
   for (size_t k = lo; k < hi; ++k) lds = std::max(lds, affine_exact_lds(q.len[jobs[k].q]));
   if (lds > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine: query longer than the exact kernel's LDS diagonals hold");
-  path_note(ctx, bands ? "affine_exact_band" : "affine_exact");
-  if (ctx->probs.ensure(n * (bands ? sizeof(ExactBandProblem) : sizeof(ExactProblem))) || ctx->outs_f.ensure(n * 4) || ctx->outs_i.ensure(n * 16))
+  path_note(ctx, BAND ? "affine_exact_band" : "affine_exact");
+  if (ctx->probs.ensure(n * sizeof(Problem)) || ctx->outs_f.ensure(n * 4) || ctx->outs_i.ensure(n * 16))
     return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(exact scratch) failed");
-  std::vector<ExactProblem> pr(n);
-  std::vector<ExactBandProblem> bpr(bands ? n : 0);
+  std::vector<Problem> pr(n);
   for (size_t k = 0; k < n; ++k) {
-    const ExactJob &j = jobs[lo + k];
-    ExactProblem &e = pr[k];
+    const Job &j = jobs[lo + k];
+    ExactProblem *ep;
+    if constexpr (BAND) { ep = &pr[k].e; pr[k].blo = j.blo; pr[k].bhi = j.bhi; } else ep = &pr[k];
+    ExactProblem &e = *ep;
     e.x = q.bytes.as<uint8_t>() + q.off[j.q];
     e.y = ref.bytes.as<uint8_t>() + j.ylo;
     e.m = q.len[j.q];
@@ -160,21 +173,11 @@ int run_affine_exact(const AffineCall &c, std::vector<ExactJob> &jobs, size_t lo
     e.hout = nullptr;
     e.best = ctx->outs_f.as<float>() + k;
     e.cell = ctx->outs_i.as<int64_t>() + 2 * k;
-    if (bands) { bpr[k].e = e; bpr[k].blo = bands[2 * (lo + k)]; bpr[k].bhi = bands[2 * (lo + k) + 1]; }
   }
-  if (bands) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, bpr.data(), n * sizeof(ExactBandProblem), hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactProblem), hipMemcpyHostToDevice, ctx->stream));
-  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(Problem), hipMemcpyHostToDevice, ctx->stream));
   AffineScoring sc;
   { int rc = affine_scoring(ctx, c.p, sc); if (rc) return rc; }
-  if (bands) {
-    launch_dyn_lds(&sw_affine_exact_kernel<false, true>, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactBandProblem>(), sc);
-  } else {
-    launch_dyn_lds(c.e2e() ? &sw_affine_exact_kernel<true> : &sw_affine_exact_kernel<false>, dim3((unsigned)n), dim3(64), lds, ctx->stream,
-                   ctx->probs.as<ExactProblem>(), sc);
-  }
+  launch_dyn_lds(affine_exact_instance(c, pr.data()), dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<Problem>(), sc);
   HIPCHK(ctx, hipGetLastError());
   std::vector<float> bf(n);
   std::vector<int64_t> ci(2 * n);
@@ -196,14 +199,15 @@ bool affine_whole_job(const AffineCall &c, int q, int64_t lo, int64_t n, size_t 
   return true;
 }
 
-// The exact kernel over all of `jobs`, 65536 per launch; its interval (ev[2]..ev[3]) goes to timings[1].
-// bands (may be null): as run_affine_exact.
-int affine_exact_stage(const AffineCall &c, std::vector<ExactJob> &jobs, const int32_t *bands = nullptr) {
+// The exact kernel over all of `jobs` (ExactJob, or ExactBandJob: the BAND instance), 65536 per launch; its interval
+// (ev[2]..ev[3]) goes to timings[1].
+template <class Job>
+int affine_exact_stage(const AffineCall &c, std::vector<Job> &jobs) {
   mi355_sw_ctx *ctx = c.ctx;
   if (jobs.empty()) return 0;
   HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
   for (size_t lo = 0; lo < jobs.size(); lo += 65536) {
-    { int rc = run_affine_exact(c, jobs, lo, std::min(jobs.size(), lo + 65536), bands); if (rc) return rc; }
+    { int rc = run_affine_exact(c, jobs, lo, std::min(jobs.size(), lo + 65536)); if (rc) return rc; }
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
   ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
@@ -537,12 +541,10 @@ int affine_trace(const AffineCall &c, const std::vector<AffineTraceItem> &items,
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr.data(), n * sizeof(Problem), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-    if constexpr (BAND) {
-      launch_dyn_lds(&sw_affine_trace_kernel<false, true>, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<Problem>(), sc);
-    } else {
-      launch_dyn_lds(c.e2e() ? &sw_affine_trace_kernel<true> : &sw_affine_trace_kernel<false>, dim3((unsigned)n), dim3(64), lds, ctx->stream,
-                     ctx->wprobs.as<AffineTraceProblem>(), sc);
-    }
+    void (*kern)(const Problem *, const AffineScoring);               // the instance: under a band, else by the call's mode
+    if constexpr (BAND) kern = &sw_affine_trace_kernel<false, true>;
+    else kern = c.e2e() ? &sw_affine_trace_kernel<true> : &sw_affine_trace_kernel<false>;
+    launch_dyn_lds(kern, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<Problem>(), sc);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     std::vector<int64_t> wo(3 * n);
@@ -767,186 +769,229 @@ constexpr size_t kAffinePairGroupProblems = (size_t)1 << 22;   // problems betwe
 
 size_t affine_pair_lds(const RefData &ref, const AffineProfPlan &plan) { return (size_t)ref.ncodes * (size_t)plan.nclass * 4; }
 
-// the instance of the least R of kPairR with 16 R >= rows (0: none)
+// The caller's list (validated there, not owned): pair k is query qid[k] of the batch against [lefts[k], rights[k]) of the reference,
+// counting only cells with band_lo[k] <= j - i <= band_hi[k] (both null: no bands).
+struct AffinePairList {
+  size_t npairs; const int32_t *qid; const int64_t *lefts, *rights, *band_lo, *band_hi;
+  int64_t cols(size_t k) const { return rights[k] - lefts[k]; }
+};
+
+// pair k as both list kernels take it: the query's bytes, the window's codes
+template <class Problem>
+void affine_pair_fill(const AffineCall &c, const AffinePairList &pl, size_t k, Problem &p) {
+  p.x = c.q.bytes.as<uint8_t>() + c.q.off[pl.qid[k]];
+  p.y = c.ref.codes.as<uint8_t>() + pl.lefts[k];
+  p.m = c.q.len[pl.qid[k]];
+  p.n = (int32_t)pl.cols(k);
+}
+
+// the instance of the least R of kPairR with 16 R >= rows, of kBandR with 16 R >= W diagonals (0: none)
 int affine_pair_R(int rows) {
   for (int R : kPairR) if (16 * R >= rows) return R;
   return 0;
 }
-typedef void (*AffinePairKernel)(const AffinePairProblem *, int, const AffinePairArgs);
-
-// sw_affine_pair_kernel over the pairs of `fast`: by instance, longest window first, so that the slots of a wavefront run similar
-// step counts; score / ends of the pairs with a positive maximum.
-int affine_pair_stage(const AffineCall &c, const int32_t *qid, const int64_t *lefts, const int64_t *rights, const AffineProfPlan &plan,
-                      std::vector<uint32_t> &fast, int mmax, float *score, int64_t *ends) {
-  mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q;
-  if (fast.empty()) return 0;
-  std::sort(fast.begin(), fast.end(), [&](uint32_t a, uint32_t b) {
-    const int Ra = affine_pair_R(q.len[qid[a]]), Rb = affine_pair_R(q.len[qid[b]]);
-    if (Ra != Rb) return Ra < Rb;
-    const int64_t na = rights[a] - lefts[a], nb = rights[b] - lefts[b];
-    return na != nb ? na > nb : a < b;
-  });
-  const int nl = ref.ncodes - 1, nrows = nl + 1, ncls = plan.nclass;
-  const size_t tab_floats = (size_t)nrows * ncls;
-  AffinePairArgs sa;
-  sa.nrows = nrows; sa.ncls = ncls;
-  int rc = affine_class_table(c, plan, mmax, tab_floats, 1, ncls, "hipMalloc(affine pair table) failed", sa.tab, sa);
-  if (rc) return rc;
-  for (size_t g0 = 0; g0 < fast.size(); g0 += kAffinePairGroupProblems) {
-    const size_t np = std::min(kAffinePairGroupProblems, fast.size() - g0);
-    const char *nomem = "affine pairs: allocation of the pair scratch failed";
-    if (ctx->wprobs.ensure(np * sizeof(AffinePairProblem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16) ||
-        ctx->pin_probs.ensure(np * sizeof(AffinePairProblem)))
-      return fail(ctx, MI355_SW_ENOMEM, nomem);
-    AffinePairProblem *pr = ctx->pin_probs.as<AffinePairProblem>();
-    for (size_t i = 0; i < np; ++i) {                              // one upload of the pair list
-      const uint32_t id = fast[g0 + i];
-      pr[i].x = q.bytes.as<uint8_t>() + q.off[qid[id]];
-      pr[i].y = ref.codes.as<uint8_t>() + lefts[id];
-      pr[i].m = q.len[qid[id]];
-      pr[i].n = (int32_t)(rights[id] - lefts[id]);
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr, np * sizeof(AffinePairProblem), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    for (size_t i0 = 0; i0 < np;) {                                // one launch per instance
-      const int R = affine_pair_R(pr[i0].m);
-      size_t i1 = i0;
-      double cells = 0;
-      while (i1 < np && affine_pair_R(pr[i1].m) == R) { cells += (double)pr[i1].m * (double)pr[i1].n; ++i1; }
-      AffinePairKernel kern = nullptr;
-      with_listed_R<kPairR>(R, [&](auto r) {
-        kern = c.e2e() ? &sw_affine_pair_e2e_kernel<decltype(r)::value> : &sw_affine_pair_kernel<decltype(r)::value>;
-      });
-      if (!kern) return fail(ctx, MI355_SW_ENODEV, "internal: no sw_affine_pair_kernel instance for this query");
-      sa.best = ctx->outs_f.as<float>() + i0;
-      sa.cell = ctx->outs_i.as<int64_t>() + 2 * i0;
-      launch_dyn_lds(kern, dim3((unsigned)((i1 - i0 + 15) / 16)), dim3(256), tab_floats * 4, ctx->stream,
-                     ctx->wprobs.as<AffinePairProblem>() + i0, (int)(i1 - i0), sa);
-      HIPCHK(ctx, hipGetLastError());
-      ctx->timings[4] += 1;
-      if (c.e2e()) {
-        // per step and lane: seven ops, the table address' v_add and the winner row's select per cell, and eleven of overhead (the
-        // local instance's twelve without the key's v_or); no key, no maximum3 fold.  The 16 border steps of a slot are not counted
-        path_note(ctx, "affine_pair_e2e[R=%d]", R);
-        affine_note_kernel(ctx, cells, MI355_SW_CELL_F32, 16, R, pr[i0].n, pr[i0].n, 0, (9.0 * R + 11.0) / (double)R,
-                           "sw_affine_pair_e2e_kernel<R=%d>", R);
-        i0 = i1;
-        continue;
-      }
-      path_note(ctx, "affine_pair[R=%d]", R);
-      // per step and lane: seven ops, the table address' v_add and the key's v_or per cell, a maximum3 per two cells for the
-      // step's best key, and twelve of overhead as compiled (two DPP moves and their two copies, the row pointer's multiply
-      // and add, the column, the code's address, and compare, two selects and the v_or of the value-only key update)
-      affine_note_kernel(ctx, cells, MI355_SW_CELL_F32, 16, R, pr[i0].n, pr[i0].n, 0, (9.0 * R + (R + 1) / 2 + 12.0) / (double)R,
-                         "sw_affine_pair_kernel<R=%d>", R);
-      i0 = i1;
-    }
-    const float *h_best = nullptr; const int64_t *h_cell = nullptr;
-    rc = affine_download(ctx, np, nomem, h_best, h_cell); if (rc) return rc;
-    for (size_t i = 0; i < np; ++i) {
-      const uint32_t id = fast[g0 + i];
-      if (!c.e2e() && !(h_best[i] > 0)) continue;
-      score[id] = h_best[i]; ends[2 * (size_t)id] = h_cell[2 * i]; ends[2 * (size_t)id + 1] = h_cell[2 * i + 1];
-    }
-  }
-  return 0;
-}
-
-// ---- sw_affine_band_kernel (sw_affine_band_kernel.h): pairs with a diagonal band ----------------------------------------------------
-// the instance of the least R of kBandR with 16 R >= W diagonals (0: none)
 int affine_band_R(int64_t W) {
   for (int R : kBandR) if (16 * (int64_t)R >= W) return R;
   return 0;
 }
-typedef void (*AffineBandKernel)(const AffineBandProblem *, int, const AffinePairArgs);
 
-// One banded pair as the band kernel and the banded exact job take it: the band clipped to the matrix.
+// A kernel family as affine_list_stage takes it: the problem and the item it is made from, the instance R of either, what comes first
+// among items of one R (the larger `size`), the instance itself, the cells of a problem and the description of a launch.
+// sw_affine_pair_kernel / sw_affine_pair_e2e_kernel (by the call's mode): an item is the pair's index.
+struct AffinePairFamily {
+  typedef AffinePairProblem Problem; typedef uint32_t Item;
+  const AffineCall &c; const AffinePairList &pl;
+  static constexpr const char *kNoInstance = "internal: no sw_affine_pair_kernel instance for this query";
+  bool keep_all() const { return c.e2e(); }                        // end-to-end: a score may be <= 0
+  static uint32_t id(Item a) { return a; }
+  int R(Item a) const { return affine_pair_R(c.q.len[pl.qid[a]]); }
+  static int R(const Problem &p) { return affine_pair_R(p.m); }
+  int64_t size(Item a) const { return pl.cols(a); }                // longest window first: the slots of a wavefront run similar step counts
+  void fill(Item a, Problem &p) const { affine_pair_fill(c, pl, a, p); }
+  static double cells(const Problem &p) { return (double)p.m * (double)p.n; }
+  auto kernel(int R) const {
+    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
+    with_listed_R<kPairR>(R, [&](auto r) {
+      kern = c.e2e() ? &sw_affine_pair_e2e_kernel<decltype(r)::value> : &sw_affine_pair_kernel<decltype(r)::value>;
+    });
+    return kern;
+  }
+  void note(double cells, int R, const Problem &first) const {
+    // end-to-end, per step and lane: seven ops, the table address' v_add and the winner row's select per cell, and eleven of overhead
+    // (the local instance's twelve without the key's v_or); no key, no maximum3 fold.  The 16 border steps of a slot are not counted
+    // local, per step and lane: seven ops, the table address' v_add and the key's v_or per cell, a maximum3 per two cells for the
+    // step's best key, and twelve of overhead as compiled (two DPP moves and their two copies, the row pointer's multiply
+    // and add, the column, the code's address, and compare, two selects and the v_or of the value-only key update)
+    const double ops = c.e2e() ? (9.0 * R + 11.0) / (double)R : (9.0 * R + (R + 1) / 2 + 12.0) / (double)R;
+    path_note(c.ctx, c.e2e() ? "affine_pair_e2e[R=%d]" : "affine_pair[R=%d]", R);
+    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, first.n, first.n, 0, ops,
+                       c.e2e() ? "sw_affine_pair_e2e_kernel<R=%d>" : "sw_affine_pair_kernel<R=%d>", R);
+  }
+};
+
+// One banded pair as the band kernel takes it: the band clipped to the matrix, its lowest diagonal and its width.
 struct AffineBandPair { uint32_t id; int32_t lo, W; };
 
-// sw_affine_band_kernel over the pairs of `band`: by instance, then longest query first, so that the slots of a wavefront leave
-// the row loop at similar steps; score / ends of the pairs with a positive maximum.  The table is affine_pair_stage's.
-int affine_band_stage(const AffineCall &c, const int32_t *qid, const int64_t *lefts, const int64_t *rights, const AffineProfPlan &plan,
-                      std::vector<AffineBandPair> &band, int mmax, float *score, int64_t *ends) {
-  mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q;
-  if (band.empty()) return 0;
-  std::sort(band.begin(), band.end(), [&](const AffineBandPair &a, const AffineBandPair &b) {
-    const int Ra = affine_band_R(a.W), Rb = affine_band_R(b.W);
+// sw_affine_band_kernel (sw_affine_band_kernel.h): pairs with a diagonal band; the table is the pair kernel's.
+struct AffineBandFamily {
+  typedef AffineBandProblem Problem; typedef AffineBandPair Item;
+  const AffineCall &c; const AffinePairList &pl;
+  static constexpr const char *kNoInstance = "internal: no sw_affine_band_kernel instance for this band";
+  bool keep_all() const { return false; }
+  static uint32_t id(const Item &a) { return a.id; }
+  static int R(const Item &a) { return affine_band_R(a.W); }
+  static int R(const Problem &p) { return affine_band_R(p.W); }
+  int64_t size(const Item &a) const { return c.q.len[pl.qid[a.id]]; }   // longest query first: the slots of a wavefront leave the row loop at similar steps
+  void fill(const Item &a, Problem &p) const { affine_pair_fill(c, pl, a.id, p); p.lo = a.lo; p.W = a.W; }
+  static double cells(const Problem &p) { return (double)p.m * (double)p.W; }
+  auto kernel(int R) const {
+    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
+    with_listed_R<kBandR>(R, [&](auto r) { kern = &sw_affine_band_kernel<decltype(r)::value>; });
+    return kern;
+  }
+  void note(double cells, int R, const Problem &) const {
+    path_note(c.ctx, "affine_band[R=%d]", R);
+    // per step and lane, as compiled: fourteen ops per register — the table address' multiply-add, the clamped add,
+    // sub / max for F, max for Ht, Ht - o, sub / max of the lane's scan, maximum3 for H, the cap's min, the key's v_or, H - o, the
+    // carry's sub and one move — a maximum3 per two registers for the step's key, and 29 of overhead: two DPP moves for F, five DPP
+    // moves (each with the move of its `old`) and four sub / max pairs for the lanes' scan, the explicit (value, column) compare
+    // with its selects, the window addresses.  All 16 R registers of a lane row work whatever W is: the model's time is rows x 16 R
+    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, 16 * R, 16 * R, 0, (14.0 * R + (R + 1) / 2 + 29.0) / (double)R,
+                       "sw_affine_band_kernel<R=%d>", R);
+  }
+};
+
+// The kernel of family F (AffinePairFamily, AffineBandFamily) over `items`: by instance, then F's larger size first, then index; one
+// class table for queries of at most mmax rows; per group of kAffinePairGroupProblems one upload of the descriptors, one launch per
+// instance and one download; score / ends of the pairs with a positive maximum (F::keep_all: of every pair).
+template <class F>
+int affine_list_stage(const F &f, const AffineProfPlan &plan, std::vector<typename F::Item> &items, int mmax, float *score, int64_t *ends) {
+  typedef typename F::Problem Problem;
+  const AffineCall &c = f.c; mi355_sw_ctx *ctx = c.ctx;
+  if (items.empty()) return 0;
+  std::sort(items.begin(), items.end(), [&](const typename F::Item &a, const typename F::Item &b) {
+    const int Ra = f.R(a), Rb = f.R(b);
     if (Ra != Rb) return Ra < Rb;
-    const int ma = q.len[qid[a.id]], mb = q.len[qid[b.id]];
-    return ma != mb ? ma > mb : a.id < b.id;
+    const int64_t sa = f.size(a), sb = f.size(b);
+    return sa != sb ? sa > sb : f.id(a) < f.id(b);
   });
-  const int nl = ref.ncodes - 1, nrows = nl + 1, ncls = plan.nclass;
+  const int nl = c.ref.ncodes - 1, nrows = nl + 1, ncls = plan.nclass;
   const size_t tab_floats = (size_t)nrows * ncls;
   AffinePairArgs sa;
   sa.nrows = nrows; sa.ncls = ncls;
   int rc = affine_class_table(c, plan, mmax, tab_floats, 1, ncls, "hipMalloc(affine pair table) failed", sa.tab, sa);
   if (rc) return rc;
-  for (size_t g0 = 0; g0 < band.size(); g0 += kAffinePairGroupProblems) {
-    const size_t np = std::min(kAffinePairGroupProblems, band.size() - g0);
+  for (size_t g0 = 0; g0 < items.size(); g0 += kAffinePairGroupProblems) {
+    const size_t np = std::min(kAffinePairGroupProblems, items.size() - g0);
     const char *nomem = "affine pairs: allocation of the pair scratch failed";
-    if (ctx->wprobs.ensure(np * sizeof(AffineBandProblem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16) ||
-        ctx->pin_probs.ensure(np * sizeof(AffineBandProblem)))
+    if (ctx->wprobs.ensure(np * sizeof(Problem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16) ||
+        ctx->pin_probs.ensure(np * sizeof(Problem)))
       return fail(ctx, MI355_SW_ENOMEM, nomem);
-    AffineBandProblem *pr = ctx->pin_probs.as<AffineBandProblem>();
-    for (size_t i = 0; i < np; ++i) {                              // one upload of the pair list
-      const AffineBandPair &b = band[g0 + i];
-      pr[i].x = q.bytes.as<uint8_t>() + q.off[qid[b.id]];
-      pr[i].y = ref.codes.as<uint8_t>() + lefts[b.id];
-      pr[i].m = q.len[qid[b.id]];
-      pr[i].n = (int32_t)(rights[b.id] - lefts[b.id]);
-      pr[i].lo = b.lo; pr[i].W = b.W;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr, np * sizeof(AffineBandProblem), hipMemcpyHostToDevice, ctx->stream));
+    Problem *pr = ctx->pin_probs.as<Problem>();
+    for (size_t i = 0; i < np; ++i) f.fill(items[g0 + i], pr[i]);  // one upload of the pair list
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr, np * sizeof(Problem), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     for (size_t i0 = 0; i0 < np;) {                                // one launch per instance
-      const int R = affine_band_R(pr[i0].W);
-      size_t i1 = i0;
-      double cells = 0;
-      while (i1 < np && affine_band_R(pr[i1].W) == R) { cells += (double)pr[i1].m * (double)pr[i1].W; ++i1; }
-      AffineBandKernel kern = nullptr;
-      with_listed_R<kBandR>(R, [&](auto r) { kern = &sw_affine_band_kernel<decltype(r)::value>; });
-      if (!kern) return fail(ctx, MI355_SW_ENODEV, "internal: no sw_affine_band_kernel instance for this band");
+      const int R = F::R(pr[i0]);
+      size_t i1 = i0; double cells = 0;
+      while (i1 < np && F::R(pr[i1]) == R) { cells += F::cells(pr[i1]); ++i1; }
+      const auto kern = f.kernel(R);
+      if (!kern) return fail(ctx, MI355_SW_ENODEV, F::kNoInstance);
       sa.best = ctx->outs_f.as<float>() + i0;
       sa.cell = ctx->outs_i.as<int64_t>() + 2 * i0;
       launch_dyn_lds(kern, dim3((unsigned)((i1 - i0 + 15) / 16)), dim3(256), tab_floats * 4, ctx->stream,
-                     ctx->wprobs.as<AffineBandProblem>() + i0, (int)(i1 - i0), sa);
+                     ctx->wprobs.as<Problem>() + i0, (int)(i1 - i0), sa);
       HIPCHK(ctx, hipGetLastError());
       ctx->timings[4] += 1;
-      path_note(ctx, "affine_band[R=%d]", R);
-      // per step and lane, as compiled: fourteen ops per register — the table address' multiply-add, the clamped add,
-      // sub / max for F, max for Ht, Ht - o, sub / max of the lane's scan, maximum3 for H, the cap's min, the key's v_or, H - o, the
-      // carry's sub and one move — a maximum3 per two registers for the step's key, and 29 of overhead: two DPP moves for F, five DPP
-      // moves (each with the move of its `old`) and four sub / max pairs for the lanes' scan, the explicit (value, column) compare
-      // with its selects, the window addresses.  All 16 R registers of a lane row work whatever W is: the model's time is rows x 16 R
-      affine_note_kernel(ctx, cells, MI355_SW_CELL_F32, 16, R, 16 * R, 16 * R, 0, (14.0 * R + (R + 1) / 2 + 29.0) / (double)R,
-                         "sw_affine_band_kernel<R=%d>", R);
+      f.note(cells, R, pr[i0]);
       i0 = i1;
     }
     const float *h_best = nullptr; const int64_t *h_cell = nullptr;
     rc = affine_download(ctx, np, nomem, h_best, h_cell); if (rc) return rc;
     for (size_t i = 0; i < np; ++i) {
-      const uint32_t id = band[g0 + i].id;
-      if (!(h_best[i] > 0)) continue;
-      score[id] = h_best[i]; ends[2 * (size_t)id] = h_cell[2 * i]; ends[2 * (size_t)id + 1] = h_cell[2 * i + 1];
+      const size_t id = f.id(items[g0 + i]);
+      if (!f.keep_all() && !(h_best[i] > 0)) continue;
+      score[id] = h_best[i]; ends[2 * id] = h_cell[2 * i]; ends[2 * id + 1] = h_cell[2 * i + 1];
     }
   }
   return 0;
 }
 
-// npairs independent problems: query qid[k] of `q` against [lefts[k], rights[k]) of `ref` (validated by the caller), each with
-// zero borders.  score[npairs]; ends[npairs][2] = row, column relative to the window start; tout (may be null): the traceback of
-// every pair (affine_trace).  A pair of 1..512 rows and 1..2^20 columns under the bounds of the header takes sw_affine_pair_kernel,
-// every other one is a whole problem of the exact kernel; results come back in the caller's order.
-// mode MI355_SW_AFFINE_END_TO_END: the end-to-end model of the header on the E2E instances of the same kernels; the pair kernel's
-// bounds are then those of affine_e2e_exact, and only an empty query or an empty window leaves the zeros (a score may be <= 0).
-// band_lo / band_hi (both null: none; local mode only, validated by the caller): pair k counts only cells with band_lo[k] <= j - i <=
-// band_hi[k] (include/mi355_sw.h, "banded pairs").  With the band clipped to the matrix, lo_e .. hi_e, a pair is one of four kinds:
-// zeros (the band misses the matrix), the unbanded pair (the band covers the matrix: the two paths above, untouched), a problem of
-// sw_affine_band_kernel (affine_band_stage: 1..512 rows, at most 256 diagonals, the pair kernel's table and float32 bounds), or a
-// banded job of the exact kernel.  A banded pair never runs on an unbanded kernel.
-int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, int mode, size_t npairs, const int32_t *qid, const int64_t *lefts,
-                 const int64_t *rights, const mi355_sw_affine_params &p, float *score, int64_t *ends, std::vector<TraceOut> *tout,
-                 const int64_t *band_lo = nullptr, const int64_t *band_hi = nullptr) {
+// Which kernel a pair takes.  kPairZeros: an empty query or window, or a band that misses the matrix — the zeroed outputs stand.  kPairKernel / kPairExact: the
+// unbanded pair, which a band that covers the matrix is too.  kPairBand / kPairExactBand: a banded pair; it never runs on an unbanded kernel.
+enum AffinePairKind { kPairZeros, kPairKernel, kPairBand, kPairExact, kPairExactBand };
+struct AffinePairRoute {
+  AffinePairKind kind; int64_t lo_e, hi_e;   // the band clipped to the matrix (no bands: the matrix, 1 - m .. n - 1)
+  bool banded() const { return kind == kPairBand || kind == kPairExactBand; }
+};
+
+// The route of pair k.  table_ok: the call's class table fits the list kernels (affine_pairs).  The list kernels take 1..512 rows
+// whose values are exact in float32 (local mode: the key's bits free, smax * (rows + 1) < 2^18; end-to-end: affine_e2e_exact) — the
+// pair kernel windows of at most 2^20 columns, the band kernel at most 256 diagonals (an instance of kBandR) of windows whose
+// columns fit int32 with room for the band; every other pair is a whole problem of the exact kernel (affine_pair_whole_job).
+AffinePairRoute affine_pair_route(const AffineCall &c, const AffinePairList &pl, bool table_ok, size_t k) {
+  const int64_t m = c.q.len[pl.qid[k]], n = pl.cols(k);
+  AffinePairRoute r{kPairZeros, 1 - m, n - 1};
+  if (m < 1 || n < 1) return r;
+  if (pl.band_lo) { r.lo_e = std::max(pl.band_lo[k], r.lo_e); r.hi_e = std::min(pl.band_hi[k], r.hi_e); }
+  if (r.lo_e > r.hi_e) return r;
+  const bool exact_f32 = c.e2e() ? affine_e2e_exact(c.t, (double)m) : (double)c.t.smax * ((double)m + 1.0) < kAffineProfBound;
+  if (r.lo_e != 1 - m || r.hi_e != n - 1) {
+    const bool list = table_ok && !opt().no_affine_band && m <= kBandRowsMax && affine_band_R(r.hi_e - r.lo_e + 1) != 0 && n <= 0x7fff0000 && exact_f32;
+    r.kind = list ? kPairBand : kPairExactBand;
+  } else {
+    r.kind = table_ok && m <= kMaxRowsFast && n <= kAffinePairColsMax && exact_f32 ? kPairKernel : kPairExact;
+  }
+  return r;
+}
+
+// why pair k, routed to the exact kernel, cannot run at all: outside its list kernel and too large for a whole problem
+std::string affine_pair_refusal(const AffineCall &c, const AffinePairList &pl, const AffinePairRoute &r, size_t k) {
+  const int m = c.q.len[pl.qid[k]];
+  char msg[360];
+  if (r.banded())
+    std::snprintf(msg, sizeof msg, "affine pairs: banded pair %zu (%d rows x %lld columns, %lld diagonals) is outside the band kernel "
+                  "(1..512 rows, at most 256 diagonals, smax * (rows + 1) < 2^18, gap_open < 2^18, a score table within 32 KiB%s) and has "
+                  "more than 2^26 cells for the exact kernel", k, m, (long long)pl.cols(k), (long long)(r.hi_e - r.lo_e + 1),
+                  opt().no_affine_band ? "; option no_affine_band is set" : "");
+  else
+    std::snprintf(msg, sizeof msg, "affine pairs: pair %zu (%d rows x %lld columns) is outside the pair kernel (1..512 rows, 1..2^20 columns, "
+                  "%s) and has more than 2^26 cells for the exact kernel", k, m, (long long)pl.cols(k),
+                  c.e2e() ? "end-to-end: 2 gap_open + (rows + 1) gap_extend - min(smin, 0) < 2^24, smax * (rows + 1) + gap_open < 2^24"
+                          : "smax * (rows + 1) < 2^18, gap_open < 2^18");
+  return msg;
+}
+
+// Pair k joins `jobs` as a whole problem of the exact kernel (ExactJob::index: the pair; ExactBandJob: under its clipped band), or the
+// refusal: too many cells or scores beyond float32's integers (affine_whole_job), or more rows than the kernel's LDS diagonals hold.
+template <class Job>
+int affine_pair_whole_job(const AffineCall &c, const AffinePairList &pl, const AffinePairRoute &r, size_t k, std::vector<Job> &jobs) {
+  Job j;
+  if (!affine_whole_job(c, pl.qid[k], pl.lefts[k], pl.cols(k), k, j)) return fail(c.ctx, MI355_SW_ENOTSUP, affine_pair_refusal(c, pl, r, k));
+  if (affine_exact_lds(c.q.len[pl.qid[k]]) > kExactLdsMax) return fail(c.ctx, MI355_SW_ENOTSUP, "affine pairs: query longer than the exact kernel's LDS diagonals hold");
+  if constexpr (std::is_same<Job, ExactBandJob>::value) { j.blo = (int32_t)r.lo_e; j.bhi = (int32_t)r.hi_e; }   // (|lo_e|, |hi_e| < 2^26 cells: int32)
+  jobs.push_back(j);
+  return 0;
+}
+
+// (best, cell) of whole jobs back to their pairs: of those with a positive maximum (keep_all: of every one)
+template <class Job>
+void affine_scatter_jobs(const std::vector<Job> &jobs, bool keep_all, float *score, int64_t *ends) {
+  for (const Job &j : jobs) {
+    if (!keep_all && !(j.best > 0)) continue;
+    score[j.index] = j.best; ends[2 * j.index] = j.ci; ends[2 * j.index + 1] = j.cj;
+  }
+}
+
+// The pairs of `pl`, each an independent problem with zero borders.  score[npairs]; ends[npairs][2] = row, column relative to the
+// window start; tout (may be null): the traceback of every pair (affine_trace).  Results come back in the caller's order.
+// Every pair goes where affine_pair_route sends it; the stages run in a fixed order: the pair kernel, the band kernel, the exact
+// kernel's unbanded and then its banded jobs, the traceback.
+// mode MI355_SW_AFFINE_END_TO_END: the end-to-end model of the header on the E2E instances of the same kernels (no bands: the caller
+// refuses them); only an empty query or an empty window leaves the zeros (a score may be <= 0).
+int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, int mode, const AffinePairList &pl, const mi355_sw_affine_params &p,
+                 float *score, int64_t *ends, std::vector<TraceOut> *tout) {
+  const size_t npairs = pl.npairs;
   for (size_t k = 0; k < npairs; ++k) { score[k] = 0.0f; ends[2 * k] = 0; ends[2 * k + 1] = 0; }
   if (tout) tout->assign(npairs, TraceOut());
   AffineCall c{ctx, ref, q, p, AffineTable(), mode};
@@ -966,87 +1011,38 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, int
   }
   const bool table_ok = plan.ok && affine_pair_lds(ref, plan) <= kAffinePairLdsMax;
 
-  // ---- which kernel a pair takes (ExactJob::index: the pair) ------------------------------------------------------------------------
   if (npairs > 0xFFFFFFFFull) return fail(ctx, MI355_SW_ENOTSUP, "affine pairs: more than 2^32 pairs");
   std::vector<uint32_t> fast;                                      // pair indices of sw_affine_pair_kernel
-  std::vector<ExactJob> jobs;
   std::vector<AffineBandPair> band;                                // pairs of sw_affine_band_kernel
-  std::vector<ExactJob> bjobs;                                     // banded jobs of the exact kernel, their bands in bbands
-  std::vector<int32_t> bbands;
-  std::vector<char> banded(band_lo ? npairs : 0, 0);               // the pair's alignment is confined to its band (the traceback)
+  std::vector<ExactJob> jobs;                                      // whole problems of the exact kernel
+  std::vector<ExactBandJob> bjobs;                                 // and of its BAND instance
+  std::vector<AffineTraceItem> items(tout ? npairs : 0);
   int mmax = 0, band_mmax = 0;
   for (size_t k = 0; k < npairs; ++k) {
-    const int m = q.len[qid[k]];
-    const int64_t n = rights[k] - lefts[k];
-    if (m < 1 || n < 1) continue;
-    const bool exact_f32 = c.e2e() ? affine_e2e_exact(c.t, (double)m) : (double)c.t.smax * ((double)m + 1.0) < kAffineProfBound;
-    if (band_lo) {
-      const int64_t lo_e = std::max<int64_t>(band_lo[k], 1 - (int64_t)m), hi_e = std::min<int64_t>(band_hi[k], n - 1);
-      if (lo_e > hi_e) continue;                                   // the band misses the matrix: zeros
-      if (lo_e != 1 - (int64_t)m || hi_e != n - 1) {               // (else the band covers the matrix: the unbanded pair, below)
-        const int64_t W = hi_e - lo_e + 1;
-        banded[k] = 1;
-        if (table_ok && !opt().no_affine_band && m <= kBandRowsMax && affine_band_R(W) != 0 && n <= 0x7fff0000 && exact_f32) {
-          band.push_back(AffineBandPair{(uint32_t)k, (int32_t)lo_e, (int32_t)W});
-          band_mmax = std::max(band_mmax, m);
-          continue;
-        }
-        ExactJob j;
-        if (!affine_whole_job(c, qid[k], lefts[k], n, k, j)) {
-          char msg[360];
-          std::snprintf(msg, sizeof msg, "affine pairs: banded pair %zu (%d rows x %lld columns, %lld diagonals) is outside the band kernel "
-                        "(1..512 rows, at most 256 diagonals, smax * (rows + 1) < 2^18, gap_open < 2^18, a score table within 32 KiB%s) and has "
-                        "more than 2^26 cells for the exact kernel", k, m, (long long)n, (long long)W,
-                        opt().no_affine_band ? "; option no_affine_band is set" : "");
-          return fail(ctx, MI355_SW_ENOTSUP, msg);
-        }
-        if (affine_exact_lds(m) > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine pairs: query longer than the exact kernel's LDS diagonals hold");
-        bjobs.push_back(j);
-        bbands.push_back((int32_t)lo_e); bbands.push_back((int32_t)hi_e);   // (|lo_e|, |hi_e| < 2^26 cells: int32)
-        continue;
-      }
+    const AffinePairRoute r = affine_pair_route(c, pl, table_ok, k);
+    const int m = q.len[pl.qid[k]];
+    if (tout) {
+      items[k] = AffineTraceItem{pl.qid[k], pl.lefts[k], 0.0f, 0, 0};
+      if (r.banded()) { items[k].banded = true; items[k].blo = r.lo_e; items[k].bhi = r.hi_e; }
     }
-    if (table_ok && m <= kMaxRowsFast && n <= kAffinePairColsMax && exact_f32) {
-      fast.push_back((uint32_t)k);
-      mmax = std::max(mmax, m);
-      continue;
+    switch (r.kind) {
+      case kPairZeros: break;
+      case kPairKernel: fast.push_back((uint32_t)k); mmax = std::max(mmax, m); break;
+      case kPairBand: band.push_back(AffineBandPair{(uint32_t)k, (int32_t)r.lo_e, (int32_t)(r.hi_e - r.lo_e + 1)}); band_mmax = std::max(band_mmax, m); break;
+      case kPairExact: rc = affine_pair_whole_job(c, pl, r, k, jobs); break;
+      case kPairExactBand: rc = affine_pair_whole_job(c, pl, r, k, bjobs); break;
     }
-    ExactJob j;
-    if (!affine_whole_job(c, qid[k], lefts[k], n, k, j)) {
-      char msg[360];
-      std::snprintf(msg, sizeof msg, "affine pairs: pair %zu (%d rows x %lld columns) is outside the pair kernel (1..512 rows, 1..2^20 columns, "
-                    "%s) and has more than 2^26 cells for the exact kernel", k, m, (long long)n,
-                    c.e2e() ? "end-to-end: 2 gap_open + (rows + 1) gap_extend - min(smin, 0) < 2^24, smax * (rows + 1) + gap_open < 2^24"
-                            : "smax * (rows + 1) < 2^18, gap_open < 2^18");
-      return fail(ctx, MI355_SW_ENOTSUP, msg);
-    }
-    if (affine_exact_lds(m) > kExactLdsMax) return fail(ctx, MI355_SW_ENOTSUP, "affine pairs: query longer than the exact kernel's LDS diagonals hold");
-    jobs.push_back(j);
+    if (rc) return rc;
   }
 
-  // ---- sw_affine_pair_kernel, then the exact kernel: every other pair as a whole problem ------------------------------------------
-  rc = affine_pair_stage(c, qid, lefts, rights, plan, fast, mmax, score, ends);
-  if (!rc) rc = affine_band_stage(c, qid, lefts, rights, plan, band, band_mmax, score, ends);
+  // (one class table per list stage, each for its own tallest query)
+  rc = affine_list_stage(AffinePairFamily{c, pl}, plan, fast, mmax, score, ends);
+  if (!rc) rc = affine_list_stage(AffineBandFamily{c, pl}, plan, band, band_mmax, score, ends);
   if (!rc) rc = affine_exact_stage(c, jobs);
-  if (!rc) rc = affine_exact_stage(c, bjobs, bbands.data());
+  if (!rc) rc = affine_exact_stage(c, bjobs);
   if (rc) return rc;
-  for (const ExactJob &j : jobs) {
-    if (!c.e2e() && !(j.best > 0)) continue;
-    score[j.index] = j.best; ends[2 * j.index] = j.ci; ends[2 * j.index + 1] = j.cj;
-  }
-  for (const ExactJob &j : bjobs) {
-    if (!(j.best > 0)) continue;
-    score[j.index] = j.best; ends[2 * j.index] = j.ci; ends[2 * j.index + 1] = j.cj;
-  }
-  std::vector<AffineTraceItem> items(tout ? npairs : 0);
-  for (size_t k = 0; k < items.size(); ++k) {
-    items[k] = AffineTraceItem{qid[k], lefts[k], 0.0f, 0, 0};
-    if (band_lo && banded[k]) {                                    // (clipped to the matrix: the same cells, and no overflow when shifted)
-      items[k].banded = true;
-      items[k].blo = std::max<int64_t>(band_lo[k], 1 - (int64_t)q.len[qid[k]]);
-      items[k].bhi = std::min<int64_t>(band_hi[k], rights[k] - lefts[k] - 1);
-    }
-  }
+  affine_scatter_jobs(jobs, c.e2e(), score, ends);
+  affine_scatter_jobs(bjobs, false, score, ends);
   return affine_end(c, items, score, ends, tout);
 }
 

@@ -10,7 +10,8 @@
 //   (sw_exact_kernel + sw_walk_kernel, host_exact.h: table scoring on short queries, whole uint8 problems)
 //   affine gaps (score, end cell, traceback): sw_affine_kernel sweep + sw_affine_exact / _trace_kernel, and
 //                      sw_affine_prof_kernel for references (ranges) of at most 512 letters,
-//                      sw_affine_pair_kernel for lists of (query, window) pairs                      host_affine.h
+//                      sw_affine_pair_kernel (end-to-end: sw_affine_pair_e2e_kernel) for lists of (query, window)
+//                      pairs and sw_affine_band_kernel for those with a diagonal band               host_affine.h
 //                      (entry points: affine_align_any, affine_batch_any, affine_pairs_any — one body per run / trace twin)
 // Problems the score kernel does not cover (see bucket_fast_ok) run 2+3 on the whole matrix.
 // The host code is one translation unit; the fragments below are included in order.
@@ -495,8 +496,8 @@ static int affine_pairs_any(mi355_sw_ctx *ctx, int mode, size_t npairs, const in
   std::vector<float> sc(npairs, 0.0f);
   std::vector<int64_t> ends(2 * npairs, 0);
   std::vector<TraceOut> tout(trace ? npairs : 0);
-  rc = affine_pairs(ctx, ctx->ref, ctx->batch, mode, npairs, query, lefts, rights, *params, sc.data(), ends.data(), trace ? &tout : nullptr,
-                    band_lo, band_hi);
+  const AffinePairList pl{npairs, query, lefts, rights, band_lo, band_hi};
+  rc = affine_pairs(ctx, ctx->ref, ctx->batch, mode, pl, *params, sc.data(), ends.data(), trace ? &tout : nullptr);
   if (rc) return rc;
   if (trace) {
     memset(outs, 0, npairs * sizeof *outs);

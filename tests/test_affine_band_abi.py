@@ -83,7 +83,8 @@ def test_there_is_an_instance_list_and_it_is_dispatched():
     assert re.search(r"template\s*<\s*int\s+R\s*>\s*__global__[^\n]*\bsw_affine_band_kernel\(", kernel)
     host = _read(CSRC, "host_affine.h")
     assert re.search(r"with_listed_R<kBandR>\(R,[^;]*&sw_affine_band_kernel<decltype\(r\)::value>", host, re.S)
-    assert re.search(r"int\s+affine_band_stage\(", host) and "affine_band[R=%d]" in host
+    # the band kernel's family runs on the list stage it shares with the pair kernel
+    assert re.search(r"int\s+affine_list_stage\(", host) and re.search(r"affine_list_stage\(AffineBandFamily\b", host) and "affine_band[R=%d]" in host
     # the shared fill takes the band as a template parameter whose default is the unbanded code
     assert re.search(r"template\s*<\s*bool\s+TRACE\s*,\s*bool\s+E2E\s*=\s*false\s*,\s*bool\s+BAND\s*=\s*false\s*>", _read(CSRC, "sw_affine_kernel.h"))
     assert '#include "sw_affine_band_kernel.h"' in _read(CSRC, "mi355_sw.hip")

@@ -336,6 +336,45 @@ def test_one_mixed_call_keeps_the_order(ctx, pgs):
     assert any(t.startswith("affine_pair[") for t in path), path
 
 
+def test_one_call_takes_all_five_routes(ctx, pgs):
+    """Zeros, the pair kernel, the band kernel, the exact kernel and the exact kernel under a band in one list, interleaved; the pair
+    stage's table is built for 150 rows and the band stage's for 37."""
+    y = dna(pgs, 9751, 3000)
+    lens = [150, 37, 513, 0]
+    at = [400, 900, 1500, 0]
+    xs = [read_of(pgs, y, 9760 + k, at[k], m) if m else b"" for k, m in enumerate(lens)]
+    cover = (-10 ** 9, 10 ** 9)
+    w513 = (at[2] - 50, at[2] + 513 + 50)                                 # the read's own diagonal is 50
+    first = (0, at[0] - 100, at[0] + 250, *cover)                         # 150 rows, full cover: the pair kernel, R = 10
+    pairs = [
+        first,
+        (2, *w513, 40, 60),                                               # 513 rows under a band: the exact kernel's BAND instance
+        (1, at[1] - 60, at[1] + 37 + 60, 52, 68),                         # 37 rows, 17 diagonals around its own (60): the band kernel
+        (0, at[0] - 100, at[0] + 250, 5000, 6000),                        # the band misses the matrix
+        (2, *w513, *cover),                                               # 513 rows, full cover: the exact kernel
+        (3, 0, 100, -5, 5),                                               # an empty query
+        first,
+    ]
+    assert instance_of(17) == BAND_R[1] and effective(xs, pairs, 2) == (52, 68)
+    exp = expected(xs, y, pairs)
+    # the checkers alone: the reads are found, the covering bands are the unbanded pairs, and the band of pair 1 binds (the read's
+    # dropped letter moves it to diagonal 51 and its inserted one back: both inside; the band that lacks diagonal 50 loses the head)
+    assert exp[0]["score"] > 3 * 150 * 0.8 and exp[2]["score"] > 3 * 37 * 0.7 and exp[4]["score"] > 3 * 513 * 0.8
+    assert exp[0]["score"] == affine_ref.locate(xs[0], y[first[1]:first[2]])[0] and exp[4]["score"] == affine_ref.locate(xs[2], y[w513[0]:w513[1]])[0]
+    assert exp[1]["score"] == exp[4]["score"] and "D" in exp[1]["cigar"] and "I" in exp[1]["cigar"]
+    assert 0 < br.trace(xs[2], y[w513[0]:w513[1]], 51, 60, **DEFAULT)["score"] < exp[1]["score"]
+    assert exp[3]["score"] == exp[5]["score"] == 0 and exp[0] == exp[6]
+    check(ctx, xs, y, pairs, exp=exp)
+    for off in (0, 1):
+        got, path = call(ctx, pairs, trace=True, off=off)
+        for f in TRACE_FIELDS:
+            assert got[f][0] == got[f][-1], (off, f)
+        if off == 0:
+            assert [t for t in path if t.startswith("affine_pair[")] == ["affine_pair[R=10]"], path
+            assert band_tags(path) == ["affine_band[R=%d]" % BAND_R[1]], path
+            assert "affine_exact" in path and "affine_exact_band" in path, path
+
+
 # ---- tables -------------------------------------------------------------------------------------------------------------------------------
 def test_a_25_by_21_table_and_a_table_beyond_32_kib(ctx, pgs):
     lut = pgs.synth.make_lut(4242, 1.0)
