@@ -370,6 +370,81 @@ int mi355_sw_affine_pairs_trace_band(mi355_sw_ctx *ctx, int mode, size_t npairs,
                                      const int64_t *rights, const int64_t *band_lo, const int64_t *band_hi,
                                      const mi355_sw_affine_params *params, mi355_sw_result *outs);
 
+/* ---- lists of pairs, anchored seed extension, forward and backward (BWA-MEM ksw_extend, minimap2 ksw_extz) ----------------
+ * A mapper starts AT its seed and extends away from it: the alignment is anchored at the seed's edge and ends where the score
+ * peaks (a soft clip) or at the read's end; the mapper picks between the two by comparing the two scores, to the right of the
+ * seed and again to the left on both strings reversed.
+ *
+ * Pair k is the letters [q_lo[k], q_hi[k]) of resident query query[k] against the window [lefts[k], rights[k]) of the resident
+ * reference, in direction backward[k].  Call the letters x (m = q_hi - q_lo rows) and the window y (n columns).
+ * Forward (backward[k] == 0): x and y as they stand; the anchor is in front of x[1] and y[1].  Backward: x and y both reversed;
+ * the anchor is behind the query range's last letter and the window's last column: the left extension of a seed.  It is DEFINED
+ * as the forward model on the two reversed strings.  With s = f(x[i], y[j]), o = gap_open, e = gap_extend, o >= e > 0:
+ *
+ *   E(i,j) = max(E(i,j-1) - e, H(i,j-1) - o)
+ *   F(i,j) = max(F(i-1,j) - e, H(i-1,j) - o)
+ *   H(i,j) = max(H(i-1,j-1) + s, E(i,j), F(i,j))                          no zero floor
+ *   H(0,0) = 0
+ *   H(0,j) = E(0,j) = -(o + (j-1) e), F(0,j) = -infinity   for j >= 1     the anchor is fixed: a flank is a gap
+ *   H(i,0) = F(i,0) = -(o + (i-1) e), E(i,0) = -infinity   for i >= 1
+ *
+ * Best extension: score = max of H over 0 <= i <= m, 0 <= j <= n.  It is >= 0, because cell (0,0) competes; score 0 means
+ * "extend nothing".  end_x, end_y = the first maximum in column-major order (smallest column, then smallest row), reported as
+ * lengths: the letters of x and the columns of y the extension consumes.  A forward extension covers query letters
+ * [q_lo, q_lo + end_x) and reference columns [left, left + end_y); a backward extension covers [q_hi - end_x, q_hi) and
+ * [right - end_y, right).  Score 0 always comes with end 0 / 0: column 0 wins every tie, and the border cells are negative.
+ *
+ * To the end: to_end_score = max over 0 <= j <= n of H(m, j), of any sign; to_end_y = the smallest such j, which may be 0: the
+ * whole of x as one insertion.  This is what a mapper compares with score + clip penalty; the library does not take that decision.
+ *
+ * Traceback: the priorities of the other models (diagonal over E over F, opening wins a tie with extending).  The walk starts in
+ * state M at the chosen cell — the best extension's by default, (m, to_end_y) where to_end[k] != 0 — and stops at (0,0) and
+ * nowhere else; in row 0 only E moves happen, in column 0 only F moves.  The strings run from the far end to the anchor: a forward
+ * pair's cons_x / cons_y are reversed, as in every mi355_sw_result, and a backward pair's strings therefore read left to right in
+ * the original strings.  The value of the strings under (f, o, e) is the traced cell's score; cons_x without '-' has end_x
+ * letters and cons_y without '-' has end_y letters; pos = 1 when the strings hold a letter of y, else 0.  outs[k].score / end_x /
+ * end_y describe the traced alignment.
+ *
+ * Degenerate pairs.  m = 0: everything is 0 and the strings are empty.  n = 0, m >= 1: the best extension is 0 / 0 / 0,
+ * to_end_score = -(o + (m-1) e) and to_end_y = 0; its traceback is m letters of x against m '-'; the host fills this in, no
+ * kernel runs.
+ *
+ * Arguments: to_end_score and to_end_y may both be NULL; to_end == NULL: the best extension for every pair; backward == NULL:
+ * every pair forward; q_lo == q_hi == NULL: the whole query.  Argument checks and their order follow the pairs calls.
+ * MI355_SW_EINVAL: list is NULL; query, lefts or rights is NULL; exactly one of q_lo / q_hi is NULL; q_lo < 0, q_hi < q_lo or
+ * q_hi > the query's length; the pairs calls' own checks fail.  npairs == 0 returns 0 and writes nothing.  After any error the
+ * context stays usable.
+ *
+ * Dispatch: the extension instance of the pair kernel for 1..512 rows and 1..2^20 columns while the score table fits 32 KiB of
+ * LDS and the admission test holds — every value the kernel forms is an integer below 2^24 in magnitude, and a positive score
+ * leaves the winner's key five mantissa bits; with smin (smax) the least (greatest) substitution score, both taken with 0:
+ *     3 gap_open + (rows + columns) gap_extend - smin < 2^24,   smax rows + gap_open < 2^24   and   smax (rows + 1) < 2^18
+ * (H(i,j) >= -(2o + (i+j-2) e) by the path along row 0 and down column j; H - o, E, F >= -(3o + (m+n-2) e), and one e lower
+ * before their maximum; the diagonal term is (H - o) + (s + o) with s + o >= smin + o) — else the exact kernel (2^26 cells,
+ * about 5 600 rows; 3 gap_open + (rows + columns) gap_extend < 2^24, 2 gap_open + (rows + columns) gap_extend - smin < 2^24,
+ * smax (rows + 1) < 2^24), else MI355_SW_ENOTSUP naming the pair.  The traceback fills the whole rectangle from the anchor to
+ * the traced cell: at most 2^30 decision bytes and about 5 600 rows, else MI355_SW_ENOTSUP.  Option no_affine_pairs sends every
+ * pair to the exact kernel.  A backward pair runs as the forward pair on window [N - right, N - left) and letters
+ * [len - q_hi, len - q_lo) of reversed copies of the reference and the batch, which the context builds on the device at the first
+ * backward pair and keeps until the next mi355_sw_set_reference / mi355_sw_batch_upload; calls without a backward pair allocate
+ * nothing for them.
+ * mi355_sw_last_path: "affine_pair_ext[R=..]" once per instance of the pair kernel that ran, "affine_exact" and "affine_trace" as
+ * above.  mi355_sw_last_timings and mi355_sw_last_kernel as for the pairs calls; the kernel's name is
+ * "sw_affine_pair_ext_kernel<R=..>", with its ops per cell.  DESIGN.md §3.8, L21. */
+typedef struct {
+  size_t npairs;
+  const int32_t *query;            /* resident query of pair k */
+  const int32_t *q_lo, *q_hi;      /* its letters [q_lo, q_hi), 0-based, half open; both NULL: the whole query */
+  const int64_t *lefts, *rights;   /* the window, as in mi355_sw_affine_pairs_run */
+  const uint8_t *backward;         /* NULL: every pair forward */
+} mi355_sw_extend_list;
+
+int mi355_sw_affine_extend_run(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const mi355_sw_affine_params *params,
+                               float *score, int64_t *end_x, int64_t *end_y, float *to_end_score, int64_t *to_end_y);
+int mi355_sw_affine_extend_trace(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const mi355_sw_affine_params *params,
+                                 const uint8_t *to_end /* NULL: best extension for every pair */,
+                                 mi355_sw_result *outs, float *to_end_score, int64_t *to_end_y);
+
 /* Host-only helper: piece ranges [left,right). Returns MI355_SW_ERANGE where the reference asserts. */
 int mi355_sw_make_string_range(int npiece, int64_t shortlen, int64_t longlen, float overlap_ratio,
                                int64_t *lefts, int64_t *rights);

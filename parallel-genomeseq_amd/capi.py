@@ -26,6 +26,7 @@ EXPORTS = [
     "mi355_sw_affine_align_trace", "mi355_sw_affine_batch_trace", "mi355_sw_affine_pairs_run", "mi355_sw_affine_pairs_trace",
     "mi355_sw_prefix_values", "mi355_sw_affine_pairs_run_mode", "mi355_sw_affine_pairs_trace_mode",
     "mi355_sw_affine_pairs_run_band", "mi355_sw_affine_pairs_trace_band",
+    "mi355_sw_affine_extend_run", "mi355_sw_affine_extend_trace",
 ]
 AFFINE_LOCAL, AFFINE_END_TO_END = 0, 1                 # mode of the affine pairs calls (include/mi355_sw.h)
 AFFINE_MODES = {"local": AFFINE_LOCAL, "end_to_end": AFFINE_END_TO_END}
@@ -40,6 +41,12 @@ class Params(C.Structure):
 class AffineParams(C.Structure):
     _fields_ = [("lut", C.POINTER(C.c_float)), ("match", C.c_float), ("mismatch", C.c_float),
                 ("gap_open", C.c_float), ("gap_extend", C.c_float)]
+
+
+class ExtendList(C.Structure):
+    """mi355_sw_extend_list: the pairs of the extension calls."""
+    _fields_ = [("npairs", C.c_size_t), ("query", C.POINTER(C.c_int32)), ("q_lo", C.POINTER(C.c_int32)), ("q_hi", C.POINTER(C.c_int32)),
+                ("lefts", C.POINTER(C.c_int64)), ("rights", C.POINTER(C.c_int64)), ("backward", C.POINTER(C.c_uint8))]
 
 
 class Result(C.Structure):
@@ -488,6 +495,81 @@ class Context:
         self._L.mi355_sw_free_results(res, C.c_size_t(n))
         out = dict(score=np.array([r["score"] for r in rows], dtype=np.float32))
         for k in ("end_x", "end_y", "begin_x", "begin_y", "pos"):
+            out[k] = np.array([r[k] for r in rows], dtype=np.int64)
+        for k in ("cons_x", "cons_y", "cigar"):
+            out[k] = [r[k] for r in rows]
+        return out
+
+    @staticmethod
+    def _per_pair(v, n, dtype, name):
+        """None, or an array of n values of `dtype`: v is a scalar for every pair, or an array per pair."""
+        if v is None:
+            return None
+        a = np.full(n, v, dtype=dtype) if np.ndim(v) == 0 else np.ascontiguousarray(v, dtype=dtype).reshape(-1)
+        if len(a) != n:
+            raise ValueError("%s must be a scalar or hold one value per pair" % name)
+        return a
+
+    def _extend_list(self, query, lefts, rights, q_lo, q_hi, backward):
+        """(mi355_sw_extend_list, n, the arrays it points into)."""
+        q, lo, hi = self._pair_arrays(query, lefts, rights)
+        n = len(q)
+        if (q_lo is None) != (q_hi is None):
+            raise ValueError("q_lo and q_hi must both be given, or neither")
+        ql, qh = self._per_pair(q_lo, n, np.int32, "q_lo"), self._per_pair(q_hi, n, np.int32, "q_hi")
+        back = self._per_pair(None if backward is None else np.asarray(backward).astype(bool), n, np.uint8, "backward")
+        i32, i64, u8 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+        el = ExtendList()
+        el.npairs = n
+        el.query, el.lefts, el.rights = q.ctypes.data_as(i32), lo.ctypes.data_as(i64), hi.ctypes.data_as(i64)
+        if ql is not None:
+            el.q_lo, el.q_hi = ql.ctypes.data_as(i32), qh.ctypes.data_as(i32)
+        if back is not None:
+            el.backward = back.ctypes.data_as(u8)
+        return el, n, (q, lo, hi, ql, qh, back)
+
+    def affine_extend_run(self, query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0,
+                          gap_extend=1.0, lut=None):
+        """Anchored seed extension (mi355_sw_affine_extend_run): pair k = the letters [q_lo[k], q_hi[k]) of resident query query[k]
+        (both None: the whole query) against the window [lefts[k], rights[k]) of the resident reference, anchored in front of both;
+        backward[k]: anchored behind both, on both strings reversed (the left extension of a seed).  No zero floor, and both flanks
+        cost a gap.  Dict of arrays: score (>= 0), end_x, end_y — the best extension, as LENGTHS of query letters and reference
+        columns consumed from the anchor — and to_end_score (any sign), to_end_y: the best extension that reaches the query
+        range's end.  q_lo, q_hi and backward each take a scalar for every pair, or an array."""
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        el, n, arrays = self._extend_list(query, lefts, rights, q_lo, q_hi, backward)
+        score, tscore = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+        ex, ey, ty = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        f32, i64 = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+        self._chk(self._L.mi355_sw_affine_extend_run(self._ctx, C.byref(el), C.byref(p), score.ctypes.data_as(f32), ex.ctypes.data_as(i64),
+                                                     ey.ctypes.data_as(i64), tscore.ctypes.data_as(f32), ty.ctypes.data_as(i64)))
+        return dict(score=score, end_x=ex, end_y=ey, to_end_score=tscore, to_end_y=ty)
+
+    def affine_extend_trace(self, query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0,
+                            gap_extend=1.0, lut=None, to_end=None):
+        """affine_extend_run with the traceback (mi355_sw_affine_extend_trace): score, end_x, end_y describe the TRACED alignment —
+        the best extension, or where to_end[k] is set (a scalar for every pair, or an array) the one that ends in (m, to_end_y) —
+        with pos, cons_x, cons_y and cigar; to_end_score / to_end_y as affine_extend_run.  The strings run from the far end to the
+        anchor: reversed for a forward pair, left to right in the original strings for a backward pair.  The CIGAR is in reading
+        order for both directions."""
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        el, n, arrays = self._extend_list(query, lefts, rights, q_lo, q_hi, backward)
+        te = self._per_pair(None if to_end is None else np.asarray(to_end).astype(bool), n, np.uint8, "to_end")
+        res = (Result * max(1, n))()
+        tscore, ty = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int64)
+        self._chk(self._L.mi355_sw_affine_extend_trace(self._ctx, C.byref(el), C.byref(p),
+                                                       te.ctypes.data_as(C.POINTER(C.c_uint8)) if te is not None else None, res,
+                                                       tscore.ctypes.data_as(C.POINTER(C.c_float)), ty.ctypes.data_as(C.POINTER(C.c_int64))))
+        back = arrays[5]
+        rows = []
+        for k in range(n):
+            r = _take(res[k])
+            b = back is not None and bool(back[k])
+            r["cigar"] = cigar(r["cons_x"][::-1], r["cons_y"][::-1]) if b else cigar(r["cons_x"], r["cons_y"])
+            rows.append(r)
+        self._L.mi355_sw_free_results(res, C.c_size_t(n))
+        out = dict(score=np.array([r["score"] for r in rows], dtype=np.float32), to_end_score=tscore, to_end_y=ty)
+        for k in ("end_x", "end_y", "pos"):
             out[k] = np.array([r[k] for r in rows], dtype=np.int64)
         for k in ("cons_x", "cons_y", "cigar"):
             out[k] = [r[k] for r in rows]

@@ -1,11 +1,13 @@
 // host_affine.h — affine-gap score, end cell and traceback.  Part of the single translation unit mi355_sw.hip
-// (included there, in order; not a standalone header).  Two drivers:
+// (included there, in order; not a standalone header).  Three drivers:
 //   affine_run    every query of the batch against ranges of the reference: affine_prof_run (sw_affine_prof_kernel, ranges of at most
 //                 512 letters), affine_sweep (sw_affine_kernel) and the exact kernel behind both
 //   affine_pairs  a list of (query, window) pairs, local or end-to-end (AffineCall::mode), with or without a diagonal band per pair:
 //                 affine_pair_route sends each pair to affine_list_stage (sw_affine_pair_kernel, sw_affine_pair_e2e_kernel or
 //                 sw_affine_band_kernel) or to the exact kernel (its E2E or BAND instance)
-// Both share one AffineCall (affine_begin .. affine_end, the latter with affine_trace: sw_affine_trace_kernel), affine_exact_stage
+//   affine_extend the anchored seed extension of a list of (letters of a query, window) pairs, forward or backward: the same list
+//                 stage on sw_affine_pair_ext_kernel, sw_affine_exact_ext_kernel and sw_affine_trace_ext_kernel behind it
+// All share one AffineCall (affine_begin .. affine_end, the latter with affine_trace: sw_affine_trace_kernel), affine_exact_stage
 // (sw_affine_exact_kernel), affine_class_table, affine_download and affine_note_kernel.
 namespace {
 
@@ -72,6 +74,9 @@ int affine_table(mi355_sw_ctx *ctx, const RefData &ref, const mi355_sw_affine_pa
   return 0;
 }
 
+// AffineCall::mode of the extension calls: internal, beside the two public values (the public enum keeps its two members)
+constexpr int kAffineModeExt = 2;
+
 // One affine call, as every stage below takes it: where it runs, on what, its scoring and the table of that scoring
 struct AffineCall {
   mi355_sw_ctx *ctx;
@@ -80,6 +85,7 @@ struct AffineCall {
   AffineTable t;
   int mode = MI355_SW_AFFINE_LOCAL;          // pairs calls: MI355_SW_AFFINE_END_TO_END (no floor, row m wins; include/mi355_sw.h)
   bool e2e() const { return mode == MI355_SW_AFFINE_END_TO_END; }
+  bool ext() const { return mode == kAffineModeExt; }              // the anchored model of the extension calls (affine_extend)
 };
 
 // End-to-end mode: are all values of a problem of m rows integers below 2^24 in magnitude (exact in float32, no bit reserved)?
@@ -99,7 +105,7 @@ bool affine_e2e_whole_exact(const AffineTable &t, double m) {
 // stand; negative: the error.
 int affine_begin(AffineCall &c) {
   { int rc = affine_table(c.ctx, c.ref, c.p, c.t); if (rc) return rc; }
-  if (c.t.smax <= 0 && !c.e2e()) return 1;                         // no positive cell: every maximum is 0 (end-to-end: no floor)
+  if (c.t.smax <= 0 && !c.e2e() && !c.ext()) return 1;             // no positive cell: every maximum is 0 (end-to-end, anchored: no floor)
   HIPCHK(c.ctx, hipEventRecord(c.ctx->ev[4], c.ctx->stream));
   return 0;
 }
@@ -802,6 +808,7 @@ struct AffinePairFamily {
   typedef AffinePairProblem Problem; typedef uint32_t Item;
   const AffineCall &c; const AffinePairList &pl;
   static constexpr const char *kNoInstance = "internal: no sw_affine_pair_kernel instance for this query";
+  static constexpr int kOuts = 1;                                  // (best, cell) a problem writes
   bool keep_all() const { return c.e2e(); }                        // end-to-end: a score may be <= 0
   static uint32_t id(Item a) { return a; }
   int R(Item a) const { return affine_pair_R(c.q.len[pl.qid[a]]); }
@@ -837,6 +844,7 @@ struct AffineBandFamily {
   typedef AffineBandProblem Problem; typedef AffineBandPair Item;
   const AffineCall &c; const AffinePairList &pl;
   static constexpr const char *kNoInstance = "internal: no sw_affine_band_kernel instance for this band";
+  static constexpr int kOuts = 1;
   bool keep_all() const { return false; }
   static uint32_t id(const Item &a) { return a.id; }
   static int R(const Item &a) { return affine_band_R(a.W); }
@@ -863,7 +871,8 @@ struct AffineBandFamily {
 
 // The kernel of family F (AffinePairFamily, AffineBandFamily) over `items`: by instance, then F's larger size first, then index; one
 // class table for queries of at most mmax rows; per group of kAffinePairGroupProblems one upload of the descriptors, one launch per
-// instance and one download; score / ends of the pairs with a positive maximum (F::keep_all: of every pair).
+// instance and one download; score / ends of the pairs with a positive maximum (F::keep_all: of every pair).  A problem of F
+// writes F::kOuts results (best, cell): score[npairs][kOuts], ends[npairs][kOuts][2].
 template <class F>
 int affine_list_stage(const F &f, const AffineProfPlan &plan, std::vector<typename F::Item> &items, int mmax, float *score, int64_t *ends) {
   typedef typename F::Problem Problem;
@@ -884,7 +893,8 @@ int affine_list_stage(const F &f, const AffineProfPlan &plan, std::vector<typena
   for (size_t g0 = 0; g0 < items.size(); g0 += kAffinePairGroupProblems) {
     const size_t np = std::min(kAffinePairGroupProblems, items.size() - g0);
     const char *nomem = "affine pairs: allocation of the pair scratch failed";
-    if (ctx->wprobs.ensure(np * sizeof(Problem)) || ctx->outs_f.ensure(np * 4 + 64) || ctx->outs_i.ensure(np * 16) ||
+    constexpr size_t NO = F::kOuts;
+    if (ctx->wprobs.ensure(np * sizeof(Problem)) || ctx->outs_f.ensure(NO * np * 4 + 64) || ctx->outs_i.ensure(NO * np * 16) ||
         ctx->pin_probs.ensure(np * sizeof(Problem)))
       return fail(ctx, MI355_SW_ENOMEM, nomem);
     Problem *pr = ctx->pin_probs.as<Problem>();
@@ -897,8 +907,8 @@ int affine_list_stage(const F &f, const AffineProfPlan &plan, std::vector<typena
       while (i1 < np && F::R(pr[i1]) == R) { cells += F::cells(pr[i1]); ++i1; }
       const auto kern = f.kernel(R);
       if (!kern) return fail(ctx, MI355_SW_ENODEV, F::kNoInstance);
-      sa.best = ctx->outs_f.as<float>() + i0;
-      sa.cell = ctx->outs_i.as<int64_t>() + 2 * i0;
+      sa.best = ctx->outs_f.as<float>() + NO * i0;
+      sa.cell = ctx->outs_i.as<int64_t>() + 2 * NO * i0;
       launch_dyn_lds(kern, dim3((unsigned)((i1 - i0 + 15) / 16)), dim3(256), tab_floats * 4, ctx->stream,
                      ctx->wprobs.as<Problem>() + i0, (int)(i1 - i0), sa);
       HIPCHK(ctx, hipGetLastError());
@@ -907,9 +917,9 @@ int affine_list_stage(const F &f, const AffineProfPlan &plan, std::vector<typena
       i0 = i1;
     }
     const float *h_best = nullptr; const int64_t *h_cell = nullptr;
-    rc = affine_download(ctx, np, nomem, h_best, h_cell); if (rc) return rc;
-    for (size_t i = 0; i < np; ++i) {
-      const size_t id = f.id(items[g0 + i]);
+    rc = affine_download(ctx, NO * np, nomem, h_best, h_cell); if (rc) return rc;
+    for (size_t i = 0; i < NO * np; ++i) {
+      const size_t id = NO * f.id(items[g0 + i / NO]) + i % NO;
       if (!f.keep_all() && !(h_best[i] > 0)) continue;
       score[id] = h_best[i]; ends[2 * id] = h_cell[2 * i]; ends[2 * id + 1] = h_cell[2 * i + 1];
     }
@@ -1044,6 +1054,323 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, int
   affine_scatter_jobs(jobs, c.e2e(), score, ends);
   affine_scatter_jobs(bjobs, false, score, ends);
   return affine_end(c, items, score, ends, tout);
+}
+
+// ---- the anchored seed extension (include/mi355_sw.h "anchored seed extension", DESIGN.md §3.8 lemma L21) -------------------------
+// The caller's list (validated there, not owned): pair k is the letters [q_lo[k], q_hi[k]) of query qid[k] (both null: the whole
+// query) against [lefts[k], rights[k]) of the reference, backward[k] != 0: on both strings reversed (null: every pair forward).
+struct AffineExtList {
+  size_t npairs; const int32_t *qid, *q_lo, *q_hi; const int64_t *lefts, *rights; const uint8_t *backward;
+  bool back(size_t k) const { return backward && backward[k]; }
+};
+
+// Pair `id` as every kernel takes it: where its letters and its window lie on the device — in the resident buffers, or for a
+// backward pair in their reversed copies — so that no stage below knows a direction.
+struct AffineExtItem { uint32_t id; const uint8_t *x, *ycodes, *ybytes; int32_t m; int64_t n; };
+
+// Lemma L21, the admission test of sw_affine_pair_ext_kernel: every value of a real cell is an integer below 2^24 in magnitude.
+// H(i,j) >= -(2o + (i+j-2) e), the path along row 0 and down column j, so Ho, E, F >= -(3o + (m+n-2) e), E - e and F - e one e
+// lower, the diagonal term Ho + (s + o) >= -(2o + (m+n-2) e) + smin and the table's |s + o| <= o - smin: one inequality covers the
+// low side, 3o + (m+n) e - smin < 2^24.  Upwards H <= smax m and s + o <= smax + o.  A positive H lends the key its five low
+// mantissa bits: smax (m + 1) < 2^18, as in the local instance.  The exact kernel forms neither sum and has no key.
+bool affine_ext_exact(const AffineTable &t, double m, double n) {
+  return 3.0 * t.open + (m + n) * t.ext - t.smin < 16777216.0 && (double)t.smax * m + t.open < 16777216.0 &&
+         (double)t.smax * (m + 1.0) < kAffineProfBound;
+}
+bool affine_ext_whole_exact(const AffineTable &t, double m, double n) {
+  return 3.0 * t.open + (m + n) * t.ext < 16777216.0 && 2.0 * t.open + (m + n) * t.ext - t.smin < 16777216.0 &&
+         (double)t.smax * (m + 1.0) < 16777216.0;
+}
+
+// The reversed copies of the resident reference (codes and bytes) and of the batch's bytes, built with reverse_bytes_kernel where
+// the cached ones are of another version.
+int affine_ext_reversed(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q) {
+  auto reverse = [&](const DevBuf &src, DevBuf &dst, size_t n) -> int {
+    if (n == 0) return 0;
+    if (dst.ensure(n)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(reversed copy) failed");
+    const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(reverse_bytes_kernel, dim3(blocks), dim3(256), 0, ctx->stream, src.as<uint8_t>(), dst.as<uint8_t>(), n);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+  };
+  if (!ctx->rev_ref_valid || ctx->rev_ref_version != ref.version) {
+    ctx->rev_ref_valid = false;
+    { int rc = reverse(ref.codes, ctx->rev_codes, ref.n); if (rc) return rc; }
+    { int rc = reverse(ref.bytes, ctx->rev_bytes, ref.n); if (rc) return rc; }
+    ctx->rev_ref_valid = true; ctx->rev_ref_version = ref.version;
+  }
+  if (!ctx->rev_q_valid || ctx->rev_q_version != q.version) {
+    ctx->rev_q_valid = false;
+    size_t total = 0;
+    for (size_t k = 0; k < q.nq; ++k) total = std::max(total, (size_t)q.off[k] + (size_t)q.len[k]);
+    { int rc = reverse(q.bytes, ctx->rev_q, total); if (rc) return rc; }
+    ctx->rev_q_total = total;
+    ctx->rev_q_valid = true; ctx->rev_q_version = q.version;
+  }
+  return 0;
+}
+
+// sw_affine_pair_ext_kernel for affine_list_stage: an item carries its own pointers; two results per problem (best extension, to
+// the end).
+struct AffineExtFamily {
+  typedef AffinePairProblem Problem; typedef AffineExtItem Item;
+  const AffineCall &c;
+  static constexpr const char *kNoInstance = "internal: no sw_affine_pair_ext_kernel instance for this query";
+  static constexpr int kOuts = 2;
+  bool keep_all() const { return true; }                           // a to-end score may be <= 0, a best extension is 0 at least
+  static uint32_t id(const Item &a) { return a.id; }
+  static int R(const Item &a) { return affine_pair_R(a.m); }
+  static int R(const Problem &p) { return affine_pair_R(p.m); }
+  int64_t size(const Item &a) const { return a.n; }                // longest window first, as AffinePairFamily
+  void fill(const Item &a, Problem &p) const { p.x = a.x; p.y = a.ycodes; p.m = a.m; p.n = (int32_t)a.n; }
+  static double cells(const Problem &p) { return (double)p.m * (double)p.n; }
+  auto kernel(int R) const {
+    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
+    with_listed_R<kPairR>(R, [&](auto r) { kern = &sw_affine_pair_ext_kernel<decltype(r)::value>; });
+    return kern;
+  }
+  void note(double cells, int R, const Problem &first) const {
+    // per step and lane: the local instance's count (AffinePairFamily::note) and two more per cell: the max with 0 in front of the
+    // key and the row-m select; the row-0 subtract and max, the second compare and its selects are three more of overhead.  The 16
+    // border steps of a slot are not counted
+    path_note(c.ctx, "affine_pair_ext[R=%d]", R);
+    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, first.n, first.n, 0, (11.0 * R + (R + 1) / 2 + 15.0) / (double)R,
+                       "sw_affine_pair_ext_kernel<R=%d>", R);
+  }
+};
+
+// sw_affine_exact_ext_kernel over all of `jobs`, 65536 per launch: score[npairs][2], ends[npairs][2][2] as the list stage; its
+// interval goes to timings[1].
+int affine_ext_exact_stage(const AffineCall &c, const std::vector<AffineExtItem> &jobs, float *score, int64_t *ends) {
+  mi355_sw_ctx *ctx = c.ctx;
+  if (jobs.empty()) return 0;
+  path_note(ctx, "affine_exact");
+  AffineScoring sc;
+  { int rc = affine_scoring(ctx, c.p, sc); if (rc) return rc; }
+  HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+  for (size_t lo = 0; lo < jobs.size(); lo += 65536) {
+    const size_t n = std::min<size_t>(65536, jobs.size() - lo);
+    size_t lds = 0;
+    for (size_t k = 0; k < n; ++k) lds = std::max(lds, affine_exact_lds(jobs[lo + k].m));
+    if (ctx->probs.ensure(n * sizeof(ExactProblem)) || ctx->outs_f.ensure(n * 8) || ctx->outs_i.ensure(n * 32))
+      return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(exact scratch) failed");
+    std::vector<ExactProblem> pr(n);
+    for (size_t k = 0; k < n; ++k) {
+      const AffineExtItem &j = jobs[lo + k];
+      ExactProblem &e = pr[k];
+      memset(&e, 0, sizeof e);
+      e.x = j.x; e.y = j.ybytes; e.m = j.m; e.nw = (int32_t)j.n; e.full_n = j.n; e.own_lo = 1; e.target = -1.0f;
+      e.best = ctx->outs_f.as<float>() + 2 * k;
+      e.cell = ctx->outs_i.as<int64_t>() + 4 * k;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactProblem), hipMemcpyHostToDevice, ctx->stream));
+    launch_dyn_lds(&sw_affine_exact_ext_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactProblem>(), sc);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<float> bf(2 * n);
+    std::vector<int64_t> ci(4 * n);
+    HIPCHK(ctx, hipMemcpyAsync(bf.data(), ctx->outs_f.p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ci.data(), ctx->outs_i.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t k = 0; k < n; ++k) {
+      const size_t id = jobs[lo + k].id;
+      score[2 * id] = bf[2 * k]; score[2 * id + 1] = bf[2 * k + 1];
+      for (int v = 0; v < 4; ++v) ends[4 * id + v] = ci[4 * k + v];
+    }
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+  ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+  return 0;
+}
+
+// Traceback of pair k from the cell (tx[k], ty[k]) of value ts[k]: one sw_affine_trace_ext_kernel problem over the whole rectangle
+// from the anchor to that cell, in launch groups of at most kAffineTraceDirsMax decision bytes.  A cell in column 0 (the letters of
+// x against as many '-') is written here from a copy of the letters: no kernel runs.  tout[npairs]: views into ctx->arenas.
+int affine_ext_trace(const AffineCall &c, const std::vector<AffineExtItem> &pairs, const float *ts, const int64_t *tx, const int64_t *ty,
+                     std::vector<TraceOut> &tout) {
+  mi355_sw_ctx *ctx = c.ctx;
+  struct Job { size_t k; size_t dirs_off, cons_off; };
+  std::vector<Job> jobs;
+  std::vector<size_t> col0;                                        // pairs traced from a cell in column 0
+  size_t col0_bytes = 0;
+  for (size_t k = 0; k < pairs.size(); ++k) {
+    if (tx[k] < 1) continue;
+    if (ty[k] < 1) { col0.push_back(k); col0_bytes += 2 * (size_t)tx[k]; continue; }
+    if (dirs_bytes(tx[k], ty[k]) > kAffineTraceDirsMax || affine_exact_lds((int)std::min<int64_t>(tx[k], 1 << 24)) > kExactLdsMax) {
+      char msg[240];
+      std::snprintf(msg, sizeof msg, "affine extension traceback: pair %zu needs a rectangle of %lld rows x %lld columns, more than %zu "
+                    "decision bytes or more rows than the exact kernel's LDS diagonals hold", k, (long long)tx[k], (long long)ty[k], kAffineTraceDirsMax);
+      return fail(ctx, MI355_SW_ENOTSUP, msg);
+    }
+    jobs.push_back(Job{k, 0, 0});
+  }
+  if (!col0.empty()) {                                             // one arena, one copy per pair, one wait for all of them
+    std::vector<char> cons(col0_bytes, '-');
+    size_t at = 0;
+    hipError_t copied = hipSuccess;
+    for (size_t k : col0) {
+      copied = hipMemcpyAsync(cons.data() + at, pairs[k].x, (size_t)tx[k], hipMemcpyDeviceToHost, ctx->stream);
+      if (copied != hipSuccess) break;
+      at += 2 * (size_t)tx[k];
+    }
+    const hipError_t waited = hipStreamSynchronize(ctx->stream);    // (before `cons` can go: copies may be in flight)
+    HIPCHK(ctx, copied);
+    HIPCHK(ctx, waited);
+    ctx->arenas.push_back(std::move(cons));
+    char *base = ctx->arenas.back().data();
+    at = 0;
+    for (size_t k : col0) {
+      const size_t len = (size_t)tx[k];
+      std::reverse(base + at, base + at + len);                     // from the far end to the anchor
+      TraceOut &o = tout[k];
+      o.len = len; o.cx = base + at; o.cy = base + at + len; o.pos = 0;
+      at += 2 * len;
+    }
+  }
+  if (jobs.empty()) return 0;
+  path_note(ctx, "affine_trace");
+  AffineScoring sc;
+  { int rc = affine_scoring(ctx, c.p, sc); if (rc) return rc; }
+  for (size_t lo = 0; lo < jobs.size();) {
+    size_t hi = lo, dirs_total = 0, cons_total = 0, lds = 0;
+    while (hi < jobs.size() && hi - lo < 65536) {
+      Job &j = jobs[hi];
+      const size_t db = (dirs_bytes(tx[j.k], ty[j.k]) + 15) & ~(size_t)15;
+      if (hi > lo && dirs_total + db > kAffineTraceDirsMax) break;
+      j.dirs_off = dirs_total; dirs_total += db;
+      j.cons_off = cons_total; cons_total += 2 * ((size_t)tx[j.k] + (size_t)ty[j.k]);
+      lds = std::max(lds, affine_exact_lds((int)tx[j.k]));
+      ++hi;
+    }
+    const size_t n = hi - lo;
+    if (ctx->wprobs.ensure(n * sizeof(AffineTraceProblem)) || ctx->walkp.ensure(n * 24) || ctx->dirs.ensure(dirs_total) ||
+        ctx->cons.ensure(cons_total + 16))
+      return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine traceback scratch) failed");
+    std::vector<AffineTraceProblem> pr(n);
+    for (size_t k = 0; k < n; ++k) {
+      const Job &j = jobs[lo + k];
+      AffineTraceProblem &a = pr[k];
+      memset(&a, 0, sizeof a);
+      a.e.x = pairs[j.k].x; a.e.y = pairs[j.k].ybytes;
+      a.e.m = (int32_t)tx[j.k]; a.e.nw = (int32_t)ty[j.k];
+      a.e.own_lo = 1;
+      a.e.target = ts[j.k];
+      a.e.dirs = ctx->dirs.as<uint8_t>() + j.dirs_off;
+      a.cap = a.e.m + a.e.nw;
+      a.cons_x = ctx->cons.as<char>() + j.cons_off;
+      a.cons_y = a.cons_x + a.cap;
+      a.clamped = 1; a.row_clamped = 1;
+      a.out = ctx->walkp.as<int64_t>() + 3 * k;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr.data(), n * sizeof(AffineTraceProblem), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    launch_dyn_lds(&sw_affine_trace_ext_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<AffineTraceProblem>(), sc);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+    std::vector<int64_t> wo(3 * n);
+    std::vector<char> cons(cons_total);
+    HIPCHK(ctx, hipMemcpyAsync(wo.data(), ctx->walkp.p, n * 24, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cons.data(), ctx->cons.p, cons_total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->timings[2] += elapsed_us(ctx, ctx->ev[6], ctx->ev[7]);
+    ctx->arenas.push_back(std::move(cons));
+    const char *base = ctx->arenas.back().data();
+    for (size_t k = 0; k < n; ++k) {
+      const Job &j = jobs[lo + k];
+      const int64_t st = wo[3 * k + 2];
+      if (st == 2) return fail(ctx, MI355_SW_ENODEV, "internal: the affine extension traceback exceeded its string capacity");
+      if (st != 0) return fail(ctx, MI355_SW_ENODEV, "internal: the traced cell of the affine extension does not hold its score");
+      TraceOut &o = tout[j.k];
+      o.len = (size_t)wo[3 * k];
+      o.cx = base + j.cons_off;
+      o.cy = base + j.cons_off + (size_t)tx[j.k] + (size_t)ty[j.k];
+      o.pos = (uint32_t)wo[3 * k + 1];
+    }
+    lo = hi;
+  }
+  return 0;
+}
+
+// The pairs of `el` under the anchored model.  score[npairs][2] = best extension, to-end score; ends[npairs][2][2] = end_x, end_y
+// (lengths), then m, to_end_y.  tout (may be null): the traceback of every pair, from the best extension's cell or, where
+// to_end[k] != 0 (to_end may be null), from (m, to_end_y).  A pair runs on sw_affine_pair_ext_kernel while rows, columns, table and
+// admission (affine_ext_exact) allow, else as a whole problem of the exact kernel; an empty window is filled in here.
+int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const AffineExtList &el, const mi355_sw_affine_params &p,
+                  const uint8_t *to_end, float *score, int64_t *ends, std::vector<TraceOut> *tout) {
+  const size_t npairs = el.npairs;
+  for (size_t k = 0; k < 2 * npairs; ++k) { score[k] = 0.0f; ends[2 * k] = 0; ends[2 * k + 1] = 0; }
+  if (tout) tout->assign(npairs, TraceOut());
+  if (npairs > 0xFFFFFFFFull) return fail(ctx, MI355_SW_ENOTSUP, "affine extension: more than 2^32 pairs");
+  AffineCall c{ctx, ref, q, p, AffineTable(), kAffineModeExt};
+  int rc = affine_begin(c);
+  if (rc) return rc > 0 ? 0 : rc;
+  AffineProfPlan plan;
+  if (!opt().no_affine_pairs) {
+    affine_byte_classes(ref, p, c.t, plan, 16777216.0);
+    if (!plan.ok && ref.ncodes >= 2 && ref.ncodes <= 256 && (double)c.t.open < 16777216.0) {
+      plan.rep.resize(256);                                        // every byte its own class, as affine_pairs
+      for (int a = 0; a < 256; ++a) { plan.cls[a] = (uint8_t)a; plan.rep[a] = a; }
+      plan.nclass = 257;
+      plan.ok = true;
+    }
+  }
+  const bool table_ok = plan.ok && affine_pair_lds(ref, plan) <= kAffinePairLdsMax;
+  bool any_back = false;
+  for (size_t k = 0; k < npairs && !any_back; ++k) any_back = el.back(k);
+  if (any_back) { rc = affine_ext_reversed(ctx, ref, q); if (rc) return rc; }
+
+  std::vector<AffineExtItem> pairs(npairs), fast, jobs;
+  int mmax = 0;
+  for (size_t k = 0; k < npairs; ++k) {
+    const int qi = el.qid[k];
+    const int64_t qlo = el.q_lo ? el.q_lo[k] : 0, qhi = el.q_hi ? el.q_hi[k] : q.len[qi];
+    const int64_t m = qhi - qlo, n = el.rights[k] - el.lefts[k];
+    AffineExtItem &it = pairs[k];
+    it.id = (uint32_t)k; it.m = (int32_t)m; it.n = n;
+    if (el.back(k)) {
+      it.x = ctx->rev_q.as<uint8_t>() + ((int64_t)ctx->rev_q_total - q.off[qi] - qhi);
+      it.ycodes = ctx->rev_codes.as<uint8_t>() + ((int64_t)ref.n - el.rights[k]);
+      it.ybytes = ctx->rev_bytes.as<uint8_t>() + ((int64_t)ref.n - el.rights[k]);
+    } else {
+      it.x = q.bytes.as<uint8_t>() + q.off[qi] + qlo;
+      it.ycodes = ref.codes.as<uint8_t>() + el.lefts[k];
+      it.ybytes = ref.bytes.as<uint8_t>() + el.lefts[k];
+    }
+    if (m < 1) continue;
+    if (n < 1) {                                                   // the whole of x as one insertion; nothing to extend
+      score[2 * k + 1] = -((float)c.t.open + (float)(m - 1) * (float)c.t.ext);
+      ends[4 * k + 2] = m;
+      continue;
+    }
+    if (table_ok && m <= kMaxRowsFast && n <= kAffinePairColsMax && affine_ext_exact(c.t, (double)m, (double)n)) {
+      fast.push_back(it); mmax = std::max(mmax, (int)m);
+      continue;
+    }
+    if ((double)m * (double)n > kAffineExactCellsMax || !affine_ext_whole_exact(c.t, (double)m, (double)n) || affine_exact_lds((int)m) > kExactLdsMax) {
+      char msg[400];
+      std::snprintf(msg, sizeof msg, "affine extension: pair %zu (%lld rows x %lld columns) is outside the pair kernel (1..512 rows, 1..2^20 columns, "
+                    "3 gap_open + (rows + columns) gap_extend - min(smin, 0) < 2^24, smax * (rows + 1) < 2^18, a score table within 32 KiB%s) and "
+                    "outside the exact kernel (at most 2^26 cells and 5600 rows, 3 gap_open + (rows + columns) gap_extend < 2^24)", k,
+                    (long long)m, (long long)n, opt().no_affine_pairs ? "; option no_affine_pairs is set" : "");
+      return fail(ctx, MI355_SW_ENOTSUP, msg);
+    }
+    jobs.push_back(it);
+  }
+  rc = affine_list_stage(AffineExtFamily{c}, plan, fast, mmax, score, ends);
+  if (!rc) rc = affine_ext_exact_stage(c, jobs, score, ends);
+  if (rc) return rc;
+  if (tout) {
+    std::vector<float> ts(npairs);
+    std::vector<int64_t> tx(npairs), ty(npairs);
+    for (size_t k = 0; k < npairs; ++k) {
+      const size_t w = (to_end && to_end[k]) ? 1 : 0;
+      ts[k] = score[2 * k + w]; tx[k] = ends[4 * k + 2 * w]; ty[k] = ends[4 * k + 2 * w + 1];
+    }
+    rc = affine_ext_trace(c, pairs, ts.data(), tx.data(), ty.data(), *tout);
+    if (rc) return rc;
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+  ctx->timings[3] += elapsed_us(ctx, ctx->ev[4], ctx->ev[5]);
+  return 0;
 }
 
 }  // namespace

@@ -346,6 +346,12 @@ struct mi355_sw_ctx {
   std::vector<uint16_t> h_atab;
   DevBuf aprof;                   // affine calls: class scores [nclass][letters] and the byte -> class table of sw_affine_prof_kernel
   std::vector<float> h_aprof;
+  // affine extension calls, backward pairs (host_affine.h: affine_ext_reversed): the resident reference's codes and bytes and the
+  // resident batch's bytes, each whole buffer reversed; built at the first backward pair, kept while the versions stand
+  DevBuf rev_codes, rev_bytes, rev_q;
+  bool rev_ref_valid = false, rev_q_valid = false;
+  uint64_t rev_ref_version = 0, rev_q_version = 0;
+  size_t rev_q_total = 0;         // bytes of the batch buffer that rev_q mirrors
   std::vector<uint8_t> h_pieces;  // host side of the piece table of the running call (host_batch.h)
   size_t saved_locates = 0, saved_traces = 0, saved_fallbacks = 0;   // finish steps of the running call that started from saved state / fell back
   size_t walk_widened = 0;        // times a traceback window's budget was multiplied by 4 in the running call (walk status 1)

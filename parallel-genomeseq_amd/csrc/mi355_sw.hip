@@ -11,8 +11,10 @@
 //   affine gaps (score, end cell, traceback): sw_affine_kernel sweep + sw_affine_exact / _trace_kernel, and
 //                      sw_affine_prof_kernel for references (ranges) of at most 512 letters,
 //                      sw_affine_pair_kernel (end-to-end: sw_affine_pair_e2e_kernel) for lists of (query, window)
-//                      pairs and sw_affine_band_kernel for those with a diagonal band               host_affine.h
-//                      (entry points: affine_align_any, affine_batch_any, affine_pairs_any — one body per run / trace twin)
+//                      pairs, sw_affine_band_kernel for those with a diagonal band and sw_affine_pair_ext_kernel
+//                      for the anchored seed extension, forward and backward                          host_affine.h
+//                      (entry points: affine_align_any, affine_batch_any, affine_pairs_any, affine_extend_any — one body
+//                      per run / trace twin)
 // Problems the score kernel does not cover (see bucket_fast_ok) run 2+3 on the whole matrix.
 // The host code is one translation unit; the fragments below are included in order.
 #include "../../include/mi355_sw.h"
@@ -106,7 +108,8 @@ void mi355_sw_destroy(mi355_sw_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   DevBuf *bufs[] = {&c->qcnt, &c->sel2, &c->gcnt, &c->wlut, &c->ref.bytes, &c->ref.codes, &c->batch.bytes, &c->batch.lens, &c->keys, &c->ranges, &c->stab,
-                    &c->batch.offs, &c->batch.sel, &c->colsave, &c->rowsave, &c->pieces, &c->ftab, &c->ftab_s, &c->htab, &c->htab8, &c->soloblk, &c->flags, &c->submax, &c->lut, &c->probs, &c->dirs, &c->outs_f, &c->outs_i, &c->cons, &c->walkp, &c->hmat, &c->brow, &c->wprobs, &c->scan, &c->batch.cum, &c->ckpt, &c->first, &c->recs, &c->atab, &c->aprof, &c->pkeys, &c->pthr, &c->psel, &c->psel2};
+                    &c->batch.offs, &c->batch.sel, &c->colsave, &c->rowsave, &c->pieces, &c->ftab, &c->ftab_s, &c->htab, &c->htab8, &c->soloblk, &c->flags, &c->submax, &c->lut, &c->probs, &c->dirs, &c->outs_f, &c->outs_i, &c->cons, &c->walkp, &c->hmat, &c->brow, &c->wprobs, &c->scan, &c->batch.cum, &c->ckpt, &c->first, &c->recs, &c->atab, &c->aprof, &c->pkeys, &c->pthr, &c->psel, &c->psel2,
+                    &c->rev_codes, &c->rev_bytes, &c->rev_q};
   for (DevBuf *b : bufs) b->release();
   c->adhoc.release(); c->one.release();
   c->pin_probs.release(); c->pin_walk.release(); c->pin_out.release(); c->pin_solo_up.release(); c->pin_solo_down.release();
@@ -538,6 +541,58 @@ int mi355_sw_affine_pairs_run_band(mi355_sw_ctx *ctx, int mode, size_t npairs, c
 int mi355_sw_affine_pairs_trace_band(mi355_sw_ctx *ctx, int mode, size_t npairs, const int32_t *query, const int64_t *lefts, const int64_t *rights,
                                      const int64_t *band_lo, const int64_t *band_hi, const mi355_sw_affine_params *params, mi355_sw_result *outs) {
   return affine_pairs_any(ctx, mode, npairs, query, lefts, rights, params, true, nullptr, nullptr, nullptr, outs, band_lo, band_hi);
+}
+
+// mi355_sw_affine_extend_run (score .. to_end_y) and, with `trace`, mi355_sw_affine_extend_trace (outs), written only after success
+static int affine_extend_any(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const mi355_sw_affine_params *params, bool trace,
+                             const uint8_t *to_end, float *score, int64_t *end_x, int64_t *end_y, mi355_sw_result *outs, float *to_end_score,
+                             int64_t *to_end_y) {
+  OptScope opt_scope_(ctx);
+  int rc = affine_check(ctx, params);
+  if (rc) return rc;
+  if (!list) return fail(ctx, MI355_SW_EINVAL, "affine extension: list is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  reset_timings(ctx);
+  const size_t npairs = list->npairs;
+  if (npairs == 0) return 0;
+  if (trace && !outs) return fail(ctx, MI355_SW_EINVAL, "outs is NULL");
+  if ((!trace && (!score || !end_x || !end_y)) || !list->query || !list->lefts || !list->rights) return fail(ctx, MI355_SW_EINVAL, "null argument");
+  if ((list->q_lo == nullptr) != (list->q_hi == nullptr)) return fail(ctx, MI355_SW_EINVAL, "affine extension: q_lo and q_hi must both be given, or neither");
+  for (size_t k = 0; k < npairs; ++k) {
+    if (list->query[k] < 0 || (size_t)list->query[k] >= ctx->batch.nq) return fail(ctx, MI355_SW_EINVAL, "pair: query index outside the resident batch");
+    if (list->lefts[k] < 0 || list->rights[k] < list->lefts[k] || list->rights[k] > (int64_t)ctx->ref.n)
+      return fail(ctx, MI355_SW_EINVAL, "pair: window outside the resident reference");
+    if (list->q_lo && (list->q_lo[k] < 0 || list->q_hi[k] < list->q_lo[k] || list->q_hi[k] > ctx->batch.len[list->query[k]]))
+      return fail(ctx, MI355_SW_EINVAL, "pair: letters [q_lo, q_hi) outside the query");
+  }
+  std::vector<float> sc(2 * npairs, 0.0f);
+  std::vector<int64_t> ends(4 * npairs, 0);
+  std::vector<TraceOut> tout(trace ? npairs : 0);
+  const AffineExtList el{npairs, list->query, list->q_lo, list->q_hi, list->lefts, list->rights, list->backward};
+  rc = affine_extend(ctx, ctx->ref, ctx->batch, el, *params, trace ? to_end : nullptr, sc.data(), ends.data(), trace ? &tout : nullptr);
+  if (rc) return rc;
+  for (size_t k = 0; k < npairs; ++k) {
+    const size_t w = (trace && to_end && to_end[k]) ? 1 : 0;         // the traced alignment: best extension, or to the end
+    if (trace) {
+      memset(&outs[k], 0, sizeof outs[k]);
+      set_result(outs[k], sc[2 * k + w], ends[4 * k + 2 * w], ends[4 * k + 2 * w + 1], &tout[k]);
+      outs[k].end_x = ends[4 * k + 2 * w]; outs[k].end_y = ends[4 * k + 2 * w + 1];   // (whatever the sign of the score)
+      outs[k].timings_us[0] = outs[k].timings_us[1] = (float)ctx->timings[0];
+    } else { score[k] = sc[2 * k]; end_x[k] = ends[4 * k]; end_y[k] = ends[4 * k + 1]; }
+    if (to_end_score) to_end_score[k] = sc[2 * k + 1];
+    if (to_end_y) to_end_y[k] = ends[4 * k + 3];
+  }
+  return 0;
+}
+
+int mi355_sw_affine_extend_run(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const mi355_sw_affine_params *params,
+                               float *score, int64_t *end_x, int64_t *end_y, float *to_end_score, int64_t *to_end_y) {
+  return affine_extend_any(ctx, list, params, false, nullptr, score, end_x, end_y, nullptr, to_end_score, to_end_y);
+}
+
+int mi355_sw_affine_extend_trace(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const mi355_sw_affine_params *params,
+                                 const uint8_t *to_end, mi355_sw_result *outs, float *to_end_score, int64_t *to_end_y) {
+  return affine_extend_any(ctx, list, params, true, to_end, nullptr, nullptr, nullptr, outs, to_end_score, to_end_y);
 }
 
 int mi355_sw_best_range(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,

@@ -25,6 +25,8 @@
 //     are too small for the sweep (or all of them under option no_affine_sweep).
 //   * sw_affine_trace_kernel: the same cells (affine_exact_fill) over the window behind an end cell (lemma L17), one decision
 //     byte per cell, and the walk over them by the traceback rule of include/mi355_sw.h: pos and the reversed consensus strings.
+// The anchored model of the extension calls (include/mi355_sw.h "anchored seed extension") is a third model of the same fill
+// (affine_exact_fill_model): sw_affine_exact_ext_kernel and sw_affine_trace_ext_kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -246,10 +248,17 @@ enum : int { kAffStop = 0, kAffDiag = 1, kAffE = 2, kAffF = 3, kAffEExt = 4, kAf
 // two later diagonals read at most one row beyond them on either side, and the three rotating buffers hold nothing older; so the loop
 // runs over the in-band rows and one more on each side, work in proportion to the band.  Such a cell competes for nothing and gets no
 // decision byte: the walk never reaches it (its E and F never equal a positive H).  The layout of dirs is the unbanded one.
-struct AffineBest { float best; int64_t i, j; };
-template <bool TRACE, bool E2E = false, bool BAND = false>
-__device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, const AffineScoring sc, uint8_t *smem_raw, const int blo = 0,
-                                                        const int bhi = 0) {
+// EXT (kAffineModelExt): the anchored model of include/mi355_sw.h — the end-to-end model with row 0 a gap as well: H(0,j) = E(0,j) =
+// -(o + (j-1) e), F(0,j) = -inf, H(0,0) = 0.  Two winners: the first column-major maximum over all cells — the local model's key
+// order; only a positive cell can beat cell (0,0) = 0, and the border cells are negative, so the cells of the loop are all that
+// compete — and the maximum of row m with its smallest column (end, end_j; column 0 is the caller's to fold in).  TRACE: as E2E.
+struct AffineBest { float best; int64_t i, j; float end; int64_t end_j; };
+enum : int { kAffineModelLocal = 0, kAffineModelE2E = 1, kAffineModelExt = 2 };
+template <bool TRACE, int MODEL, bool BAND>
+__device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem P, const AffineScoring sc, uint8_t *smem_raw, const int blo,
+                                                              const int bhi) {
+  constexpr bool EXT = MODEL == kAffineModelExt;
+  constexpr bool E2E = MODEL != kAffineModelLocal;                 // no floor and the column-0 border: both floor-free models
   static_assert(!(BAND && E2E), "the banded end-to-end model is not defined");
   const int lane = threadIdx.x;
   const int m = P.m, nw = P.nw;
@@ -263,8 +272,11 @@ __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, co
   for (int k = lane; k < 4 * plen; k += 64) E0[k] = ninf;
   for (int k = lane; k < m; k += 64) xs[k] = P.x[k];
   if (E2E && lane == 0 && m >= 1) { H0[1] = -sc.gap_open; F0[1] = -sc.gap_open; }   // diagonal 1: cell (1, 0)
+  if (EXT && lane == 0) { H0[0] = -sc.gap_open; E0[0] = -sc.gap_open; }             // and cell (0, 1)
 
-  float best = E2E ? ninf : -1.0f;
+  float best = (E2E && (TRACE || !EXT)) ? ninf : -1.0f;            // (EXT, score pass: only a positive cell beats cell (0,0))
+  float end = ninf;                                                // EXT: the greatest H(m, jl) and its first column
+  int64_t end_j = 0;
   unsigned long long bkey = ~0ull;
   int64_t bi = 0, bj = 0;
   const float go = sc.gap_open, ge = sc.gap_extend;
@@ -279,6 +291,7 @@ __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, co
     // border cells of this diagonal: row 0 (index 0) and column 0 (index d)
     if (lane == 0) {
       Hc[0] = 0.0f; Fc[0] = ninf; Ec[0] = ninf;
+      if (EXT) { const float r0 = -(sc.gap_open + (float)(d - 1) * sc.gap_extend); Hc[0] = r0; Ec[0] = r0; }   // cell (0, d)
       if (d <= m) {
         const float b0 = E2E ? -(sc.gap_open + (float)(d - 1) * sc.gap_extend) : 0.0f;   // (integers below 2^24: exact)
         Hc[d] = b0; Ec[d] = ninf; Fc[d] = E2E ? b0 : ninf;
@@ -307,6 +320,12 @@ __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, co
         const int src = (!E2E && h == 0.0f) ? kAffStop : h == x ? kAffDiag : h == e ? kAffE : kAffF;
         P.dirs[(size_t)d * (size_t)dstride + (size_t)(i - ilo)] = (uint8_t)(src | (e != eo ? kAffEExt : 0) | (f != fo ? kAffFExt : 0));
         if (d == m + nw) best = h;                                 // (one cell, one lane)
+      } else if (EXT) {
+        if (i == m && h > end) { end = h; end_j = jl; }            // (a lane meets its columns in rising order)
+        if (h > 0.0f && h >= best) {
+          const unsigned long long key = order_key<0>(i, jl, m, 0);
+          if (h > best || key < bkey) { best = h; bkey = key; bi = i; bj = jl; }
+        }
       } else if (E2E) {
         // row m, own columns; a lane meets its columns in rising order, so '>' keeps its first, and the key orders the lanes
         if (i == m && jl >= P.own_lo && h > best) { best = h; bkey = (unsigned long long)(P.col_offset + jl); bi = i; bj = P.col_offset + jl; }
@@ -328,8 +347,20 @@ __device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, co
     const long long oi = __shfl_xor((long long)bi, off);
     const long long oj = __shfl_xor((long long)bj, off);
     if (ob > best || (ob == best && ok < bkey)) { best = ob; bkey = ok; bi = oi; bj = oj; }
+    if (EXT) {
+      const float oe = __shfl_xor(end, off);
+      const long long oej = __shfl_xor((long long)end_j, off);
+      if (oe > end || (oe == end && oej < end_j)) { end = oe; end_j = oej; }
+    }
   }
-  return AffineBest{best, bi, bj};
+  return AffineBest{best, bi, bj, end, end_j};
+}
+
+// the fill by its two switches, as the local, end-to-end and banded instances name it
+template <bool TRACE, bool E2E = false, bool BAND = false>
+__device__ __forceinline__ AffineBest affine_exact_fill(const ExactProblem P, const AffineScoring sc, uint8_t *smem_raw, const int blo = 0,
+                                                        const int bhi = 0) {
+  return affine_exact_fill_model<TRACE, E2E ? kAffineModelE2E : kAffineModelLocal, BAND>(P, sc, smem_raw, blo, bhi);
 }
 
 // BAND: the problems carry their band (ExactBandProblem), in the window's local coordinates
@@ -353,6 +384,24 @@ __global__ __launch_bounds__(64) void sw_affine_exact_kernel(const typename Affi
   if (threadIdx.x == 0) {
     if (P.best) *P.best = best;
     if (P.cell) { P.cell[0] = (E2E || best > 0.0f) ? bi : 0; P.cell[1] = (E2E || best > 0.0f) ? bj : 0; }
+  }
+}
+
+// The anchored model (EXT of affine_exact_fill_model) on whole problems: P.best[0] / P.cell[0..1] = the best extension (0 / 0 / 0
+// when no cell is positive), P.best[1] / P.cell[2..3] = the maximum of row m over columns 0..nw — H(m,0) = -(o + (m-1) e) folded in
+// here, column 0 winning a tie — as (m, column).  own_lo, col_offset and target are unused.
+__global__ __launch_bounds__(64) void sw_affine_exact_ext_kernel(const ExactProblem *probs, const AffineScoring sc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  const ExactProblem P = probs[blockIdx.x];
+  const AffineBest r = affine_exact_fill_model<false, kAffineModelExt, false>(P, sc, smem_raw, 0, 0);
+  if (threadIdx.x == 0) {
+    const bool pos = r.best > 0.0f;
+    const float col0 = -(sc.gap_open + (float)(P.m - 1) * sc.gap_extend);
+    const bool at0 = col0 >= r.end;
+    P.best[0] = pos ? r.best : 0.0f;
+    P.best[1] = at0 ? col0 : r.end;
+    P.cell[0] = pos ? r.i : 0; P.cell[1] = pos ? r.j : 0;
+    P.cell[2] = P.m; P.cell[3] = at0 ? 0 : r.end_j;
   }
 }
 
@@ -388,12 +437,15 @@ __device__ __forceinline__ int affine_band_hi(const AffineTraceProblem &) { retu
 __device__ __forceinline__ int affine_band_lo(const AffineTraceBandProblem &p) { return p.blo; }
 __device__ __forceinline__ int affine_band_hi(const AffineTraceBandProblem &p) { return p.bhi; }
 
-template <bool E2E = false, bool BAND = false>
-__global__ __launch_bounds__(64) void sw_affine_trace_kernel(const typename AffineTraceProblemOf<BAND>::type *probs, const AffineScoring sc) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+// EXT: the window is the whole rectangle from the anchor to the traced cell, so both clamps hold by construction.  The walk ends at
+// (0,0) and nowhere else; in row 0 only E moves ('-', y[j]) happen, in column 0 only F moves (x[i], '-').
+template <int MODEL, bool BAND, class Problem>
+__device__ __forceinline__ void affine_trace_body(const Problem *probs, const AffineScoring sc, uint8_t *smem_raw) {
+  constexpr bool EXT = MODEL == kAffineModelExt;
+  constexpr bool E2E = MODEL == kAffineModelE2E;
   const AffineTraceProblem T = affine_problem(probs[blockIdx.x]);
   const ExactProblem &P = T.e;
-  const float corner = affine_exact_fill<true, E2E, BAND>(P, sc, smem_raw, affine_band_lo(probs[blockIdx.x]), affine_band_hi(probs[blockIdx.x])).best;
+  const float corner = affine_exact_fill_model<true, MODEL, BAND>(P, sc, smem_raw, affine_band_lo(probs[blockIdx.x]), affine_band_hi(probs[blockIdx.x])).best;
   // the walk reads what other lanes of this wavefront stored: wait for the stores, then keep the loads behind the barrier
   __threadfence();
   __syncthreads();
@@ -403,7 +455,15 @@ __global__ __launch_bounds__(64) void sw_affine_trace_kernel(const typename Affi
   int i = m, jl = nw, len = 0, state = kAffDiag;                   // kAffDiag stands for state M
   int64_t status = corner == P.target ? 0 : 3, pos = 0;
   while (status == 0) {
-    if (E2E) {
+    if (EXT) {
+      if (i <= 0 && jl <= 0) break;
+      if (i <= 0 || jl <= 0) {
+        if (len >= T.cap) { status = 2; break; }
+        if (i <= 0) { T.cons_x[len] = '-'; T.cons_y[len] = (char)P.y[jl - 1]; ++len; pos = P.col_offset + jl; --jl; }
+        else { T.cons_x[len] = (char)P.x[i - 1]; T.cons_y[len] = '-'; ++len; --i; }
+        continue;
+      }
+    } else if (E2E) {
       if (i <= 0) break;
       if (jl <= 0) {
         if (!T.clamped) { status = 1; break; }
@@ -440,6 +500,17 @@ __global__ __launch_bounds__(64) void sw_affine_trace_kernel(const typename Affi
     }
   }
   T.out[0] = len; T.out[1] = pos; T.out[2] = status;
+}
+
+template <bool E2E = false, bool BAND = false>
+__global__ __launch_bounds__(64) void sw_affine_trace_kernel(const typename AffineTraceProblemOf<BAND>::type *probs, const AffineScoring sc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  affine_trace_body<E2E ? kAffineModelE2E : kAffineModelLocal, BAND>(probs, sc, smem_raw);
+}
+
+__global__ __launch_bounds__(64) void sw_affine_trace_ext_kernel(const AffineTraceProblem *probs, const AffineScoring sc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  affine_trace_body<kAffineModelExt, false>(probs, sc, smem_raw);
 }
 
 }  // namespace mi355sw

@@ -335,4 +335,190 @@ __global__ __launch_bounds__(256) void sw_affine_pair_e2e_kernel(const AffinePai
   }
 }
 
+// sw_affine_pair_ext_kernel — the ANCHORED sibling (include/mi355_sw.h "anchored seed extension", DESIGN.md §3.8 lemma L21): the
+// alignment starts at cell (0,0), in front of x[1] and y[1], both flanks are gaps, and it ends where the score peaks (the best
+// extension, over all cells) or in row m (to the end).  A sibling and not a flag, as the end-to-end kernel above, whose geometry,
+// stream window, table, cell chain, column-0 border (the 16-step prologue) and row-m select it copies; a change of the scaffold must
+// visit all three.  What differs from the end-to-end kernel:
+//   * row 0: H(0,j) = E(0,j) = -(o + (j-1) e), F(0,j) = -inf.  The slot's first lane takes Ho(0,j) = H(0,j) - o and F(1,j) =
+//     H(0,j) - o — the same number, -(2 o + (j-1) e) — from the `old` operand of its two DPP moves: `rowo`, -2 o at step 0 (lane 0
+//     stands on column 1 there) and e lower every step: one subtract per step, not per cell.  Cell (1,1) takes its diagonal from
+//     up_prev = -o: H(0,0) = 0.  Beyond the window the value stays at that of column n (one max per step), so that no register
+//     leaves the admitted range while the slot idles behind a longer window of its wavefront;
+//   * best extension: the local kernel's key fold (WaveKeyFold: value bits | 31 - row, a later column only with a greater VALUE) over
+//     max(H, 0) — one more max per cell.  Cell (0,0) = 0 always competes and every border cell is negative, so the winner is a
+//     positive cell or 0 / 0 / 0, and a negative cell never wins.  The lane's best restarts at its border step: nothing computed left
+//     of column 1 competes;
+//   * to the end: the end-to-end kernel's row-m select and strict compare; after the slot's result H(m,0) = -(o + (m-1) e) is folded
+//     in, and column 0 wins a tie.
+// Padding (L21 (c), restating L19 (c) / (d) for the row-0 border): a padding row (> m) or column (> n) has E and F only, since
+// kPadScoreF enters its diagonal term.  Its E and F derive, by opening or extending a gap, from a real cell in the same row or
+// column — strictly below that cell, which lies in no later column — or from a border cell, which is negative; inductively every
+// padding cell is negative or strictly below a real cell of no later column: it wins neither fold (max(H, 0) and the value-only
+// compare; the strict compare of row m, where the frozen row 0 repeats the all-F value of column n at most).  A padding row never
+// feeds a real one.  Every register stays finite: kPadScoreF enters one sum per cell, whose other operand is an Ho.
+// Exactness: every value of a real cell is an integer of magnitude below 2^24 and every positive H is below 2^19, so that the key's
+// five mantissa bits are free (host_affine.h: affine_ext_exact); the scale 2^-k moves no mantissa bit.
+// best[2 pid] = the best extension, cell[4 pid ..] = end_x, end_y (lengths; 0 / 0 at score 0); best[2 pid + 1] = max over 0 <= j <= n
+// of H(m, j), cell[4 pid + 2 ..] = m and the smallest such column (0: the whole of x as one insertion).
+template <int R>
+__global__ __launch_bounds__(256) void sw_affine_pair_ext_kernel(const AffinePairProblem *probs, int nprob, const AffinePairArgs sa) {
+  static_assert(R >= 1 && R <= 32, "the key holds the row within the lane in five bits");
+  extern __shared__ __attribute__((aligned(16))) uint32_t pairsmem[];
+  __shared__ __attribute__((aligned(16))) uint8_t win[16 * kWaveBuf];
+  float *tab = reinterpret_cast<float *>(pairsmem);                // [nrows][ncls]
+  const int tid = threadIdx.x;
+  const int l = tid & 15;
+  const int slot = tid >> 4;
+  const int pid = blockIdx.x * 16 + slot;
+  const bool active = pid < nprob;
+  const uint8_t *xb = nullptr, *yc = nullptr;
+  int m = 0, n = 0;
+  if (active) { xb = probs[pid].x; yc = probs[pid].y; m = probs[pid].m; n = probs[pid].n; }
+  for (int e = tid; e < sa.nrows * sa.ncls; e += 256) tab[e] = sa.tab[e];
+  uint32_t boff[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = l * R + r;
+    boff[r] = 4u * (i < m ? (uint32_t)sa.cls[xb[i]] : (uint32_t)(sa.ncls - 1));
+  }
+  __syncthreads();
+
+  const uint32_t outside = (uint32_t)(sa.nrows - 1);
+  auto stage_load = [&](int seg) -> uint32_t {
+    return wave_stage_word(yc, n, seg * kWaveSeg + 4 * l, [&](bool in, uint32_t byte) { return in ? byte : outside; });
+  };
+  int nseg, steps4;
+  wave_steps(n, 16, nseg, steps4);
+  uint8_t *buf = win + slot * kWaveBuf;
+  uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
+  const uint8_t *buf_lane = buf + 16 - l;
+  uint32_t nextc = stage_load(0);
+  if (l < 4) buf32[l] = outside * 0x01010101u;
+  buf32[4 + l] = nextc;
+  nextc = stage_load(1);
+
+  float ov = sa.open_s, ev = sa.ext_s;
+  asm volatile("" : "+v"(ov), "+v"(ev));
+  // row 0 as the slot's first lane sees it: Ho(0, j) = F(1, j) = -(2 o + (j - 1) e), column j = step + 1; never below column n's
+  float rowo = -2.0f * sa.open_s;
+  const float rowmin = -(2.0f * sa.open_s + (float)max(n - 1, 0) * sa.ext_s);
+  // Ho = E = H(i,0) - o = -(2 o + (i - 1) e) of the lane's first row, i - 1 = l R (integers below 2^24 units: exact)
+  const float bord0 = -(2.0f * sa.open_s + (float)(l * R) * sa.ext_s);
+  float E[R], Ho[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) { E[r] = bord0 - (float)r * sa.ext_s; Ho[r] = E[r]; }   // lane 0 stands on column 0 here
+  float up_prev = -ov;                                             // Ho(0, 0) of lane 0: H(0,0) = 0
+  float fout = -ov;
+  const float ninf = -__builtin_inff();
+  float blk = 0.0f, blk31 = __uint_as_float(31u);                  // best extension: the lane's best key, and the same with its row bits set
+  int tl = 0;                                                      // the column (0-based) blk was first seen at
+  float best = ninf;                                               // to the end: the greatest H(m, j) so far, first seen at column te
+  int te = 0;
+  const uint32_t row_bytes = 4u * (uint32_t)sa.ncls;
+  const char *tab_b = reinterpret_cast<const char *>(tab);
+  const int wrow = (m > 0 && (m - 1) / R == l) ? (m - 1) % R : -1;
+  bool wsel[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) wsel[r] = wrow == r;
+
+  auto step = [&](auto border, const int gstep, const int k) {
+    constexpr bool BORDER = decltype(border)::value;
+    const int t = gstep - l;
+    const uint32_t c = (uint32_t)buf_lane[k];
+    const char *rowp = tab_b + c * row_bytes;
+    const int rowo_i = (int)__float_as_uint(rowo);
+    const float up = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(rowo_i, (int)__float_as_uint(Ho[R - 1]), 0x111, 0xf, 0xf, false));
+    float frun = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(rowo_i, (int)__float_as_uint(fout), 0x111, 0xf, 0xf, false));
+    rowo = fmaxf(rowo - ev, rowmin);
+    float diag = up_prev;                                          // H(i-1, j-1) - o
+    up_prev = up;
+    float hm = ninf;                                               // H(m, t + 1) in the lane that holds row m
+    float mx = 0.0f, tpend = 0.0f;
+    (void)tpend;
+    const bool on_border = BORDER && t == -1;
+    float bord = bord0;
+    float sv[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) sv[r] = *reinterpret_cast<const float *>(rowp + boff[r]);
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float w = Ho[r];                                       // H(i, j-1) - o
+      const float s = sv[r];
+      float x, g, h, hp, ho, fs;
+      asm("v_add_f32 %0, %1, %2" : "=v"(x) : "v"(diag), "v"(s));   // no clamp: no floor
+      asm("v_sub_f32 %0, %1, %2" : "=v"(g) : "v"(E[r]), "v"(ev));
+      asm("v_max_f32 %0, %1, %2" : "=v"(g) : "v"(g), "v"(w));
+      asm("v_max3_f32 %0, %1, %2, %3" : "=v"(h) : "v"(x), "v"(g), "v"(frun));
+      hm = wsel[r] ? h : hm;
+      asm("v_max_f32 %0, 0, %1" : "=v"(hp) : "v"(h));              // the floor on the answer: cell (0,0) competes
+      WaveKeyFold::cell<R>(r, hp, mx, tpend);
+      asm("v_sub_f32 %0, %1, %2" : "=v"(ho) : "v"(h), "v"(ov));
+      asm("v_sub_f32 %0, %1, %2" : "=v"(fs) : "v"(frun), "v"(ev));
+      asm("v_max_f32 %0, %1, %2" : "=v"(frun) : "v"(fs), "v"(ho));
+      if constexpr (BORDER) { g = on_border ? bord : g; ho = on_border ? bord : ho; bord -= ev; }
+      E[r] = g;
+      Ho[r] = ho;
+      diag = w;
+    }
+    fout = frun;
+    // best extension: a later column wins only with a greater VALUE; to the end: only a strictly greater value
+    const bool take = mx > blk31;
+    tl = take ? t : tl;
+    blk = take ? mx : blk;
+    const bool take_e = hm > best;
+    te = take_e ? t : te;
+    best = take_e ? hm : best;
+    if constexpr (BORDER) { blk = on_border ? 0.0f : blk; best = on_border ? ninf : best; }   // at the border step both restart
+    blk31 = __uint_as_float(__float_as_uint(blk) | 31u);
+  };
+
+  for (int seg = 0; seg < nseg; ++seg) {
+    const int kq = min(kWaveSeg, steps4 - seg * kWaveSeg) >> 2;
+    int k4 = 0;
+    if (seg == 0) {                                                // the 16 steps that hold every lane's border step (steps4 >= 16)
+#pragma unroll 1
+      for (int k = 0; k < 16; ++k) step(std::true_type(), k, k);
+      k4 = 4;
+    }
+    for (; k4 < kq; ++k4) {
+#pragma unroll
+      for (int ku = 0; ku < 4; ++ku) step(std::false_type(), seg * kWaveSeg + 4 * k4 + ku, 4 * k4 + ku);
+    }
+    const uint32_t hist = buf32[kWaveSeg / 4 + (l & 3)];
+    if (l < 4) buf32[l] = hist;
+    buf32[4 + l] = nextc;
+    nextc = stage_load(seg + 2);
+  }
+
+  // the best extension: the lane's winner, then the slot's (value, smaller column, smaller row)
+  const uint32_t kb = __float_as_uint(blk);
+  float bv = __uint_as_float(kb & ~31u) * sa.unscale;
+  long long bi = (long long)l * R + (31 - (int)(kb & 31u)) + 1;
+  long long bj = (long long)tl + 1;
+  if (!(bv > 0.0f)) { bv = 0.0f; bi = 0; bj = 0; }
+  slot_first_max(bv, bi, bj);
+  // to the end: value and column of the lane that holds row m, then column 0, which wins a tie
+  const int wl = m > 0 ? (m - 1) / R : 0;
+  float ev_best = __shfl(best, wl, 16);
+  long long ej = (long long)__shfl(te, wl, 16) + 1;
+  const float col0 = -(sa.open_s + (float)max(m - 1, 0) * sa.ext_s);
+  if (col0 >= ev_best) { ev_best = col0; ej = 0; }
+  if (l == 0 && active) {
+    sa.best[2 * (size_t)pid] = bv;
+    sa.best[2 * (size_t)pid + 1] = ev_best * sa.unscale;
+    sa.cell[4 * (size_t)pid] = bv > 0.0f ? bi : 0;
+    sa.cell[4 * (size_t)pid + 1] = bv > 0.0f ? bj : 0;
+    sa.cell[4 * (size_t)pid + 2] = m;
+    sa.cell[4 * (size_t)pid + 3] = ej;
+  }
+}
+
+// dst[k] = src[n - 1 - k]: the reversed copies behind the backward pairs of the extension calls (no kernel above knows a direction)
+__global__ __launch_bounds__(256) void reverse_bytes_kernel(const uint8_t *src, uint8_t *dst, size_t n) {
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += stride) dst[k] = src[n - 1 - k];
+}
+
 }  // namespace mi355sw

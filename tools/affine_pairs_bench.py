@@ -17,12 +17,19 @@
     the banded exact kernel (option no_affine_band), once per width; kernel time, ratio and the op-count model (ops per cell x cells
     of both kernels, from mi355_sw_last_kernel) come side by side.  Default --out: profiles/affine_pairs_band_n1.json.
 
+  * --extend: the same reads, each window cut to START at the read's true start (the anchored model needs that) and to end 64
+    columns behind it: Context.affine_extend_run on sw_affine_pair_ext_kernel against the local instance (sw_affine_pair_kernel) on the
+    same pairs, alternating in one process, medians; the op-count model of both comes from mi355_sw_last_kernel, and the extension
+    result is checked once against the same call on the exact kernel (option no_affine_pairs).  Default --out:
+    profiles/affine_pairs_extend_n1.json.
+
 Prints ONE JSON line and writes it to --out; kernel times are those of mi355_sw_last_timings (device events), call times are wall
 clock around the call.
 
     python tools/affine_pairs_bench.py [--pairs 100000 --ref-len 5000000 --steps 5 --warmup 1 --out profiles/affine_pairs_n1.json]
     python tools/affine_pairs_bench.py --mode end_to_end
     python tools/affine_pairs_bench.py --band 8,16,32,64
+    python tools/affine_pairs_bench.py --extend
 """
 import argparse
 import json
@@ -48,12 +55,15 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mode", choices=("local", "end_to_end"), default="local")
     ap.add_argument("--band", default=None, help="half widths of the band around the read's diagonal, comma separated")
+    ap.add_argument("--extend", action="store_true", help="the anchored extension call against the local instance")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.extend and (args.band is not None or args.mode != "local"):
+        ap.error("--extend stands alone")
     if args.band is not None and args.mode != "local":
         ap.error("--band needs the local mode")
     if args.out is None:
-        name = "affine_pairs_band_n1.json" if args.band is not None else "affine_pairs_e2e_n1.json" if args.mode == "end_to_end" else "affine_pairs_n1.json"
+        name = "affine_pairs_extend_n1.json" if args.extend else "affine_pairs_band_n1.json" if args.band is not None else "affine_pairs_e2e_n1.json" if args.mode == "end_to_end" else "affine_pairs_n1.json"
         args.out = os.path.join(ROOT, "profiles", name)
     import __graft_entry__ as entry
     pgs = entry._load_package()
@@ -63,13 +73,15 @@ def main(argv=None):
     for k in range(args.pairs):
         read, at = pgs.synth.read_from_ref(ref, 1000 + k, READ_LEN, sub_rate=0.03, indel_rate=0.02)[:2]
         reads.append(read.tobytes())
-        lefts[k] = max(0, int(at) - FLANK)
+        lefts[k] = int(at) if args.extend else max(0, int(at) - FLANK)
         rights[k] = min(args.ref_len, int(at) + READ_LEN + FLANK)
         diag[k] = int(at) - lefts[k]
     query = np.arange(args.pairs, dtype=np.int32)
     ctx = pgs.Context(0)
     ctx.set_reference(ref.tobytes())
     ctx.batch_upload(reads)
+    if args.extend:
+        return extend_against_local(args, ctx, reads, query, lefts, rights)
     if args.mode == "end_to_end":
         return e2e_against_local(args, ctx, reads, query, lefts, rights)
     if args.band is not None:
@@ -151,6 +163,53 @@ def e2e_against_local(args, ctx, reads, query, lefts, rights):
         f.write(text + "\n")
     print(text)
     return 0 if equal and line["not_above_local"] else 1
+
+
+def extend_against_local(args, ctx, reads, query, lefts, rights):
+    """The local instance of the pair kernel and the extension instance on the same pairs (windows that start at the read's true
+    start), alternating; one JSON line."""
+    sides = ("local", "extend")
+    t = {s: dict(kernel_us=[], call_ms=[]) for s in sides}
+    info, results = {}, {}
+    for step in range(args.warmup + args.steps):
+        for side in sides:                                          # alternating: both sides see the same clocks
+            t0 = time.perf_counter()
+            got = ctx.affine_pairs_run(query, lefts, rights, **SCORING) if side == "local" else ctx.affine_extend_run(query, lefts, rights, **SCORING)
+            wall = time.perf_counter() - t0
+            lt, ki = ctx.last_timings(), ctx.last_kernel()
+            info[side] = dict(path=ctx.last_path(), kernel=ki["name"], launches=lt["score_launches"], valu_ops_per_cell=ki["valu_ops_per_cell"])
+            results[side] = got
+            if step >= args.warmup:
+                t[side]["kernel_us"].append(lt["score_us"])
+                t[side]["call_ms"].append(wall * 1e3)
+    ctx.set_option("no_affine_pairs", 1)
+    try:
+        exact = ctx.affine_extend_run(query, lefts, rights, **SCORING)
+    finally:
+        ctx.set_option("no_affine_pairs", 0)
+    fields = ("score", "end_x", "end_y", "to_end_score", "to_end_y")
+    equal = all(np.array_equal(results["extend"][f], exact[f]) for f in fields)
+    ext = results["extend"]
+    cells = float(np.dot([len(r) for r in reads], rights - lefts))
+    line = dict(bench="affine_pairs_bench", mode="extend", pairs=args.pairs, read_len=READ_LEN, window=READ_LEN + FLANK,
+                ref_len=args.ref_len, scoring="3/-3/5/1", steps=args.steps, cells=cells, results_equal_exact_kernel=bool(equal),
+                mean_score=float(ext["score"].mean()), mean_to_end_score=float(ext["to_end_score"].mean()),
+                mean_score_local=float(results["local"]["score"].mean()), clipped=float((ext["end_x"] < READ_LEN).mean()),
+                not_above_local=bool((ext["score"] <= results["local"]["score"]).all()),
+                to_end_not_above_best=bool((ext["to_end_score"] <= ext["score"]).all()))
+    for side in sides:
+        k_us, c_ms = statistics.median(t[side]["kernel_us"]), statistics.median(t[side]["call_ms"])
+        line[side] = dict(info[side], kernel_ms=k_us / 1e3, call_ms=c_ms, gcups_kernel=cells / max(k_us, 1e-9) / 1e3)
+    line["kernel_ratio_ext_over_local"] = line["extend"]["kernel_ms"] / max(line["local"]["kernel_ms"], 1e-9)
+    line["call_ratio_ext_over_local"] = line["extend"]["call_ms"] / max(line["local"]["call_ms"], 1e-9)
+    line["model_ratio_ext_over_local"] = line["extend"]["valu_ops_per_cell"] / line["local"]["valu_ops_per_cell"]
+    ctx.close()
+    text = json.dumps(line)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    print(text)
+    return 0 if equal and line["not_above_local"] and line["to_end_not_above_best"] else 1
 
 
 def banded_against_local(args, ctx, reads, query, lefts, rights, diag):
