@@ -445,6 +445,63 @@ int mi355_sw_affine_extend_trace(mi355_sw_ctx *ctx, const mi355_sw_extend_list *
                                  const uint8_t *to_end /* NULL: best extension for every pair */,
                                  mi355_sw_result *outs, float *to_end_score, int64_t *to_end_y);
 
+/* ---- lists of pairs, anchored seed extension inside a diagonal band (BWA-MEM ksw_extend w, minimap2 ksw_extz -r) ----------
+ * A mapper never extends a seed over the full rectangle: it extends inside a band around the seed's diagonal.  Pair k is as in
+ * mi355_sw_affine_extend_run — x with m rows, y with n columns, forward or backward — and has a band
+ *
+ *     band_lo[k] <= j - i <= band_hi[k]          i the letters of x, j the columns of y consumed from the anchor; signed
+ *
+ * The anchor (0,0) lies on diagonal 0, so band_lo <= 0 <= band_hi is required (ksw_extend's w is [-w, w]).  i and j are counted
+ * from the anchor, so the band means the same for a backward pair, which stays the forward model on both strings reversed.
+ *
+ * Cells outside the band are not part of the matrix: H = E = F = -infinity there — -infinity and not 0, because the model has
+ * no floor.  Inside the band the anchored recurrence and its borders hold unchanged: H(0,0) = 0, H(0,j) = E(0,j) =
+ * -(o + (j-1) e) for in-band j >= 1, H(i,0) = F(i,0) = -(o + (i-1) e) for in-band i >= 1.  Every in-band cell is finite: it is
+ * reachable from the anchor along diagonal 0 and then one gap.
+ *
+ * Best extension: the maximum of H over the in-band cells, >= 0 because (0,0) competes; the end cell is the first maximum in
+ * column-major order, reported as lengths; score 0 comes with 0 / 0.
+ * To the end: the maximum of H(m, j) over the in-band j in 0..n, at the smallest such j.  Row m has an in-band cell exactly when
+ * band_lo <= n - m.  Otherwise the read's end is unreachable: to_end_score = -INFINITY and to_end_y = -1; no kernel decides
+ * this, the host fills it in.  A pair with n = 0 and m >= 1 keeps the host-filled answer of the unbanded call when
+ * band_lo <= -m, and is unreachable otherwise.
+ * Traceback: the rule of the anchored model, unchanged.  An equality with -infinity never holds, so every emitted pair and gap
+ * letter lies on an in-band cell, and the value of the strings is the traced score.  Where to_end[k] != 0 on an unreachable
+ * pair: score -INFINITY, end 0 / 0, pos 0 and empty strings.
+ *
+ * Effective band: lo_e = max(band_lo, -m), hi_e = min(band_hi, n), W = hi_e - lo_e + 1 diagonals.  lo_e == -m and hi_e == n (the
+ * band covers the matrix): the pair IS the unbanded pair, on the unbanded code path with its bytes and its mi355_sw_last_path.
+ * Columns beyond m + hi_e are out of band in every row: the window is clipped to min(n, m + hi_e) columns before anything is
+ * sized or dispatched, so a long window under a narrow band never reaches a cell-count limit.
+ *
+ * Dispatch: the extension instance of the band kernel for 1..512 rows and W <= 256 while the score table fits 32 KiB of LDS and
+ * the admission test holds — every value of a real cell is an integer below 2^24 in magnitude, and a positive score leaves the
+ * winner's key five mantissa bits; with smin (smax) the least (greatest) substitution score, both taken with 0, and a = -smin:
+ *     a rows + 3 gap_open + (W + 1) gap_extend - smin < 2^24,   smax rows + gap_open < 2^24   and   smax (rows + 1) < 2^18
+ * (the cheapest in-band path runs along diagonal 0 and then one gap, not along the borders: H(i,j) >= -(a min(i,j) + o +
+ * (|j-i|-1) e); H - o, E, F one o lower, the scan's H - o of an F another o lower, and one e lower before their maximum; the
+ * diagonal term is (H - o) + (s + o) with s + o >= smin + o) — work in proportion to rows x W.  Every other banded pair: the
+ * exact kernel under the band, within its limits on the CLIPPED window (2^26 cells, about 5 600 rows, a rows + 2 gap_open +
+ * W gap_extend - smin < 2^24 and smax (rows + 1) < 2^24); one pair beyond those fails the whole call with MI355_SW_ENOTSUP,
+ * naming the pair.  A banded pair never runs on an unbanded kernel.  Option no_affine_band sends every banded extension to the
+ * exact kernel; no_affine_pairs does so too.  Backward pairs reuse the reversed copies of the unbanded calls.
+ *
+ * Arguments, their checks and the order of those checks, ownership of the results and "the context stays usable after any
+ * error" are those of mi355_sw_affine_extend_run / _trace; the band checks come last.  band_lo == NULL and band_hi == NULL: the
+ * unbanded call itself (same code path, same bytes).  Exactly one of the two NULL, band_lo[k] > 0 or band_hi[k] < 0:
+ * MI355_SW_EINVAL.
+ * mi355_sw_last_path: "affine_band_ext[R=..]" once per instance of the band kernel that ran (R one of kBandR), "affine_exact_band"
+ * when the exact kernel ran under a band, beside the tags above.  mi355_sw_last_timings: [0] includes the band kernel, [4] /
+ * [5] count its launches and its cells, rows x W per pair.  mi355_sw_last_kernel names the instance
+ * ("sw_affine_band_ext_kernel<R=..>") and its ops per cell.  DESIGN.md §3.8, L22. */
+int mi355_sw_affine_extend_run_band(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo,
+                                    const int64_t *band_hi, const mi355_sw_affine_params *params, float *score,
+                                    int64_t *end_x, int64_t *end_y, float *to_end_score, int64_t *to_end_y);
+int mi355_sw_affine_extend_trace_band(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo,
+                                      const int64_t *band_hi, const mi355_sw_affine_params *params,
+                                      const uint8_t *to_end /* NULL: best extension for every pair */,
+                                      mi355_sw_result *outs, float *to_end_score, int64_t *to_end_y);
+
 /* Host-only helper: piece ranges [left,right). Returns MI355_SW_ERANGE where the reference asserts. */
 int mi355_sw_make_string_range(int npiece, int64_t shortlen, int64_t longlen, float overlap_ratio,
                                int64_t *lefts, int64_t *rights);

@@ -180,18 +180,22 @@ class AffineSWAligner:
 
     @staticmethod
     def extend_pairs(query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0,
-                     scoring=None, context=None, traceback=False, to_end=None):
+                     scoring=None, context=None, traceback=False, to_end=None, band=None):
         """A mapper's seed extension: pair k = the letters [q_lo[k], q_hi[k]) of query[k] against the window [lefts[k], rights[k]),
         anchored in front of both (backward: behind both, the left extension of a seed, on both strings reversed)
         (Context.affine_extend_run, or affine_extend_trace with traceback=True).  Returns that call's dict: the best extension
         (score >= 0, end_x / end_y as lengths) and the extension to the query's end (to_end_score of any sign, to_end_y).
-        q_lo, q_hi, backward and to_end each take a scalar for every pair, or an array; to_end picks the traced alignment."""
+        q_lo, q_hi, backward and to_end each take a scalar for every pair, or an array; to_end picks the traced alignment.
+        band=(lo, hi), lo <= 0 <= hi, each a scalar or an array per pair: extend inside the diagonals lo <= j - i <= hi around the
+        anchor's (BWA-MEM's w is (-w, w)); a read end the band cannot reach has to_end_score float("-inf") and to_end_y -1."""
         ctx = context if context is not None else default_context()
         lut = None
         if scoring is not None:
             lut = _lut_from_function(scoring) if callable(scoring) else np.asarray(scoring, dtype=np.float32)
         kw = dict(q_lo=q_lo, q_hi=q_hi, backward=backward, match=float(match), mismatch=float(mismatch), gap_open=float(gap_open),
                   gap_extend=float(gap_extend), lut=lut)
+        if band is not None:
+            kw["band_lo"], kw["band_hi"] = band
         if traceback:
             return ctx.affine_extend_trace(query, lefts, rights, to_end=to_end, **kw)
         return ctx.affine_extend_run(query, lefts, rights, **kw)

@@ -27,6 +27,7 @@ EXPORTS = [
     "mi355_sw_prefix_values", "mi355_sw_affine_pairs_run_mode", "mi355_sw_affine_pairs_trace_mode",
     "mi355_sw_affine_pairs_run_band", "mi355_sw_affine_pairs_trace_band",
     "mi355_sw_affine_extend_run", "mi355_sw_affine_extend_trace",
+    "mi355_sw_affine_extend_run_band", "mi355_sw_affine_extend_trace_band",
 ]
 AFFINE_LOCAL, AFFINE_END_TO_END = 0, 1                 # mode of the affine pairs calls (include/mi355_sw.h)
 AFFINE_MODES = {"local": AFFINE_LOCAL, "end_to_end": AFFINE_END_TO_END}
@@ -528,38 +529,59 @@ class Context:
             el.backward = back.ctypes.data_as(u8)
         return el, n, (q, lo, hi, ql, qh, back)
 
+    def _extend_bands(self, band_lo, band_hi, n):
+        """(lo, hi) int64 arrays of n bands, or (None, None): each of band_lo / band_hi is a scalar (every pair) or an array per pair."""
+        if (band_lo is None) != (band_hi is None):
+            raise ValueError("band_lo and band_hi must both be given, or neither")
+        return self._per_pair(band_lo, n, np.int64, "band_lo"), self._per_pair(band_hi, n, np.int64, "band_hi")
+
     def affine_extend_run(self, query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0,
-                          gap_extend=1.0, lut=None):
+                          gap_extend=1.0, lut=None, band_lo=None, band_hi=None):
         """Anchored seed extension (mi355_sw_affine_extend_run): pair k = the letters [q_lo[k], q_hi[k]) of resident query query[k]
         (both None: the whole query) against the window [lefts[k], rights[k]) of the resident reference, anchored in front of both;
         backward[k]: anchored behind both, on both strings reversed (the left extension of a seed).  No zero floor, and both flanks
         cost a gap.  Dict of arrays: score (>= 0), end_x, end_y — the best extension, as LENGTHS of query letters and reference
         columns consumed from the anchor — and to_end_score (any sign), to_end_y: the best extension that reaches the query
-        range's end.  q_lo, q_hi and backward each take a scalar for every pair, or an array."""
+        range's end.  q_lo, q_hi and backward each take a scalar for every pair, or an array.
+        band_lo / band_hi (mi355_sw_affine_extend_run_band; a scalar or an array per pair, band_lo <= 0 <= band_hi): only cells with
+        band_lo <= j - i <= band_hi count, i and j the letters and columns consumed from the anchor.  A read end the band cannot
+        reach comes back as to_end_score = float("-inf") and to_end_y = -1."""
         p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
         el, n, arrays = self._extend_list(query, lefts, rights, q_lo, q_hi, backward)
+        blo, bhi = self._extend_bands(band_lo, band_hi, n)
         score, tscore = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
         ex, ey, ty = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
         f32, i64 = C.POINTER(C.c_float), C.POINTER(C.c_int64)
-        self._chk(self._L.mi355_sw_affine_extend_run(self._ctx, C.byref(el), C.byref(p), score.ctypes.data_as(f32), ex.ctypes.data_as(i64),
-                                                     ey.ctypes.data_as(i64), tscore.ctypes.data_as(f32), ty.ctypes.data_as(i64)))
+        outs = (score.ctypes.data_as(f32), ex.ctypes.data_as(i64), ey.ctypes.data_as(i64), tscore.ctypes.data_as(f32), ty.ctypes.data_as(i64))
+        if blo is None:
+            self._chk(self._L.mi355_sw_affine_extend_run(self._ctx, C.byref(el), C.byref(p), *outs))
+        else:
+            self._chk(self._L.mi355_sw_affine_extend_run_band(self._ctx, C.byref(el), blo.ctypes.data_as(i64), bhi.ctypes.data_as(i64),
+                                                              C.byref(p), *outs))
         return dict(score=score, end_x=ex, end_y=ey, to_end_score=tscore, to_end_y=ty)
 
     def affine_extend_trace(self, query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0,
-                            gap_extend=1.0, lut=None, to_end=None):
+                            gap_extend=1.0, lut=None, to_end=None, band_lo=None, band_hi=None):
         """affine_extend_run with the traceback (mi355_sw_affine_extend_trace): score, end_x, end_y describe the TRACED alignment —
         the best extension, or where to_end[k] is set (a scalar for every pair, or an array) the one that ends in (m, to_end_y) —
         with pos, cons_x, cons_y and cigar; to_end_score / to_end_y as affine_extend_run.  The strings run from the far end to the
         anchor: reversed for a forward pair, left to right in the original strings for a backward pair.  The CIGAR is in reading
-        order for both directions."""
+        order for both directions.  band_lo / band_hi (mi355_sw_affine_extend_trace_band): as affine_extend_run; every emitted cell
+        lies in the band, and a pair traced to an end the band cannot reach has score float("-inf"), end 0 / 0 and empty strings."""
         p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
         el, n, arrays = self._extend_list(query, lefts, rights, q_lo, q_hi, backward)
+        blo, bhi = self._extend_bands(band_lo, band_hi, n)
         te = self._per_pair(None if to_end is None else np.asarray(to_end).astype(bool), n, np.uint8, "to_end")
         res = (Result * max(1, n))()
         tscore, ty = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int64)
-        self._chk(self._L.mi355_sw_affine_extend_trace(self._ctx, C.byref(el), C.byref(p),
-                                                       te.ctypes.data_as(C.POINTER(C.c_uint8)) if te is not None else None, res,
-                                                       tscore.ctypes.data_as(C.POINTER(C.c_float)), ty.ctypes.data_as(C.POINTER(C.c_int64))))
+        i64 = C.POINTER(C.c_int64)
+        tail = (te.ctypes.data_as(C.POINTER(C.c_uint8)) if te is not None else None, res,
+                tscore.ctypes.data_as(C.POINTER(C.c_float)), ty.ctypes.data_as(i64))
+        if blo is None:
+            self._chk(self._L.mi355_sw_affine_extend_trace(self._ctx, C.byref(el), C.byref(p), *tail))
+        else:
+            self._chk(self._L.mi355_sw_affine_extend_trace_band(self._ctx, C.byref(el), blo.ctypes.data_as(i64), bhi.ctypes.data_as(i64),
+                                                                C.byref(p), *tail))
         back = arrays[5]
         rows = []
         for k in range(n):

@@ -6,7 +6,8 @@
 //                 affine_pair_route sends each pair to affine_list_stage (sw_affine_pair_kernel, sw_affine_pair_e2e_kernel or
 //                 sw_affine_band_kernel) or to the exact kernel (its E2E or BAND instance)
 //   affine_extend the anchored seed extension of a list of (letters of a query, window) pairs, forward or backward: the same list
-//                 stage on sw_affine_pair_ext_kernel, sw_affine_exact_ext_kernel and sw_affine_trace_ext_kernel behind it
+//                 stage on sw_affine_pair_ext_kernel, sw_affine_exact_ext_kernel and sw_affine_trace_ext_kernel behind it; with a
+//                 diagonal band per pair: sw_affine_band_ext_kernel, sw_affine_exact_ext_band_kernel, sw_affine_trace_ext_band_kernel
 // All share one AffineCall (affine_begin .. affine_end, the latter with affine_trace: sw_affine_trace_kernel), affine_exact_stage
 // (sw_affine_exact_kernel), affine_class_table, affine_download and affine_note_kernel.
 namespace {
@@ -1059,14 +1060,17 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, int
 // ---- the anchored seed extension (include/mi355_sw.h "anchored seed extension", DESIGN.md §3.8 lemma L21) -------------------------
 // The caller's list (validated there, not owned): pair k is the letters [q_lo[k], q_hi[k]) of query qid[k] (both null: the whole
 // query) against [lefts[k], rights[k]) of the reference, backward[k] != 0: on both strings reversed (null: every pair forward).
+// band_lo / band_hi (both null: no bands): pair k counts only cells with band_lo[k] <= j - i <= band_hi[k], i and j from the anchor.
 struct AffineExtList {
   size_t npairs; const int32_t *qid, *q_lo, *q_hi; const int64_t *lefts, *rights; const uint8_t *backward;
+  const int64_t *band_lo = nullptr, *band_hi = nullptr;
   bool back(size_t k) const { return backward && backward[k]; }
 };
 
 // Pair `id` as every kernel takes it: where its letters and its window lie on the device — in the resident buffers, or for a
 // backward pair in their reversed copies — so that no stage below knows a direction.
-struct AffineExtItem { uint32_t id; const uint8_t *x, *ycodes, *ybytes; int32_t m; int64_t n; };
+// banded: the pair runs under its effective band blo <= j - i <= bhi (W diagonals), n the CLIPPED window (affine_extend).
+struct AffineExtItem { uint32_t id; const uint8_t *x, *ycodes, *ybytes; int32_t m; int64_t n; bool banded = false; int32_t blo = 0, bhi = 0, W = 0; };
 
 // Lemma L21, the admission test of sw_affine_pair_ext_kernel: every value of a real cell is an integer below 2^24 in magnitude.
 // H(i,j) >= -(2o + (i+j-2) e), the path along row 0 and down column j, so Ho, E, F >= -(3o + (m+n-2) e), E - e and F - e one e
@@ -1080,6 +1084,24 @@ bool affine_ext_exact(const AffineTable &t, double m, double n) {
 bool affine_ext_whole_exact(const AffineTable &t, double m, double n) {
   return 3.0 * t.open + (m + n) * t.ext < 16777216.0 && 2.0 * t.open + (m + n) * t.ext - t.smin < 16777216.0 &&
          (double)t.smax * (m + 1.0) < 16777216.0;
+}
+
+// Lemma L22, the admission test of sw_affine_band_ext_kernel for a pair of m rows under a band of W diagonals.  The low side is not
+// L21's: the path along row 0 and down a column leaves the band.  The cheapest in-band path to (i,j) runs along diagonal 0 to
+// (min(i,j), min(i,j)), every step at least smin = -a (a = max(-smin, 0); t.smin <= 0), and then one gap of |j-i| <= W - 1 letters, all
+// of it in the band because the band holds diagonal 0: H(i,j) >= -(a min(i,j) + o + (|j-i|-1) e) >= -(a m + o + (W-2) e).
+// So Ho, E, F >= -(a m + 2o + (W-2) e), the scan's Ht - o >= F - o >= -(a m + 3o + (W-2) e) and one e lower inside the lane, E - e and
+// F - e one e lower, the diagonal term Ho + (s + o) >= -(a m + 2o + (W-2) e) + smin + o and the table's |s + o| <= o - smin: one
+// inequality covers the low side, a m + 3o + (W+1) e - smin < 2^24.  (A decayed carry of the scan may fall below: it is rounded,
+// stays below every real value and wins no maximum.)  Upwards H <= smax m and s + o <= smax + o; a positive H lends the key its
+// five low mantissa bits: smax (m + 1) < 2^18.  The exact kernel under a band forms no s + o, runs no scan and has no key: its lowest
+// values are H - o and E - e, F - e >= -(a m + 2o + (W-1) e) and the diagonal term H + s >= -(a m + o + (W-2) e) + smin.
+bool affine_band_ext_exact(const AffineTable &t, double m, double W) {
+  return -(double)t.smin * m + 3.0 * t.open + (W + 1.0) * t.ext - t.smin < 16777216.0 && (double)t.smax * m + t.open < 16777216.0 &&
+         (double)t.smax * (m + 1.0) < kAffineProfBound;
+}
+bool affine_band_ext_whole_exact(const AffineTable &t, double m, double W) {
+  return -(double)t.smin * m + 2.0 * t.open + W * t.ext - t.smin < 16777216.0 && (double)t.smax * (m + 1.0) < 16777216.0;
 }
 
 // The reversed copies of the resident reference (codes and bytes) and of the batch's bytes, built with reverse_bytes_kernel where
@@ -1139,12 +1161,45 @@ struct AffineExtFamily {
   }
 };
 
+// sw_affine_band_ext_kernel (sw_affine_band_kernel.h) for affine_list_stage: the banded pairs of the extension calls, an item with its
+// own pointers, its clipped window and its effective band; two results per problem, as AffineExtFamily.
+struct AffineBandExtFamily {
+  typedef AffineBandProblem Problem; typedef AffineExtItem Item;
+  const AffineCall &c;
+  static constexpr const char *kNoInstance = "internal: no sw_affine_band_ext_kernel instance for this band";
+  static constexpr int kOuts = 2;
+  bool keep_all() const { return true; }
+  static uint32_t id(const Item &a) { return a.id; }
+  static int R(const Item &a) { return affine_band_R(a.W); }
+  static int R(const Problem &p) { return affine_band_R(p.W); }
+  int64_t size(const Item &a) const { return a.m; }                // longest query first, as AffineBandFamily
+  void fill(const Item &a, Problem &p) const { p.x = a.x; p.y = a.ycodes; p.m = a.m; p.n = (int32_t)a.n; p.lo = a.blo; p.W = a.W; }
+  static double cells(const Problem &p) { return (double)p.m * (double)p.W; }
+  auto kernel(int R) const {
+    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
+    with_listed_R<kBandR>(R, [&](auto r) { kern = &sw_affine_band_ext_kernel<decltype(r)::value>; });
+    return kern;
+  }
+  void note(double cells, int R, const Problem &) const {
+    path_note(c.ctx, "affine_band_ext[R=%d]", R);
+    // per step and lane, as compiled: the local band instance's count (AffineBandFamily::note), one more per register — the max with
+    // 0 in front of the key — and four more of overhead (the compare of the step's row with the slot's m in front of the to-end
+    // branch, and moves of the -inf operands).  The branch's four scalar compares are no vector ops, and its fold (six ops per
+    // register) runs at one step of a slot's rows: not counted.  All 16 R registers of a lane row work whatever W is
+    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, 16 * R, 16 * R, 0, (15.0 * R + (R + 1) / 2 + 33.0) / (double)R,
+                       "sw_affine_band_ext_kernel<R=%d>", R);
+  }
+};
+
 // sw_affine_exact_ext_kernel over all of `jobs`, 65536 per launch: score[npairs][2], ends[npairs][2][2] as the list stage; its
 // interval goes to timings[1].
+// BAND: sw_affine_exact_ext_band_kernel over jobs that carry their band (AffineExtItem::blo, bhi) and their clipped window.
+template <bool BAND = false>
 int affine_ext_exact_stage(const AffineCall &c, const std::vector<AffineExtItem> &jobs, float *score, int64_t *ends) {
+  typedef typename AffineExactProblemOf<BAND>::type Problem;
   mi355_sw_ctx *ctx = c.ctx;
   if (jobs.empty()) return 0;
-  path_note(ctx, "affine_exact");
+  path_note(ctx, BAND ? "affine_exact_band" : "affine_exact");
   AffineScoring sc;
   { int rc = affine_scoring(ctx, c.p, sc); if (rc) return rc; }
   HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
@@ -1152,19 +1207,22 @@ int affine_ext_exact_stage(const AffineCall &c, const std::vector<AffineExtItem>
     const size_t n = std::min<size_t>(65536, jobs.size() - lo);
     size_t lds = 0;
     for (size_t k = 0; k < n; ++k) lds = std::max(lds, affine_exact_lds(jobs[lo + k].m));
-    if (ctx->probs.ensure(n * sizeof(ExactProblem)) || ctx->outs_f.ensure(n * 8) || ctx->outs_i.ensure(n * 32))
+    if (ctx->probs.ensure(n * sizeof(Problem)) || ctx->outs_f.ensure(n * 8) || ctx->outs_i.ensure(n * 32))
       return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(exact scratch) failed");
-    std::vector<ExactProblem> pr(n);
+    std::vector<Problem> pr(n);
     for (size_t k = 0; k < n; ++k) {
       const AffineExtItem &j = jobs[lo + k];
-      ExactProblem &e = pr[k];
-      memset(&e, 0, sizeof e);
+      memset(&pr[k], 0, sizeof pr[k]);
+      ExactProblem *ep;
+      if constexpr (BAND) { ep = &pr[k].e; pr[k].blo = j.blo; pr[k].bhi = j.bhi; } else ep = &pr[k];
+      ExactProblem &e = *ep;
       e.x = j.x; e.y = j.ybytes; e.m = j.m; e.nw = (int32_t)j.n; e.full_n = j.n; e.own_lo = 1; e.target = -1.0f;
       e.best = ctx->outs_f.as<float>() + 2 * k;
       e.cell = ctx->outs_i.as<int64_t>() + 4 * k;
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactProblem), hipMemcpyHostToDevice, ctx->stream));
-    launch_dyn_lds(&sw_affine_exact_ext_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactProblem>(), sc);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(Problem), hipMemcpyHostToDevice, ctx->stream));
+    if constexpr (BAND) launch_dyn_lds(&sw_affine_exact_ext_band_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<Problem>(), sc);
+    else launch_dyn_lds(&sw_affine_exact_ext_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactProblem>(), sc);
     HIPCHK(ctx, hipGetLastError());
     std::vector<float> bf(2 * n);
     std::vector<int64_t> ci(4 * n);
@@ -1185,8 +1243,12 @@ int affine_ext_exact_stage(const AffineCall &c, const std::vector<AffineExtItem>
 // Traceback of pair k from the cell (tx[k], ty[k]) of value ts[k]: one sw_affine_trace_ext_kernel problem over the whole rectangle
 // from the anchor to that cell, in launch groups of at most kAffineTraceDirsMax decision bytes.  A cell in column 0 (the letters of
 // x against as many '-') is written here from a copy of the letters: no kernel runs.  tout[npairs]: views into ctx->arenas.
+// BAND: the banded pairs on sw_affine_trace_ext_band_kernel, the others on today's — one pass each (affine_extend); the pass without
+// BAND writes the column-0 cells of both kinds (no kernel runs for them, and the whole of column 0 up to an in-band cell is in band).
+template <bool BAND = false>
 int affine_ext_trace(const AffineCall &c, const std::vector<AffineExtItem> &pairs, const float *ts, const int64_t *tx, const int64_t *ty,
                      std::vector<TraceOut> &tout) {
+  typedef typename AffineTraceProblemOf<BAND>::type Problem;
   mi355_sw_ctx *ctx = c.ctx;
   struct Job { size_t k; size_t dirs_off, cons_off; };
   std::vector<Job> jobs;
@@ -1194,7 +1256,8 @@ int affine_ext_trace(const AffineCall &c, const std::vector<AffineExtItem> &pair
   size_t col0_bytes = 0;
   for (size_t k = 0; k < pairs.size(); ++k) {
     if (tx[k] < 1) continue;
-    if (ty[k] < 1) { col0.push_back(k); col0_bytes += 2 * (size_t)tx[k]; continue; }
+    if (ty[k] < 1) { if (!BAND) { col0.push_back(k); col0_bytes += 2 * (size_t)tx[k]; } continue; }
+    if (pairs[k].banded != BAND) continue;
     if (dirs_bytes(tx[k], ty[k]) > kAffineTraceDirsMax || affine_exact_lds((int)std::min<int64_t>(tx[k], 1 << 24)) > kExactLdsMax) {
       char msg[240];
       std::snprintf(msg, sizeof msg, "affine extension traceback: pair %zu needs a rectangle of %lld rows x %lld columns, more than %zu "
@@ -1242,14 +1305,16 @@ int affine_ext_trace(const AffineCall &c, const std::vector<AffineExtItem> &pair
       ++hi;
     }
     const size_t n = hi - lo;
-    if (ctx->wprobs.ensure(n * sizeof(AffineTraceProblem)) || ctx->walkp.ensure(n * 24) || ctx->dirs.ensure(dirs_total) ||
+    if (ctx->wprobs.ensure(n * sizeof(Problem)) || ctx->walkp.ensure(n * 24) || ctx->dirs.ensure(dirs_total) ||
         ctx->cons.ensure(cons_total + 16))
       return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(affine traceback scratch) failed");
-    std::vector<AffineTraceProblem> pr(n);
+    std::vector<Problem> pr(n);
     for (size_t k = 0; k < n; ++k) {
       const Job &j = jobs[lo + k];
-      AffineTraceProblem &a = pr[k];
-      memset(&a, 0, sizeof a);
+      memset(&pr[k], 0, sizeof pr[k]);
+      AffineTraceProblem *ap;
+      if constexpr (BAND) { ap = &pr[k].t; pr[k].blo = pairs[j.k].blo; pr[k].bhi = pairs[j.k].bhi; } else ap = &pr[k];
+      AffineTraceProblem &a = *ap;
       a.e.x = pairs[j.k].x; a.e.y = pairs[j.k].ybytes;
       a.e.m = (int32_t)tx[j.k]; a.e.nw = (int32_t)ty[j.k];
       a.e.own_lo = 1;
@@ -1261,9 +1326,10 @@ int affine_ext_trace(const AffineCall &c, const std::vector<AffineExtItem> &pair
       a.clamped = 1; a.row_clamped = 1;
       a.out = ctx->walkp.as<int64_t>() + 3 * k;
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr.data(), n * sizeof(AffineTraceProblem), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr.data(), n * sizeof(Problem), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-    launch_dyn_lds(&sw_affine_trace_ext_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<AffineTraceProblem>(), sc);
+    if constexpr (BAND) launch_dyn_lds(&sw_affine_trace_ext_band_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<Problem>(), sc);
+    else launch_dyn_lds(&sw_affine_trace_ext_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<AffineTraceProblem>(), sc);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     std::vector<int64_t> wo(3 * n);
@@ -1294,6 +1360,10 @@ int affine_ext_trace(const AffineCall &c, const std::vector<AffineExtItem> &pair
 // (lengths), then m, to_end_y.  tout (may be null): the traceback of every pair, from the best extension's cell or, where
 // to_end[k] != 0 (to_end may be null), from (m, to_end_y).  A pair runs on sw_affine_pair_ext_kernel while rows, columns, table and
 // admission (affine_ext_exact) allow, else as a whole problem of the exact kernel; an empty window is filled in here.
+// With bands (el.band_lo): a pair whose clipped band covers its matrix takes that same route; every other pair is a banded pair on its
+// clipped window — sw_affine_band_ext_kernel while rows, diagonals, table and admission (affine_band_ext_exact) allow and option
+// no_affine_band is off, else the exact kernel under the band — and never runs on an unbanded kernel.  The stages run in a fixed
+// order: the pair kernel, the band kernel, the exact kernel's unbanded and then its banded jobs, the two passes of the traceback.
 int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const AffineExtList &el, const mi355_sw_affine_params &p,
                   const uint8_t *to_end, float *score, int64_t *ends, std::vector<TraceOut> *tout) {
   const size_t npairs = el.npairs;
@@ -1319,7 +1389,9 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   if (any_back) { rc = affine_ext_reversed(ctx, ref, q); if (rc) return rc; }
 
   std::vector<AffineExtItem> pairs(npairs), fast, jobs;
-  int mmax = 0;
+  std::vector<AffineExtItem> bfast, bjobs;                         // banded pairs of sw_affine_band_ext_kernel, and of the exact kernel under a band
+  std::vector<char> unreach(el.band_lo ? npairs : 0, 0);           // the band misses row m: the host fills in to_end
+  int mmax = 0, band_mmax = 0;
   for (size_t k = 0; k < npairs; ++k) {
     const int qi = el.qid[k];
     const int64_t qlo = el.q_lo ? el.q_lo[k] : 0, qhi = el.q_hi ? el.q_hi[k] : q.len[qi];
@@ -1336,6 +1408,35 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
       it.ybytes = ref.bytes.as<uint8_t>() + el.lefts[k];
     }
     if (m < 1) continue;
+    if (el.band_lo) {
+      // the band clipped to the matrix; one that covers it leaves the pair unbanded: today's route below, today's bytes
+      const int64_t lo_e = std::max(el.band_lo[k], -m), hi_e = std::min(el.band_hi[k], n);
+      if (lo_e != -m || hi_e != n) {
+        const bool reach = lo_e <= n - m;                          // row m holds an in-band cell
+        if (!reach) unreach[k] = 1;
+        if (n < 1) continue;                                       // (lo_e > -m: unreachable) nothing to extend: the zeros stand
+        // columns beyond m + hi_e are out of band in every row: the window is clipped before anything is sized
+        const int64_t nc = std::min(n, m + hi_e), W = hi_e - lo_e + 1;
+        it.n = nc; it.banded = true; it.blo = (int32_t)lo_e; it.bhi = (int32_t)std::min(hi_e, nc); it.W = (int32_t)std::min<int64_t>(W, 0x7fffffff);
+        if (table_ok && !opt().no_affine_band && m <= kBandRowsMax && affine_band_R(W) != 0 && affine_band_ext_exact(c.t, (double)m, (double)W)) {
+          bfast.push_back(it); band_mmax = std::max(band_mmax, (int)m);
+          continue;
+        }
+        if ((double)m * (double)nc > kAffineExactCellsMax || !affine_band_ext_whole_exact(c.t, (double)m, (double)W) || affine_exact_lds((int)m) > kExactLdsMax) {
+          char msg[800];
+          std::snprintf(msg, sizeof msg, "affine extension: banded pair %zu (%lld rows x %lld columns, clipped to %lld; %lld diagonals) is outside the band "
+                        "kernel (1..512 rows, at most 256 diagonals, a rows + 3 gap_open + (diagonals + 1) gap_extend - min(smin, 0) < 2^24 with a = "
+                        "max(-smin, 0), smax * (rows + 1) < 2^18, a score table within 32 KiB%s) and outside the exact kernel under a band (at most "
+                        "2^26 cells of rows x clipped columns and 5600 rows, a rows + 2 gap_open + diagonals gap_extend - min(smin, 0) < 2^24, "
+                        "smax * (rows + 1) < 2^24)", k, (long long)m,
+                        (long long)n, (long long)nc, (long long)W,
+                        opt().no_affine_band ? "; option no_affine_band is set" : opt().no_affine_pairs ? "; option no_affine_pairs is set" : "");
+          return fail(ctx, MI355_SW_ENOTSUP, msg);
+        }
+        bjobs.push_back(it);
+        continue;
+      }
+    }
     if (n < 1) {                                                   // the whole of x as one insertion; nothing to extend
       score[2 * k + 1] = -((float)c.t.open + (float)(m - 1) * (float)c.t.ext);
       ends[4 * k + 2] = m;
@@ -1356,8 +1457,16 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     jobs.push_back(it);
   }
   rc = affine_list_stage(AffineExtFamily{c}, plan, fast, mmax, score, ends);
+  if (!rc) rc = affine_list_stage(AffineBandExtFamily{c}, plan, bfast, band_mmax, score, ends);
   if (!rc) rc = affine_ext_exact_stage(c, jobs, score, ends);
+  if (!rc) rc = affine_ext_exact_stage<true>(c, bjobs, score, ends);
   if (rc) return rc;
+  // a read whose end the band cannot reach: no kernel decides this.  Such a pair still ran on its kernel above, for the best
+  // extension; what that kernel wrote for the to-end half (-inf / -1 as it happens) is deliberately ignored and overwritten here, so
+  // that the header's rule band_lo > n - m alone decides.  Keep the overwrite.  Traced to the end the pair is an empty alignment
+  // (row 0 of `ends`: affine_ext_trace skips it)
+  for (size_t k = 0; k < unreach.size(); ++k)
+    if (unreach[k]) { score[2 * k + 1] = -INFINITY; ends[4 * k + 2] = 0; ends[4 * k + 3] = -1; }
   if (tout) {
     std::vector<float> ts(npairs);
     std::vector<int64_t> tx(npairs), ty(npairs);
@@ -1366,6 +1475,7 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
       ts[k] = score[2 * k + w]; tx[k] = ends[4 * k + 2 * w]; ty[k] = ends[4 * k + 2 * w + 1];
     }
     rc = affine_ext_trace(c, pairs, ts.data(), tx.data(), ty.data(), *tout);
+    if (!rc && (!bfast.empty() || !bjobs.empty())) rc = affine_ext_trace<true>(c, pairs, ts.data(), tx.data(), ty.data(), *tout);
     if (rc) return rc;
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));

@@ -12,7 +12,8 @@
 //                      sw_affine_prof_kernel for references (ranges) of at most 512 letters,
 //                      sw_affine_pair_kernel (end-to-end: sw_affine_pair_e2e_kernel) for lists of (query, window)
 //                      pairs, sw_affine_band_kernel for those with a diagonal band and sw_affine_pair_ext_kernel
-//                      for the anchored seed extension, forward and backward                          host_affine.h
+//                      for the anchored seed extension, forward and backward (inside a band per pair:
+//                      sw_affine_band_ext_kernel)                                                      host_affine.h
 //                      (entry points: affine_align_any, affine_batch_any, affine_pairs_any, affine_extend_any — one body
 //                      per run / trace twin)
 // Problems the score kernel does not cover (see bucket_fast_ok) run 2+3 on the whole matrix.
@@ -544,9 +545,10 @@ int mi355_sw_affine_pairs_trace_band(mi355_sw_ctx *ctx, int mode, size_t npairs,
 }
 
 // mi355_sw_affine_extend_run (score .. to_end_y) and, with `trace`, mi355_sw_affine_extend_trace (outs), written only after success
+// (and their _band twins: without bands the call itself; the band checks come last)
 static int affine_extend_any(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const mi355_sw_affine_params *params, bool trace,
                              const uint8_t *to_end, float *score, int64_t *end_x, int64_t *end_y, mi355_sw_result *outs, float *to_end_score,
-                             int64_t *to_end_y) {
+                             int64_t *to_end_y, const int64_t *band_lo = nullptr, const int64_t *band_hi = nullptr) {
   OptScope opt_scope_(ctx);
   int rc = affine_check(ctx, params);
   if (rc) return rc;
@@ -565,10 +567,14 @@ static int affine_extend_any(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list
     if (list->q_lo && (list->q_lo[k] < 0 || list->q_hi[k] < list->q_lo[k] || list->q_hi[k] > ctx->batch.len[list->query[k]]))
       return fail(ctx, MI355_SW_EINVAL, "pair: letters [q_lo, q_hi) outside the query");
   }
+  if ((band_lo == nullptr) != (band_hi == nullptr)) return fail(ctx, MI355_SW_EINVAL, "banded extension: band_lo and band_hi must both be given, or neither");
+  if (band_lo)
+    for (size_t k = 0; k < npairs; ++k)
+      if (band_lo[k] > 0 || band_hi[k] < 0) return fail(ctx, MI355_SW_EINVAL, "banded extension: the band must hold the anchor's diagonal, band_lo <= 0 <= band_hi");
   std::vector<float> sc(2 * npairs, 0.0f);
   std::vector<int64_t> ends(4 * npairs, 0);
   std::vector<TraceOut> tout(trace ? npairs : 0);
-  const AffineExtList el{npairs, list->query, list->q_lo, list->q_hi, list->lefts, list->rights, list->backward};
+  const AffineExtList el{npairs, list->query, list->q_lo, list->q_hi, list->lefts, list->rights, list->backward, band_lo, band_hi};
   rc = affine_extend(ctx, ctx->ref, ctx->batch, el, *params, trace ? to_end : nullptr, sc.data(), ends.data(), trace ? &tout : nullptr);
   if (rc) return rc;
   for (size_t k = 0; k < npairs; ++k) {
@@ -577,6 +583,7 @@ static int affine_extend_any(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list
       memset(&outs[k], 0, sizeof outs[k]);
       set_result(outs[k], sc[2 * k + w], ends[4 * k + 2 * w], ends[4 * k + 2 * w + 1], &tout[k]);
       outs[k].end_x = ends[4 * k + 2 * w]; outs[k].end_y = ends[4 * k + 2 * w + 1];   // (whatever the sign of the score)
+      if (w == 1 && sc[2 * k + 1] == -INFINITY) outs[k].end_x = outs[k].end_y = 0;   // traced to an end the band cannot reach: empty
       outs[k].timings_us[0] = outs[k].timings_us[1] = (float)ctx->timings[0];
     } else { score[k] = sc[2 * k]; end_x[k] = ends[4 * k]; end_y[k] = ends[4 * k + 1]; }
     if (to_end_score) to_end_score[k] = sc[2 * k + 1];
@@ -593,6 +600,18 @@ int mi355_sw_affine_extend_run(mi355_sw_ctx *ctx, const mi355_sw_extend_list *li
 int mi355_sw_affine_extend_trace(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const mi355_sw_affine_params *params,
                                  const uint8_t *to_end, mi355_sw_result *outs, float *to_end_score, int64_t *to_end_y) {
   return affine_extend_any(ctx, list, params, true, to_end, nullptr, nullptr, nullptr, outs, to_end_score, to_end_y);
+}
+
+int mi355_sw_affine_extend_run_band(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo, const int64_t *band_hi,
+                                    const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y, float *to_end_score,
+                                    int64_t *to_end_y) {
+  return affine_extend_any(ctx, list, params, false, nullptr, score, end_x, end_y, nullptr, to_end_score, to_end_y, band_lo, band_hi);
+}
+
+int mi355_sw_affine_extend_trace_band(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo, const int64_t *band_hi,
+                                      const mi355_sw_affine_params *params, const uint8_t *to_end, mi355_sw_result *outs, float *to_end_score,
+                                      int64_t *to_end_y) {
+  return affine_extend_any(ctx, list, params, true, to_end, nullptr, nullptr, nullptr, outs, to_end_score, to_end_y, band_lo, band_hi);
 }
 
 int mi355_sw_best_range(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,

@@ -252,6 +252,11 @@ enum : int { kAffStop = 0, kAffDiag = 1, kAffE = 2, kAffF = 3, kAffEExt = 4, kAf
 // -(o + (j-1) e), F(0,j) = -inf, H(0,0) = 0.  Two winners: the first column-major maximum over all cells — the local model's key
 // order; only a positive cell can beat cell (0,0) = 0, and the border cells are negative, so the cells of the loop are all that
 // compete — and the maximum of row m with its smallest column (end, end_j; column 0 is the caller's to fold in).  TRACE: as E2E.
+// EXT with BAND: the anchored model inside blo <= jl - i <= bhi, blo <= 0 <= bhi (include/mi355_sw.h).  An out-of-band cell is written as
+// H = E = F = -inf, not 0: the model has no floor, so a 0 outside would win.  A border cell of row 0 or column 0 keeps its value only
+// where it lies in the band, else it is -inf as well.  The loop is the banded one, so both folds see in-band cells only, all finite;
+// a row m without an in-band cell leaves end = -inf (the host reports the pair as unreachable).  TRACE: an equality with -inf never
+// holds, so the walk stays in the band; it meets row 0 or column 0 on an in-band cell, and the rest of that border towards (0,0) is.
 struct AffineBest { float best; int64_t i, j; float end; int64_t end_j; };
 enum : int { kAffineModelLocal = 0, kAffineModelE2E = 1, kAffineModelExt = 2 };
 template <bool TRACE, int MODEL, bool BAND>
@@ -259,7 +264,8 @@ __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem
                                                               const int bhi) {
   constexpr bool EXT = MODEL == kAffineModelExt;
   constexpr bool E2E = MODEL != kAffineModelLocal;                 // no floor and the column-0 border: both floor-free models
-  static_assert(!(BAND && E2E), "the banded end-to-end model is not defined");
+  static_assert(!(BAND && MODEL == kAffineModelE2E), "the banded end-to-end model is not defined");
+  constexpr bool XB = EXT && BAND;                                 // the anchored model under a band: outside is -inf, borders only in the band
   const int lane = threadIdx.x;
   const int m = P.m, nw = P.nw;
   const int plen = m + 2;
@@ -273,6 +279,10 @@ __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem
   for (int k = lane; k < m; k += 64) xs[k] = P.x[k];
   if (E2E && lane == 0 && m >= 1) { H0[1] = -sc.gap_open; F0[1] = -sc.gap_open; }   // diagonal 1: cell (1, 0)
   if (EXT && lane == 0) { H0[0] = -sc.gap_open; E0[0] = -sc.gap_open; }             // and cell (0, 1)
+  if (XB && lane == 0) {                                           // the two border cells of diagonal 1 where they miss the band
+    if (m >= 1 && blo > -1) { H0[1] = ninf; F0[1] = ninf; }
+    if (bhi < 1) { H0[0] = ninf; E0[0] = ninf; }
+  }
 
   float best = (E2E && (TRACE || !EXT)) ? ninf : -1.0f;            // (EXT, score pass: only a positive cell beats cell (0,0))
   float end = ninf;                                                // EXT: the greatest H(m, jl) and its first column
@@ -296,6 +306,10 @@ __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem
         const float b0 = E2E ? -(sc.gap_open + (float)(d - 1) * sc.gap_extend) : 0.0f;   // (integers below 2^24: exact)
         Hc[d] = b0; Ec[d] = ninf; Fc[d] = E2E ? b0 : ninf;
       }
+      if (XB) {                                                    // cells (0, d) and (d, 0) outside the band
+        if (d > bhi) { Hc[0] = ninf; Ec[0] = ninf; }
+        if (d <= m && -d < blo) { Hc[d] = ninf; Fc[d] = ninf; }
+      }
     }
     const int ilo = d - nw > 1 ? d - nw : 1;
     const int ihi = d - 1 < m ? d - 1 : m;
@@ -307,7 +321,7 @@ __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem
     }
     for (int i = i0 + lane; i <= i1; i += 64) {
       const int jl = d - i;
-      if (BAND && (jl - i < blo || jl - i > bhi)) { Hc[i] = 0.0f; Ec[i] = ninf; Fc[i] = ninf; continue; }
+      if (BAND && (jl - i < blo || jl - i > bhi)) { Hc[i] = XB ? ninf : 0.0f; Ec[i] = ninf; Fc[i] = ninf; continue; }
       const uint8_t xa = xs[i - 1], yb = P.y[jl - 1];
       const float s = sc.lut ? sc.lut[(int)xa * 256 + yb] : (xa == yb ? sc.match : sc.mismatch);
       const float eo = Hp[i] - go, fo = Hp[i - 1] - go;            // a gap opened from (i, jl-1) / (i-1, jl) on d-1
@@ -402,6 +416,25 @@ __global__ __launch_bounds__(64) void sw_affine_exact_ext_kernel(const ExactProb
     P.best[1] = at0 ? col0 : r.end;
     P.cell[0] = pos ? r.i : 0; P.cell[1] = pos ? r.j : 0;
     P.cell[2] = P.m; P.cell[3] = at0 ? 0 : r.end_j;
+  }
+}
+
+// The same under a band (ExactBandProblem: blo <= 0 <= bhi, in the pair's own coordinates — the anchor is the window's corner).  Column
+// 0 of row m competes only where it lies in the band; a row m that the band misses: P.best[1] = -inf, P.cell[3] = -1.
+__global__ __launch_bounds__(64) void sw_affine_exact_ext_band_kernel(const ExactBandProblem *probs, const AffineScoring sc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  const ExactProblem P = probs[blockIdx.x].e;
+  const int blo = probs[blockIdx.x].blo, bhi = probs[blockIdx.x].bhi;
+  const AffineBest r = affine_exact_fill_model<false, kAffineModelExt, true>(P, sc, smem_raw, blo, bhi);
+  if (threadIdx.x == 0) {
+    const bool pos = r.best > 0.0f;
+    const float col0 = blo <= -P.m ? -(sc.gap_open + (float)(P.m - 1) * sc.gap_extend) : -__builtin_inff();
+    const bool at0 = col0 >= r.end && blo <= -P.m;
+    const float end = at0 ? col0 : r.end;
+    P.best[0] = pos ? r.best : 0.0f;
+    P.best[1] = end;
+    P.cell[0] = pos ? r.i : 0; P.cell[1] = pos ? r.j : 0;
+    P.cell[2] = P.m; P.cell[3] = at0 ? 0 : (end == -__builtin_inff() ? -1 : r.end_j);
   }
 }
 
@@ -511,6 +544,12 @@ __global__ __launch_bounds__(64) void sw_affine_trace_kernel(const typename Affi
 __global__ __launch_bounds__(64) void sw_affine_trace_ext_kernel(const AffineTraceProblem *probs, const AffineScoring sc) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   affine_trace_body<kAffineModelExt, false>(probs, sc, smem_raw);
+}
+
+// under a band, in the pair's own coordinates: the rectangle runs from the anchor to the traced cell, so the band needs no shift
+__global__ __launch_bounds__(64) void sw_affine_trace_ext_band_kernel(const AffineTraceBandProblem *probs, const AffineScoring sc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  affine_trace_body<kAffineModelExt, true>(probs, sc, smem_raw);
 }
 
 }  // namespace mi355sw

@@ -23,6 +23,12 @@
     result is checked once against the same call on the exact kernel (option no_affine_pairs).  Default --out:
     profiles/affine_pairs_extend_n1.json.
 
+  * --extend --band W_HALF[,W_HALF..]: the pairs of --extend with the band [-w, w] around the anchor's diagonal,
+    Context.affine_extend_run(band_lo=, band_hi=) on sw_affine_band_ext_kernel, against the unbanded extension call
+    (sw_affine_pair_ext_kernel) on the same pairs, alternating in one process, medians.  A band is a different answer, so the check
+    is the exact kernel under the band (option no_affine_band), once per width; kernel time, ratio and the ratio the row loop's op
+    count predicts come side by side.  Default --out: profiles/affine_extend_band_n1.json.
+
 Prints ONE JSON line and writes it to --out; kernel times are those of mi355_sw_last_timings (device events), call times are wall
 clock around the call.
 
@@ -30,6 +36,7 @@ clock around the call.
     python tools/affine_pairs_bench.py --mode end_to_end
     python tools/affine_pairs_bench.py --band 8,16,32,64
     python tools/affine_pairs_bench.py --extend
+    python tools/affine_pairs_bench.py --extend --band 8,16,32,64
 """
 import argparse
 import json
@@ -58,12 +65,12 @@ def main(argv=None):
     ap.add_argument("--extend", action="store_true", help="the anchored extension call against the local instance")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
-    if args.extend and (args.band is not None or args.mode != "local"):
-        ap.error("--extend stands alone")
+    if args.extend and args.mode != "local":
+        ap.error("--extend needs the local mode")
     if args.band is not None and args.mode != "local":
         ap.error("--band needs the local mode")
     if args.out is None:
-        name = "affine_pairs_extend_n1.json" if args.extend else "affine_pairs_band_n1.json" if args.band is not None else "affine_pairs_e2e_n1.json" if args.mode == "end_to_end" else "affine_pairs_n1.json"
+        name = "affine_extend_band_n1.json" if args.extend and args.band is not None else "affine_pairs_extend_n1.json" if args.extend else "affine_pairs_band_n1.json" if args.band is not None else "affine_pairs_e2e_n1.json" if args.mode == "end_to_end" else "affine_pairs_n1.json"
         args.out = os.path.join(ROOT, "profiles", name)
     import __graft_entry__ as entry
     pgs = entry._load_package()
@@ -80,6 +87,8 @@ def main(argv=None):
     ctx = pgs.Context(0)
     ctx.set_reference(ref.tobytes())
     ctx.batch_upload(reads)
+    if args.extend and args.band is not None:
+        return banded_extend_against_extend(args, ctx, reads, query, lefts, rights)
     if args.extend:
         return extend_against_local(args, ctx, reads, query, lefts, rights)
     if args.mode == "end_to_end":
@@ -210,6 +219,68 @@ def extend_against_local(args, ctx, reads, query, lefts, rights):
         f.write(text + "\n")
     print(text)
     return 0 if equal and line["not_above_local"] and line["to_end_not_above_best"] else 1
+
+
+def banded_extend_against_extend(args, ctx, reads, query, lefts, rights):
+    """The unbanded extension instance and the banded one at every half width of --band on the same pairs, alternating; one JSON line."""
+    widths = [int(w) for w in str(args.band).split(",")]
+    sides = ["extend"] + ["band_w%d" % w for w in widths]
+    bands = {"band_w%d" % w: (-w, w) for w in widths}
+    fields = ("score", "end_x", "end_y", "to_end_score", "to_end_y")
+    t = {s: dict(kernel_us=[], call_ms=[]) for s in sides}
+    info, results = {}, {}
+    for step in range(args.warmup + args.steps):
+        for side in sides:                                          # alternating: all sides see the same clocks
+            kw = dict(band_lo=bands[side][0], band_hi=bands[side][1]) if side in bands else {}
+            t0 = time.perf_counter()
+            got = ctx.affine_extend_run(query, lefts, rights, **kw, **SCORING)
+            wall = time.perf_counter() - t0
+            lt, ki = ctx.last_timings(), ctx.last_kernel()
+            info[side] = dict(path=ctx.last_path(), kernel=ki["name"], launches=lt["score_launches"], valu_ops_per_cell=ki["valu_ops_per_cell"],
+                              rows_per_lane=ki["rows_per_lane"], cells=lt["cells"])
+            results[side] = got
+            if step >= args.warmup:
+                t[side]["kernel_us"].append(lt["score_us"])
+                t[side]["call_ms"].append(wall * 1e3)
+    equal = {}
+    ctx.set_option("no_affine_band", 1)
+    try:
+        for side in bands:
+            exact = ctx.affine_extend_run(query, lefts, rights, band_lo=bands[side][0], band_hi=bands[side][1], **SCORING)
+            equal[side] = all(np.array_equal(results[side][f], exact[f]) for f in fields)
+    finally:
+        ctx.set_option("no_affine_band", 0)
+    line = dict(bench="affine_pairs_bench", mode="extend", band_half_widths=widths, pairs=args.pairs, read_len=READ_LEN,
+                window=READ_LEN + FLANK, ref_len=args.ref_len, scoring="3/-3/5/1", steps=args.steps, results_equal_exact_kernel=equal)
+    for side in sides:
+        k_us, c_ms = statistics.median(t[side]["kernel_us"]), statistics.median(t[side]["call_ms"])
+        line[side] = dict(info[side], kernel_ms=k_us / 1e3, call_ms=c_ms, gcups_kernel=info[side]["cells"] / max(k_us, 1e-9) / 1e3,
+                          mean_score=float(results[side]["score"].mean()), mean_to_end_score=float(results[side]["to_end_score"][np.isfinite(results[side]["to_end_score"])].mean()))
+        # the spread of the timed steps, beside the medians: a ratio of a few percent means nothing inside it
+        line[side].update(kernel_ms_min=min(t[side]["kernel_us"]) / 1e3, kernel_ms_max=max(t[side]["kernel_us"]) / 1e3,
+                          call_ms_min=min(t[side]["call_ms"]), call_ms_max=max(t[side]["call_ms"]))
+    base = line["extend"]
+    steps_ext, steps_band = float((rights - lefts + 15).sum()), float(sum(len(r) for r in reads))
+    for side in bands:
+        b = line[side]
+        b["same_score_as_unbanded"] = float((results[side]["score"] == results["extend"]["score"]).mean())
+        b["same_to_end_as_unbanded"] = float((results[side]["to_end_score"] == results["extend"]["to_end_score"]).mean())
+        b["unreachable"] = float((results[side]["to_end_y"] < 0).mean())
+        b["not_above_unbanded"] = bool((results[side]["score"] <= results["extend"]["score"]).all() and
+                                       (results[side]["to_end_score"] <= results["extend"]["to_end_score"]).all())
+        b["kernel_ratio_unbanded_over_band"] = base["kernel_ms"] / max(b["kernel_ms"], 1e-9)
+        b["call_ratio_unbanded_over_band"] = base["call_ms"] / max(b["call_ms"], 1e-9)
+        # ops of a lane per pair: steps x registers x ops per register — the pair instance streams the window's columns + 15 of skew
+        # past its rows, the band kernel steps through the rows over all 16 R diagonals of its instance, whatever W is
+        b["model_ratio_unbanded_over_band"] = (steps_ext * base["rows_per_lane"] * base["valu_ops_per_cell"]) / \
+                                              (steps_band * b["rows_per_lane"] * b["valu_ops_per_cell"])
+    ctx.close()
+    text = json.dumps(line)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    print(text)
+    return 0 if all(equal.values()) and all(line[s]["not_above_unbanded"] for s in bands) else 1
 
 
 def banded_against_local(args, ctx, reads, query, lefts, rights, diag):
