@@ -555,6 +555,12 @@ int mi355_sw_last_counters(const mi355_sw_ctx *ctx, uint64_t out[4]);
  * offenders of that pass take ONE prefix pass at the next height before the sweep of all rows; "prefix_second_pass" counts the reads
  * that took it.  "no_prefix_cascade" gives such buckets the flow of the smaller ones, "no_prefix_step" keeps the chain on the tiles
  * that fold every 4th step (both A/Bs).
+ * On those step tiles the flags of a pass are thinned before the locate stage: each flagged sub-chunk is evaluated on the read's first
+ * 38 rows, and only the sub-chunks where that row reaches its own threshold go on.  A read over its candidate cap
+ * with up to 1024 flags is thinned instead of offending (65 536 flags for all such reads of a pass, the fewest first); "prefix_thinned" counts the reads whose flags took the thin stage,
+ * "prefix_thin_items" the (read, sub-chunk) items it evaluated, and "candidates" what reached the locate stage.  "no_prefix_thin"
+ * switches the stage off (the A/B); "prefix_thin_min_cols" = n moves the reference length from which it engages (default 4 Mi columns:
+ * below the default of "prefix_min_cols").
  * MI355_SW_EINVAL for an unknown name. */
 int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *out);
 
@@ -564,6 +570,16 @@ int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *o
  * nothing written) when the last call left no such values; values may be NULL to ask for *n_sub alone.
  * mi355_sw_set_option("prefix_rowp_step", R) works the same way on the instance that folds row P at every step. */
 int mi355_sw_prefix_values(mi355_sw_ctx *ctx, float *values, size_t capacity, size_t *n_sub);
+
+/* Test hook, open only under mi355_sw_set_option("prefix_thin_items", "1").  The thin stage of the prefix filter
+ * on a caller's list: items[2 k], items[2 k + 1] = (resident query, sub-chunk of sub_len columns) of the range [left, right) of the
+ * resident reference, as a row-P pass (P rows) would flag them; P2 is the taller height (38).  Per item the kernel sweeps the
+ * read's first P2 rows over [s sub_len - 64 - warm, (s + 1) sub_len + W12) clipped to the range; values[k * *n_per_item + t] is the
+ * maximum of row P2 over the item's own columns — from s sub_len - 63 on — inside sub-chunk s - 1 + t, -1 where there is no such
+ * column.  values may be NULL to ask for *n_per_item alone.  MI355_SW_ENOTSUP where the library would not thin (heights, reads of at
+ * most P2 rows, sub_len below 64, non-integer scores). */
+int mi355_sw_prefix_thin_items(mi355_sw_ctx *ctx, size_t n_items, const uint32_t *items, int P, int P2, int64_t sub_len, int64_t left, int64_t right,
+                               const mi355_sw_params *params, float *values, size_t capacity, size_t *n_per_item);
 
 /* Which kernels and pipeline decisions the last call used: space-separated tags, each at most once, e.g.
  * "score[cell=f16,SL=8,R=19,...,sampled=1,...] strip[R=3,mode=max,...] wave[orient=0,...,dirs=1,...] walk_wave" — what the parity

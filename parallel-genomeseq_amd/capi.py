@@ -24,7 +24,7 @@ EXPORTS = [
     "mi355_sw_set_option", "mi355_sw_option_names", "mi355_sw_multi_set_option", "mi355_sw_last_counters", "mi355_sw_last_counter", "mi355_sw_batch_upload_packed", "mi355_sw_best_range", "mi355_sw_last_path",
     "mi355_sw_default_affine_params", "mi355_sw_affine_align", "mi355_sw_affine_batch_run", "mi355_sw_affine_score_ranges",
     "mi355_sw_affine_align_trace", "mi355_sw_affine_batch_trace", "mi355_sw_affine_pairs_run", "mi355_sw_affine_pairs_trace",
-    "mi355_sw_prefix_values", "mi355_sw_affine_pairs_run_mode", "mi355_sw_affine_pairs_trace_mode",
+    "mi355_sw_prefix_values", "mi355_sw_prefix_thin_items", "mi355_sw_affine_pairs_run_mode", "mi355_sw_affine_pairs_trace_mode",
     "mi355_sw_affine_pairs_run_band", "mi355_sw_affine_pairs_trace_band",
     "mi355_sw_affine_extend_run", "mi355_sw_affine_extend_trace",
     "mi355_sw_affine_extend_run_band", "mi355_sw_affine_extend_trace_band",
@@ -615,7 +615,7 @@ class Context:
         self._L.mi355_sw_last_counters(self._ctx, c)
         out = dict(requeried=int(c[0]), whole_batch_again=int(c[1]), candidates=int(c[2]), left_window=int(c[3]))
         for name in ("first_settled", "saved_locates", "saved_traces", "saved_fallbacks", "walk_widened", "wait_retries", "early_settled", "beyond_f16", "prefix_certified",
-                     "prefix_second_pass"):
+                     "prefix_second_pass", "prefix_thinned", "prefix_thin_items"):
             v = C.c_uint64(0)
             rc = self._L.mi355_sw_last_counter(self._ctx, name.encode(), C.byref(v))
             if rc:
@@ -632,6 +632,20 @@ class Context:
             return None
         out = np.zeros((self._nbatch, nsub.value), dtype=np.float32)
         self._chk(self._L.mi355_sw_prefix_values(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size), C.byref(nsub)))
+        return out
+
+    def prefix_thin_items(self, items, P, left, right, P2=38, sub_len=256, semantics=F32, match=3.0, mismatch=-3.0, gap=2.0, lut=None):
+        """Test hook (set_option("prefix_thin_items", 1)): the thin stage's kernel on items = [(resident query, sub-chunk)] of the range
+        [left, right) of the resident reference, as a pass at P rows flags them.  Array [n_items, n_per_item]: the maximum of row P2 over
+        the item's own columns inside sub-chunk s - 1 + t, -1 where it has none (mi355_sw_prefix_thin_items)."""
+        p, keep = make_params(semantics, match, mismatch, gap, lut)
+        flat = np.ascontiguousarray(np.asarray(items, dtype=np.uint32).reshape(-1, 2))
+        per = C.c_size_t(0)
+        args = (self._ctx, C.c_size_t(len(flat)), flat.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_int(P), C.c_int(P2), C.c_int64(sub_len),
+                C.c_int64(left), C.c_int64(right), C.byref(p))
+        self._chk(self._L.mi355_sw_prefix_thin_items(*args, None, C.c_size_t(0), C.byref(per)))
+        out = np.zeros((len(flat), per.value), dtype=np.float32)
+        self._chk(self._L.mi355_sw_prefix_thin_items(*args, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size), C.byref(per)))
         return out
 
     def last_path(self):

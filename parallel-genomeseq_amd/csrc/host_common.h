@@ -15,8 +15,8 @@ constexpr size_t kExactLdsMax = 159 * 1024;    // dynamic part; the wide instanc
   X(no_f16) X(no_unsat) X(no_sample) X(no_satflag) X(no_solo) X(no_wave) X(no_comb) X(no_twin) X(no_wide) X(no_strip) \
   X(no_quant) X(no_devlist) X(no_ref_cache) X(no_strip_groups) X(u8_long_twin) X(long_twin) X(no_long) \
   X(no_requery) X(force_f32) X(no_long_p32) X(no_opt_margin) X(no_wave_prof) X(no_wave_window) X(no_first) X(no_long_save) X(u8_sample_short) X(no_wave_pieces) X(no_u8_early) X(no_wave_f16) X(no_devlist_by_id) X(no_f16_mirror) X(no_f16m_int_diag) X(no_affine_sweep) X(no_affine_prof) X(no_affine_pairs) X(no_prefix) X(trace) \
-  X(no_prefix_low) X(no_prefix_cascade) X(no_prefix_step) X(no_affine_band)
-#define MI355_SW_INT_OPTIONS(X) X(strip_r) X(slot) X(few_r) X(chunk) X(long_pipes) X(long_wgs) X(long_sub) X(long_r) X(long_groups) X(assume_cus) X(long_save_what) X(prefix_min_cols)
+  X(no_prefix_low) X(no_prefix_cascade) X(no_prefix_step) X(no_affine_band) X(no_prefix_thin)
+#define MI355_SW_INT_OPTIONS(X) X(strip_r) X(slot) X(few_r) X(chunk) X(long_pipes) X(long_wgs) X(long_sub) X(long_r) X(long_groups) X(assume_cus) X(long_save_what) X(prefix_min_cols) X(prefix_thin_min_cols)
 struct Options {
 #define X(n) bool n = false;
   MI355_SW_BOOL_OPTIONS(X)
@@ -30,6 +30,7 @@ struct Options {
                                   // R rows per lane that folds row P = 2 R alone (R on the list of sampled 8-lane shapes); the sub-chunk values stay for
                                   // mi355_sw_prefix_values
   long prefix_rowp_step = 0;      // test hook, set_option only: as prefix_rowp, with the instance that folds row P at every step
+  bool prefix_thin_items = false; // test hook, set_option only: opens mi355_sw_prefix_thin_items (sw_prefix_thin_kernel on a caller's item list, every value returned)
   int fault_inject = 0;          // test hook, only through mi355_sw_set_option("fault_inject", "strip_stall" | "long_stall"): never from the environment
 };
 inline std::string option_env_name(const char *n) {
@@ -63,6 +64,7 @@ inline int option_set(Options &o, const char *key, const char *value) {
   if (k == "prefix_tiles") { o.prefix_tiles = on; return 0; }
   if (k == "prefix_rowp") { o.prefix_rowp = on ? std::atol(v.c_str()) : 0; return 0; }
   if (k == "prefix_rowp_step") { o.prefix_rowp_step = on ? std::atol(v.c_str()) : 0; return 0; }
+  if (k == "prefix_thin_items") { o.prefix_thin_items = on; return 0; }
   if (k == "fault_inject") { o.fault_inject = v == "strip_stall" ? 1 : (v == "long_stall" ? 2 : 0); return 0; }
   return -1;
 }
@@ -71,7 +73,7 @@ inline const char *option_names() {
 #define X(n) #n ","
   MI355_SW_BOOL_OPTIONS(X) MI355_SW_INT_OPTIONS(X)
 #undef X
-  "prefix_tiles,prefix_rowp,prefix_rowp_step,fault_inject";
+  "prefix_tiles,prefix_rowp,prefix_rowp_step,prefix_thin_items,fault_inject";
 }
 thread_local const Options *tl_opt = nullptr;
 inline const Options &opt() {
@@ -328,6 +330,8 @@ struct mi355_sw_ctx {
   std::vector<int32_t> hook_ids;  // test hook prefix_rowp: query id of every value row the last mi355_sw_score_ranges left in `submax` ...
   int64_t hook_nsub = 0;          // ... and the sub-chunks per row (0: nothing to read, mi355_sw_prefix_values)
   size_t prefix_second_pass = 0;  // ... of those that offended a pass of a chained bucket, the ones that took the taller second pass (prefix_chain)
+  size_t prefix_thinned = 0;      // reads of the running call whose flags went through the thin stage (sw_prefix_thin_kernel, host_pipeline.h prefix_bucket) ...
+  size_t prefix_thin_items = 0;   // ... and the {read, sub-chunk} items it evaluated
   size_t prefix_certified = 0;    // queries of the running call settled by the prefix filter (lemma L19), without a sweep of all their rows
   const void *wlut_ref = nullptr; // reference (and its version) whose byte -> code tables are in `wlut` (sw_wave_prof_kernel)
   uint64_t wlut_version = 0;
@@ -355,6 +359,7 @@ struct mi355_sw_ctx {
   std::vector<uint8_t> h_pieces;  // host side of the piece table of the running call (host_batch.h)
   size_t saved_locates = 0, saved_traces = 0, saved_fallbacks = 0;   // finish steps of the running call that started from saved state / fell back
   size_t walk_widened = 0;        // times a traceback window's budget was multiplied by 4 in the running call (walk status 1)
+  DevBuf thin_items, thin_out, thin_vals;   // the thin stage's item list, its survivors (count, then the list) and the test hook's value rows
   DevBuf pkeys, pthr, psel, psel2, qcnt, sel2, gcnt, wlut, ckpt, first, keys, ranges, stab, ftab, ftab_s, htab, htab8, soloblk, flags, submax, lut, probs, dirs, outs_f, outs_i, cons, walkp, hmat, brow, wprobs, scan;
   // host sides of small per-call uploads: they must outlive the asynchronous copies, and the tables are only
   // sent again when they change

@@ -491,6 +491,86 @@ float elapsed_us(mi355_sw_ctx *ctx, hipEvent_t a, hipEvent_t b) {
   return ms * 1000.0f;
 }
 
+// The thin stage of a row-P pass at P rows (DESIGN.md §3.3 lemma L20; host_score.h kThinP2): its taller height P2, the columns W12 a
+// crossing of row P2 may lie right of a flagged column of row P, the warm-up in front of an item's own columns (the margin of L1
+// for P2 rows, as Bucket::warm without its rounding to whole segments), the sub-chunks D2 a survivor's end cell may lie right of it, and the values per item.  P2 = 0: no thin
+// stage — option no_prefix_thin, a pass at P2 rows or more, reads of P2 rows or fewer, sub-chunks shorter than the 63 columns of lag
+// (an item's own columns would start below its left neighbour), or a score table beyond the kernel's LDS.
+struct ThinPlan {
+  int P2 = 0, nout = 0;
+  int64_t W12 = 0, warm2 = 0, D2 = 0;
+};
+constexpr size_t kThinTableMax = 32 * 1024;
+ThinPlan thin_plan(const RefData &ref, const ScoreTable &t, int P, int minlen, int maxlen, int64_t E) {
+  ThinPlan tp;
+  if (opt().no_prefix_thin || !t.integral || t.gap <= 0 || t.smax <= 0 || t.ftab.empty()) return tp;
+  if (P >= kThinP2 || minlen <= kThinP2 || E < 64 || E > (1 << 20) || (size_t)256 * ref.ncodes * 4 > kThinTableMax) return tp;
+  const Margin mg = t.margin(kThinP2);
+  if (!mg.finite()) return tp;
+  tp.P2 = kThinP2;
+  tp.W12 = (int64_t)(tp.P2 - P) + (int64_t)((int64_t)t.smax * (tp.P2 - P) / t.gap);
+  tp.warm2 = mg.cols(tp.P2);
+  const int64_t W2 = (int64_t)(maxlen - tp.P2) + (int64_t)((int64_t)t.smax * (maxlen - tp.P2) / t.gap);
+  tp.D2 = (W2 + E - 1) / E;
+  tp.nout = 3 + (int)((tp.W12 - 1) / E);
+  return tp;
+}
+
+// sw_prefix_thin_kernel over `items` = {query id, sub-chunk}, sorted; thr2 by query id (> 0 for every listed query).  kept: the
+// {query id, sub-chunk} whose row-P2 maximum reaches thr2, sorted and without duplicates.  vals (test hook): [items][tp.nout].
+int run_thin(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const ScoreTable &table, const ThinPlan &tp, int64_t E,
+             const std::vector<std::pair<uint32_t, uint32_t>> &items, const std::vector<float> &thr2,
+             std::vector<std::pair<uint32_t, uint32_t>> &kept, std::vector<float> *vals = nullptr) {
+  HostTrace trace_("run_thin");
+  kept.clear();
+  const size_t ni = items.size(), nq = q.nq;
+  if (ni == 0) return 0;
+  if (tp.P2 != kThinP2) return fail(ctx, MI355_SW_ENODEV, "internal: no sw_prefix_thin_kernel instance of that height");
+  // an item as `split` lanes on sub-chunks of E / split columns: the same own columns, a shorter window per lane (host_score.h kThinSplit)
+  int split = vals ? 1 : kThinSplit;
+  while (split > 1 && (E % split != 0 || E / split < 64)) split /= 2;
+  const size_t nl = ni * (size_t)split;
+  const int64_t El = E / split;
+  const int nout = vals ? tp.nout : 3 + (int)((tp.W12 - 1) / El);
+  if (nl * (size_t)nout > 0x7FFFFFFFull) return fail(ctx, MI355_SW_ENOTSUP, "too many items for the thin stage");
+  std::vector<uint32_t> raw(2 * nl);
+  for (size_t k = 0; k < ni; ++k)
+    for (int h = 0; h < split; ++h) { raw[2 * (k * split + h)] = items[k].first; raw[2 * (k * split + h) + 1] = items[k].second * (uint32_t)split + (uint32_t)h; }
+  if (ctx->thin_items.ensure(nl * 8 + 16) || ctx->thin_out.ensure(8 + nl * (size_t)nout * 8 + 16) || ctx->pthr.ensure(nq * 4 + 16) ||
+      (vals && ctx->thin_vals.ensure(nl * (size_t)nout * 4 + 16)))
+    return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(score scratch) failed");
+  HIPCHK(ctx, hipMemcpyAsync(ctx->thin_items.p, raw.data(), nl * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->pthr.p, thr2.data(), nq * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->thin_out.p, 0, 8, ctx->stream));
+  ThinArgs a;
+  a.items = ctx->thin_items.as<uint2>(); a.nitems = (uint32_t)nl;
+  a.thr2 = ctx->pthr.as<float>();
+  a.codes = ref.codes.as<uint8_t>() + rg.lo; a.n = rg.hi - rg.lo;
+  a.qbytes = q.bytes.as<uint8_t>(); a.qoff = q.offs.as<int64_t>();
+  a.ftab = ctx->ftab.as<float>(); a.ncodes = ref.ncodes; a.gap = table.gapf;
+  a.E = (int32_t)El; a.warm2 = (int32_t)tp.warm2; a.W12 = (int32_t)tp.W12; a.nout = nout;
+  a.count = ctx->thin_out.as<unsigned int>(); a.list = reinterpret_cast<uint2 *>(ctx->thin_out.as<unsigned int>() + 2);
+  a.vals = vals ? ctx->thin_vals.as<float>() : nullptr;
+  hipLaunchKernelGGL(sw_prefix_thin_kernel<kThinP2>, dim3((unsigned)((nl + 63) / 64)), dim3(64), (size_t)256 * ref.ncodes * 4, ctx->stream, a);
+  HIPCHK(ctx, hipGetLastError());
+  unsigned int nkept = 0;
+  HIPCHK(ctx, hipMemcpyAsync(&nkept, ctx->thin_out.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if ((size_t)nkept > nl * (size_t)nout) return fail(ctx, MI355_SW_ENODEV, "internal: the thin stage kept more than it was given");
+  std::vector<uint32_t> out(2 * (size_t)nkept);
+  if (nkept) HIPCHK(ctx, hipMemcpy(out.data(), ctx->thin_out.as<unsigned int>() + 2, (size_t)nkept * 8, hipMemcpyDeviceToHost));
+  kept.reserve(nkept);
+  for (size_t k = 0; k < nkept; ++k) kept.push_back({out[2 * k], out[2 * k + 1] / (uint32_t)split});
+  std::sort(kept.begin(), kept.end());
+  kept.erase(std::unique(kept.begin(), kept.end()), kept.end());
+  if (vals) {
+    vals->resize(ni * (size_t)tp.nout);
+    HIPCHK(ctx, hipMemcpy(vals->data(), ctx->thin_vals.p, vals->size() * 4, hipMemcpyDeviceToHost));
+  }
+  ctx->prefix_thin_items += ni;
+  return 0;
+}
+
 // (DESIGN.md §3.3 lemma L19.)  The prefix filter of one bucket (host_score.h prefix_ok), in front of the full sweep: a sampled sweep of
 // the first P = kPrefixLanes * R rows of every read, then all rows only where those rows allow the maximum.
 //   round 1: the sub-chunk of the read's prefix key and its right neighbours, evaluated exactly on all rows: B0, an exact alignment score;
@@ -498,8 +578,13 @@ float elapsed_us(mi355_sw_ctx *ctx, hipEvent_t a, hipEvent_t b) {
 //            stands for f .. f + D (D = ceil(W / sub_len): the end cell lies at most W columns right of its crossing of row P; the
 //            left neighbour is covered by the 63 columns a candidate window starts in front of its sub-chunk, locate_saturated),
 //            and what round 1 has not evaluated is evaluated now; the read's result is the first maximum over both rounds.
+//            On the step tiles the flags pass the THIN stage first (thin_plan, run_thin; lemma L20): each is evaluated on the prefix of
+//            P2 > P rows over its own columns, a survivor is the sub-chunk that holds a row-P2 cell at B0 - smax (m - P2) or more, and
+//            stands for itself and D2 <= D right neighbours.  Thinned: every read over its cap (up to thin_flag_cap flags), and everybody
+//            else once the pass has more than kThinMinFlags flags; only reads with B0 > smax max(m - P2, P2), and only ranges of
+//            thin_cols_min() columns or more (option no_prefix_thin: none).
 // A read is an OFFENDER (appended to `offenders`, nothing written for it) when B0 cannot certify — B0 <= smax (m - P) + slack —
-// or when it flags more sub-chunks than its cap.  Everybody else: loc[] and qdone[] are final, qchunk[] / qwarm[] set.
+// or when it sends more sub-chunks to the locate stage than its cap.  Everybody else: loc[] and qdone[] are final, qchunk[] / qwarm[] set.
 // The prefix is P = kPrefixLanes * prefR rows, which need not be the bucket's own R (a probed bucket tries a lower height first,
 // align_range_core).  rowp: the tiles fold row P alone — slack = rowp_slack, and a read also offends unless B0 > smax P (prefix_bound).
 // vote (by query id, may be null; a probe at a lower height asks): could a row-P pass of voteR rows per lane certify the read?  1 when
@@ -586,7 +671,7 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   const uint32_t qcap = query_flag_cap(nq);
   unsigned int nflag = 0;
   std::vector<uint32_t> cnt(nq, 0);
-  auto run_filter = [&](const std::vector<float> &t) -> int {
+  auto run_filter = [&](const std::vector<float> &t, uint32_t cap) -> int {
     HIPCHK(ctx, hipMemcpyAsync(ctx->pthr.p, t.data(), nq * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->flags.p, 0, 8, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->qcnt.p, 0, nq * 4, ctx->stream));
@@ -596,7 +681,7 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
       hipLaunchKernelGGL(sw_prefix_filter, fgrid, dim3(256), 0, ctx->stream, (const uint16_t *)ctx->submax.as<uint16_t>(), stride, stride,
                          (const int32_t *)q.sel.as<int32_t>(), b.first, f0, b.count, (const float *)ctx->pthr.as<float>(),
                          ctx->flags.as<unsigned int>(), reinterpret_cast<uint2 *>(ctx->flags.as<unsigned int>() + 2), ctx->flag_cap,
-                         ctx->qcnt.as<unsigned int>(), qcap);
+                         ctx->qcnt.as<unsigned int>(), cap);
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(&nflag, ctx->flags.p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -613,7 +698,7 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
       const int id = q.order[b.first + k];
       if (B0[id] > prefix_bound(table, q.len[id], vP, vslack, true)) vthr[id] = B0[id] - smax * (float)(q.len[id] - vP) - vslack;
     }
-    rc = run_filter(vthr);
+    rc = run_filter(vthr, qcap);
     if (rc) return rc;
     for (int k = 0; k < b.count; ++k) {
       const int id = q.order[b.first + k];
@@ -621,24 +706,104 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     }
   }
   if (2 * noff > (size_t)b.count) return give_up();
-  // c. round 2: the filter with the thresholds of this height
-  rc = run_filter(thr);
+  // c. round 2: the filter with the thresholds of this height, under query_flag_cap as ever: the per-read counts it returns are exact
+  // whatever the cap, the list holds at most cap + 1 entries per read.
+  int minlen = b.maxlen;
+  for (int k = 0; k < b.count; ++k) minlen = std::min<int>(minlen, q.len[q.order[b.first + k]]);
+  ThinPlan tp;
+  if (rowp && ask.step && n >= thin_cols_min()) tp = thin_plan(ref, table, P, minlen, b.maxlen, E);
+  rc = run_filter(thr, qcap);
   if (rc) return rc;
   std::vector<uint32_t> raw(2 * (size_t)nflag);
   if (nflag) HIPCHK(ctx, hipMemcpy(raw.data(), ctx->flags.as<unsigned int>() + 2, (size_t)nflag * 8, hipMemcpyDeviceToHost));
-  // d. offenders by the cap
+  // d. offenders by the cap.  A read over query_flag_cap is thinned instead, if row P2 can certify it — B0 > smax (m - P2) and B0 >
+  // smax P2 (L20) — and while there is room: at most thin_flag_cap flags per read and kThinItemsMax for all such reads of the pass,
+  // the reads with the fewest flags first (host_score.h).  Their flags are listed by a second filter launch with thresholds for them alone.
+  std::vector<char> thin(nq, 0);
+  std::vector<float> thr2(nq, 0.0f);
+  auto thin_ok = [&](int id) { return tp.P2 && B0[id] > prefix_bound(table, q.len[id], tp.P2, 0.0f, true); };
+  std::vector<std::pair<uint32_t, int>> over;                                      // {flags, read}: over the cap, and the stage may take it
   for (int k = 0; k < b.count; ++k) {
     const int id = q.order[b.first + k];
-    if (!off[id] && cnt[id] > qcap) { off[id] = 1; ++noff; }
+    if (off[id] || cnt[id] <= qcap) continue;
+    if (cnt[id] <= thin_flag_cap(qcap) && thin_ok(id)) over.push_back({cnt[id], id});
+    else { off[id] = 1; ++noff; }
+  }
+  std::sort(over.begin(), over.end());
+  size_t room = kThinItemsMax;
+  std::vector<float> thr_thin(nq, 0.0f);
+  for (const auto &o : over) {
+    if (o.first <= room) { room -= o.first; thin[o.second] = 1; thr_thin[o.second] = thr[o.second]; }
+    else { off[o.second] = 1; ++noff; }
+  }
+  if (room < kThinItemsMax) {
+    const std::vector<uint32_t> cnt_all(cnt);
+    rc = run_filter(thr_thin, thin_flag_cap(qcap));
+    if (rc) return rc;
+    if (nflag >= ctx->flag_cap) {
+      // the list may be cut short (kThinItemsMax + a read each is far below kFlagCap: not expected): nothing is read from it, and
+      // these reads offend by the cap, as in the flow without the stage
+      for (const auto &o : over)
+        if (thin[o.second]) { thin[o.second] = 0; off[o.second] = 1; ++noff; }
+    } else {
+      const size_t was = raw.size();
+      raw.resize(was + 2 * (size_t)nflag);
+      if (nflag) HIPCHK(ctx, hipMemcpy(raw.data() + was, ctx->flags.as<unsigned int>() + 2, (size_t)nflag * 8, hipMemcpyDeviceToHost));
+    }
+    nflag = (unsigned int)(raw.size() / 2);
+    cnt = cnt_all;
   }
   if (opt().trace) std::fprintf(stderr, "[mi355_sw] prefix filter: %u flagged sub-chunks, %zu of %d reads offend (D = %lld)\n", nflag, noff, b.count, (long long)D);
   if (2 * noff > (size_t)b.count) return give_up();
   // e. what the flags add to round 1
-  std::vector<std::pair<uint32_t, uint32_t>> f2, f2new;
+  std::vector<std::pair<uint32_t, uint32_t>> flagged, f2, f2new;
   for (size_t f = 0; f < nflag; ++f) {
     const uint32_t id = raw[2 * f];
-    if (id >= nq || !mine[id] || off[id]) continue;
-    for (int64_t sc = raw[2 * f + 1]; sc <= (int64_t)raw[2 * f + 1] + D && sc < nsub; ++sc) f2.push_back({id, (uint32_t)sc});
+    if (id >= nq || !mine[id] || off[id] || raw[2 * f + 1] >= (uint64_t)nsub) continue;
+    flagged.push_back({id, raw[2 * f + 1]});
+  }
+  std::sort(flagged.begin(), flagged.end());
+  flagged.erase(std::unique(flagged.begin(), flagged.end()), flagged.end());
+  // Reads within query_flag_cap are thinned as well once the pass has more than kThinMinFlags flags beyond round 1's own sub-chunks for
+  // the thin stage: below that its launch and synchronisation cost more than the locate candidates it saves (CHANGELOG.md).
+  if (tp.P2) {
+    size_t fresh = 0;
+    for (const auto &f : flagged) fresh += (thin[f.first] || thin_ok((int)f.first)) && !std::binary_search(f1.begin(), f1.end(), f) ? 1 : 0;
+    const bool everybody = fresh > kThinMinFlags;
+    std::vector<std::pair<uint32_t, uint32_t>> items, kept;
+    for (const auto &f : flagged)
+      if (thin[f.first] || (everybody && thin_ok((int)f.first))) { thin[f.first] = 1; items.push_back(f); }
+    if (!items.empty()) {
+      size_t nthin = 0;
+      for (int k = 0; k < b.count; ++k) {
+        const int id = q.order[b.first + k];
+        if (!thin[id]) continue;
+        thr2[id] = B0[id] - smax * (float)(q.len[id] - tp.P2);                       // (> 0: thin_ok)
+        ++nthin;
+      }
+      HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+      rc = run_thin(ctx, ref, q, rg, table, tp, E, items, thr2, kept);
+      if (rc) return rc;
+      HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+      ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+      ctx->prefix_thinned += nthin;
+      path_note(ctx, "prefix_thin[P2=%d,items=%zu,kept=%zu]", tp.P2, items.size(), kept.size());
+      // whoever keeps more than query_flag_cap sub-chunks offends after all
+      std::vector<uint32_t> nkept(nq, 0);
+      for (const auto &f : kept) if (f.first < nq) ++nkept[f.first];
+      for (int k = 0; k < b.count; ++k) {
+        const int id = q.order[b.first + k];
+        if (thin[id] && nkept[id] > qcap) { off[id] = 1; ++noff; }
+      }
+      for (const auto &f : kept) {
+        if (f.first >= nq || !thin[f.first] || off[f.first]) continue;
+        for (int64_t sc = f.second; sc <= (int64_t)f.second + tp.D2 && sc < nsub; ++sc) f2.push_back({f.first, (uint32_t)sc});
+      }
+    }
+  }
+  for (const auto &f : flagged) {
+    if (thin[f.first] || off[f.first]) continue;
+    for (int64_t sc = f.second; sc <= (int64_t)f.second + D && sc < nsub; ++sc) f2.push_back({f.first, (uint32_t)sc});
   }
   std::sort(f2.begin(), f2.end());
   f2.erase(std::unique(f2.begin(), f2.end()), f2.end());
@@ -986,7 +1151,7 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
       if (ntried && (2 * offenders.size() > ntried || (opt().no_requery && !offenders.empty()))) {
         // most reads cannot be certified by their prefix (no hit, or a repeat family over the cap): the sweep decides for everybody
         for (size_t k = 0; k < nq; ++k) if (tried[k]) { loc[k] = Located(); qdone[k] = 0; }
-        ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_named = false; ctx->candidates = candidates_before;
+        ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->prefix_named = false; ctx->candidates = candidates_before;
         ctx->last_kernel.cells = 0; ctx->timings[4] = 0; ctx->timings[5] = 0;
         ctx->whole_again += 1;
         path_note(ctx, "whole_again");
@@ -1567,7 +1732,7 @@ void reset_timings(mi355_sw_ctx *ctx) {
   for (double &t : ctx->timings) t = 0;
   ctx->score_ev_used = 0; ctx->arenas.clear(); ctx->cons_used = 0;
   ctx->last_kernel = mi355_sw_kernel_info{};
-  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
+  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
   ctx->hook_ids.clear(); ctx->hook_nsub = 0;
   ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->walk_widened = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
   ctx->path.clear();

@@ -725,6 +725,48 @@ constexpr uint32_t kFlagCap = 1u << 20;   // (query, sub-chunk) pairs a saturati
 // candidates one query may have before IT is swept again exactly (sampled sweeps): 64, plus a share of 1024 (a lone query: 1088)
 inline uint32_t query_flag_cap(size_t nq) { return 64u + (uint32_t)(1024 / std::max<size_t>(1, nq)); }
 
+// The thin stage of the prefix filter (sw_prefix_thin_kernel.h, host_pipeline.h prefix_bucket round 2): the flags of a
+// row-P pass on the step tiles are evaluated again on the taller prefix of kThinP2 rows, sub-chunk by sub-chunk, and only what survives
+// goes to the locate stage.  query_flag_cap protects the locate stage (about 0.23 us per candidate); what protects the thin stage is
+// thin_flag_cap, the flags one read may list for it:
+//   * at most kThinCapMax = 1024, from what was measured (CHANGELOG.md "Prefix filter: thin stage").  A launch of a few ten thousand
+//     items is as long as one lane's window (0.2 ms), but a launch that fills the chip costs about 0.09 us per item (65 536 items:
+//     6 ms), and what a thinned read saves at best is its place in the second pass, 0.085 ms at 50 Mbp: 950 items.  A read with more
+//     flags is cheaper in the second pass — and the reads that draw thousands of flags at row P are mostly those whose row kThinP2
+//     keeps them all (members of a repeat family): with a cap of 4096 the repeat-rich batch of bench.py --full paid 17 ms of 195
+//     for rescuing 11 reads of 243;
+//   * at most kThinItemsMax flags for all the reads over query_flag_cap of one pass, the reads with the fewest flags first: 65 536
+//     items as four lanes each are the wavefronts the chip holds at once, so the launch stays one round (0.2 - 0.4 ms), and the host
+//     copies and sorts a list of that size at most.  The bench batch's main pass rescues 35 such reads (the CPU model: 31, with 13 766 flags); its
+//     launch, everybody's flags included, has 18 410 items.  Without
+//     a budget (and with a cap of 4096) the stage cost the repeat-rich batch 41 ms of 195: thin launches 21 ms, the rest host work on
+//     a list of a million entries;
+//   * those flags come from a second filter launch with thresholds for these reads alone; the first runs under query_flag_cap as
+//     ever (its per-read counts are exact whatever the cap), so neither list can reach ctx->flag_cap — and if the second ever did, nothing is read
+//     from it: its reads offend by the cap, as without the stage;
+//   * never below query_flag_cap.
+// The stage engages from kThinMinCols columns on (option prefix_thin_min_cols = n moves the gate, as prefix_min_cols moves the
+// filter's).  What the gate is for, plainly: with default options it never binds — the filter itself starts at kPrefixMinCols = 8 Mi
+// columns — so it only acts where prefix_min_cols was lowered, i.e. in tests and on short references, and there it keeps the flow
+// without the stage: the tests of the chain on 60 k columns go on asserting that flow's counters, and the default flow on such a
+// range is tested where both gates are lowered (tests/test_gpu_prefix_thin_flow.py).  The cost argument behind it is DERIVED, not
+// measured on a short range: one launch of the thin kernel takes 0.2 - 0.4 ms whatever its items (measured at 50 Mbp), a second pass
+// 0.085 ms per read at 50 Mbp, which scaled by the columns is 1.7 ns per read and 1000 columns — below a few million columns the
+// second pass of a handful of reads should be the cheaper of the two.
+// An item is cut into kThinSplit lanes (sub-chunks of E / kThinSplit columns, never below 64): the launch is as long as ONE lane's
+// window, E / kThinSplit + 94 + W12 + warm2 columns, while the items stay below a wavefront per SIMD.
+constexpr int kThinP2 = 38;
+constexpr uint32_t kThinCapMax = 1024;
+constexpr size_t kThinItemsMax = 65536;
+constexpr int64_t kThinMinCols = (int64_t)4 << 20;
+constexpr int kThinSplit = 4;
+inline int64_t thin_cols_min() { const long v = opt().prefix_thin_min_cols; return v > 0 ? (int64_t)v : kThinMinCols; }
+// flags of a pass from which the reads within query_flag_cap are thinned too (prefix_bucket e.).  Not a measured break-even: a small
+// launch with its synchronisation (0.2 - 0.4 ms) is worth about 1000 locate candidates at 0.23 us, some 400 flags that do not survive;
+// 1024 is on the safe side of that estimate and was not tuned (CHANGELOG.md).
+constexpr size_t kThinMinFlags = 1024;
+inline uint32_t thin_flag_cap(uint32_t qcap) { return std::max<uint32_t>(qcap, kThinCapMax); }
+
 // Uploads what every score launch of a call shares and clears the keys.
 int score_begin(mi355_sw_ctx *ctx, const QueryBatch &q, const std::vector<Range> &ranges, const ScoreTable &t) {
   const size_t nq = q.nq, nr = ranges.size();

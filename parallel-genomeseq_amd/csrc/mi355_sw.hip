@@ -44,6 +44,7 @@
 
 #include "sw_exact_kernel.h"
 #include "sw_score_kernel.h"
+#include "sw_prefix_thin_kernel.h"
 #include "sw_wave_kernel.h"
 #include "sw_strip_kernel.h"
 #include "sw_batch_kernels.h"
@@ -110,7 +111,7 @@ void mi355_sw_destroy(mi355_sw_ctx *c) {
   (void)hipSetDevice(c->device);
   DevBuf *bufs[] = {&c->qcnt, &c->sel2, &c->gcnt, &c->wlut, &c->ref.bytes, &c->ref.codes, &c->batch.bytes, &c->batch.lens, &c->keys, &c->ranges, &c->stab,
                     &c->batch.offs, &c->batch.sel, &c->colsave, &c->rowsave, &c->pieces, &c->ftab, &c->ftab_s, &c->htab, &c->htab8, &c->soloblk, &c->flags, &c->submax, &c->lut, &c->probs, &c->dirs, &c->outs_f, &c->outs_i, &c->cons, &c->walkp, &c->hmat, &c->brow, &c->wprobs, &c->scan, &c->batch.cum, &c->ckpt, &c->first, &c->recs, &c->atab, &c->aprof, &c->pkeys, &c->pthr, &c->psel, &c->psel2,
-                    &c->rev_codes, &c->rev_bytes, &c->rev_q};
+                    &c->rev_codes, &c->rev_bytes, &c->rev_q, &c->thin_items, &c->thin_out, &c->thin_vals};
   for (DevBuf *b : bufs) b->release();
   c->adhoc.release(); c->one.release();
   c->pin_probs.release(); c->pin_walk.release(); c->pin_out.release(); c->pin_solo_up.release(); c->pin_solo_down.release();
@@ -735,6 +736,8 @@ int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *o
   else if (k == "candidates") *out = ctx->candidates;
   else if (k == "prefix_certified") *out = ctx->prefix_certified;
   else if (k == "prefix_second_pass") *out = ctx->prefix_second_pass;
+  else if (k == "prefix_thinned") *out = ctx->prefix_thinned;
+  else if (k == "prefix_thin_items") *out = ctx->prefix_thin_items;
   else if (k == "left_window") *out = ctx->left_window;
   else if (k == "beyond_f16") *out = ctx->beyond_f16;
   else if (k == "first_settled") *out = ctx->first_settled;
@@ -761,6 +764,45 @@ int mi355_sw_prefix_values(mi355_sw_ctx *ctx, float *values, size_t capacity, si
   std::fill(values, values + nq * nsub, -1.0f);
   for (size_t r = 0; r < ctx->hook_ids.size(); ++r)
     for (size_t s = 0; s < nsub; ++s) values[(size_t)ctx->hook_ids[r] * nsub + s] = half_value(raw[r * nsub + s]) * kF16Scale;
+  return 0;
+}
+
+int mi355_sw_prefix_thin_items(mi355_sw_ctx *ctx, size_t n_items, const uint32_t *items, int P, int P2, int64_t sub_len, int64_t left, int64_t right,
+                               const mi355_sw_params *params, float *values, size_t capacity, size_t *n_per_item) {
+  if (!ctx || !n_per_item) return MI355_SW_EINVAL;
+  OptScope opt_scope_(ctx);
+  int rc = check_params(ctx, params);
+  if (rc) return rc;
+  if (!opt().prefix_thin_items) return fail(ctx, MI355_SW_EINVAL, "mi355_sw_prefix_thin_items: set option prefix_thin_items first (test hook)");
+  const QueryBatch &q = ctx->batch;
+  const RefData &ref = ctx->ref;
+  if (left < 0 || right <= left || right > (int64_t)ref.n) return fail(ctx, MI355_SW_EINVAL, "range outside the resident reference");
+  if (q.nq == 0 || (n_items && !items)) return fail(ctx, MI355_SW_EINVAL, "mi355_sw_prefix_thin_items: no resident batch, or null items");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const Range rg{left, right};
+  const int64_t n = right - left;
+  const ScoreTable table = plan_table(ref, *params);
+  int minlen = q.maxlen;
+  std::vector<std::pair<uint32_t, uint32_t>> list(n_items);
+  for (size_t k = 0; k < n_items; ++k) {
+    const uint32_t id = items[2 * k], s = items[2 * k + 1];
+    if (id >= q.nq || sub_len < 64 || (int64_t)s * sub_len >= n) return fail(ctx, MI355_SW_EINVAL, "mi355_sw_prefix_thin_items: item outside the batch or the range");
+    minlen = std::min<int>(minlen, q.len[id]);
+    list[k] = {id, s};
+  }
+  const ThinPlan tp = (table.ok && params->semantics == MI355_SW_F32 && P > 0) ? thin_plan(ref, table, P, minlen, q.maxlen, sub_len) : ThinPlan();
+  if (tp.P2 == 0 || tp.P2 != P2) return fail(ctx, MI355_SW_ENOTSUP, "mi355_sw_prefix_thin_items: no thin stage for these heights, reads or scores");
+  *n_per_item = (size_t)tp.nout;
+  if (!values || n_items == 0) return 0;
+  if (capacity < n_items * (size_t)tp.nout) return fail(ctx, MI355_SW_EINVAL, "mi355_sw_prefix_thin_items: capacity below n_items * n_per_item");
+  rc = score_tables(ctx, q.maxlen, n, table);
+  if (rc) return rc;
+  const std::vector<float> thr2(q.nq, 1.0e30f);                      // (nothing survives: the values are what the hook is for)
+  std::vector<std::pair<uint32_t, uint32_t>> kept;
+  std::vector<float> vals;
+  rc = run_thin(ctx, ref, q, rg, table, tp, sub_len, list, thr2, kept, &vals);
+  if (rc) return rc;
+  std::copy(vals.begin(), vals.end(), values);
   return 0;
 }
 

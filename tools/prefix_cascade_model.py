@@ -8,7 +8,8 @@ Two parts, numpy only (one maximum.accumulate per matrix row):
   * deficits of a batch: every read of the bench batch (synth.reads_from_ref(dna(3, ref), 4, reads, m)) scored exactly against the
     window at its origin.
 A read is predicted to offend at (P, slack) when its threshold is not positive above the bound (x >= smax P, or the alignment cannot
-end below row P) or when the expected number of background flags at its x exceeds the per-query cap (64).  Prints ONE JSON line.
+end below row P) or when the expected number of background flags at its x exceeds the per-query cap (64).  `thin`: per start height,
+what the thin stage (P2 = 38) takes off that — the reads it rescues, its items and a bound on its survivors.  Prints ONE JSON line.
 
     python tools/prefix_cascade_model.py [--bg-len 5000000 --prefixes 10 --ref-len 50000000 --reads 2048 --read-len 150]
 
@@ -29,6 +30,7 @@ sys.path.insert(0, ROOT)
 SUB = 256
 CAP = 64
 MATCH, MISMATCH, GAP = 3.0, -3.0, 2.0
+THIN_P2 = 38                                                         # kThinP2 of host_score.h
 HEIGHTS = (11, 12, 13, 14, 16, 19)                                   # rows per lane: P = 2 R (13, 16, 19 are compiled)
 
 
@@ -87,6 +89,7 @@ def main(argv=None):
     ap.add_argument("--reads", type=int, default=2048)
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--heights", type=lambda v: [int(t) for t in v.split(",")], default=None, help="prefix rows P to model, comma separated")
+    ap.add_argument("--thin-cap", type=int, default=1024, help="flags a read may list for the thin stage (host_score.h thin_flag_cap)")
     args = ap.parse_args(argv)
     import __graft_entry__ as entry
     pgs = entry._load_package()
@@ -104,6 +107,25 @@ def main(argv=None):
             ok = ~hopeless
             over[ok] = f[np.minimum(x[ok], len(f) - 1)] > CAP
             line["offenders"]["P=%d,slack=%d" % (P, slack)] = dict(bound=int(hopeless.sum()), cap=int(over.sum()), total=int((hopeless | over).sum()))
+    # the thin stage: a read over the cap whose flags number at most `thin_cap` is evaluated on P2 = 38 rows, flag
+    # by flag, instead of offending.  Per start height P: the reads still over the thin cap, the items per thinned read (background
+    # flags at the read's own deficit, the mean over the reads the stage takes) and, as a bound on what survives, the background
+    # flags of row P2 at the same deficit.
+    if THIN_P2 in flags:
+        line["thin"] = dict(P2=THIN_P2, thin_cap=args.thin_cap)
+        keep = flags[THIN_P2]
+        for P, f in sorted(flags.items()):
+            if P >= THIN_P2:
+                continue
+            ok = ~((d >= MATCH * P) | (MATCH * m - d <= MATCH * THIN_P2))
+            items = f[np.minimum(d[ok], len(f) - 1)]
+            take = items <= args.thin_cap
+            over_cap = items > CAP
+            line["thin"]["P=%d" % P] = dict(
+                over_thin_cap=int((~take).sum()), rescued=int((take & over_cap).sum()), items_total=round(float(items[take].sum()), 1),
+                items_per_read=round(float(items[take].mean()), 2) if take.any() else 0.0,
+                items_of_rescued=round(float(items[take & over_cap].sum()), 1),
+                survivors_per_read=round(float(keep[np.minimum(d[ok][take], len(keep) - 1)].mean()), 3) if take.any() else 0.0)
     if args.heights:
         # rows swept by start -> second with slack 0: everybody at P[i], the start's offenders at P[j], the second pass's on all rows
         off = {P: line["offenders"]["P=%d,slack=0" % P]["total"] for P in sorted(flags)}
