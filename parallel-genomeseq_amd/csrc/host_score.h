@@ -1030,6 +1030,13 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   a.chunk_len = b.chunk_len;
   a.sub_len = b.sub_len;
   a.warm = (cpr == 1) ? 0 : b.warm;              // a single tile per range starts at the range's own border
+  // A prefix pass sweeps the first P = SL R rows only, and L1 on THAT matrix asks for cols(P) columns in front of a tile, not the
+  // cols(m) of the whole read (150 rows at 3 / -3 / 2: 384; P = 26: 128) — what thin_plan does with warm2.  The tile length above and
+  // the windows of the locate stage (prefix_bucket: qwarm) keep the bucket's own margin.
+  if (b.prefix && !b.strips && a.warm > 0) {
+    const Margin pmg = t.margin(b.SL * b.R);
+    if (pmg.finite()) a.warm = std::min(a.warm, (pmg.cols(b.SL * b.R) + 63) / 64 * 64);
+  }
   a.chunks_per_range = (int)cpr;
   a.qbytes = q.bytes.as<uint8_t>();
   a.qoff = q.offs.as<int64_t>();
