@@ -43,8 +43,11 @@ int exact_full_device(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q
   const bool windows = prof && want_trace && !opt().no_wave_window;
   // Long streams in pieces (sw_batch_kernels.h; DESIGN.md §3.3 lemma L12): kPieceRows own rows behind a warm-up of the L1 margin along the stream (a path
   // that ends in row i of x spans fewer than |y| + ceil(smax |y| / g) rows) plus the reach of a decision window in front of an
-  // own row (kWindowGuard + kCkptEvery), so that own rows and the checkpoints their windows resume from are exact.  Only where the
+  // own row (kWindowGuard + kCkptEvery), so that own rows and the checkpoints their windows resume from are exact.  The state saved
+  // at step k0 holds lane l on row k0 - 1 - l: 16 rows back.  warm is a multiple of kCkptEvery, so the lowest k0 of an own-row argmax
+  // is warm - kWindowGuard, and its state reaches row warm - kWindowGuard - 16 >= cols + kCkptEvery - 16 (L12).  Only where the
   // pass keeps no whole-problem decisions (score + argmax, or checkpointed windows).
+  static_assert(64 % kCkptEvery == 0 && kCkptEvery >= 14, "L12: the warm-up is a multiple of kCkptEvery, which covers the lanes' skew");
   std::vector<int32_t> pc_seq, pc_start, pc_rows, pc_first;
   std::vector<int64_t> pc_before;
   int nlong = 0;
