@@ -561,6 +561,10 @@ int mi355_sw_last_counters(const mi355_sw_ctx *ctx, uint64_t out[4]);
  * "prefix_thin_items" the (read, sub-chunk) items it evaluated, and "candidates" what reached the locate stage.  "no_prefix_thin"
  * switches the stage off (the A/B); "prefix_thin_min_cols" = n moves the reference length from which it engages (default 4 Mi columns:
  * below the default of "prefix_min_cols").
+ * "pooled_loops" — per-item host loops that went to the library's worker threads (big batches: from 49 152 alignments per call, or
+ * from 1024 per loop when MI355_SW_POOL_THREADS is set; 0: every loop ran on the calling thread).  Unlike the others it is counted
+ * per host thread, not per context: the value is that of the last call the CALLING thread made into the library that does any
+ * work on a context (this function and the other mi355_sw_last_* readers leave it alone).
  * MI355_SW_EINVAL for an unknown name. */
 int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *out);
 

@@ -615,7 +615,7 @@ class Context:
         self._L.mi355_sw_last_counters(self._ctx, c)
         out = dict(requeried=int(c[0]), whole_batch_again=int(c[1]), candidates=int(c[2]), left_window=int(c[3]))
         for name in ("first_settled", "saved_locates", "saved_traces", "saved_fallbacks", "walk_widened", "wait_retries", "early_settled", "beyond_f16", "prefix_certified",
-                     "prefix_second_pass", "prefix_thinned", "prefix_thin_items"):
+                     "prefix_second_pass", "prefix_thinned", "prefix_thin_items", "pooled_loops"):
             v = C.c_uint64(0)
             rc = self._L.mi355_sw_last_counter(self._ctx, name.encode(), C.byref(v))
             if rc:

@@ -94,6 +94,9 @@ inline int dev_cus() {
   return tl_dev ? std::max(1, tl_dev->cus) : 256;
 }
 inline size_t dev_lds() { return tl_dev ? tl_dev->lds : (size_t)160 * 1024; }
+// Per-item host loops of the calling thread's running C-ABI call that parallel_for gave to the worker pool (counter "pooled_loops" of
+// mi355_sw_last_counter: what a test asserts the pooled path ENGAGED with).  Reset where the call's outermost OptScope opens.
+thread_local size_t tl_pooled_loops = 0;
 // Set for the rest of a C-ABI call after a kernel whose workgroups wait for each other (sw_long_kernel with several workgroups per
 // tile, the grouped sw_strip_kernel) reported an expired wait: the work is repeated on the instances whose waits stay inside one
 // workgroup — resident by construction — instead of failing the call (a partitioned or shared device may not hold every
@@ -392,7 +395,10 @@ namespace {
 struct OptScope {
   const Options *prev;
   const DevInfo *prev_dev;
-  explicit OptScope(const mi355_sw_ctx *c) : prev(tl_opt), prev_dev(tl_dev) { if (c) { tl_opt = &c->opts; tl_dev = &c->dev; } }
+  explicit OptScope(const mi355_sw_ctx *c) : prev(tl_opt), prev_dev(tl_dev) {
+    if (!prev) tl_pooled_loops = 0;                                // (the outermost scope of a call: nested ones belong to it)
+    if (c) { tl_opt = &c->opts; tl_dev = &c->dev; }
+  }
   ~OptScope() { tl_opt = prev; tl_dev = prev_dev; if (!prev) tl_no_wait = false; }
 };
 
@@ -575,13 +581,15 @@ Hash128 content_hash_part(const char *p, size_t n) {
 class WorkerPool {
  public:
   static WorkerPool &get() { static WorkerPool p; return p; }
+  // the most parts one run() executes (the workers and the caller): whoever cuts work into parts cuts it into at most this many
+  static constexpr int kMaxParts = 8;
   // runs job(t) for t = 1 .. nt - 1 on the workers and job(0) on the caller; returns when all are done.
   // The loops of one C-ABI call follow each other within a millisecond or so (defaults while the device works, results, view):
   // a worker that has finished SPINS on the generation counter for kSpinUs before it goes to sleep on the condition variable,
   // and the caller spins on the count of pending parts — waking seven sleepers through one mutex cost 0.05-0.1 ms per loop,
   // a third of a world-8 rank's whole call on the UniProt-shaped batch.
   void run(int nt, const std::function<void(int)> &job) {
-    nt = std::min(nt, kWorkers + 1);
+    nt = std::min(nt, (int)kMaxParts);
     if (nt <= 1) { job(0); return; }
     std::lock_guard<std::mutex> turn(turn_);
     {
@@ -619,7 +627,7 @@ class WorkerPool {
   }
 
  private:
-  static constexpr int kWorkers = 7;
+  static constexpr int kWorkers = kMaxParts - 1;
   // (MI355_SW_POOL_SPIN_US in the environment, read once: 0 = sleep at once)
   const int kSpinUs = [] { const char *e = std::getenv("MI355_SW_POOL_SPIN_US"); return e && *e ? std::max(0, atoi(e)) : 1000; }();
   static void cpu_relax() {
@@ -668,11 +676,12 @@ class WorkerPool {
   std::atomic<bool> quit_{false};
 };
 
-// items from which a per-item host loop of the running call goes to the pool (set per call by align_range_core)
+// items from which a per-item host loop of the running call goes to the pool: 49 152 inside a PoolFromScope (align_range_core and
+// align_range_view open one, with or without traceback), 131 072 outside one
 thread_local size_t tl_pool_from = 131072;
-struct PoolFromScope {                                             // (all loops of a call or none, see parallel_for)
+struct PoolFromScope {                                             // (all loops inside the scope or none, see parallel_for)
   size_t was = tl_pool_from;
-  explicit PoolFromScope(bool) { tl_pool_from = 49152; }
+  PoolFromScope() { tl_pool_from = 49152; }
   ~PoolFromScope() { tl_pool_from = was; }
 };
 
@@ -684,12 +693,17 @@ void parallel_for(size_t n, F fn) {
   // the calling thread, 1.03 ms on the pool; with traceback 1.40 against 1.31 ms — and 1.50 ms when only SOME loops of the call
   // took the pool: a call pools all of its loops or none.  With the records in id order (host_batch.h: one sequential loop + the
   // defaults written while the device works, which also wakes the workers): 0.64-0.69 against 0.76-0.81 ms, 1.00-1.08 against
-  // 1.03-1.04 ms: calls pool from 49 152 items (PoolFromScope), anything else from 131 072.
+  // 1.03-1.04 ms: the loops inside a PoolFromScope (those of align_range_core and of the view, score-only calls included) pool from
+  // 49 152 items, every other loop (the result objects of align_range among them) from 131 072.
+  // MI355_SW_POOL_THREADS (read once): parts per loop, and every loop from 1024 items pools.  The pool runs at most
+  // WorkerPool::kMaxParts parts: a higher value means that many — the clamp comes BEFORE the step, or the parts behind the pool's
+  // last one (items [kMaxParts * step, n)) would belong to nobody.
   static const int nt_env = [] { const char *e = std::getenv("MI355_SW_POOL_THREADS"); return e && *e ? std::max(1, atoi(e)) : 0; }();
   if (n < pool_from && !nt_env) { fn((size_t)0, n); return; }
-  const int nt = nt_env ? nt_env : 8;
+  const int nt = std::min(nt_env ? nt_env : 8, (int)WorkerPool::kMaxParts);
   if (nt <= 1 || n < 1024) { fn((size_t)0, n); return; }
   const size_t step = (n + nt - 1) / nt;
+  ++tl_pooled_loops;
   const Options *caller = tl_opt;                                  // the workers see the calling context's options, not the environment's
   const DevInfo *caller_dev = tl_dev;
   WorkerPool::get().run(nt, [&](int t) {
@@ -698,7 +712,7 @@ void parallel_for(size_t n, F fn) {
     fn(std::min(n, (size_t)t * step), std::min(n, (size_t)(t + 1) * step));
     tl_opt = was; tl_dev = was_dev;
   });
-}
+}  // parallel_for (tests/test_parallel_for_ref.py cuts its text from the pool's class to this line)
 
 inline Hash128 combine_hash(Hash128 r, const Hash128 &o) {
   r.a = (r.a ^ o.a) * 0xBF58476D1CE4E5B9ull + (r.a >> 29);

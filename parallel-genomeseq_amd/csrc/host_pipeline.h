@@ -940,7 +940,7 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
   const int64_t n = rg.hi - rg.lo;
   HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
   // (half a million small alignments per call: the per-query host arrays are sized only where a path reads them)
-  PoolFromScope pool_from_(want_trace);
+  PoolFromScope pool_from_;
   loc.resize(nq);
   tout.resize(want_trace ? nq : 0);
   auto fill_defaults = [&loc, &tout, nq, want_trace]() {
@@ -1517,7 +1517,7 @@ int align_range_view(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
   const size_t nq = q.nq;
   std::vector<Located> &loc = ctx->loc_store;
   std::vector<TraceOut> &tout = ctx->tout_store;
-  PoolFromScope pool_from_(want_trace);
+  PoolFromScope pool_from_;
   ViewStore &v = ctx->view;
   v.score.resize(nq); v.pos.resize(nq); v.cons_len.resize(nq); v.end_x.resize(nq); v.end_y.resize(nq);
   v.cx.resize(nq); v.cy.resize(nq);

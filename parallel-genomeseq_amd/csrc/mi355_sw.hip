@@ -747,6 +747,7 @@ int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *o
   else if (k == "saved_traces") *out = ctx->saved_traces;
   else if (k == "saved_fallbacks") *out = ctx->saved_fallbacks;
   else if (k == "walk_widened") *out = ctx->walk_widened;
+  else if (k == "pooled_loops") *out = tl_pooled_loops;            // (the calling thread's last call: this function opens no OptScope)
   else return MI355_SW_EINVAL;
   return 0;
 }

@@ -3,7 +3,7 @@ torch.distributed (backend "nccl" = RCCL over xGMI on the GPU box, "gloo" in CPU
 
 * query sharding  — the shape of src/mpi_sw_solve_uniprot.cpp:95-138 (independent alignments farmed to
   ranks) without its MPI_Send/MPI_Recv writer rank: reads are block- or LPT-partitioned, the reference is
-  replicated, there is no exchange during compute; results stay rank-local or are all-gathered (16 B per
+  replicated, there is no exchange during compute; results stay rank-local or are all-gathered (20 B per
   alignment); "best over the batch" is ONE 8-byte all-reduce(MAX) of a packed (score, ~index) key.
 * reference sharding — the shape of OMPParallelLocalAligner (src/aligner/plocalaligner.cpp:105-143):
   pieces from _make_string_range dealt round-robin to ranks, per-piece maxima computed locally, ONE
@@ -93,22 +93,38 @@ def align_queries_sharded(align_fn, queries, weights=None, gather=True):
     res = align_fn([queries[i] for i in idx]) if len(idx) else []
     gathered = None
     if gather:
-        # ONE all_gather of 16 B per alignment: (score as float32 bits, pos, end_x, end_y) as four int32 —
-        # pos is the reference's unsigned int, end_x / end_y are below 2^31 for every reference this engine holds; shards are
-        # padded to the longest one (all_gather wants equal shapes), the padding is dropped on arrival
+        # ONE all_gather of 20 B per alignment: (score as float32 bits, pos, end_x, end_y low word, end_y high word)
+        # as five int32 — pos is the reference's unsigned int; end_x is a row of the traceback scratch, far below 2^31 (checked:
+        # nothing wraps silently); end_y is the C-ABI's int64 column (references of 2^31 letters and more: a human genome), so it
+        # travels exactly, as its two halves.  Shards are padded to the longest one (all_gather wants equal shapes), the padding is
+        # dropped on arrival
         longest = max(len(p) for p in parts) if parts else 0
-        rec = np.zeros((max(1, longest), 4), dtype=np.int32)
+        rec = np.zeros((max(1, longest), 5), dtype=np.int32)
+        bad = False
         if len(idx):
+            ex = np.array([r["end_x"] for r in res], dtype=np.int64)
+            ey = np.array([r["end_y"] for r in res], dtype=np.int64)
+            bad = bool(((ex < 0) | (ex >= 2 ** 31) | (ey < 0)).any())
+        if bad:
+            # nothing of this shard is packed; one rank raising alone would leave the others waiting in the collective, so the
+            # verdict travels in its place (end_x = -1 in the first record) and every rank raises behind the gather
+            rec[0, 2] = -1
+        elif len(idx):
             rec[:len(idx), 0] = np.array([r["score"] for r in res], dtype=np.float32).view(np.int32)
             rec[:len(idx), 1] = np.array([r["pos"] for r in res], dtype=np.int64).astype(np.uint32).view(np.int32)
-            rec[:len(idx), 2] = np.array([r["end_x"] for r in res], dtype=np.int64)
-            rec[:len(idx), 3] = np.array([r["end_y"] for r in res], dtype=np.int64)
+            rec[:len(idx), 2] = ex.astype(np.int32)
+            rec[:len(idx), 3] = (ey & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+            rec[:len(idx), 4] = (ey >> 32).astype(np.int32)
         mine = torch.from_numpy(rec).to(_dev())
         if size > 1:
             every = [torch.empty_like(mine) for _ in range(size)]
             dist.all_gather(every, mine)
         else:
             every = [mine]
+        culprits = [r for r in range(size) if int(every[r][0, 2]) < 0]
+        if culprits:
+            raise ValueError("align_queries_sharded: rank(s) %r hold an end_x outside [0, 2^31) or a negative end_y, which the "
+                             "gather cannot carry" % culprits)
         score = np.zeros(n, dtype=np.float32)
         pos = np.zeros(n, dtype=np.int64)
         end_x = np.zeros(n, dtype=np.int64)
@@ -121,7 +137,7 @@ def align_queries_sharded(align_fn, queries, weights=None, gather=True):
             score[parts[r]] = a[:, 0].copy().view(np.float32)
             pos[parts[r]] = a[:, 1].copy().view(np.uint32)
             end_x[parts[r]] = a[:, 2]
-            end_y[parts[r]] = a[:, 3]
+            end_y[parts[r]] = a[:, 3].copy().view(np.uint32).astype(np.int64) | (a[:, 4].astype(np.int64) << 32)
         gathered = dict(score=score, pos=pos, end_x=end_x, end_y=end_y)
     return idx, res, gathered
 

@@ -214,3 +214,62 @@ def test_ref_sharding_certified_gloo():
                 assert res[k] == exp[k], (rank, name, k)
             assert rounds == (1 if name == "above" else 2), (rank, name, rounds, calls)
             assert calls[0] == 0.0 and (name == "above" or calls[1] > 0)
+
+
+# ---- the gather of align_queries_sharded carries what the C-ABI returns: end_y is an int64 column (references of 2^31 letters and more)
+WIDE_END_Y = [0, 2 ** 31 - 1, 2 ** 31, 2 ** 31 + 5, 3_100_000_000, 2 ** 40 + 7]
+WIDE = [dict(score=s, pos=p, end_x=x, end_y=y)
+        for s, p, x, y in zip([0.0, 12.5, 12.25, 0.7, 1234.75, 3.0000002], [0, 1, 2 ** 31, 2 ** 32 - 1, 2 ** 32 - 2, 77],
+                              [0, 1, 2 ** 31 - 1, 64, 40000, 7], WIDE_END_Y)]
+WIDE_WEIGHTS = [5, 1, 9, 2, 8, 3]                                    # LPT at world 2: interleaved shards {0, 2, 5} / {1, 3, 4}
+
+
+def _gather_wide(rank, size, pgs, ob, weights, rows=WIDE):
+    from parallel_genomeseq_amd import dist as pd
+    idx, res, g = pd.align_queries_sharded(lambda qs: [dict(rows[q]) for q in qs], list(range(len(rows))), weights=weights)
+    assert all(g[k].dtype == (np.float32 if k == "score" else np.int64) for k in g)
+    return dict(idx=idx.tolist(), **{k: g[k].tolist() for k in ("score", "pos", "end_x", "end_y")})
+
+
+def _case_gather_wide_block(rank, size, pgs, ob):
+    return _gather_wide(rank, size, pgs, ob, None)
+
+
+def _case_gather_wide_lpt(rank, size, pgs, ob):
+    return _gather_wide(rank, size, pgs, ob, WIDE_WEIGHTS)
+
+
+def _case_gather_end_x_too_wide(rank, size, pgs, ob):
+    rows = [dict(r) for r in WIDE]
+    rows[4]["end_x"] = 2 ** 31                                       # (block shards at world 2: rank 1 alone holds it)
+    try:
+        _gather_wide(rank, size, pgs, ob, None, rows)
+    except ValueError as e:
+        return str(e)
+    return None
+
+
+@pytest.mark.parametrize("size", (1, 2))
+@pytest.mark.parametrize("shards", ("block", "lpt"))
+def test_gather_carries_wide_end_y_gloo(size, shards):
+    """end_y of 2^31 and beyond (int64 in the C-ABI), pos up to 2^32 - 1 and fractional scores arrive exactly on every rank; packed
+    into one int32 word, end_y = 2^31 + 5 came back as -2147483643 and 3 100 000 000 as -1194967296."""
+    out = _run("_case_gather_wide_" + shards, size)
+    assert sorted(out) == list(range(size))
+    every = sorted(i for o in out.values() for i in o["idx"])
+    assert every == list(range(len(WIDE)))
+    if size == 2 and shards == "lpt":
+        assert out[0]["idx"] != list(range(len(out[0]["idx"])))      # shards that are no contiguous blocks
+    for rank in range(size):
+        o = out[rank]
+        assert o["score"] == [float(np.float32(r["score"])) for r in WIDE], rank
+        for k in ("pos", "end_x", "end_y"):
+            assert o[k] == [r[k] for r in WIDE], (rank, k, o[k])
+
+
+@pytest.mark.parametrize("size", (1, 2))
+def test_gather_refuses_end_x_beyond_int32_gloo(size):
+    """end_x = 2^31 is refused, not wrapped — on EVERY rank, so none is left waiting in the collective."""
+    out = _run("_case_gather_end_x_too_wide", size)
+    for rank in range(size):
+        assert out[rank] is not None and "end_x" in out[rank], (rank, out[rank])
