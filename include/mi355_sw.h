@@ -502,6 +502,58 @@ int mi355_sw_affine_extend_trace_band(mi355_sw_ctx *ctx, const mi355_sw_extend_l
                                       const uint8_t *to_end /* NULL: best extension for every pair */,
                                       mi355_sw_result *outs, float *to_end_score, int64_t *to_end_y);
 
+/* ---- lists of pairs, global alignment between two anchors, plain and banded (BWA-MEM ksw_global, minimap2's gap-filling ksw_extz) ----
+ * The alignment BETWEEN two consecutive seeds of a chain: anchored at both ends.  Pair k is as in mi355_sw_affine_extend_run — x, the
+ * letters [q_lo, q_hi) of resident query query[k], with m rows; y, the window [lefts[k], rights[k]) of the resident reference, with
+ * n columns; backward[k] != 0 runs the pair on both strings reversed and is DEFINED as the forward model on the reversed strings, on
+ * the reversed copies of the extension calls.  A gap fill has no direction: backward only chooses toward which side ties of the
+ * walk fall.
+ *
+ * Model: the anchored model of mi355_sw_affine_extend_run, unchanged — the recurrence, o >= e > 0, no zero floor, and the borders
+ * H(0,0) = 0, H(0,j) = E(0,j) = -(o + (j-1) e), H(i,0) = F(i,0) = -(o + (i-1) e).
+ *
+ * Score = H(m, n), of any sign; end_x = m and end_y = n always (lengths, as in the extension calls).
+ *
+ * Traceback: the anchored model's rule (diagonal over E over F, opening wins a tie with extending).  The walk starts in state M at
+ * (m, n) and stops at (0,0) and nowhere else; in row 0 only E moves happen, in column 0 only F moves.  cons_x without '-' is all m
+ * letters, cons_y without '-' is all n columns, and the value of the strings under (f, o, e) is the score.  pos = 1 when n >= 1,
+ * else 0.  String orientation as in the extension calls: reversed for a forward pair, reading order for a backward pair.
+ *
+ * Degenerate pairs, filled in by the host (no kernel runs).  m = 0, n = 0: score 0, end 0 / 0, empty strings.  m >= 1, n = 0: score
+ * -(o + (m-1) e), the m letters of x against m '-'.  m = 0, n >= 1: score -(o + (n-1) e), n '-' against the n letters of y — a pure
+ * deletion between two adjacent seeds.
+ *
+ * Band (band_lo, band_hi: both NULL, or both given): the in-band cells are band_lo[k] <= j - i <= band_hi[k], i and j counted from
+ * the anchor; band_lo[k] > 0 or band_hi[k] < 0: MI355_SW_EINVAL.  Outside the band H = E = F = -infinity.  Effective band: lo_e =
+ * max(band_lo, -m), hi_e = min(band_hi, n), W = hi_e - lo_e + 1.  lo_e == -m and hi_e == n: the pair IS the unbanded pair — same
+ * path, same bytes, same mi355_sw_last_path.  The corner is reachable exactly when band_lo <= n - m <= band_hi.  Otherwise the run
+ * call returns score = -INFINITY, the trace call score -INFINITY, end 0 / 0, pos 0 and empty strings, and no kernel runs for such a
+ * pair.  These rules cover the degenerate pairs too: n = 0 needs band_lo <= -m, and m = 0 needs band_hi >= n.  A reachable pair
+ * has n <= m + hi_e: no window is clipped.
+ *
+ * Arguments, their checks and the order of those checks are those of mi355_sw_affine_extend_run_band; the band checks come last.
+ * score == NULL (run) or outs == NULL (trace): MI355_SW_EINVAL.  npairs == 0 returns 0 and writes nothing.  After any error the
+ * context stays usable.
+ *
+ * Dispatch.  The kernels form no key, so no value lends mantissa bits and the extension calls' smax (rows + 1)
+ * < 2^18 does not apply; every value a kernel forms is an integer below 2^24 in magnitude; smin (smax) the least (greatest)
+ * substitution score, both taken with 0, and a = -smin.  Unbanded: the global instance of the pair kernel for 1..512 rows and
+ * 1..2^20 columns while the score table fits 32 KiB of LDS and
+ *     3 gap_open + (rows + columns) gap_extend - smin < 2^24 and smax rows + gap_open < 2^24
+ * Banded: the global instance of the band kernel for 1..512 rows and W <= 256 while the table fits and
+ *     a rows + 3 gap_open + (W + 1) gap_extend - smin < 2^24 and smax rows + gap_open < 2^24
+ * Every other pair: the exact kernel within the bounds of the extension calls (unbanded and under a band), else MI355_SW_ENOTSUP
+ * naming the pair.  A banded pair never runs on an unbanded kernel.  The traceback is the extension calls', started at (m, n).
+ * Option no_affine_pairs sends every pair to the exact kernel, no_affine_band every banded pair.
+ * mi355_sw_last_path: "affine_pair_glob[R=..]" and "affine_band_glob[R=..]" once per instance that ran, "affine_exact",
+ * "affine_exact_band" and "affine_trace" as above; a list of host-filled pairs alone leaves no kernel tag.  mi355_sw_last_timings as
+ * for the pairs calls.  mi355_sw_last_kernel names "sw_affine_pair_glob_kernel<R=..>" or "sw_affine_band_glob_kernel<R=..>", with
+ * its ops per cell. */
+int mi355_sw_affine_global_run(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo, const int64_t *band_hi,
+                               const mi355_sw_affine_params *params, float *score);
+int mi355_sw_affine_global_trace(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo, const int64_t *band_hi,
+                                 const mi355_sw_affine_params *params, mi355_sw_result *outs);
+
 /* Host-only helper: piece ranges [left,right). Returns MI355_SW_ERANGE where the reference asserts. */
 int mi355_sw_make_string_range(int npiece, int64_t shortlen, int64_t longlen, float overlap_ratio,
                                int64_t *lefts, int64_t *rights);

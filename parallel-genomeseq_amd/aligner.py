@@ -200,6 +200,27 @@ class AffineSWAligner:
             return ctx.affine_extend_trace(query, lefts, rights, to_end=to_end, **kw)
         return ctx.affine_extend_run(query, lefts, rights, **kw)
 
+    @staticmethod
+    def global_pairs(query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0,
+                     scoring=None, traceback=False, context=None, band=None):
+        """A mapper's gap fill: pair k = the letters [q_lo[k], q_hi[k]) of query[k] against the window [lefts[k], rights[k]), anchored
+        at BOTH ends — the alignment between two consecutive seeds of a chain (Context.affine_global_run, or affine_global_trace
+        with traceback=True).  Returns that call's dict: score = H(m, n) of any sign, and with traceback end_x = m, end_y = n, pos,
+        the strings and the CIGAR.  An empty letter range or an empty window is one gap (or nothing).  band=(lo, hi), lo <= 0 <= hi,
+        each a scalar or an array per pair: only the diagonals lo <= j - i <= hi count; a band that does not hold n - m gives score
+        float("-inf") and empty strings."""
+        ctx = context if context is not None else default_context()
+        lut = None
+        if scoring is not None:
+            lut = _lut_from_function(scoring) if callable(scoring) else np.asarray(scoring, dtype=np.float32)
+        kw = dict(q_lo=q_lo, q_hi=q_hi, backward=backward, match=float(match), mismatch=float(mismatch), gap_open=float(gap_open),
+                  gap_extend=float(gap_extend), lut=lut)
+        if band is not None:
+            kw["band_lo"], kw["band_hi"] = band
+        if traceback:
+            return ctx.affine_global_trace(query, lefts, rights, **kw)
+        return ctx.affine_global_run(query, lefts, rights, **kw)
+
 
 class ParallelLocalAligner:
     """localaligner.h:19-28"""

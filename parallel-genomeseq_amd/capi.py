@@ -28,6 +28,7 @@ EXPORTS = [
     "mi355_sw_affine_pairs_run_band", "mi355_sw_affine_pairs_trace_band",
     "mi355_sw_affine_extend_run", "mi355_sw_affine_extend_trace",
     "mi355_sw_affine_extend_run_band", "mi355_sw_affine_extend_trace_band",
+    "mi355_sw_affine_global_run", "mi355_sw_affine_global_trace",
 ]
 AFFINE_LOCAL, AFFINE_END_TO_END = 0, 1                 # mode of the affine pairs calls (include/mi355_sw.h)
 AFFINE_MODES = {"local": AFFINE_LOCAL, "end_to_end": AFFINE_END_TO_END}
@@ -591,6 +592,50 @@ class Context:
             rows.append(r)
         self._L.mi355_sw_free_results(res, C.c_size_t(n))
         out = dict(score=np.array([r["score"] for r in rows], dtype=np.float32), to_end_score=tscore, to_end_y=ty)
+        for k in ("end_x", "end_y", "pos"):
+            out[k] = np.array([r[k] for r in rows], dtype=np.int64)
+        for k in ("cons_x", "cons_y", "cigar"):
+            out[k] = [r[k] for r in rows]
+        return out
+
+    def affine_global_run(self, query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0,
+                          gap_extend=1.0, lut=None, band_lo=None, band_hi=None):
+        """Global alignment between two anchors (mi355_sw_affine_global_run): pair k as in affine_extend_run, anchored in front of
+        AND behind both strings — the gap fill between two consecutive seeds of a chain.  dict(score=): H(m, n) of the anchored
+        model, of any sign.  band_lo / band_hi (a scalar or an array per pair, band_lo <= 0 <= band_hi): only cells with
+        band_lo <= j - i <= band_hi count; a band that misses the corner (n - m outside it) gives float("-inf")."""
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        el, n, arrays = self._extend_list(query, lefts, rights, q_lo, q_hi, backward)
+        blo, bhi = self._extend_bands(band_lo, band_hi, n)
+        score = np.zeros(n, dtype=np.float32)
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._L.mi355_sw_affine_global_run(self._ctx, C.byref(el), blo.ctypes.data_as(i64) if blo is not None else None,
+                                                     bhi.ctypes.data_as(i64) if bhi is not None else None, C.byref(p),
+                                                     score.ctypes.data_as(C.POINTER(C.c_float))))
+        return dict(score=score)
+
+    def affine_global_trace(self, query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0,
+                            gap_extend=1.0, lut=None, band_lo=None, band_hi=None):
+        """affine_global_run with the traceback (mi355_sw_affine_global_trace): score, end_x (= m), end_y (= n), pos, cons_x, cons_y
+        and cigar of the walk from (m, n) to the anchor.  The strings hold all of x and all of the window; they run from the far end
+        to the anchor, as affine_extend_trace's, and the CIGAR is in reading order for both directions.  A band that misses the
+        corner: score float("-inf"), end 0 / 0, pos 0 and empty strings."""
+        p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
+        el, n, arrays = self._extend_list(query, lefts, rights, q_lo, q_hi, backward)
+        blo, bhi = self._extend_bands(band_lo, band_hi, n)
+        res = (Result * max(1, n))()
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._L.mi355_sw_affine_global_trace(self._ctx, C.byref(el), blo.ctypes.data_as(i64) if blo is not None else None,
+                                                       bhi.ctypes.data_as(i64) if bhi is not None else None, C.byref(p), res))
+        back = arrays[5]
+        rows = []
+        for k in range(n):
+            r = _take(res[k])
+            b = back is not None and bool(back[k])
+            r["cigar"] = cigar(r["cons_x"][::-1], r["cons_y"][::-1]) if b else cigar(r["cons_x"], r["cons_y"])
+            rows.append(r)
+        self._L.mi355_sw_free_results(res, C.c_size_t(n))
+        out = dict(score=np.array([r["score"] for r in rows], dtype=np.float32))
         for k in ("end_x", "end_y", "pos"):
             out[k] = np.array([r[k] for r in rows], dtype=np.int64)
         for k in ("cons_x", "cons_y", "cigar"):

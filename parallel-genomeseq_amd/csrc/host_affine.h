@@ -1,5 +1,5 @@
 // host_affine.h — affine-gap score, end cell and traceback.  Part of the single translation unit mi355_sw.hip
-// (included there, in order; not a standalone header).  Three drivers:
+// (included there, in order; not a standalone header).  Four drivers:
 //   affine_run    every query of the batch against ranges of the reference: affine_prof_run (sw_affine_prof_kernel, ranges of at most
 //                 512 letters), affine_sweep (sw_affine_kernel) and the exact kernel behind both
 //   affine_pairs  a list of (query, window) pairs, local or end-to-end (AffineCall::mode), with or without a diagonal band per pair:
@@ -8,6 +8,9 @@
 //   affine_extend the anchored seed extension of a list of (letters of a query, window) pairs, forward or backward: the same list
 //                 stage on sw_affine_pair_ext_kernel, sw_affine_exact_ext_kernel and sw_affine_trace_ext_kernel behind it; with a
 //                 diagonal band per pair: sw_affine_band_ext_kernel, sw_affine_exact_ext_band_kernel, sw_affine_trace_ext_band_kernel
+//   affine_global the pairs of affine_extend anchored at both ends, plain and banded (the gap fill between two seeds of a chain): affine_extend's
+//                 items and stages on sw_affine_pair_glob_kernel, sw_affine_band_glob_kernel and sw_affine_exact_glob_kernel, its
+//                 traceback started at the corner
 // All share one AffineCall (affine_begin .. affine_end, the latter with affine_trace: sw_affine_trace_kernel), affine_exact_stage
 // (sw_affine_exact_kernel), affine_class_table, affine_download and affine_note_kernel.
 namespace {
@@ -1104,6 +1107,19 @@ bool affine_band_ext_whole_exact(const AffineTable &t, double m, double W) {
   return -(double)t.smin * m + 2.0 * t.open + W * t.ext - t.smin < 16777216.0 && (double)t.smax * (m + 1.0) < 16777216.0;
 }
 
+// Lemma L23, the admission tests of sw_affine_pair_glob_kernel and sw_affine_band_glob_kernel: the loops of the two kernels above
+// without their folds, so every value they form is one L21 / L22 bound already — the same recurrence on the same borders (the same
+// band), the same table of s + o, the same scan.  What the folds needed and these kernels do not is the key: no value lends five
+// mantissa bits, and smax (m + 1) < 2^18 goes.  The capture forms no new value (a select; the band kernel's Ho + o is H, within
+// [-(a m + o + (W-2) e), smax m]).  The exact kernel's bounds are the extension calls': affine_ext_whole_exact and
+// affine_band_ext_whole_exact.
+bool affine_glob_exact(const AffineTable &t, double m, double n) {
+  return 3.0 * t.open + (m + n) * t.ext - t.smin < 16777216.0 && (double)t.smax * m + t.open < 16777216.0;
+}
+bool affine_band_glob_exact(const AffineTable &t, double m, double W) {
+  return -(double)t.smin * m + 3.0 * t.open + (W + 1.0) * t.ext - t.smin < 16777216.0 && (double)t.smax * m + t.open < 16777216.0;
+}
+
 // The reversed copies of the resident reference (codes and bytes) and of the batch's bytes, built with reverse_bytes_kernel where
 // the cached ones are of another version.
 int affine_ext_reversed(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q) {
@@ -1130,6 +1146,49 @@ int affine_ext_reversed(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch 
     ctx->rev_q_valid = true; ctx->rev_q_version = q.version;
   }
   return 0;
+}
+
+// What the anchored calls (affine_extend, affine_global) share in front of their routing.
+// The classes of the call's scoring for the list kernels — none under option no_affine_pairs; every byte its own class where the table
+// scores all 256 bytes differently, as affine_pairs — and whether their table fits the kernels' LDS.
+bool affine_ext_plan(const AffineCall &c, AffineProfPlan &plan) {
+  const RefData &ref = c.ref;
+  if (!opt().no_affine_pairs) {
+    affine_byte_classes(ref, c.p, c.t, plan, 16777216.0);
+    if (!plan.ok && ref.ncodes >= 2 && ref.ncodes <= 256 && (double)c.t.open < 16777216.0) {
+      plan.rep.resize(256);                                        // every byte its own class, as affine_pairs
+      for (int a = 0; a < 256; ++a) { plan.cls[a] = (uint8_t)a; plan.rep[a] = a; }
+      plan.nclass = 257;
+      plan.ok = true;
+    }
+  }
+  return plan.ok && affine_pair_lds(ref, plan) <= kAffinePairLdsMax;
+}
+
+// the reversed copies, where the list holds a backward pair
+int affine_ext_any_reversed(const AffineCall &c, const AffineExtList &el) {
+  bool any_back = false;
+  for (size_t k = 0; k < el.npairs && !any_back; ++k) any_back = el.back(k);
+  return any_back ? affine_ext_reversed(c.ctx, c.ref, c.q) : 0;
+}
+
+// pair k of the list as an item: its rows, its window and where both lie on the device (unbanded; the caller sets the band)
+AffineExtItem affine_ext_item(const AffineCall &c, const AffineExtList &el, size_t k) {
+  mi355_sw_ctx *ctx = c.ctx; const RefData &ref = c.ref; const QueryBatch &q = c.q;
+  const int qi = el.qid[k];
+  const int64_t qlo = el.q_lo ? el.q_lo[k] : 0, qhi = el.q_hi ? el.q_hi[k] : q.len[qi];
+  AffineExtItem it;
+  it.id = (uint32_t)k; it.m = (int32_t)(qhi - qlo); it.n = el.rights[k] - el.lefts[k];
+  if (el.back(k)) {
+    it.x = ctx->rev_q.as<uint8_t>() + ((int64_t)ctx->rev_q_total - q.off[qi] - qhi);
+    it.ycodes = ctx->rev_codes.as<uint8_t>() + ((int64_t)ref.n - el.rights[k]);
+    it.ybytes = ctx->rev_bytes.as<uint8_t>() + ((int64_t)ref.n - el.rights[k]);
+  } else {
+    it.x = q.bytes.as<uint8_t>() + q.off[qi] + qlo;
+    it.ycodes = ref.codes.as<uint8_t>() + el.lefts[k];
+    it.ybytes = ref.bytes.as<uint8_t>() + el.lefts[k];
+  }
+  return it;
 }
 
 // sw_affine_pair_ext_kernel for affine_list_stage: an item carries its own pointers; two results per problem (best extension, to
@@ -1194,9 +1253,11 @@ struct AffineBandExtFamily {
 // sw_affine_exact_ext_kernel over all of `jobs`, 65536 per launch: score[npairs][2], ends[npairs][2][2] as the list stage; its
 // interval goes to timings[1].
 // BAND: sw_affine_exact_ext_band_kernel over jobs that carry their band (AffineExtItem::blo, bhi) and their clipped window.
-template <bool BAND = false>
+// GLOB (affine_global): sw_affine_exact_glob_kernel, one result per problem — score[npairs], ends[npairs][2].
+template <bool BAND = false, bool GLOB = false>
 int affine_ext_exact_stage(const AffineCall &c, const std::vector<AffineExtItem> &jobs, float *score, int64_t *ends) {
   typedef typename AffineExactProblemOf<BAND>::type Problem;
+  constexpr size_t NO = GLOB ? 1 : 2;                              // (best, cell) a problem writes
   mi355_sw_ctx *ctx = c.ctx;
   if (jobs.empty()) return 0;
   path_note(ctx, BAND ? "affine_exact_band" : "affine_exact");
@@ -1207,7 +1268,7 @@ int affine_ext_exact_stage(const AffineCall &c, const std::vector<AffineExtItem>
     const size_t n = std::min<size_t>(65536, jobs.size() - lo);
     size_t lds = 0;
     for (size_t k = 0; k < n; ++k) lds = std::max(lds, affine_exact_lds(jobs[lo + k].m));
-    if (ctx->probs.ensure(n * sizeof(Problem)) || ctx->outs_f.ensure(n * 8) || ctx->outs_i.ensure(n * 32))
+    if (ctx->probs.ensure(n * sizeof(Problem)) || ctx->outs_f.ensure(NO * n * 4) || ctx->outs_i.ensure(NO * n * 16))
       return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(exact scratch) failed");
     std::vector<Problem> pr(n);
     for (size_t k = 0; k < n; ++k) {
@@ -1217,22 +1278,23 @@ int affine_ext_exact_stage(const AffineCall &c, const std::vector<AffineExtItem>
       if constexpr (BAND) { ep = &pr[k].e; pr[k].blo = j.blo; pr[k].bhi = j.bhi; } else ep = &pr[k];
       ExactProblem &e = *ep;
       e.x = j.x; e.y = j.ybytes; e.m = j.m; e.nw = (int32_t)j.n; e.full_n = j.n; e.own_lo = 1; e.target = -1.0f;
-      e.best = ctx->outs_f.as<float>() + 2 * k;
-      e.cell = ctx->outs_i.as<int64_t>() + 4 * k;
+      e.best = ctx->outs_f.as<float>() + NO * k;
+      e.cell = ctx->outs_i.as<int64_t>() + 2 * NO * k;
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(Problem), hipMemcpyHostToDevice, ctx->stream));
-    if constexpr (BAND) launch_dyn_lds(&sw_affine_exact_ext_band_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<Problem>(), sc);
+    if constexpr (GLOB) launch_dyn_lds(&sw_affine_exact_glob_kernel<BAND>, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<Problem>(), sc);
+    else if constexpr (BAND) launch_dyn_lds(&sw_affine_exact_ext_band_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<Problem>(), sc);
     else launch_dyn_lds(&sw_affine_exact_ext_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactProblem>(), sc);
     HIPCHK(ctx, hipGetLastError());
-    std::vector<float> bf(2 * n);
-    std::vector<int64_t> ci(4 * n);
-    HIPCHK(ctx, hipMemcpyAsync(bf.data(), ctx->outs_f.p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ci.data(), ctx->outs_i.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<float> bf(NO * n);
+    std::vector<int64_t> ci(2 * NO * n);
+    HIPCHK(ctx, hipMemcpyAsync(bf.data(), ctx->outs_f.p, NO * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ci.data(), ctx->outs_i.p, NO * n * 16, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t k = 0; k < n; ++k) {
       const size_t id = jobs[lo + k].id;
-      score[2 * id] = bf[2 * k]; score[2 * id + 1] = bf[2 * k + 1];
-      for (int v = 0; v < 4; ++v) ends[4 * id + v] = ci[4 * k + v];
+      for (size_t v = 0; v < NO; ++v) score[NO * id + v] = bf[NO * k + v];
+      for (size_t v = 0; v < 2 * NO; ++v) ends[2 * NO * id + v] = ci[2 * NO * k + v];
     }
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
@@ -1374,39 +1436,17 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   int rc = affine_begin(c);
   if (rc) return rc > 0 ? 0 : rc;
   AffineProfPlan plan;
-  if (!opt().no_affine_pairs) {
-    affine_byte_classes(ref, p, c.t, plan, 16777216.0);
-    if (!plan.ok && ref.ncodes >= 2 && ref.ncodes <= 256 && (double)c.t.open < 16777216.0) {
-      plan.rep.resize(256);                                        // every byte its own class, as affine_pairs
-      for (int a = 0; a < 256; ++a) { plan.cls[a] = (uint8_t)a; plan.rep[a] = a; }
-      plan.nclass = 257;
-      plan.ok = true;
-    }
-  }
-  const bool table_ok = plan.ok && affine_pair_lds(ref, plan) <= kAffinePairLdsMax;
-  bool any_back = false;
-  for (size_t k = 0; k < npairs && !any_back; ++k) any_back = el.back(k);
-  if (any_back) { rc = affine_ext_reversed(ctx, ref, q); if (rc) return rc; }
+  const bool table_ok = affine_ext_plan(c, plan);
+  rc = affine_ext_any_reversed(c, el); if (rc) return rc;
 
   std::vector<AffineExtItem> pairs(npairs), fast, jobs;
   std::vector<AffineExtItem> bfast, bjobs;                         // banded pairs of sw_affine_band_ext_kernel, and of the exact kernel under a band
   std::vector<char> unreach(el.band_lo ? npairs : 0, 0);           // the band misses row m: the host fills in to_end
   int mmax = 0, band_mmax = 0;
   for (size_t k = 0; k < npairs; ++k) {
-    const int qi = el.qid[k];
-    const int64_t qlo = el.q_lo ? el.q_lo[k] : 0, qhi = el.q_hi ? el.q_hi[k] : q.len[qi];
-    const int64_t m = qhi - qlo, n = el.rights[k] - el.lefts[k];
     AffineExtItem &it = pairs[k];
-    it.id = (uint32_t)k; it.m = (int32_t)m; it.n = n;
-    if (el.back(k)) {
-      it.x = ctx->rev_q.as<uint8_t>() + ((int64_t)ctx->rev_q_total - q.off[qi] - qhi);
-      it.ycodes = ctx->rev_codes.as<uint8_t>() + ((int64_t)ref.n - el.rights[k]);
-      it.ybytes = ctx->rev_bytes.as<uint8_t>() + ((int64_t)ref.n - el.rights[k]);
-    } else {
-      it.x = q.bytes.as<uint8_t>() + q.off[qi] + qlo;
-      it.ycodes = ref.codes.as<uint8_t>() + el.lefts[k];
-      it.ybytes = ref.bytes.as<uint8_t>() + el.lefts[k];
-    }
+    it = affine_ext_item(c, el, k);
+    const int64_t m = it.m, n = it.n;
     if (m < 1) continue;
     if (el.band_lo) {
       // the band clipped to the matrix; one that covers it leaves the pair unbanded: today's route below, today's bytes
@@ -1476,6 +1516,189 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     }
     rc = affine_ext_trace(c, pairs, ts.data(), tx.data(), ty.data(), *tout);
     if (!rc && (!bfast.empty() || !bjobs.empty())) rc = affine_ext_trace<true>(c, pairs, ts.data(), tx.data(), ty.data(), *tout);
+    if (rc) return rc;
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+  ctx->timings[3] += elapsed_us(ctx, ctx->ev[4], ctx->ev[5]);
+  return 0;
+}
+
+// ---- global alignment between two anchors (include/mi355_sw.h "global alignment between two anchors", DESIGN.md §3.8 lemma L23) ----
+// sw_affine_pair_glob_kernel for affine_list_stage: AffineExtFamily's items, one result per problem, the corner H(m, n).
+struct AffineGlobFamily {
+  typedef AffinePairProblem Problem; typedef AffineExtItem Item;
+  const AffineCall &c;
+  static constexpr const char *kNoInstance = "internal: no sw_affine_pair_glob_kernel instance for this query";
+  static constexpr int kOuts = 1;
+  bool keep_all() const { return true; }                           // the corner's value may have any sign
+  static uint32_t id(const Item &a) { return a.id; }
+  static int R(const Item &a) { return affine_pair_R(a.m); }
+  static int R(const Problem &p) { return affine_pair_R(p.m); }
+  int64_t size(const Item &a) const { return a.n; }                // longest window first, as AffinePairFamily
+  void fill(const Item &a, Problem &p) const { p.x = a.x; p.y = a.ycodes; p.m = a.m; p.n = (int32_t)a.n; }
+  static double cells(const Problem &p) { return (double)p.m * (double)p.n; }
+  auto kernel(int R) const {
+    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
+    with_listed_R<kPairR>(R, [&](auto r) { kern = &sw_affine_pair_glob_kernel<decltype(r)::value>; });
+    return kern;
+  }
+  void note(double cells, int R, const Problem &first) const {
+    // per step and lane, counted in the compiled steady-state loop (four steps, every R of kPairR): the extension instance's count
+    // (AffineExtFamily::note) without the max with 0, the key's v_or and the maximum3 fold — seven ops, the table address' v_add and
+    // the row-m select per cell — and 10.5 of overhead: the two DPP moves and their copies, the row pointer's multiply and add, the
+    // code's address, the row-0 subtract and max, the capture's compare.  The compiler puts the capture behind an exec-mask branch
+    // that a wavefront takes when one of its lanes stands on its column n, and moves a quarter of the selects out of line with it:
+    // 8.75 R + 10.5 fits all six instances to within half an op.  The 16 border steps of a slot are not counted
+    path_note(c.ctx, "affine_pair_glob[R=%d]", R);
+    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, first.n, first.n, 0, (8.75 * R + 10.5) / (double)R,
+                       "sw_affine_pair_glob_kernel<R=%d>", R);
+  }
+};
+
+// sw_affine_band_glob_kernel for affine_list_stage: AffineBandExtFamily's items (the window is never clipped: a band that holds the
+// corner has n <= m + hi_e), one result per problem.
+struct AffineBandGlobFamily {
+  typedef AffineBandProblem Problem; typedef AffineExtItem Item;
+  const AffineCall &c;
+  static constexpr const char *kNoInstance = "internal: no sw_affine_band_glob_kernel instance for this band";
+  static constexpr int kOuts = 1;
+  bool keep_all() const { return true; }
+  static uint32_t id(const Item &a) { return a.id; }
+  static int R(const Item &a) { return affine_band_R(a.W); }
+  static int R(const Problem &p) { return affine_band_R(p.W); }
+  int64_t size(const Item &a) const { return a.m; }                // longest query first, as AffineBandFamily
+  void fill(const Item &a, Problem &p) const { p.x = a.x; p.y = a.ycodes; p.m = a.m; p.n = (int32_t)a.n; p.lo = a.blo; p.W = a.W; }
+  static double cells(const Problem &p) { return (double)p.m * (double)p.W; }
+  auto kernel(int R) const {
+    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
+    with_listed_R<kBandR>(R, [&](auto r) { kern = &sw_affine_band_glob_kernel<decltype(r)::value>; });
+    return kern;
+  }
+  void note(double cells, int R, const Problem &) const {
+    path_note(c.ctx, "affine_band_glob[R=%d]", R);
+    // per step and lane, counted in the compiled loop (every R of kBandR, to within five ops of a step): the extension instance's
+    // count (AffineBandExtFamily::note) without the max with 0 and the key's v_or per register and without the step's (value, column)
+    // compare — thirteen ops per register, a move per two registers, and 26 of overhead.  The corner's read (one compare and one
+    // select per register) runs behind the branch, at one step of a slot's rows: not counted
+    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, 16 * R, 16 * R, 0, (13.0 * R + (R + 1) / 2 + 26.0) / (double)R,
+                       "sw_affine_band_glob_kernel<R=%d>", R);
+  }
+};
+
+// The pairs traced from a cell in row 0 (tx = 0, ty >= 1: an empty x against a window of ty columns, ty '-' against its letters) are
+// written here from a copy of the window's bytes: no kernel runs, and affine_ext_trace skips them.  One arena, one copy per pair, one
+// wait for all of them, as that function's column-0 cells.
+int affine_glob_row0_fill(const AffineCall &c, const std::vector<AffineExtItem> &pairs, const int64_t *tx, const int64_t *ty,
+                          std::vector<TraceOut> &tout) {
+  mi355_sw_ctx *ctx = c.ctx;
+  std::vector<size_t> row0;
+  size_t bytes = 0;
+  for (size_t k = 0; k < pairs.size(); ++k)
+    if (tx[k] < 1 && ty[k] >= 1) { row0.push_back(k); bytes += 2 * (size_t)ty[k]; }
+  if (row0.empty()) return 0;
+  std::vector<char> cons(bytes, '-');
+  size_t at = 0;
+  hipError_t copied = hipSuccess;
+  for (size_t k : row0) {
+    copied = hipMemcpyAsync(cons.data() + at + (size_t)ty[k], pairs[k].ybytes, (size_t)ty[k], hipMemcpyDeviceToHost, ctx->stream);
+    if (copied != hipSuccess) break;
+    at += 2 * (size_t)ty[k];
+  }
+  const hipError_t waited = hipStreamSynchronize(ctx->stream);      // (before `cons` can go: copies may be in flight)
+  HIPCHK(ctx, copied);
+  HIPCHK(ctx, waited);
+  ctx->arenas.push_back(std::move(cons));
+  char *base = ctx->arenas.back().data();
+  at = 0;
+  for (size_t k : row0) {
+    const size_t len = (size_t)ty[k];
+    std::reverse(base + at + len, base + at + 2 * len);             // from the far end to the anchor
+    TraceOut &o = tout[k];
+    o.len = len; o.cx = base + at; o.cy = base + at + len; o.pos = 1;
+    at += 2 * len;
+  }
+  return 0;
+}
+
+// The pairs of `el` under the anchored model, anchored at BOTH ends: score[npairs] = H(m, n), -INFINITY where the pair's band misses
+// the corner; tout (may be null): the traceback of every pair from (m, n).  Items, class table, reversed copies, the stage order (the
+// pair kernel, the band kernel, the exact kernel's unbanded and then its banded jobs, the two passes of the traceback) and the bounds
+// of the exact kernel are affine_extend's.  A pair runs on sw_affine_pair_glob_kernel while rows, columns, table and admission
+// (affine_glob_exact) allow, under a band that does not cover its matrix on sw_affine_band_glob_kernel (affine_band_glob_exact, option
+// no_affine_band off), else as a whole problem of the exact kernel; a banded pair never runs on an unbanded kernel.  A pair without
+// rows or without columns, and a pair whose band misses the corner, is filled in here: no kernel runs for it.
+int affine_global(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const AffineExtList &el, const mi355_sw_affine_params &p,
+                  float *score, std::vector<TraceOut> *tout) {
+  const size_t npairs = el.npairs;
+  for (size_t k = 0; k < npairs; ++k) score[k] = 0.0f;
+  if (tout) tout->assign(npairs, TraceOut());
+  if (npairs > 0xFFFFFFFFull) return fail(ctx, MI355_SW_ENOTSUP, "affine global: more than 2^32 pairs");
+  AffineCall c{ctx, ref, q, p, AffineTable(), kAffineModeExt};
+  int rc = affine_begin(c);
+  if (rc) return rc > 0 ? 0 : rc;
+  AffineProfPlan plan;
+  const bool table_ok = affine_ext_plan(c, plan);
+  rc = affine_ext_any_reversed(c, el); if (rc) return rc;
+
+  std::vector<AffineExtItem> pairs(npairs), fast, jobs, bfast, bjobs;
+  std::vector<int64_t> ends(2 * npairs, 0), tx(npairs, 0), ty(npairs, 0);   // (tx, ty): the cell a pair is traced from; 0 / 0: nothing
+  int mmax = 0, band_mmax = 0;
+  const float go = (float)c.t.open, ge = (float)c.t.ext;
+  for (size_t k = 0; k < npairs; ++k) {
+    AffineExtItem &it = pairs[k];
+    it = affine_ext_item(c, el, k);
+    const int64_t m = it.m, n = it.n;
+    if (el.band_lo && (el.band_lo[k] > n - m || el.band_hi[k] < n - m)) { score[k] = -INFINITY; continue; }   // the band misses the corner
+    tx[k] = m; ty[k] = n;
+    if (m < 1 || n < 1) {                                          // one gap, or nothing: H(m,0) / H(0,n) of the border
+      const int64_t g = m + n;
+      score[k] = g < 1 ? 0.0f : -(go + (float)(g - 1) * ge);
+      continue;
+    }
+    const int64_t lo_e = el.band_lo ? std::max(el.band_lo[k], -m) : -m, hi_e = el.band_lo ? std::min(el.band_hi[k], n) : n;
+    if (lo_e != -m || hi_e != n) {                                 // a banded pair; its window needs no clip: n <= m + hi_e
+      const int64_t W = hi_e - lo_e + 1;
+      it.banded = true; it.blo = (int32_t)lo_e; it.bhi = (int32_t)hi_e; it.W = (int32_t)std::min<int64_t>(W, 0x7fffffff);
+      if (table_ok && !opt().no_affine_band && m <= kBandRowsMax && affine_band_R(W) != 0 && affine_band_glob_exact(c.t, (double)m, (double)W)) {
+        bfast.push_back(it); band_mmax = std::max(band_mmax, (int)m);
+        continue;
+      }
+      if ((double)m * (double)n > kAffineExactCellsMax || !affine_band_ext_whole_exact(c.t, (double)m, (double)W) || affine_exact_lds((int)m) > kExactLdsMax) {
+        char msg[800];
+        std::snprintf(msg, sizeof msg, "affine global: banded pair %zu (%lld rows x %lld columns, %lld diagonals) is outside the band kernel (1..512 rows, "
+                      "at most 256 diagonals, a rows + 3 gap_open + (diagonals + 1) gap_extend - min(smin, 0) < 2^24 with a = max(-smin, 0), "
+                      "smax * rows + gap_open < 2^24, a score table within 32 KiB%s) and outside the exact kernel under a band (at most 2^26 cells "
+                      "and 5600 rows, a rows + 2 gap_open + diagonals gap_extend - min(smin, 0) < 2^24, smax * (rows + 1) < 2^24)", k,
+                      (long long)m, (long long)n, (long long)W,
+                      opt().no_affine_band ? "; option no_affine_band is set" : opt().no_affine_pairs ? "; option no_affine_pairs is set" : "");
+        return fail(ctx, MI355_SW_ENOTSUP, msg);
+      }
+      bjobs.push_back(it);
+      continue;
+    }
+    if (table_ok && m <= kMaxRowsFast && n <= kAffinePairColsMax && affine_glob_exact(c.t, (double)m, (double)n)) {
+      fast.push_back(it); mmax = std::max(mmax, (int)m);
+      continue;
+    }
+    if ((double)m * (double)n > kAffineExactCellsMax || !affine_ext_whole_exact(c.t, (double)m, (double)n) || affine_exact_lds((int)m) > kExactLdsMax) {
+      char msg[400];
+      std::snprintf(msg, sizeof msg, "affine global: pair %zu (%lld rows x %lld columns) is outside the pair kernel (1..512 rows, 1..2^20 columns, "
+                    "3 gap_open + (rows + columns) gap_extend - min(smin, 0) < 2^24, smax * rows + gap_open < 2^24, a score table within 32 KiB%s) and "
+                    "outside the exact kernel (at most 2^26 cells and 5600 rows, 3 gap_open + (rows + columns) gap_extend < 2^24)", k,
+                    (long long)m, (long long)n, opt().no_affine_pairs ? "; option no_affine_pairs is set" : "");
+      return fail(ctx, MI355_SW_ENOTSUP, msg);
+    }
+    jobs.push_back(it);
+  }
+  rc = affine_list_stage(AffineGlobFamily{c}, plan, fast, mmax, score, ends.data());
+  if (!rc) rc = affine_list_stage(AffineBandGlobFamily{c}, plan, bfast, band_mmax, score, ends.data());
+  if (!rc) rc = affine_ext_exact_stage<false, true>(c, jobs, score, ends.data());
+  if (!rc) rc = affine_ext_exact_stage<true, true>(c, bjobs, score, ends.data());
+  if (rc) return rc;
+  if (tout) {
+    rc = affine_ext_trace(c, pairs, score, tx.data(), ty.data(), *tout);
+    if (!rc && (!bfast.empty() || !bjobs.empty())) rc = affine_ext_trace<true>(c, pairs, score, tx.data(), ty.data(), *tout);
+    if (!rc) rc = affine_glob_row0_fill(c, pairs, tx.data(), ty.data(), *tout);
     if (rc) return rc;
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));

@@ -615,6 +615,59 @@ int mi355_sw_affine_extend_trace_band(mi355_sw_ctx *ctx, const mi355_sw_extend_l
   return affine_extend_any(ctx, list, params, true, to_end, nullptr, nullptr, nullptr, outs, to_end_score, to_end_y, band_lo, band_hi);
 }
 
+// mi355_sw_affine_global_run (score) and, with `trace`, mi355_sw_affine_global_trace (outs), written only after success; the checks and
+// their order are affine_extend_any's, the band checks last
+static int affine_global_any(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo, const int64_t *band_hi,
+                             const mi355_sw_affine_params *params, bool trace, float *score, mi355_sw_result *outs) {
+  OptScope opt_scope_(ctx);
+  int rc = affine_check(ctx, params);
+  if (rc) return rc;
+  if (!list) return fail(ctx, MI355_SW_EINVAL, "affine global: list is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  reset_timings(ctx);
+  const size_t npairs = list->npairs;
+  if (npairs == 0) return 0;
+  if (trace && !outs) return fail(ctx, MI355_SW_EINVAL, "outs is NULL");
+  if ((!trace && !score) || !list->query || !list->lefts || !list->rights) return fail(ctx, MI355_SW_EINVAL, "null argument");
+  if ((list->q_lo == nullptr) != (list->q_hi == nullptr)) return fail(ctx, MI355_SW_EINVAL, "affine global: q_lo and q_hi must both be given, or neither");
+  for (size_t k = 0; k < npairs; ++k) {
+    if (list->query[k] < 0 || (size_t)list->query[k] >= ctx->batch.nq) return fail(ctx, MI355_SW_EINVAL, "pair: query index outside the resident batch");
+    if (list->lefts[k] < 0 || list->rights[k] < list->lefts[k] || list->rights[k] > (int64_t)ctx->ref.n)
+      return fail(ctx, MI355_SW_EINVAL, "pair: window outside the resident reference");
+    if (list->q_lo && (list->q_lo[k] < 0 || list->q_hi[k] < list->q_lo[k] || list->q_hi[k] > ctx->batch.len[list->query[k]]))
+      return fail(ctx, MI355_SW_EINVAL, "pair: letters [q_lo, q_hi) outside the query");
+  }
+  if ((band_lo == nullptr) != (band_hi == nullptr)) return fail(ctx, MI355_SW_EINVAL, "affine global: band_lo and band_hi must both be given, or neither");
+  if (band_lo)
+    for (size_t k = 0; k < npairs; ++k)
+      if (band_lo[k] > 0 || band_hi[k] < 0) return fail(ctx, MI355_SW_EINVAL, "affine global: the band must hold the anchor's diagonal, band_lo <= 0 <= band_hi");
+  std::vector<float> sc(npairs, 0.0f);
+  std::vector<TraceOut> tout(trace ? npairs : 0);
+  const AffineExtList el{npairs, list->query, list->q_lo, list->q_hi, list->lefts, list->rights, list->backward, band_lo, band_hi};
+  rc = affine_global(ctx, ctx->ref, ctx->batch, el, *params, sc.data(), trace ? &tout : nullptr);
+  if (rc) return rc;
+  for (size_t k = 0; k < npairs; ++k) {
+    if (!trace) { score[k] = sc[k]; continue; }
+    const bool reach = sc[k] != -INFINITY;                           // a band that misses the corner: an empty alignment
+    const int64_t m = (list->q_lo ? list->q_hi[k] - list->q_lo[k] : ctx->batch.len[list->query[k]]), n = list->rights[k] - list->lefts[k];
+    memset(&outs[k], 0, sizeof outs[k]);
+    set_result(outs[k], sc[k], 0, 0, &tout[k]);
+    outs[k].end_x = reach ? m : 0; outs[k].end_y = reach ? n : 0;   // lengths, whatever the sign of the score
+    outs[k].timings_us[0] = outs[k].timings_us[1] = (float)ctx->timings[0];
+  }
+  return 0;
+}
+
+int mi355_sw_affine_global_run(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo, const int64_t *band_hi,
+                               const mi355_sw_affine_params *params, float *score) {
+  return affine_global_any(ctx, list, band_lo, band_hi, params, false, score, nullptr);
+}
+
+int mi355_sw_affine_global_trace(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo, const int64_t *band_hi,
+                                 const mi355_sw_affine_params *params, mi355_sw_result *outs) {
+  return affine_global_any(ctx, list, band_lo, band_hi, params, true, nullptr, outs);
+}
+
 int mi355_sw_best_range(mi355_sw_ctx *ctx, size_t nranges, const int64_t *lefts, const int64_t *rights,
                         const mi355_sw_params *params, float known_best, float *maxima, float *best, int64_t *best_range,
                         float *exact_above) {

@@ -333,4 +333,119 @@ __global__ __launch_bounds__(256) void sw_affine_band_ext_kernel(const AffineBan
   }
 }
 
+// sw_affine_band_glob_kernel — the sibling ANCHORED AT BOTH ENDS (include/mi355_sw.h "global alignment between two anchors", DESIGN.md
+// §3.8 lemma L23): the banded anchored model of the kernel above, whose answer is the one cell H(m, n).  A sibling and not a flag;
+// geometry, the two row_shl:1 moves for F, the max-plus scan for E, the windows in LDS, -inf outside the band, the cap, the initial
+// row-0 registers are copies of the kernel above, which a change of the scaffold must visit as well.  What differs: less.
+//   * nothing competes: no max(H, 0), no key, no per-step fold and no (bval, bcol, brow) state;
+//   * the answer is READ, not folded: in row m the cell of column n lies on diagonal n - m, register D = n - m - lo.  At the step
+//     it + 1 == m — the branch of the kernel above, which a wavefront skips unless one of its slots stands on its row m — the lane
+//     that holds D takes Ho + o of that one register.  The host sends only pairs with lo <= n - m <= lo + W - 1 (the corner lies in
+//     the band), so D is one of the 16 R registers and holds a finite value.  The four slots of a wavefront have different m and run
+//     to the longest: a slot reads at its own step, once; steps behind row m write nothing.
+// Padding and exactness: as the kernel above, without its key — every value of a real cell is an integer below 2^24 in magnitude
+// (host_affine.h: affine_band_glob_exact), no mantissa bit is reserved.
+// best[pid] = H(m, n), of any sign; cell[2 pid ..] = m, n.
+template <int R>
+__global__ __launch_bounds__(256) void sw_affine_band_glob_kernel(const AffineBandProblem *probs, int nprob, const AffinePairArgs sa) {
+  static_assert(R >= 1 && R <= 32, "instances of kBandR");
+  constexpr int YW = kBandRowsMax + 16 * R;
+  extern __shared__ __attribute__((aligned(16))) uint32_t bandsmem[];
+  __shared__ uint8_t ywin[16 * YW];
+  __shared__ uint16_t xwin[16 * kBandRowsMax];
+  float *tab = reinterpret_cast<float *>(bandsmem);
+  const int tid = threadIdx.x;
+  const int l = tid & 15;
+  const int slot = tid >> 4;
+  const int pid = blockIdx.x * 16 + slot;
+  const bool active = pid < nprob;
+  const uint8_t *xb = nullptr, *yc = nullptr;
+  int m = 0, n = 0, lo = 0, W = 0;
+  if (active) { xb = probs[pid].x; yc = probs[pid].y; m = probs[pid].m; n = probs[pid].n; lo = probs[pid].lo; W = probs[pid].W; }
+  m = min(m, kBandRowsMax);
+  for (int e = tid; e < sa.nrows * sa.ncls; e += 256) tab[e] = sa.tab[e];
+  int steps = m;
+  steps = max(steps, __shfl_xor(steps, 16));
+  steps = max(steps, __shfl_xor(steps, 32));
+  const uint32_t row_bytes = 4u * (uint32_t)sa.ncls;
+  const uint32_t outside = (uint32_t)(sa.nrows - 1);
+  uint8_t *yw = ywin + slot * YW;
+  uint16_t *xw = xwin + slot * kBandRowsMax;
+  for (int p = l; p < steps + 16 * R; p += 16) {                   // entry p: column lo + 1 + p; column 0 is `outside` too
+    const long long j = (long long)lo + 1 + p;
+    const uint32_t c = (j >= 1 && j <= (long long)n) ? (uint32_t)yc[j - 1] : outside;
+    yw[p] = (uint8_t)c;
+  }
+  for (int i = l; i < steps; i += 16) xw[i] = (uint16_t)(4u * (i < m ? (uint32_t)sa.cls[xb[i]] : (uint32_t)(sa.ncls - 1)));
+  __syncthreads();
+
+  const float ov = sa.open_s, ev = sa.ext_s;
+  const float ninf = -__builtin_inff(), pinf = __builtin_inff();   // outside the band, and the cap of a register inside it
+  const float dec1 = (float)R * sa.ext_s, dec2 = 2.0f * dec1, dec4 = 4.0f * dec1, dec8 = 8.0f * dec1;
+  float Ho[R], F[R], cap[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int D = l * R + r, delta = lo + D;                       // row 0: cell (0, delta), in the band for D < W (delta <= hi_e <= n)
+    const float h0 = delta == 0 ? 0.0f : -(sa.open_s + (float)(delta - 1) * sa.ext_s);
+    Ho[r] = (D < W && delta >= 0) ? h0 - sa.open_s : ninf;
+    F[r] = ninf;
+    cap[r] = D < W ? pinf : ninf;
+    asm volatile("" : "+v"(cap[r]));                               // (a register, so that the cap stays one v_min_f32 and not a min and a select)
+  }
+  float corner = ninf;                                             // H(m, n), in the lane that holds diagonal n - m
+  const int dsel = n - m - lo - l * R;                             // that diagonal's register within this lane (0..R-1: this lane holds it)
+  const char *tab_b = reinterpret_cast<const char *>(tab);
+  const uint8_t *yl = yw + l * R;
+
+  for (int it = 0; it < steps; ++it) {
+    const uint32_t xo = xw[it];
+    const uint8_t *yp = yl + it;
+    const float hnext = band_dpp<0x101>(ninf, Ho[0]);
+    const float fnext = band_dpp<0x101>(ninf, F[0]);
+    float Ht[R], q[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float hon = r + 1 < R ? Ho[r + 1] : hnext;             // H(i-1, j) - o
+      const float fpn = r + 1 < R ? F[r + 1] : fnext;              // F(i-1, j)
+      const float s = *reinterpret_cast<const float *>(tab_b + (__umul24((uint32_t)yp[r], row_bytes) + xo));
+      const float x = Ho[r] + s;                                   // no clamp: no floor
+      const float f = fmaxf(fpn - ev, hon);
+      const float ht = fmaxf(x, f);
+      const float a = ht - ov;
+      F[r] = f;
+      Ht[r] = ht;
+      q[r] = r == 0 ? a : fmaxf(q[r - 1] - ev, a);
+    }
+    float G = q[R - 1];
+    G = fmaxf(G, band_dpp<0x111>(ninf, G) - dec1);
+    G = fmaxf(G, band_dpp<0x112>(ninf, G) - dec2);
+    G = fmaxf(G, band_dpp<0x114>(ninf, G) - dec4);
+    G = fmaxf(G, band_dpp<0x118>(ninf, G) - dec8);
+    float ce = band_dpp<0x111>(ninf, G);                           // E of register 0: everything left of the lane
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float h = r == 0 ? fmaxf(Ht[0], ce) : fmaxf(fmaxf(Ht[r], q[r - 1]), ce);
+      h = fminf(h, cap[r]);
+      Ho[r] = h - ov;
+      if (r + 1 < R) ce = ce - ev;
+    }
+    // the corner: only at the step where the slot stands on its row m (an idle slot: m = 0, which no step matches); the wavefront
+    // skips the block unless one of its four slots does
+    if (it + 1 == m) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) corner = dsel == r ? Ho[r] + ov : corner;   // H(m, n): exact, both are integers below 2^24 units
+    }
+  }
+
+  // the slot's result: the value of the lane that holds diagonal n - m
+  const int wd = n - m - lo;
+  const int wl = (active && wd >= 0 && wd < 16 * R) ? wd / R : 0;
+  const float bv = __shfl(corner, wl, 16) * sa.unscale;
+  if (l == 0 && active) {
+    sa.best[pid] = bv;
+    sa.cell[2 * (size_t)pid] = m;
+    sa.cell[2 * (size_t)pid + 1] = n;
+  }
+}
+
 }  // namespace mi355sw

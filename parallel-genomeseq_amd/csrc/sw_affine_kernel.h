@@ -257,13 +257,18 @@ enum : int { kAffStop = 0, kAffDiag = 1, kAffE = 2, kAffF = 3, kAffEExt = 4, kAf
 // where it lies in the band, else it is -inf as well.  The loop is the banded one, so both folds see in-band cells only, all finite;
 // a row m without an in-band cell leaves end = -inf (the host reports the pair as unreachable).  TRACE: an equality with -inf never
 // holds, so the walk stays in the band; it meets row 0 or column 0 on an in-band cell, and the rest of that border towards (0,0) is.
+// GLOB (kAffineModelGlob): the anchored model again — EXT's borders, EXT's cells, with or without BAND — whose answer is the corner:
+// nothing competes, `best` is the value of cell (m, nw) (the lane that computes it; -inf in the others, and where the band misses the
+// corner, which the host never sends).  It has no TRACE instance of its own: the traceback of a corner is EXT's walk from (m, nw).
 struct AffineBest { float best; int64_t i, j; float end; int64_t end_j; };
-enum : int { kAffineModelLocal = 0, kAffineModelE2E = 1, kAffineModelExt = 2 };
+enum : int { kAffineModelLocal = 0, kAffineModelE2E = 1, kAffineModelExt = 2, kAffineModelGlob = 3 };
 template <bool TRACE, int MODEL, bool BAND>
 __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem P, const AffineScoring sc, uint8_t *smem_raw, const int blo,
                                                               const int bhi) {
-  constexpr bool EXT = MODEL == kAffineModelExt;
-  constexpr bool E2E = MODEL != kAffineModelLocal;                 // no floor and the column-0 border: both floor-free models
+  constexpr bool GLOB = MODEL == kAffineModelGlob;                 // EXT's matrix, the corner for an answer
+  static_assert(!(GLOB && TRACE), "the corner is traced by the anchored model's walk");
+  constexpr bool EXT = MODEL == kAffineModelExt || GLOB;
+  constexpr bool E2E = MODEL != kAffineModelLocal;                 // no floor and the column-0 border: every floor-free model
   static_assert(!(BAND && MODEL == kAffineModelE2E), "the banded end-to-end model is not defined");
   constexpr bool XB = EXT && BAND;                                 // the anchored model under a band: outside is -inf, borders only in the band
   const int lane = threadIdx.x;
@@ -284,7 +289,7 @@ __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem
     if (bhi < 1) { H0[0] = ninf; E0[0] = ninf; }
   }
 
-  float best = (E2E && (TRACE || !EXT)) ? ninf : -1.0f;            // (EXT, score pass: only a positive cell beats cell (0,0))
+  float best = (E2E && (TRACE || !EXT || GLOB)) ? ninf : -1.0f;    // (EXT, score pass: only a positive cell beats cell (0,0))
   float end = ninf;                                                // EXT: the greatest H(m, jl) and its first column
   int64_t end_j = 0;
   unsigned long long bkey = ~0ull;
@@ -333,6 +338,8 @@ __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem
       if (TRACE) {
         const int src = (!E2E && h == 0.0f) ? kAffStop : h == x ? kAffDiag : h == e ? kAffE : kAffF;
         P.dirs[(size_t)d * (size_t)dstride + (size_t)(i - ilo)] = (uint8_t)(src | (e != eo ? kAffEExt : 0) | (f != fo ? kAffFExt : 0));
+        if (d == m + nw) best = h;                                 // (one cell, one lane)
+      } else if (GLOB) {
         if (d == m + nw) best = h;                                 // (one cell, one lane)
       } else if (EXT) {
         if (i == m && h > end) { end = h; end_j = jl; }            // (a lane meets its columns in rising order)
@@ -436,6 +443,16 @@ __global__ __launch_bounds__(64) void sw_affine_exact_ext_band_kernel(const Exac
     P.cell[0] = pos ? r.i : 0; P.cell[1] = pos ? r.j : 0;
     P.cell[2] = P.m; P.cell[3] = at0 ? 0 : (end == -__builtin_inff() ? -1 : r.end_j);
   }
+}
+
+// The anchored model's corner (GLOB of affine_exact_fill_model) on whole problems of at least one row and one column, with or without a
+// band that holds the corner: P.best[0] = H(m, nw), P.cell[0..1] = m, nw.  own_lo, col_offset and target are unused.
+template <bool BAND>
+__global__ __launch_bounds__(64) void sw_affine_exact_glob_kernel(const typename AffineExactProblemOf<BAND>::type *probs, const AffineScoring sc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  const ExactProblem P = affine_problem(probs[blockIdx.x]);
+  const AffineBest r = affine_exact_fill_model<false, kAffineModelGlob, BAND>(P, sc, smem_raw, affine_band_lo(probs[blockIdx.x]), affine_band_hi(probs[blockIdx.x]));
+  if (threadIdx.x == 0) { P.best[0] = r.best; P.cell[0] = P.m; P.cell[1] = P.nw; }
 }
 
 // Traceback under affine gaps: the window [end_y - nw, end_y] x [end_x - m, end_x] of one alignment (lemmas L17 and L18, DESIGN.md

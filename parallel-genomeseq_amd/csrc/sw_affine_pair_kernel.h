@@ -515,6 +515,150 @@ __global__ __launch_bounds__(256) void sw_affine_pair_ext_kernel(const AffinePai
   }
 }
 
+// sw_affine_pair_glob_kernel — the sibling ANCHORED AT BOTH ENDS (include/mi355_sw.h "global alignment between two anchors", DESIGN.md
+// §3.8 lemma L23): the anchored model of the kernel above, whose answer is the one cell H(m, n).  A sibling and not a flag, as its
+// neighbours; geometry, stream window, table, cell chain, the column-0 border (the 16-step prologue), the row-0 border (`rowo`, frozen
+// at column n's value: `rowmin`) and the row-m select are copies of the kernel above, and a change of the scaffold must visit all
+// four.  What differs from the extension kernel: less.
+//   * nothing competes: no max(H, 0), no key, no WaveKeyFold, no (blk, tl), no (best, te) and no compare of values;
+//   * the answer is CAPTURED, not folded: the lane that holds row m keeps the row-m select of the kernel above (one select per cell,
+//     masks fixed before the loop), and the step's value replaces the lane's result at the one step with t == n - 1, the lane's
+//     column n — one integer compare and one select per step.  The four slots of a wavefront have different n and run to the longest:
+//     the compare is with the slot's own n, so a slot takes its value once, at its own step, and no padding step behind column n can
+//     overwrite it (t only rises; it equals n - 1 once).  "The last value seen" would be wrong for every slot but the longest.
+// Padding: a padding row (> m) or column (> n) never feeds a real cell (F and the diagonal run downwards, E to the right), and the
+// capture reads a real cell by construction; every register stays finite as in the kernel above (kPadScoreF enters one sum per cell,
+// whose other operand is an Ho; row 0 is frozen at column n's value).
+// Exactness: every value of a real cell is an integer below 2^24 in magnitude (host_affine.h: affine_glob_exact).  No key is formed, so
+// no mantissa bit is reserved: the extension kernel's smax (rows + 1) < 2^18 has no counterpart here.  The scale 2^-k moves no bit.
+// best[pid] = H(m, n), of any sign; cell[2 pid ..] = m, n.
+template <int R>
+__global__ __launch_bounds__(256) void sw_affine_pair_glob_kernel(const AffinePairProblem *probs, int nprob, const AffinePairArgs sa) {
+  static_assert(R >= 1 && R <= 32, "instances of kPairR");
+  extern __shared__ __attribute__((aligned(16))) uint32_t pairsmem[];
+  __shared__ __attribute__((aligned(16))) uint8_t win[16 * kWaveBuf];
+  float *tab = reinterpret_cast<float *>(pairsmem);                // [nrows][ncls]
+  const int tid = threadIdx.x;
+  const int l = tid & 15;
+  const int slot = tid >> 4;
+  const int pid = blockIdx.x * 16 + slot;
+  const bool active = pid < nprob;
+  const uint8_t *xb = nullptr, *yc = nullptr;
+  int m = 0, n = 0;
+  if (active) { xb = probs[pid].x; yc = probs[pid].y; m = probs[pid].m; n = probs[pid].n; }
+  for (int e = tid; e < sa.nrows * sa.ncls; e += 256) tab[e] = sa.tab[e];
+  uint32_t boff[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = l * R + r;
+    boff[r] = 4u * (i < m ? (uint32_t)sa.cls[xb[i]] : (uint32_t)(sa.ncls - 1));
+  }
+  __syncthreads();
+
+  const uint32_t outside = (uint32_t)(sa.nrows - 1);
+  auto stage_load = [&](int seg) -> uint32_t {
+    return wave_stage_word(yc, n, seg * kWaveSeg + 4 * l, [&](bool in, uint32_t byte) { return in ? byte : outside; });
+  };
+  int nseg, steps4;
+  wave_steps(n, 16, nseg, steps4);
+  uint8_t *buf = win + slot * kWaveBuf;
+  uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
+  const uint8_t *buf_lane = buf + 16 - l;
+  uint32_t nextc = stage_load(0);
+  if (l < 4) buf32[l] = outside * 0x01010101u;
+  buf32[4 + l] = nextc;
+  nextc = stage_load(1);
+
+  float ov = sa.open_s, ev = sa.ext_s;
+  asm volatile("" : "+v"(ov), "+v"(ev));
+  // row 0 as the slot's first lane sees it: Ho(0, j) = F(1, j) = -(2 o + (j - 1) e), column j = step + 1; never below column n's
+  float rowo = -2.0f * sa.open_s;
+  const float rowmin = -(2.0f * sa.open_s + (float)max(n - 1, 0) * sa.ext_s);
+  // Ho = E = H(i,0) - o = -(2 o + (i - 1) e) of the lane's first row, i - 1 = l R (integers below 2^24 units: exact)
+  const float bord0 = -(2.0f * sa.open_s + (float)(l * R) * sa.ext_s);
+  float E[R], Ho[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) { E[r] = bord0 - (float)r * sa.ext_s; Ho[r] = E[r]; }   // lane 0 stands on column 0 here
+  float up_prev = -ov;                                             // Ho(0, 0) of lane 0: H(0,0) = 0
+  float fout = -ov;
+  const float ninf = -__builtin_inff();
+  float corner = ninf;                                             // H(m, n), in the lane that holds row m
+  const int tcap = n - 1;                                          // the lane's column n (0-based): the one step that is captured
+  const uint32_t row_bytes = 4u * (uint32_t)sa.ncls;
+  const char *tab_b = reinterpret_cast<const char *>(tab);
+  const int wrow = (m > 0 && (m - 1) / R == l) ? (m - 1) % R : -1;
+  bool wsel[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) wsel[r] = wrow == r;
+
+  auto step = [&](auto border, const int gstep, const int k) {
+    constexpr bool BORDER = decltype(border)::value;
+    const int t = gstep - l;
+    const uint32_t c = (uint32_t)buf_lane[k];
+    const char *rowp = tab_b + c * row_bytes;
+    const int rowo_i = (int)__float_as_uint(rowo);
+    const float up = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(rowo_i, (int)__float_as_uint(Ho[R - 1]), 0x111, 0xf, 0xf, false));
+    float frun = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(rowo_i, (int)__float_as_uint(fout), 0x111, 0xf, 0xf, false));
+    rowo = fmaxf(rowo - ev, rowmin);
+    float diag = up_prev;                                          // H(i-1, j-1) - o
+    up_prev = up;
+    float hm = ninf;                                               // H(m, t + 1) in the lane that holds row m
+    const bool on_border = BORDER && t == -1;
+    float bord = bord0;
+    float sv[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) sv[r] = *reinterpret_cast<const float *>(rowp + boff[r]);
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float w = Ho[r];                                       // H(i, j-1) - o
+      const float s = sv[r];
+      float x, g, h, ho, fs;
+      asm("v_add_f32 %0, %1, %2" : "=v"(x) : "v"(diag), "v"(s));   // no clamp: no floor
+      asm("v_sub_f32 %0, %1, %2" : "=v"(g) : "v"(E[r]), "v"(ev));
+      asm("v_max_f32 %0, %1, %2" : "=v"(g) : "v"(g), "v"(w));
+      asm("v_max3_f32 %0, %1, %2, %3" : "=v"(h) : "v"(x), "v"(g), "v"(frun));
+      hm = wsel[r] ? h : hm;
+      asm("v_sub_f32 %0, %1, %2" : "=v"(ho) : "v"(h), "v"(ov));
+      asm("v_sub_f32 %0, %1, %2" : "=v"(fs) : "v"(frun), "v"(ev));
+      asm("v_max_f32 %0, %1, %2" : "=v"(frun) : "v"(fs), "v"(ho));
+      if constexpr (BORDER) { g = on_border ? bord : g; ho = on_border ? bord : ho; bord -= ev; }
+      E[r] = g;
+      Ho[r] = ho;
+      diag = w;
+    }
+    fout = frun;
+    corner = t == tcap ? hm : corner;                              // the capture: the slot's own column n, once
+  };
+
+  for (int seg = 0; seg < nseg; ++seg) {
+    const int kq = min(kWaveSeg, steps4 - seg * kWaveSeg) >> 2;
+    int k4 = 0;
+    if (seg == 0) {                                                // the 16 steps that hold every lane's border step (steps4 >= 16)
+#pragma unroll 1
+      for (int k = 0; k < 16; ++k) step(std::true_type(), k, k);
+      k4 = 4;
+    }
+    for (; k4 < kq; ++k4) {
+#pragma unroll
+      for (int ku = 0; ku < 4; ++ku) step(std::false_type(), seg * kWaveSeg + 4 * k4 + ku, 4 * k4 + ku);
+    }
+    const uint32_t hist = buf32[kWaveSeg / 4 + (l & 3)];
+    if (l < 4) buf32[l] = hist;
+    buf32[4 + l] = nextc;
+    nextc = stage_load(seg + 2);
+  }
+
+  // the slot's result: the value the lane that holds row m captured
+  const int wl = m > 0 ? (m - 1) / R : 0;
+  const float bv = __shfl(corner, wl, 16) * sa.unscale;
+  if (l == 0 && active) {
+    sa.best[pid] = bv;
+    sa.cell[2 * (size_t)pid] = m;
+    sa.cell[2 * (size_t)pid + 1] = n;
+  }
+}
+
 // dst[k] = src[n - 1 - k]: the reversed copies behind the backward pairs of the extension calls (no kernel above knows a direction)
 __global__ __launch_bounds__(256) void reverse_bytes_kernel(const uint8_t *src, uint8_t *dst, size_t n) {
   const size_t stride = (size_t)gridDim.x * 256;

@@ -29,6 +29,14 @@
     is the exact kernel under the band (option no_affine_band), once per width; kernel time, ratio and the ratio the row loop's op
     count predicts come side by side.  Default --out: profiles/affine_extend_band_n1.json.
 
+  * --global [--band W_HALF[,W_HALF..]]: the reads of --extend, each against the window [at, at + 150) behind its true start, anchored at
+    both ends: Context.affine_global_run on sw_affine_pair_glob_kernel (with --band: under [-w, w] on sw_affine_band_glob_kernel)
+    alternating with Context.affine_extend_run (with --band: the banded extension call) on the same pairs in one process, medians
+    and the spread of the steps.  The yardstick is the extension instance of the same run: the global loop is a strict subset of its
+    loop, so a kernel ratio above 1.0 is a finding.  The global result is checked once against the exact kernel (options
+    no_affine_pairs / no_affine_band); the op-count prediction from mi355_sw_last_kernel of both sides comes beside the measured
+    ratio.  Default --out: profiles/affine_global_n1.json / affine_global_band_n1.json.
+
 Prints ONE JSON line and writes it to --out; kernel times are those of mi355_sw_last_timings (device events), call times are wall
 clock around the call.
 
@@ -37,6 +45,8 @@ clock around the call.
     python tools/affine_pairs_bench.py --band 8,16,32,64
     python tools/affine_pairs_bench.py --extend
     python tools/affine_pairs_bench.py --extend --band 8,16,32,64
+    python tools/affine_pairs_bench.py --global
+    python tools/affine_pairs_bench.py --global --band 8,16,32,64
 """
 import argparse
 import json
@@ -63,14 +73,17 @@ def main(argv=None):
     ap.add_argument("--mode", choices=("local", "end_to_end"), default="local")
     ap.add_argument("--band", default=None, help="half widths of the band around the read's diagonal, comma separated")
     ap.add_argument("--extend", action="store_true", help="the anchored extension call against the local instance")
+    ap.add_argument("--global", dest="glob", action="store_true", help="the call anchored at both ends against the extension call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.glob and (args.extend or args.mode != "local"):
+        ap.error("--global stands alone (with --band or without)")
     if args.extend and args.mode != "local":
         ap.error("--extend needs the local mode")
     if args.band is not None and args.mode != "local":
         ap.error("--band needs the local mode")
     if args.out is None:
-        name = "affine_extend_band_n1.json" if args.extend and args.band is not None else "affine_pairs_extend_n1.json" if args.extend else "affine_pairs_band_n1.json" if args.band is not None else "affine_pairs_e2e_n1.json" if args.mode == "end_to_end" else "affine_pairs_n1.json"
+        name = "affine_global_band_n1.json" if args.glob and args.band is not None else "affine_global_n1.json" if args.glob else "affine_extend_band_n1.json" if args.extend and args.band is not None else "affine_pairs_extend_n1.json" if args.extend else "affine_pairs_band_n1.json" if args.band is not None else "affine_pairs_e2e_n1.json" if args.mode == "end_to_end" else "affine_pairs_n1.json"
         args.out = os.path.join(ROOT, "profiles", name)
     import __graft_entry__ as entry
     pgs = entry._load_package()
@@ -80,13 +93,15 @@ def main(argv=None):
     for k in range(args.pairs):
         read, at = pgs.synth.read_from_ref(ref, 1000 + k, READ_LEN, sub_rate=0.03, indel_rate=0.02)[:2]
         reads.append(read.tobytes())
-        lefts[k] = int(at) if args.extend else max(0, int(at) - FLANK)
-        rights[k] = min(args.ref_len, int(at) + READ_LEN + FLANK)
+        lefts[k] = int(at) if args.extend or args.glob else max(0, int(at) - FLANK)
+        rights[k] = min(args.ref_len, int(at) + READ_LEN + (0 if args.glob else FLANK))
         diag[k] = int(at) - lefts[k]
     query = np.arange(args.pairs, dtype=np.int32)
     ctx = pgs.Context(0)
     ctx.set_reference(ref.tobytes())
     ctx.batch_upload(reads)
+    if args.glob:
+        return global_against_extend(args, ctx, reads, query, lefts, rights)
     if args.extend and args.band is not None:
         return banded_extend_against_extend(args, ctx, reads, query, lefts, rights)
     if args.extend:
@@ -219,6 +234,71 @@ def extend_against_local(args, ctx, reads, query, lefts, rights):
         f.write(text + "\n")
     print(text)
     return 0 if equal and line["not_above_local"] and line["to_end_not_above_best"] else 1
+
+
+def global_against_extend(args, ctx, reads, query, lefts, rights):
+    """The extension instance and the global instance on the same pairs (windows of the read's length behind its true start), unbanded
+    or at every half width of --band, alternating; one JSON line."""
+    widths = [int(w) for w in str(args.band).split(",")] if args.band is not None else [None]
+    tag = lambda w: "" if w is None else "_w%d" % w
+    sides = [(kind + tag(w), kind, w) for w in widths for kind in ("extend", "global")]
+    t = {s: dict(kernel_us=[], call_ms=[]) for s, _, _ in sides}
+    info, results = {}, {}
+    for step in range(args.warmup + args.steps):
+        for side, kind, w in sides:                                 # alternating: all sides see the same clocks
+            kw = dict(band_lo=-w, band_hi=w) if w is not None else {}
+            call = ctx.affine_global_run if kind == "global" else ctx.affine_extend_run
+            t0 = time.perf_counter()
+            got = call(query, lefts, rights, **kw, **SCORING)
+            wall = time.perf_counter() - t0
+            lt, ki = ctx.last_timings(), ctx.last_kernel()
+            info[side] = dict(path=ctx.last_path(), kernel=ki["name"], launches=lt["score_launches"], valu_ops_per_cell=ki["valu_ops_per_cell"],
+                              rows_per_lane=ki["rows_per_lane"], cells=lt["cells"])
+            results[side] = got
+            if step >= args.warmup:
+                t[side]["kernel_us"].append(lt["score_us"])
+                t[side]["call_ms"].append(wall * 1e3)
+    equal = {}
+    option = "no_affine_pairs" if args.band is None else "no_affine_band"
+    ctx.set_option(option, 1)
+    try:
+        for side, kind, w in sides:
+            if kind == "global":
+                kw = dict(band_lo=-w, band_hi=w) if w is not None else {}
+                exact = ctx.affine_global_run(query, lefts, rights, **kw, **SCORING)
+                equal[side] = bool(np.array_equal(results[side]["score"], exact["score"]) and not any(p.startswith("affine_pair_glob") or
+                                   p.startswith("affine_band_glob") for p in ctx.last_path()))
+    finally:
+        ctx.set_option(option, 0)
+    line = dict(bench="affine_pairs_bench", mode="global", band_half_widths=None if args.band is None else widths, pairs=args.pairs,
+                read_len=READ_LEN, window=READ_LEN, ref_len=args.ref_len, scoring="3/-3/5/1", steps=args.steps,
+                results_equal_exact_kernel=equal)
+    for side, kind, w in sides:
+        k_us, c_ms = statistics.median(t[side]["kernel_us"]), statistics.median(t[side]["call_ms"])
+        line[side] = dict(info[side], kernel_ms=k_us / 1e3, call_ms=c_ms, gcups_kernel=info[side]["cells"] / max(k_us, 1e-9) / 1e3,
+                          kernel_ms_min=min(t[side]["kernel_us"]) / 1e3, kernel_ms_max=max(t[side]["kernel_us"]) / 1e3,
+                          call_ms_min=min(t[side]["call_ms"]), call_ms_max=max(t[side]["call_ms"]))
+    ok = all(equal.values())
+    for w in widths:
+        e, g = line["extend" + tag(w)], line["global" + tag(w)]
+        ge, gg = results["extend" + tag(w)], results["global" + tag(w)]
+        g["mean_score"] = float(gg["score"][np.isfinite(gg["score"])].mean())
+        g["unreachable"] = float((~np.isfinite(gg["score"])).mean())
+        g["negative"] = float((gg["score"] < 0).mean())
+        g["equals_to_end_score"] = float((gg["score"] == ge["to_end_score"]).mean())
+        g["not_above_to_end"] = bool((gg["score"] <= ge["to_end_score"]).all())   # the corner is one cell of row m
+        ok = ok and g["not_above_to_end"]
+        # same instance, same steps, same cells on both sides: the prediction is the ratio of the ops per cell
+        g["kernel_ratio_global_over_extend"] = g["kernel_ms"] / max(e["kernel_ms"], 1e-9)
+        g["call_ratio_global_over_extend"] = g["call_ms"] / max(e["call_ms"], 1e-9)
+        g["model_ratio_global_over_extend"] = (g["rows_per_lane"] * g["valu_ops_per_cell"]) / (e["rows_per_lane"] * e["valu_ops_per_cell"])
+    ctx.close()
+    text = json.dumps(line)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    print(text)
+    return 0 if ok else 1
 
 
 def banded_extend_against_extend(args, ctx, reads, query, lefts, rights):
