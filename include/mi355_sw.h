@@ -637,6 +637,32 @@ int mi355_sw_prefix_values(mi355_sw_ctx *ctx, float *values, size_t capacity, si
 int mi355_sw_prefix_thin_items(mi355_sw_ctx *ctx, size_t n_items, const uint32_t *items, int P, int P2, int64_t sub_len, int64_t left, int64_t right,
                                const mi355_sw_params *params, float *values, size_t capacity, size_t *n_per_item);
 
+/* The seed stage of the chained prefix filter.  A chained bucket (>= 1024 reads, reference of at least
+ * "prefix_seed_min_cols" columns, default 4 Mi) first looks for exact k-letter seeds of its reads in the reference — disjoint seeds at
+ * offsets 0, k, 2k, ..., one scan of the reference per call (sw_seed_kernel.h) —, takes B0 of a read from the window of its best seed
+ * cluster, and then sweeps every read at the lowest prefix height (16, 20, 26, 32 or 38 rows) that can certify it against this
+ * reference's measured background, one pass per height: path tags "prefix_seed[k=..,hits=..]", "prefix_group[R=..,n=..]" per pass,
+ * "prefix_calibrated[..]" in the call that measured the background table (once per reference and scoring), "prefix_seed_failed" when
+ * more than half of the bucket has no seed B0 (the flow is then the probed chain's, exactly).  Counters (mi355_sw_last_counter):
+ * "prefix_seeded" — reads whose B0 came from seed hits, "prefix_seed_hits" — hits the scan reported, "prefix_calibrated" — tables
+ * measured in the call.  "no_prefix_seed" gives the probed chain (the A/B).  Results are the same either way.
+ *
+ * mi355_sw_seed_k: the seed length for reads of at least min_len letters over `letters` distinct letters against n columns — the
+ * smallest k with letters^k >= (min_len / k) n that leaves 4 seeds in the shortest read; 0: none.  mi355_sw_seed_hash: the rolling
+ * hash of k code bytes.  mi355_sw_seed_cluster: the cluster rule on one read's hits (start = position - offset, offset): for every
+ * hit as the anchor the hits with start in [anchor, anchor + width]; most distinct offsets win, then the lowest start.  Returns 1
+ * and the cluster's lowest and highest start, 0 without hits.  None of the three needs a device.
+ *
+ * mi355_sw_seed_hits (test hook): the scan over [left, right) of the resident reference for the resident batch with seeds of k
+ * letters (0: the rule above on the batch's shortest read; the k used goes to *k_used).  counts[q] = hits of query q, exact;
+ * the first 32 of them, in no particular order, as starts[q * 32 + j] = position - offset relative to `left` (may be negative) and
+ * offsets[q * 32 + j].  A seed with a letter the reference does not hold is left out, and so is a seed that repeats itself with a
+ * period of at most k / 2 letters (poly-A, a microsatellite). */
+int mi355_sw_seed_k(int letters, int min_len, int64_t n);
+uint32_t mi355_sw_seed_hash(const uint8_t *codes, int k);
+int mi355_sw_seed_cluster(size_t n_hits, const int64_t *starts, const int32_t *offsets, int64_t width, int64_t *lo, int64_t *hi, int *distinct);
+int mi355_sw_seed_hits(mi355_sw_ctx *ctx, int64_t left, int64_t right, int k, uint32_t *counts, int64_t *starts, int32_t *offsets, int *k_used);
+
 /* Which kernels and pipeline decisions the last call used: space-separated tags, each at most once, e.g.
  * "score[cell=f16,SL=8,R=19,...,sampled=1,...] strip[R=3,mode=max,...] wave[orient=0,...,dirs=1,...] walk_wave" — what the parity
  * tests assert a switch of mi355_sw_set_option ENGAGED with.  A call whose single-alignment chain declined after its launches

@@ -29,7 +29,9 @@ EXPORTS = [
     "mi355_sw_affine_extend_run", "mi355_sw_affine_extend_trace",
     "mi355_sw_affine_extend_run_band", "mi355_sw_affine_extend_trace_band",
     "mi355_sw_affine_global_run", "mi355_sw_affine_global_trace",
+    "mi355_sw_seed_k", "mi355_sw_seed_hash", "mi355_sw_seed_cluster", "mi355_sw_seed_hits",
 ]
+SEED_HIT_CAP = 32                                       # hits listed per read by the seed scan (kSeedHitCap of sw_seed_kernel.h)
 AFFINE_LOCAL, AFFINE_END_TO_END = 0, 1                 # mode of the affine pairs calls (include/mi355_sw.h)
 AFFINE_MODES = {"local": AFFINE_LOCAL, "end_to_end": AFFINE_END_TO_END}
 MULTI_RCCL = 1
@@ -101,6 +103,7 @@ def lib():
         L.mi355_sw_multi_last_error.restype = C.c_char_p
         L.mi355_sw_option_names.restype = C.c_char_p
         L.mi355_sw_last_path.restype = C.c_char_p
+        L.mi355_sw_seed_hash.restype = C.c_uint32
         for name in EXPORTS:
             getattr(L, name)
         _LIB = L
@@ -660,7 +663,7 @@ class Context:
         self._L.mi355_sw_last_counters(self._ctx, c)
         out = dict(requeried=int(c[0]), whole_batch_again=int(c[1]), candidates=int(c[2]), left_window=int(c[3]))
         for name in ("first_settled", "saved_locates", "saved_traces", "saved_fallbacks", "walk_widened", "wait_retries", "early_settled", "beyond_f16", "prefix_certified",
-                     "prefix_second_pass", "prefix_thinned", "prefix_thin_items", "pooled_loops"):
+                     "prefix_second_pass", "prefix_thinned", "prefix_thin_items", "pooled_loops", "prefix_seeded", "prefix_seed_hits", "prefix_calibrated"):
             v = C.c_uint64(0)
             rc = self._L.mi355_sw_last_counter(self._ctx, name.encode(), C.byref(v))
             if rc:
@@ -692,6 +695,23 @@ class Context:
         out = np.zeros((len(flat), per.value), dtype=np.float32)
         self._chk(self._L.mi355_sw_prefix_thin_items(*args, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size), C.byref(per)))
         return out
+
+    def seed_hits(self, left, right, k=0):
+        """Test hook (mi355_sw_seed_hits): the seed scan over [left, right) of the resident reference for the resident batch, seeds of k
+        letters (0: the library's rule).  Returns (k used, counts[n_queries] — exact —, hits): hits[q] = the listed hits of query q, at
+        most SEED_HIT_CAP, as sorted (start, offset) pairs with start = position - offset relative to `left`."""
+        n = self._nbatch
+        counts = np.zeros(n, dtype=np.uint32)
+        starts = np.zeros(n * SEED_HIT_CAP, dtype=np.int64)
+        offs = np.zeros(n * SEED_HIT_CAP, dtype=np.int32)
+        used = C.c_int(0)
+        self._chk(self._L.mi355_sw_seed_hits(self._ctx, C.c_int64(left), C.c_int64(right), C.c_int(k), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             starts.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(used)))
+        hits = []
+        for q in range(n):
+            c = min(int(counts[q]), SEED_HIT_CAP)
+            hits.append(sorted(zip(starts[q * SEED_HIT_CAP:q * SEED_HIT_CAP + c].tolist(), offs[q * SEED_HIT_CAP:q * SEED_HIT_CAP + c].tolist())))
+        return used.value, counts, hits
 
     def last_path(self):
         """Tags of the kernels / pipeline decisions of the last call (mi355_sw_last_path), as a list."""
@@ -811,3 +831,27 @@ def raw2true(nx, ny, ri, rj):
     ti, tj = C.c_size_t(), C.c_size_t()
     lib().mi355_sw_raw2true(C.c_size_t(nx), C.c_size_t(ny), C.c_size_t(ri), C.c_size_t(rj), C.byref(ti), C.byref(tj))
     return ti.value, tj.value
+
+
+def seed_k(letters, min_len, n):
+    """mi355_sw_seed_k: the seed length of the seed stage, 0 where it is not used (no device needed)."""
+    return int(lib().mi355_sw_seed_k(C.c_int(letters), C.c_int(min_len), C.c_int64(n)))
+
+
+def seed_hash(codes):
+    """mi355_sw_seed_hash: the rolling hash of the code bytes `codes` (no device needed)."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(codes), dtype=np.uint8))
+    return int(lib().mi355_sw_seed_hash(a.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int(len(a))))
+
+
+def seed_cluster(hits, width):
+    """mi355_sw_seed_cluster on hits = [(start, offset)]: (lowest start, highest start, distinct offsets) of the winning cluster, or
+    None without hits (no device needed)."""
+    starts = np.ascontiguousarray([h[0] for h in hits], dtype=np.int64)
+    offs = np.ascontiguousarray([h[1] for h in hits], dtype=np.int32)
+    lo, hi, d = C.c_int64(0), C.c_int64(0), C.c_int(0)
+    rc = lib().mi355_sw_seed_cluster(C.c_size_t(len(starts)), starts.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     C.c_int64(width), C.byref(lo), C.byref(hi), C.byref(d))
+    if rc < 0:
+        raise MI355Error(rc, "mi355_sw_seed_cluster")
+    return (lo.value, hi.value, d.value) if rc == 1 else None

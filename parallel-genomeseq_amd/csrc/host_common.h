@@ -15,8 +15,8 @@ constexpr size_t kExactLdsMax = 159 * 1024;    // dynamic part; the wide instanc
   X(no_f16) X(no_unsat) X(no_sample) X(no_satflag) X(no_solo) X(no_wave) X(no_comb) X(no_twin) X(no_wide) X(no_strip) \
   X(no_quant) X(no_devlist) X(no_ref_cache) X(no_strip_groups) X(u8_long_twin) X(long_twin) X(no_long) \
   X(no_requery) X(force_f32) X(no_long_p32) X(no_opt_margin) X(no_wave_prof) X(no_wave_window) X(no_first) X(no_long_save) X(u8_sample_short) X(no_wave_pieces) X(no_u8_early) X(no_wave_f16) X(no_devlist_by_id) X(no_f16_mirror) X(no_f16m_int_diag) X(no_affine_sweep) X(no_affine_prof) X(no_affine_pairs) X(no_prefix) X(trace) \
-  X(no_prefix_low) X(no_prefix_cascade) X(no_prefix_step) X(no_affine_band) X(no_prefix_thin)
-#define MI355_SW_INT_OPTIONS(X) X(strip_r) X(slot) X(few_r) X(chunk) X(long_pipes) X(long_wgs) X(long_sub) X(long_r) X(long_groups) X(assume_cus) X(long_save_what) X(prefix_min_cols) X(prefix_thin_min_cols)
+  X(no_prefix_low) X(no_prefix_cascade) X(no_prefix_step) X(no_affine_band) X(no_prefix_thin) X(no_prefix_seed)
+#define MI355_SW_INT_OPTIONS(X) X(strip_r) X(slot) X(few_r) X(chunk) X(long_pipes) X(long_wgs) X(long_sub) X(long_r) X(long_groups) X(assume_cus) X(long_save_what) X(prefix_min_cols) X(prefix_thin_min_cols) X(prefix_seed_min_cols)
 struct Options {
 #define X(n) bool n = false;
   MI355_SW_BOOL_OPTIONS(X)
@@ -243,6 +243,20 @@ struct Hash128 {
 
 
 // One alignment's intermediate state on the host
+// The background table of the seeded prefix flow (host_pipeline.h prefix_background): for each height R and each deficit x in score
+// units, the expected number of sub-chunks of the whole range whose row-P maximum reaches smax P - x against a read that has nothing
+// to do with them.  A function of (reference, score table, sub-chunk length, range) alone; measured once and kept on the context.
+struct PrefixBackground {
+  bool valid = false;
+  const void *ref = nullptr;
+  uint64_t ref_version = 0;
+  int64_t lo = 0, hi = 0, E = 0;
+  int gap = 0, smax = 0;
+  std::vector<int16_t> stab;                // the score table it was measured with
+  std::vector<int> R;                       // heights, ascending
+  std::vector<std::vector<double>> tail;    // [height][x], x = 0 .. smax P
+};
+
 struct Located {
   float score = 0;
   int64_t ix = 0, iy = 0;         // argmax, iy relative to the range start (1-based)
@@ -363,6 +377,16 @@ struct mi355_sw_ctx {
   size_t saved_locates = 0, saved_traces = 0, saved_fallbacks = 0;   // finish steps of the running call that started from saved state / fell back
   size_t walk_widened = 0;        // times a traceback window's budget was multiplied by 4 in the running call (walk status 1)
   DevBuf thin_items, thin_out, thin_vals;   // the thin stage's item list, its survivors (count, then the list) and the test hook's value rows
+  // the seed stage of the chained prefix filter (sw_seed_kernel.h, host_pipeline.h prefix_seeded)
+  DevBuf seed_tab, seed_hits;               // the batch's seed table as one blob; hit counts, then the hit lists
+  std::vector<uint8_t> h_qbytes;            // host copy of the resident batch's bytes, kept while the batch stands ...
+  const void *h_qbytes_of = nullptr;        // ... (its device buffer and version)
+  uint64_t h_qbytes_version = 0;
+  QueryBatch calib_q;                       // the prefixes cut from the reference that measure the background table
+  PrefixBackground pbg;
+  size_t prefix_seeded = 0;                 // reads of the running call whose B0 came from seed hits, before any sweep
+  size_t prefix_seed_hits = 0;              // ... and the hits the scan reported for the call's reads
+  size_t prefix_calibrated = 0;             // background tables the running call measured (0: the context's table stood)
   DevBuf pkeys, pthr, psel, psel2, qcnt, sel2, gcnt, wlut, ckpt, first, keys, ranges, stab, ftab, ftab_s, htab, htab8, soloblk, flags, submax, lut, probs, dirs, outs_f, outs_i, cons, walkp, hmat, brow, wprobs, scan;
   // host sides of small per-call uploads: they must outlive the asynchronous copies, and the tables are only
   // sent again when they change

@@ -597,10 +597,19 @@ int run_thin(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const R
 // pass, offenders included; gave_up is set when most of the pass offended and everybody was handed back.
 struct PrefixAsk {
   bool step = false, second = false;
+  bool bulk = false;                           // the tiles of the chained main pass whatever the pass's size (score_launch: chain_main)
   std::vector<int> voteR;
   std::vector<std::vector<char>> *votes = nullptr;
   std::vector<float> *B0 = nullptr;
   bool *gave_up = nullptr;
+  // The seeded flow (prefix_seeded) knows B0 of most reads BEFORE the pass.  given[id] != 0: round 1 is not run for the read — its B0 is
+  // (*B0)[id] on entry, an exact alignment score; what was evaluated for it are its entries of `f1` ({query id, sub-chunk} in sub-chunks
+  // of f1_E columns, sorted), and their first maximum is (*loc1)[id].  B0 <= B is all L19 and L20 use, so the thresholds come from the
+  // given B0 and the read's result is the first maximum over those windows and round 2.
+  const std::vector<char> *given = nullptr;
+  const std::vector<std::pair<uint32_t, uint32_t>> *f1 = nullptr;
+  int64_t f1_E = 0;
+  const std::vector<Located> *loc1 = nullptr;
 };
 int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_params &p,
                   const ScoreTable &table, const Bucket &b, int prefR, bool rowp, std::vector<int64_t> &qchunk, std::vector<int64_t> &qwarm,
@@ -615,7 +624,7 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   HIPCHK(ctx, hipMemsetAsync(ctx->pkeys.p, 0, nq * 8, ctx->stream));
   // a. the prefix sweep: the instance of prefR rows at kPrefixLanes lanes; keys and sub-chunk values as the sampled sweep writes them
   Bucket pb = b;
-  pb.SL = kPrefixLanes; pb.R = prefR; pb.prefix = true; pb.rowp = rowp; pb.step = rowp && ask.step; pb.second = ask.second;
+  pb.SL = kPrefixLanes; pb.R = prefR; pb.prefix = true; pb.rowp = rowp; pb.step = rowp && ask.step; pb.second = ask.second; pb.bulk = ask.bulk;
   ScoreIO io;
   io.range_lo = ctx->ranges.as<int64_t>(); io.range_hi = ctx->ranges.as<int64_t>() + 1; io.keys = ctx->pkeys.as<unsigned long long>();
   rc = score_launch(ctx, ref, q, ranges, p, table, pb, &io);
@@ -634,13 +643,21 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   // b. round 1
   std::vector<float> bound(nq, 0.0f), qlow(nq, 0.0f), B0(nq, 0.0f), thr(nq, 0.0f);
   std::vector<char> off(nq, 0), mine(nq, 0);
-  std::vector<std::pair<uint32_t, uint32_t>> f1;
+  std::vector<std::pair<uint32_t, uint32_t>> f1, f1given;
+  auto is_given = [&](int id) { return ask.given && ask.B0 && ask.loc1 && ask.f1 && (*ask.given)[id] != 0; };
   for (int k = 0; k < b.count; ++k) {
     const int id = q.order[b.first + k];
     mine[id] = 1; qchunk[id] = E; qwarm[id] = b.warm;
     // windows of both rounds only have to be exact for cells that hold a maximum above the certification bound (L3)
     bound[id] = prefix_bound(table, q.len[id], P, slack, rowp);
     qlow[id] = bound[id];
+    if (is_given(id)) {                                                          // (what the seed stage evaluated, where the sub-chunks are the same)
+      if (ask.f1_E == E) {
+        auto at = std::lower_bound(ask.f1->begin(), ask.f1->end(), std::make_pair((uint32_t)id, 0u));
+        for (; at != ask.f1->end() && at->first == (uint32_t)id; ++at) f1given.push_back(*at);
+      }
+      continue;
+    }
     if (!(key_score(kKeyF16, (uint32_t)(pkeys[id] >> 32), 0) > 0)) { off[id] = 1; continue; }
     const int64_t s0 = (int64_t)(0xFFFFFFFFull - (pkeys[id] & 0xFFFFFFFFull));
     for (int64_t sc = s0; sc <= s0 + D && sc < nsub; ++sc) f1.push_back({(uint32_t)id, (uint32_t)sc});
@@ -653,9 +670,15 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   if (rc) return rc;
   HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
   ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+  const size_t nlocated1 = f1.size();
+  if (!f1given.empty()) {                                                        // from here on f1 is everything evaluated before round 2
+    f1.insert(f1.end(), f1given.begin(), f1given.end());
+    std::sort(f1.begin(), f1.end());
+  }
   size_t noff = 0;
   for (int k = 0; k < b.count; ++k) {
     const int id = q.order[b.first + k];
+    if (is_given(id)) { loc1[id] = (*ask.loc1)[id]; done1[id] = (*ask.B0)[id] > 0.0f ? 1 : 0; }
     B0[id] = done1[id] ? loc1[id].score : 0.0f;
     if (!off[id] && !(B0[id] > bound[id])) off[id] = 1;
     if (!off[id]) thr[id] = B0[id] - smax * (float)(q.len[id] - P) - slack;      // (> 0: B0 is above the bound)
@@ -808,7 +831,7 @@ int prefix_bucket(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   std::sort(f2.begin(), f2.end());
   f2.erase(std::unique(f2.begin(), f2.end()), f2.end());
   std::set_difference(f2.begin(), f2.end(), f1.begin(), f1.end(), std::back_inserter(f2new));
-  ctx->candidates += f1.size() + f2new.size();
+  ctx->candidates += nlocated1 + f2new.size();                                   // (a given read's windows were counted where they were evaluated)
   if (!f2new.empty()) {
     HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     rc = locate_flagged(ctx, ref, q, rg, p, qchunk, qwarm, B0, table, f2new, loc2, done2);
@@ -925,6 +948,346 @@ int prefix_chain(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   PrefixAsk sask;
   sask.step = step; sask.second = true;
   return prefix_bucket(ctx, ref, qv, rg, p, table, vb, hs[start + 1], true, qchunk, qwarm, loc, qdone, offenders, sask);
+}
+
+// ---- the seeded flow of a chained bucket -------------------------------------------------------------------------
+// A host copy of the batch's bytes, fetched once per upload.  (Seeds only steer: B0 is what the locate stage finds on the device's
+// own bytes, so a stale copy could cost time, never a result.)
+int batch_host_bytes(mi355_sw_ctx *ctx, const QueryBatch &q, const uint8_t *&bytes) {
+  size_t tot = 0;
+  for (size_t k = 0; k < q.nq; ++k) tot = std::max(tot, (size_t)q.off[k] + (size_t)q.len[k]);
+  if (ctx->h_qbytes_of != q.bytes.p || ctx->h_qbytes_version != q.version || ctx->h_qbytes.size() != tot) {
+    ctx->h_qbytes.resize(tot);
+    if (tot) HIPCHK(ctx, hipMemcpy(ctx->h_qbytes.data(), q.bytes.p, tot, hipMemcpyDeviceToHost));
+    ctx->h_qbytes_of = q.bytes.p; ctx->h_qbytes_version = q.version;
+  }
+  bytes = ctx->h_qbytes.data();
+  return 0;
+}
+
+// sw_seed_scan_kernel over the range for the seeds of the reads `ids`: count[id] hits (exact), the first kSeedHitCap of them as
+// start[id * kSeedHitCap + j] (position - offset, relative to the range) and hoff[...] (the seed's offset in the read).
+int seed_scan(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const std::vector<int32_t> &ids, int k,
+              std::vector<uint32_t> &count, std::vector<int64_t> &start, std::vector<int32_t> &hoff) {
+  HostTrace trace_("seed_scan");
+  const size_t nq = q.nq;
+  const int64_t n = rg.hi - rg.lo;
+  count.assign(nq, 0u); start.assign(nq * kSeedHitCap, 0); hoff.assign(nq * kSeedHitCap, 0);
+  if (k < 1 || k > kSeedMaxK) return fail(ctx, MI355_SW_EINVAL, "seed length outside 1 .. 32");
+  const uint8_t *bytes = nullptr;
+  int rc = batch_host_bytes(ctx, q, bytes);
+  if (rc) return rc;
+  SeedTable t;
+  if (!seed_table_build(t, k, bytes, q.off.data(), q.len.data(), ids.data(), ids.size(), ref.code_of))
+    return fail(ctx, MI355_SW_ENOTSUP, "too many seeds for the seed table");
+  const size_t ns = t.nseeds();
+  if (ns == 0 || n < k) return 0;
+  const int64_t threads = (n - k + 1 + kSeedStretch - 1) / kSeedStretch, blocks = (threads + kSeedThreads - 1) / kSeedThreads;
+  if (blocks > 0x7FFFFFFFll) return fail(ctx, MI355_SW_ENOTSUP, "range too long for the seed scan");
+  auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
+  const size_t o_bucket = up16(t.slots.size() * 4), o_read = o_bucket + up16(t.bucket.size() * 4), o_off = o_read + up16(ns * 4),
+               o_codes = o_off + up16(ns * 4), total = o_codes + up16(ns * (size_t)k);
+  const size_t h_start = up16(nq * 4), h_off = h_start + nq * kSeedHitCap * 8, h_total = h_off + nq * kSeedHitCap * 4;
+  if (ctx->seed_tab.ensure(total + 16) || ctx->seed_hits.ensure(h_total + 16)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(seed table) failed");
+  std::vector<uint8_t> blob(total, 0);
+  memcpy(blob.data(), t.slots.data(), t.slots.size() * 4);
+  memcpy(blob.data() + o_bucket, t.bucket.data(), t.bucket.size() * 4);
+  memcpy(blob.data() + o_read, t.read.data(), ns * 4);
+  memcpy(blob.data() + o_off, t.off.data(), ns * 4);
+  memcpy(blob.data() + o_codes, t.codes.data(), ns * (size_t)k);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->seed_tab.p, blob.data(), total, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->seed_hits.p, 0, h_start, ctx->stream));
+  uint8_t *tab = ctx->seed_tab.as<uint8_t>(), *out = ctx->seed_hits.as<uint8_t>();
+  SeedArgs a;
+  a.codes = ref.codes.as<uint8_t>() + rg.lo; a.n = n; a.k = k; a.bk = t.bk;
+  a.slots = reinterpret_cast<const uint2 *>(tab); a.bits = t.bits; a.bucket_log2 = t.bucket_log2;
+  a.bucket = reinterpret_cast<const uint32_t *>(tab + o_bucket);
+  a.seed_read = reinterpret_cast<const int32_t *>(tab + o_read); a.seed_off = reinterpret_cast<const int32_t *>(tab + o_off);
+  a.seed_codes = tab + o_codes;
+  a.count = reinterpret_cast<unsigned int *>(out); a.hit_start = reinterpret_cast<int64_t *>(out + h_start); a.hit_off = reinterpret_cast<int32_t *>(out + h_off);
+  hipLaunchKernelGGL(sw_seed_scan_kernel, dim3((unsigned)blocks), dim3(kSeedThreads), t.bucket.size() * 4, ctx->stream, a);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(count.data(), out, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(start.data(), out + h_start, nq * kSeedHitCap * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(hoff.data(), out + h_off, nq * kSeedHitCap * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+// The background table (PrefixBackground) of the heights Rs for this reference, score table and range: kCalibReads prefixes cut from
+// the reference itself at evenly spaced offsets — a function of the reference alone — swept by the step tiles of every height over
+// the first kCalibCols columns of the range; each prefix's home sub-chunks left out, the rest counted per value and scaled to the
+// range's sub-chunks.  One small launch per height, once per (reference, table, range): in real use the reference and the scoring
+// stay while the batches change, and the table does not depend on the batch.  ctx->pbg.valid is left false where it cannot be
+// measured (a range too short to cut the prefixes from).
+constexpr int kCalibReads = 16;
+constexpr int kCalibKeep = 12;                                         // prefixes whose tails make the table: the lowest three quarters at every value
+constexpr int64_t kCalibCols = (int64_t)4 << 20;
+int prefix_background(mi355_sw_ctx *ctx, const RefData &ref, const Range &rg, const mi355_sw_params &p, const ScoreTable &table,
+                      const Bucket &like, const std::vector<int> &Rs) {
+  PrefixBackground &g = ctx->pbg;
+  if (g.valid && g.ref == (const void *)&ref && g.ref_version == ref.version && g.lo == rg.lo && g.hi == rg.hi && g.gap == table.gap &&
+      g.smax == table.smax && g.R == Rs && g.stab == table.stab)
+    return 0;
+  HostTrace trace_("prefix_background");
+  g.valid = false;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int64_t n = rg.hi - rg.lo;
+  const int L = kPrefixLanes * Rs.back() + 2;                          // (longer than the tallest prefix: prefix tiles take the rows of LONGER reads)
+  if (n < (int64_t)64 * kCalibReads * L) return 0;
+  std::vector<std::vector<char>> cut(kCalibReads, std::vector<char>((size_t)L));
+  std::vector<int64_t> at(kCalibReads);
+  std::vector<const char *> xs(kCalibReads);
+  std::vector<size_t> nxs(kCalibReads, (size_t)L);
+  for (int i = 0; i < kCalibReads; ++i) {
+    at[i] = std::min<int64_t>(n - L, (2 * (int64_t)i + 1) * n / (2 * kCalibReads));
+    HIPCHK(ctx, hipMemcpy(cut[i].data(), ref.bytes.as<uint8_t>() + rg.lo + at[i], (size_t)L, hipMemcpyDeviceToHost));
+    xs[i] = cut[i].data();
+  }
+  int rc = upload_queries(ctx, ctx->calib_q, kCalibReads, xs.data(), nxs.data());
+  if (rc) return rc;
+  const QueryBatch &cq = ctx->calib_q;
+  const Range srg{rg.lo, std::min(rg.hi, rg.lo + kCalibCols)};
+  const std::vector<Range> ranges{srg};
+  const int64_t ns = srg.hi - srg.lo;
+  // (the calibration is no pass of the call: what describes the call's sweep stays as it was)
+  const mi355_sw_kernel_info kept_kernel = ctx->last_kernel;
+  const bool kept_named = ctx->prefix_named;
+  const double kept_launches = ctx->timings[4], kept_cells = ctx->timings[5];
+  const std::string kept_path = ctx->path;
+  struct Restore {                                                       // on every way out of the launches below, once
+    std::function<void()> f;
+    bool armed = true;
+    void run() { if (armed) f(); armed = false; }
+    ~Restore() { run(); }
+  } restore_{[&]() { ctx->last_kernel = kept_kernel; ctx->prefix_named = kept_named; ctx->timings[4] = kept_launches; ctx->timings[5] = kept_cells; ctx->path = kept_path; }};
+  g.R = Rs; g.tail.assign(Rs.size(), std::vector<double>());
+  for (size_t h = 0; h < Rs.size(); ++h) {
+    const int R = Rs[h], P = kPrefixLanes * R, top = table.smax * P;
+    rc = score_begin(ctx, cq, ranges, table);
+    if (rc) return rc;
+    if (ctx->pkeys.ensure((size_t)kCalibReads * 8 + 16)) return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(score scratch) failed");
+    HIPCHK(ctx, hipMemsetAsync(ctx->pkeys.p, 0, (size_t)kCalibReads * 8, ctx->stream));
+    Bucket pb = like;
+    pb.first = 0; pb.count = kCalibReads;
+    pb.SL = kPrefixLanes; pb.R = R; pb.prefix = true; pb.rowp = true; pb.step = true; pb.second = true;
+    ScoreIO io;
+    io.range_lo = ctx->ranges.as<int64_t>(); io.range_hi = ctx->ranges.as<int64_t>() + 1; io.keys = ctx->pkeys.as<unsigned long long>();
+    rc = score_launch(ctx, ref, cq, ranges, p, table, pb, &io);
+    if (rc) return rc;
+    std::vector<unsigned long long> keys;
+    rc = score_fetch(ctx, kCalibReads, keys, ctx->pkeys.p);
+    if (rc) return rc;
+    const int64_t E = pb.sub_len, stride = ((ns + pb.chunk_len - 1) / pb.chunk_len) * (pb.chunk_len / E), nsub = (ns + E - 1) / E;
+    if (h == 0) g.E = E;
+    if (E != g.E) return 0;
+    std::vector<uint16_t> raw((size_t)kCalibReads * (size_t)stride);
+    HIPCHK(ctx, hipMemcpy(raw.data(), ctx->submax.p, raw.size() * 2, hipMemcpyDeviceToHost));
+    // one tail per prefix, scaled to the range; the table is the mean of the kCalibKeep lowest at every x: a quarter of the prefixes
+    // may come out of a repeat family (thousands of sub-chunks near the full score, which say nothing about a read from elsewhere)
+    // without moving it.  A read out of such a family is then forecast too low, offends its pass by the cap and moves on, as in the chain.
+    std::vector<std::vector<double>> tails(kCalibReads, std::vector<double>((size_t)top + 1, 0.0));
+    bool all_counted = true;
+    for (int r = 0; r < kCalibReads; ++r) {
+      const int64_t home = at[cq.order[r]];                              // (relative to the range, as the sample is)
+      const int64_t x0 = (home - E) / E, x1 = (home + L + E) / E;          // the prefix's own copy, its lag and its decay
+      std::vector<double> hist((size_t)top + 1, 0.0);
+      double counted = 0;
+      for (int64_t s = 0; s < nsub; ++s) {
+        if (s >= x0 && s <= x1) continue;
+        const long v = std::lround(half_value(raw[(size_t)r * (size_t)stride + (size_t)s]) * kF16Scale);
+        hist[(size_t)std::max(0l, std::min<long>(v, top))] += 1.0;
+        counted += 1.0;
+      }
+      if (counted < 1.0) { all_counted = false; break; }
+      const double scale = ((double)n / (double)E) / counted;
+      double acc = 0;
+      for (int x = 0; x <= top; ++x) { acc += hist[(size_t)(top - x)]; tails[r][(size_t)x] = acc * scale; }
+    }
+    if (!all_counted) return 0;
+    g.tail[h].assign((size_t)top + 1, 0.0);
+    for (int x = 0; x <= top; ++x) {
+      double col[kCalibReads];
+      for (int r = 0; r < kCalibReads; ++r) col[r] = tails[r][(size_t)x];
+      std::sort(col, col + kCalibReads);
+      double sum = 0;
+      for (int r = 0; r < kCalibKeep; ++r) sum += col[r];
+      g.tail[h][(size_t)x] = sum / kCalibKeep;
+    }
+  }
+  restore_.run();                                                        // (here, in front of the call's own note below)
+  g.valid = true; g.ref = (const void *)&ref; g.ref_version = ref.version; g.lo = rg.lo; g.hi = rg.hi; g.gap = table.gap; g.smax = table.smax;
+  g.stab = table.stab;
+  ctx->prefix_calibrated += 1;
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  path_note(ctx, "prefix_calibrated[heights=%zu,ms=%.2f]", Rs.size(), ms);
+  return 0;
+}
+// expected background sub-chunks of a read with deficit d (score units below smax m) at height R; huge where the table has no such height
+double background_flags(const PrefixBackground &g, int R, long d) {
+  for (size_t h = 0; h < g.R.size(); ++h)
+    if (g.R[h] == R && !g.tail[h].empty()) return g.tail[h][(size_t)std::max(0l, std::min<long>(d, (long)g.tail[h].size() - 1))];
+  return 1.0e30;
+}
+
+// The seeded flow of a bucket of at least kPrefixChain reads, in place of prefix_chain's probe:
+//   seeds:   disjoint k-letter seeds of every read, one scan of the range (seed_scan), the hits of a read clustered by diagonal within
+//            ceil(smax m / g) (sw_seed_kernel.h seed_cluster: most distinct seeds, then the lowest diagonal); a read without a hit, or
+//            with more than kSeedHitCap, has no seed (a repeat family would steer by the order of the atomics);
+//   B0:      the sub-chunks that hold the end columns of the cluster go through locate_flagged as round 1's list does in prefix_bucket:
+//            the located score is an exact alignment score, B0 <= B, which is all L19 and L20 ask of it;
+//   height:  every seeded read takes the lowest height P of prefix_heights_seeded with B0 > prefix_bound(P) whose background table
+//            (prefix_background) expects at most query_flag_cap flags at the read's deficit; none: the full sweep, at once;
+//   groups:  one pass per height, ascending, B0 given (PrefixAsk::given).  A group of fewer than kSeedGroupMin reads rides with the next
+//            taller group; the reads without a seed ride at the chain's lowest height with B0 from their prefix key, as in prefix_chain;
+//   after:   an offender of a pass takes ONE more pass, at the next height whose bound and table admit it, else it is an offender of
+//            the bucket (requery).
+// used = false: the stage did not apply (gates) or failed — more than half of the bucket without a seed B0, path note
+// prefix_seed_failed — and nothing was settled: the caller runs prefix_chain as ever.
+// kSeedGroupMin: a pass of its own saves n (P' - P) read-rows at the bulk rate of 1.85 us per read-row (50 Mbp) and pays what small
+// passes were measured to cost, 2.2 - 2.5 us per read-row on 64 - 150 reads: at 2.5 against 1.85 a pass of its own loses whenever
+// P / P' > 0.74, which holds for every pair of neighbouring heights (16 / 20, 20 / 26, 26 / 32, 32 / 38).  No pass between 150 and
+// 960 reads has been measured; 256 is where a pass fills the chip with one tile per slot several times over and is taken as bulk.
+constexpr int64_t kPrefixSeedMinCols = (int64_t)4 << 20;
+constexpr size_t kSeedGroupMin = 256;
+constexpr int64_t kSeedEndPad = 16;                                    // columns an indel behind the last hit may move the end cell
+int prefix_seeded(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_params &p,
+                  const ScoreTable &table, const Bucket &b, std::vector<int64_t> &qchunk, std::vector<int64_t> &qwarm,
+                  std::vector<Located> &loc, std::vector<char> &qdone, std::vector<int> &offenders, bool &used) {
+  used = false;
+  const int64_t n = rg.hi - rg.lo;
+  const long gate = opt().prefix_seed_min_cols;
+  if (opt().no_prefix_seed || opt().no_prefix_step || n < (gate > 0 ? (int64_t)gate : kPrefixSeedMinCols)) return 0;
+  HostTrace trace_("prefix_seeded");
+  const size_t nq = q.nq;
+  const int minlen = q.len[q.order[b.first]];
+  const int k = seed_k(ref.ncodes - 1, minlen, n);
+  if (k == 0) return 0;
+  const std::vector<int> hs = prefix_heights_seeded(table, b, minlen);
+  const int chainR = prefix_heights(table, b, minlen, true)[0];        // where prefix_chain would probe: the seedless reads' height
+  std::vector<int32_t> ids(q.order.begin() + b.first, q.order.begin() + b.first + b.count);
+  std::vector<uint32_t> count;
+  std::vector<int64_t> start;
+  std::vector<int32_t> hoff;
+  HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+  int rc = seed_scan(ctx, ref, q, rg, ids, k, count, start, hoff);
+  if (rc) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+  const float scan_us = elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+  // the windows: the sub-chunks (of the passes' own length) that hold the columns the cluster's alignments end in
+  Bucket tb = b;
+  tb.SL = kPrefixLanes; tb.prefix = true;
+  const int64_t E = score_sub_len(p.semantics, tb);
+  std::vector<std::pair<uint32_t, uint32_t>> f0;
+  std::vector<char> given(nq, 0);
+  size_t nhits = 0, seedless = 0;
+  for (int id : ids) {
+    const uint32_t c = count[id];
+    nhits += c;
+    bool ok = c > 0 && c <= (uint32_t)kSeedHitCap;
+    int64_t lo = 0, hi = 0;
+    int distinct = 0;
+    if (ok) {
+      std::vector<SeedHit> hits(c);
+      for (uint32_t j = 0; j < c; ++j) hits[j] = SeedHit{start[(size_t)id * kSeedHitCap + j], hoff[(size_t)id * kSeedHitCap + j]};
+      const int64_t m = q.len[id];
+      ok = seed_cluster(hits, ((int64_t)table.smax * m + table.gap - 1) / table.gap, lo, hi, distinct);
+      const int64_t c_lo = std::max<int64_t>(0, lo + m - 1 - kSeedEndPad), c_hi = std::min<int64_t>(n - 1, hi + m - 1 + kSeedEndPad);
+      ok = ok && c_lo <= c_hi;
+      if (ok) for (int64_t s = c_lo / E; s <= c_hi / E; ++s) f0.push_back({(uint32_t)id, (uint32_t)s});
+    }
+    if (ok) given[id] = 1; else ++seedless;
+  }
+  ctx->prefix_seed_hits += nhits;
+  path_note(ctx, "prefix_seed[k=%d,hits=%zu,scan_us=%.0f]", k, nhits, (double)scan_us);
+  if (2 * seedless > (size_t)b.count) { path_note(ctx, "prefix_seed_failed"); return 0; }
+  // B0: round 1 on the seed windows
+  const std::vector<Range> ranges{rg};
+  rc = score_begin(ctx, q, ranges, table);
+  if (rc) return rc;
+  for (int id : ids) { qchunk[id] = E; qwarm[id] = b.warm; }
+  std::sort(f0.begin(), f0.end());
+  const std::vector<float> qlow(nq, 0.0f);                             // (no lower bound is known yet: the bucket's whole margin)
+  std::vector<Located> loc0(nq);
+  std::vector<char> done0(nq, 0);
+  HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+  rc = locate_flagged(ctx, ref, q, rg, p, qchunk, qwarm, qlow, table, f0, loc0, done0);
+  if (rc) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+  ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+  std::vector<float> B0(nq, 0.0f);
+  size_t nseeded = 0;
+  for (int id : ids) {
+    if (given[id] && done0[id] && loc0[id].score > 0.0f) { B0[id] = loc0[id].score; ++nseeded; }
+    else given[id] = 0;
+  }
+  if (2 * ((size_t)b.count - nseeded) > (size_t)b.count) { path_note(ctx, "prefix_seed_failed"); return 0; }
+  rc = prefix_background(ctx, ref, rg, p, table, b, hs);
+  if (rc) return rc;
+  if (!ctx->pbg.valid || ctx->pbg.E != E) { path_note(ctx, "prefix_seed_failed"); return 0; }
+  ctx->candidates += f0.size();
+  ctx->prefix_seeded += nseeded;
+  // heights and groups
+  const uint32_t qcap = query_flag_cap(nq);
+  auto admits = [&](int R, int id) {
+    const int P = kPrefixLanes * R, m = q.len[id];
+    if (m <= P || !(B0[id] > prefix_bound(table, m, P, 0.0f, true))) return false;
+    return background_flags(ctx->pbg, R, std::lround((double)table.smax * m - (double)B0[id])) <= (double)qcap;
+  };
+  std::map<int, std::vector<int>> groups;
+  std::vector<int> none;                                                // no height can certify them: they pay for no pass
+  for (int id : ids) {
+    if (!given[id]) { groups[chainR].push_back(id); continue; }
+    int R = 0;
+    for (int r : hs) if (admits(r, id)) { R = r; break; }
+    if (R) groups[R].push_back(id);
+    else none.push_back(id);
+  }
+  if (2 * none.size() > (size_t)b.count && (size_t)b.count == nq) {
+    // most of the bucket is beyond every height (10 % substitutions: deficits of 90 and more) and the bucket is the whole batch: the
+    // caller sweeps the whole batch again whatever the others do (whole_again), so nobody pays for a pass — what such a batch pays
+    // for the filter is the scan and the seed windows, not a probe.  (With other buckets in the call that rule may not fire: then the
+    // reads a height can certify take their passes below, and only the others go to the sweep.)
+    offenders.insert(offenders.end(), ids.begin(), ids.end());
+    path_note(ctx, "prefix_seed_hopeless[n=%zu]", none.size());
+    used = true;
+    return 0;
+  }
+  offenders.insert(offenders.end(), none.begin(), none.end());
+  for (auto it = groups.begin(); it != groups.end();) {
+    auto nx = std::next(it);
+    if (nx != groups.end() && it->second.size() < kSeedGroupMin) { nx->second.insert(nx->second.end(), it->second.begin(), it->second.end()); it = groups.erase(it); }
+    else ++it;
+  }
+  size_t biggest = 0;
+  for (const auto &gr : groups) biggest = std::max(biggest, gr.second.size());
+  std::vector<char> again(nq, 0);
+  for (auto it = groups.begin(); it != groups.end(); ++it) {
+    const int R = it->first;
+    const std::vector<int> members(it->second);
+    QueryBatch qv;
+    Bucket vb;
+    rc = prefix_view(ctx, q, members, ctx->psel2, qv, b, vb);
+    if (rc) return rc;
+    path_note(ctx, "prefix_group[R=%d,n=%zu]", R, members.size());
+    bool gave_up = false;
+    std::vector<int> roff;
+    PrefixAsk ask;
+    ask.step = true; ask.second = members.size() != biggest;           // (last_kernel describes the largest group, cells are everybody's)
+    ask.bulk = true;
+    ask.B0 = &B0; ask.gave_up = &gave_up; ask.given = &given; ask.f1 = &f0; ask.f1_E = E; ask.loc1 = &loc0;
+    rc = prefix_bucket(ctx, ref, qv, rg, p, table, vb, R, true, qchunk, qwarm, loc, qdone, roff, ask);
+    if (rc) return rc;
+    for (int id : roff) {
+      int next = 0;
+      if (!gave_up && !again[id])
+        for (int r : hs) if (r > R && admits(r, id)) { next = r; break; }
+      if (next) { groups[next].push_back(id); again[id] = 1; ctx->prefix_second_pass += 1; }
+      else offenders.push_back(id);
+    }
+  }
+  used = true;
+  return 0;
 }
 
 // All queries of `q` against one range of the reference: argmax cells and traceback views (into buffers the context
@@ -1084,8 +1447,12 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
         // A probed bucket of at least kPrefixChain reads takes its heights as a chain, with one taller pass for the offenders of the
         // height it starts at (prefix_chain; options no_prefix_cascade, no_prefix_low: the flow below, as for the smaller buckets)
         if (b.count >= kPrefixChain && !opt().no_prefix_cascade && !opt().no_prefix_low) {
-          bool failed = false;
-          int rc = prefix_chain(ctx, ref, q, rg, p, table, b, qchunk, qwarm, loc, qdone, offenders, failed);
+          // ... unless seed hits give most of its reads their B0 before any sweep: then every read runs at the lowest height that can
+          // certify IT, and there is no probe (prefix_seeded; option no_prefix_seed, size gate prefix_seed_min_cols)
+          bool failed = false, seeded = false;
+          int rc = prefix_seeded(ctx, ref, q, rg, p, table, b, qchunk, qwarm, loc, qdone, offenders, seeded);
+          if (rc) return rc;
+          if (!seeded) rc = prefix_chain(ctx, ref, q, rg, p, table, b, qchunk, qwarm, loc, qdone, offenders, failed);
           if (rc) return rc;
           const int ndone = failed ? kPrefixProbe : b.count;
           for (int k = 0; k < ndone; ++k) tried[q.order[b.first + k]] = 1;
@@ -1600,9 +1967,10 @@ int range_maxima(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     // ... (option prefix_rowp = R, a listed R whose prefix is shorter than the bucket's reads) by the instance of R rows per lane that
     // folds row P = 2 R alone; the value rows stay readable (mi355_sw_prefix_values, tests/test_gpu_prefix_rowp_tiles.py)
     // (option prefix_rowp_step = R: the instance that folds row P at every step, tests/test_gpu_prefix_step_tiles.py)
-    const bool hook_step = listed(kR8M, opt().prefix_rowp_step);
+    // (the step tiles also at the low heights of kR2Step, R = 8 and 10: tests/test_gpu_prefix_low_tiles.py)
+    const bool hook_step = prefix_step_listed(opt().prefix_rowp_step);
     const long hook_R = hook_step ? opt().prefix_rowp_step : opt().prefix_rowp;
-    if (listed(kR8M, hook_R) && nr == 1 && !winner_only && b.fast && b.sem == kSemF16 && b.mirror && !b.strips && !b.twin && !b.satflag &&
+    if ((hook_step || listed(kR8M, hook_R)) && nr == 1 && !winner_only && b.fast && b.sem == kSemF16 && b.mirror && !b.strips && !b.twin && !b.satflag &&
         !b.unsat && b.SL == 8 && b.count >= 2 && kernel_sem(b) == kSemF16M && kPrefixLanes * hook_R < q.len[q.order[b.first]] && ctx->hook_ids.empty()) {
       b.SL = kPrefixLanes; b.R = (int)hook_R; b.prefix = true; b.sampled = true; b.rowp = true; b.step = hook_step;
       for (int k = 0; k < b.count; ++k) ctx->hook_ids.push_back(q.order[b.first + k]);
@@ -1732,7 +2100,7 @@ void reset_timings(mi355_sw_ctx *ctx) {
   for (double &t : ctx->timings) t = 0;
   ctx->score_ev_used = 0; ctx->arenas.clear(); ctx->cons_used = 0;
   ctx->last_kernel = mi355_sw_kernel_info{};
-  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
+  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->prefix_seeded = 0; ctx->prefix_seed_hits = 0; ctx->prefix_calibrated = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
   ctx->hook_ids.clear(); ctx->hook_nsub = 0;
   ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->walk_widened = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
   ctx->path.clear();

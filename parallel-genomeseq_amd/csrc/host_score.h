@@ -47,6 +47,7 @@ struct Bucket {
   bool step = false;          // ... at EVERY step (the MK = 1 instances): the values are row P's maxima, rowp_slack is 0
   bool second = false;        // ... the taller second pass over the offenders of a lower one (host_pipeline.h prefix_chain): its cells are
                               // counted, the call's kernel_info keeps describing the pass that swept the bucket
+  bool bulk = false;          // ... a pass of the seeded flow (host_pipeline.h prefix_seeded): the tile length of the chained main pass, whatever its size
   int64_t warm = 0;           // exactness margin in columns
   bool fast = false;          // swept by the score kernel (else whole-matrix exact path)
   int64_t chunk_len = 0;      // own columns per tile
@@ -63,7 +64,10 @@ constexpr int kR64S[] = {20, 24, 32};                          // whole-wavefron
 constexpr int kR8M[] = {13, 16, 19, 26, 32};                   // sampled maximum (MK = 4) on 8-lane tiles
 constexpr int kR16M[] = {10, 12, 16, 20, 24, 32};              // ... on 16-lane and whole-wavefront tiles
 constexpr int kPrefixLanes = 2;                                // lanes of a prefix tile (lemma L19): P = kPrefixLanes * R rows, on the kR8M list
+constexpr int kR2Step[] = {8, 10};                             // ... LOW step tiles (P = 16, 20): a list and a table of their own (kLowStepKernels), the 8-lane families do not grow
 template <size_t N> constexpr bool listed(const int (&rs)[N], long r) { for (int v : rs) if (v == r) return true; return false; }
+// the heights the tiles that fold row P at every step are compiled at
+constexpr bool prefix_step_listed(long r) { return listed(kR8M, r) || listed(kR2Step, r); }
 
 // sw_score_kernel<R, sem, strips, SL, twin, comb, mk, rowp>
 struct ScoreInst {
@@ -147,6 +151,18 @@ template <size_t... I> constexpr std::array<ScoreKernel, sizeof...(I)> score_ker
                            kScoreInsts[I].comb, kScoreInsts[I].mk, kScoreInsts[I].rowp>...};
 }
 constexpr std::array<ScoreKernel, kScoreInsts.size()> kScoreKernels = score_kernels(std::make_index_sequence<kScoreInsts.size()>{});
+// The LOW step tiles of the seeded prefix flow (kR2Step: P = 16 and 20, row P folded at every step) stand in a table of their own.
+// kScoreShapes is the table whose rows the raw-maxima modules partition among themselves, the prefix rows being exactly kR8M at its
+// three folds (tests/test_lone_strip_instances_ref.py); these two have one fold, one cell type and one owner,
+// tests/test_gpu_prefix_low_tiles.py (tests/test_prefix_low_tiles_table_ref.py keeps the two lists equal).
+template <size_t... I> constexpr std::array<ScoreKernel, sizeof...(I)> low_step_kernels(std::index_sequence<I...>) {
+  static_assert((score_instance_ok<kSemF16M>(kR2Step[I], false, kPrefixLanes, false, false, 1, true) && ...), "an illegal low step tile");
+  return {&sw_score_kernel<kR2Step[I], kSemF16M, false, kPrefixLanes, false, false, 1, true>...};
+}
+constexpr auto kLowStepKernels = low_step_kernels(std::make_index_sequence<std::size(kR2Step)>{});
+constexpr bool low_step_inst(const ScoreInst &i) {
+  return listed(kR2Step, i.R) && i.sem == kSemF16M && !i.strips && i.SL == kPrefixLanes && !i.twin && !i.comb && i.mk == 1 && i.rowp;
+}
 
 int pick_R(int maxlen) {
   const int need = (maxlen + 15) / 16;
@@ -502,6 +518,13 @@ int launch_score(const ScoreInst &want, dim3 grid, size_t shmem, hipStream_t st,
     hipLaunchKernelGGL(kScoreKernels[k], grid, dim3(256), shmem, st, a);
     return 0;
   }
+  for (size_t k = 0; low_step_inst(want) && k < std::size(kR2Step); ++k) {
+    if (kR2Step[k] != want.R) continue;
+    if (shmem > 48 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kLowStepKernels[k]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    hipLaunchKernelGGL(kLowStepKernels[k], grid, dim3(256), shmem, st, a);
+    return 0;
+  }
   return -1;
 }
 
@@ -528,7 +551,7 @@ float prefix_bound(const ScoreTable &t, int m, int P, float slack, bool rowp) {
 // ... on R rows per lane (the bucket's own R, or a lower listed one), with either fold
 bool prefix_height_ok(const ScoreTable &t, const Bucket &b, int minlen, int R, bool rowp, bool step = false) {
   const int P = kPrefixLanes * R;
-  if (!listed(kR8M, R) || minlen <= P) return false;
+  if (!(rowp && step ? prefix_step_listed(R) : listed(kR8M, R)) || minlen <= P) return false;
   return (float)t.smax * (float)minlen > prefix_bound(t, b.maxlen, P, rowp ? rowp_slack(t, rowp_mk(step)) : sample_slack(t, b), rowp);
 }
 bool prefix_ok(const ScoreTable &t, const Bucket &b, int minlen, int64_t n, const mi355_sw_params &p) {
@@ -552,6 +575,15 @@ std::vector<int> prefix_heights(const ScoreTable &t, const Bucket &b, int minlen
   std::vector<int> hs;
   for (int r : kR8M) if (r < b.R && prefix_height_ok(t, b, minlen, r, true, step)) hs.push_back(r);
   hs.push_back(b.R);
+  return hs;
+}
+// ... of the SEEDED flow (host_pipeline.h prefix_seeded), which knows a read's B0 before any sweep and gives every read the lowest
+// height that can certify it: the low step tiles of kR2Step in front of the chain's.  Ascending (kR2Step lies below kR8M).
+static_assert(kR2Step[std::size(kR2Step) - 1] < kR8M[0], "prefix_heights_seeded: ascending");
+std::vector<int> prefix_heights_seeded(const ScoreTable &t, const Bucket &b, int minlen) {
+  std::vector<int> hs;
+  for (int r : kR2Step) if (r < b.R && prefix_height_ok(t, b, minlen, r, true, true)) hs.push_back(r);
+  for (int r : prefix_heights(t, b, minlen, true)) hs.push_back(r);
   return hs;
 }
 // The height the rest of a chained bucket starts at.  P[i] are the heights' prefix rows; o[i] of the kPrefixProbe probe reads cannot be
@@ -1012,7 +1044,10 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     const int64_t cl0 = pick_chunk_len(maxlen, npairs * nr, b.warm, b.SL, b.twin, b.maxlen, b.sub_len, 0);
     while (2 * cl0 / b.sub_len > 64) b.sub_len *= 2;
   }
-  const bool chain_main = b.prefix && b.rowp && b.step && !b.second && b.SL == kPrefixLanes && b.count >= kPrefixChain - kPrefixProbe;
+  // (the groups of the seeded flow take the main pass's tiles at every size: the bench batch's four groups of 1119, 526, 355 and 48
+  // reads under option chunk = 16384 / 32768 / 65536 for all of them: 90.76 / 99.41 / 114.82 ms per call, against 93.24 with 16384
+  // for the largest group alone — profiles/prefix_seed_tile_lengths.json)
+  const bool chain_main = b.prefix && b.rowp && b.step && b.SL == kPrefixLanes && (b.bulk || (!b.second && b.count >= kPrefixChain - kPrefixProbe));
   b.chunk_len = pick_chunk_len(maxlen, npairs * nr, b.warm, b.SL, b.twin, b.maxlen, b.sub_len, free_sub ? 64 * kSeg : b.sub_len, chain_main);
   if (free_sub && b.chunk_len % (64 * kSeg) == 0) b.sub_len = b.chunk_len / 64;
   if (b.strips) while (b.chunk_len / b.sub_len > 64) b.sub_len *= 2;      // the strip-mined instances keep <= 64 sub-chunk maxima in LDS

@@ -29,6 +29,7 @@
 #include <condition_variable>
 #include <functional>
 #include <iterator>
+#include <map>
 #include <future>
 #include <mutex>
 #include <thread>
@@ -45,6 +46,7 @@
 #include "sw_exact_kernel.h"
 #include "sw_score_kernel.h"
 #include "sw_prefix_thin_kernel.h"
+#include "sw_seed_kernel.h"
 #include "sw_wave_kernel.h"
 #include "sw_strip_kernel.h"
 #include "sw_batch_kernels.h"
@@ -111,9 +113,9 @@ void mi355_sw_destroy(mi355_sw_ctx *c) {
   (void)hipSetDevice(c->device);
   DevBuf *bufs[] = {&c->qcnt, &c->sel2, &c->gcnt, &c->wlut, &c->ref.bytes, &c->ref.codes, &c->batch.bytes, &c->batch.lens, &c->keys, &c->ranges, &c->stab,
                     &c->batch.offs, &c->batch.sel, &c->colsave, &c->rowsave, &c->pieces, &c->ftab, &c->ftab_s, &c->htab, &c->htab8, &c->soloblk, &c->flags, &c->submax, &c->lut, &c->probs, &c->dirs, &c->outs_f, &c->outs_i, &c->cons, &c->walkp, &c->hmat, &c->brow, &c->wprobs, &c->scan, &c->batch.cum, &c->ckpt, &c->first, &c->recs, &c->atab, &c->aprof, &c->pkeys, &c->pthr, &c->psel, &c->psel2,
-                    &c->rev_codes, &c->rev_bytes, &c->rev_q, &c->thin_items, &c->thin_out, &c->thin_vals};
+                    &c->rev_codes, &c->rev_bytes, &c->rev_q, &c->thin_items, &c->thin_out, &c->thin_vals, &c->seed_tab, &c->seed_hits};
   for (DevBuf *b : bufs) b->release();
-  c->adhoc.release(); c->one.release();
+  c->adhoc.release(); c->one.release(); c->calib_q.release();
   c->pin_probs.release(); c->pin_walk.release(); c->pin_out.release(); c->pin_solo_up.release(); c->pin_solo_down.release();
   for (PinBuf &b : c->pin_cons) b.release();
   for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
@@ -791,6 +793,9 @@ int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *o
   else if (k == "prefix_second_pass") *out = ctx->prefix_second_pass;
   else if (k == "prefix_thinned") *out = ctx->prefix_thinned;
   else if (k == "prefix_thin_items") *out = ctx->prefix_thin_items;
+  else if (k == "prefix_seeded") *out = ctx->prefix_seeded;
+  else if (k == "prefix_seed_hits") *out = ctx->prefix_seed_hits;
+  else if (k == "prefix_calibrated") *out = ctx->prefix_calibrated;
   else if (k == "left_window") *out = ctx->left_window;
   else if (k == "beyond_f16") *out = ctx->beyond_f16;
   else if (k == "first_settled") *out = ctx->first_settled;
@@ -857,6 +862,42 @@ int mi355_sw_prefix_thin_items(mi355_sw_ctx *ctx, size_t n_items, const uint32_t
   rc = run_thin(ctx, ref, q, rg, table, tp, sub_len, list, thr2, kept, &vals);
   if (rc) return rc;
   std::copy(vals.begin(), vals.end(), values);
+  return 0;
+}
+
+int mi355_sw_seed_k(int letters, int min_len, int64_t n) { return seed_k(letters, min_len, n); }
+
+uint32_t mi355_sw_seed_hash(const uint8_t *codes, int k) { return codes && k > 0 ? seed_hash(codes, k) : 0u; }
+
+int mi355_sw_seed_cluster(size_t n_hits, const int64_t *starts, const int32_t *offsets, int64_t width, int64_t *lo, int64_t *hi, int *distinct) {
+  if ((n_hits && (!starts || !offsets)) || !lo || !hi || !distinct || width < 0) return MI355_SW_EINVAL;
+  std::vector<SeedHit> hits(n_hits);
+  for (size_t k = 0; k < n_hits; ++k) hits[k] = SeedHit{starts[k], offsets[k]};
+  *lo = 0; *hi = 0; *distinct = 0;
+  return seed_cluster(hits, width, *lo, *hi, *distinct) ? 1 : 0;
+}
+
+int mi355_sw_seed_hits(mi355_sw_ctx *ctx, int64_t left, int64_t right, int k, uint32_t *counts, int64_t *starts, int32_t *offsets, int *k_used) {
+  if (!ctx || !counts || !starts || !offsets) return MI355_SW_EINVAL;
+  OptScope opt_scope_(ctx);
+  const QueryBatch &q = ctx->batch;
+  const RefData &ref = ctx->ref;
+  if (left < 0 || right < left || right > (int64_t)ref.n) return fail(ctx, MI355_SW_EINVAL, "range outside the resident reference");
+  if (q.nq == 0) return fail(ctx, MI355_SW_EINVAL, "mi355_sw_seed_hits: no resident batch");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (k == 0) k = seed_k(ref.ncodes - 1, q.len[q.order[0]], right - left);
+  if (k < 1 || k > kSeedMaxK) return fail(ctx, MI355_SW_ENOTSUP, "mi355_sw_seed_hits: no seed length for these reads and this range");
+  if (k_used) *k_used = k;
+  std::vector<int32_t> ids(q.nq);
+  for (size_t i = 0; i < q.nq; ++i) ids[i] = (int32_t)i;
+  std::vector<uint32_t> count;
+  std::vector<int64_t> start;
+  std::vector<int32_t> hoff;
+  const int rc = seed_scan(ctx, ref, q, Range{left, right}, ids, k, count, start, hoff);
+  if (rc) return rc;
+  std::copy(count.begin(), count.end(), counts);
+  std::copy(start.begin(), start.end(), starts);
+  std::copy(hoff.begin(), hoff.end(), offsets);
   return 0;
 }
 

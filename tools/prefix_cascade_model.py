@@ -16,6 +16,10 @@ what the thin stage (P2 = 38) takes off that — the reads it rescues, its items
 --heights takes the prefix rows P to model (default: twice the rows per lane above); with it the line also carries `flows`: the rows
 swept per batch, a full sweep counted as read-len rows, by a chain that starts at P[i] with one second pass at P[j]
 (sw_prefix_kernel's heights: --heights 18,20,22,24,26,28,30,32,38, slack 0).
+
+--per-read takes sets of prefix rows, ';' between the sets (their union goes to --heights): the seeded flow (prefix_seeded), where B0
+is known before any sweep and every read takes the lowest height of the set that can certify it — `per_read`: flags by deficit, rows
+swept per read, reads per height (--per-read "26,32,38;16,20,26,32,38" --heights 16,20,26,32,38).
 """
 import argparse
 import json
@@ -90,6 +94,8 @@ def main(argv=None):
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--heights", type=lambda v: [int(t) for t in v.split(",")], default=None, help="prefix rows P to model, comma separated")
     ap.add_argument("--thin-cap", type=int, default=1024, help="flags a read may list for the thin stage (host_score.h thin_flag_cap)")
+    ap.add_argument("--per-read", type=lambda v: [[int(t) for t in s.split(",")] for s in v.split(";")], default=None,
+                    help="sets of prefix rows for a height per read, e.g. '26,32,38;16,20,26,32,38' (give the union to --heights)")
     args = ap.parse_args(argv)
     import __graft_entry__ as entry
     pgs = entry._load_package()
@@ -132,7 +138,38 @@ def main(argv=None):
         line["heights"] = sorted(flags)
         line["flows"] = {"%d->%d" % (a, b): args.reads * a + off[a] * b + off[b] * m for a in sorted(flags) for b in sorted(flags) if a < b}
         line["flows"].update({"%d" % a: args.reads * a + off[a] * m for a in sorted(flags)})
+    if args.per_read:
+        line["per_read"] = per_read(flags, d, m, args.per_read)
     print(json.dumps(line))
+
+
+def per_read(flags, d, m, height_sets):
+    """The seeded flow (prefix_seeded): B0 of every read is known before any sweep, and the read takes the lowest height
+    of the set whose bound its B0 clears and whose expected background flags at its deficit stay within the cap; a read no height
+    takes is swept on all m rows.  Per set of heights: the expected flags by deficit, the rows swept per read, the reads per height
+    and the flags (thin items, where the thin stage takes them) the passes are expected to draw."""
+    out = {}
+    for hs in height_sets:
+        hs = [P for P in sorted(hs) if P in flags]
+        rows_swept, groups, items = 0, {}, 0.0
+        for dd in d:
+            pick = None
+            for P in hs:
+                if dd >= MATCH * P or MATCH * m - dd <= MATCH * max(P, m - P):
+                    continue
+                f = float(flags[P][min(int(dd), len(flags[P]) - 1)])
+                if f <= CAP:
+                    pick = P
+                    items += f
+                    break
+            pick = pick or m
+            rows_swept += pick
+            groups[pick] = groups.get(pick, 0) + 1
+        out[",".join(str(P) for P in hs)] = dict(
+            rows_per_read=round(rows_swept / len(d), 2), against_26=round(rows_swept / len(d) / 26.0, 3),
+            reads_per_height={str(P): n for P, n in sorted(groups.items())}, expected_flags=round(items, 1))
+    out["flags_by_deficit"] = {str(P): {str(x): round(float(f[x]), 1) for x in (0, 6, 12, 18, 24, 30) if x < len(f)} for P, f in sorted(flags.items())}
+    return out
 
 
 if __name__ == "__main__":
