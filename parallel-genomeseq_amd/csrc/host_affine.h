@@ -11,6 +11,10 @@
 //   affine_global the pairs of affine_extend anchored at both ends, plain and banded (the gap fill between two seeds of a chain): affine_extend's
 //                 items and stages on sw_affine_pair_glob_kernel, sw_affine_band_glob_kernel and sw_affine_exact_glob_kernel, its
 //                 traceback started at the corner
+// The list kernels of the last three are seven names on two geometries (sw_affine_pair_kernel.h, sw_affine_band_kernel.h: one body per
+// geometry, a name is an entry point that names its mode); affine_list_stage runs them through one family template per geometry,
+// AffinePairFamily<M> and AffineBandFamily<M>, over a mode description M that holds what differs: the kernel instance of an R, the
+// results per problem, the names, the op count and where an item comes from.
 // All share one AffineCall (affine_begin .. affine_end, the latter with affine_trace: sw_affine_trace_kernel), affine_exact_stage
 // (sw_affine_exact_kernel), affine_class_table, affine_download and affine_note_kernel.
 namespace {
@@ -806,70 +810,119 @@ int affine_band_R(int64_t W) {
 }
 
 // A kernel family as affine_list_stage takes it: the problem and the item it is made from, the instance R of either, what comes first
-// among items of one R (the larger `size`), the instance itself, the cells of a problem and the description of a launch.
-// sw_affine_pair_kernel / sw_affine_pair_e2e_kernel (by the call's mode): an item is the pair's index.
+// among items of one R (the larger `size`), the instance itself, the cells of a problem and the description of a launch.  There is
+// one family per geometry of the list kernels — AffinePairFamily (sw_affine_pair_kernel.h: sized by the window's length) and
+// AffineBandFamily (sw_affine_band_kernel.h: sized by rows) — over a MODE M, which holds what differs between the kernels of a
+// geometry and nothing else:
+//   M::Source                 where an item comes from: the caller's pair list (AffineListedPair, AffineListedBandPair) or an item
+//                             with its own pointers (AffineOwnItem, behind AffineExtItem): Item, id, rows, cols / W, fill
+//   M::kernel<R>(c)           the kernel instance of an R
+//   M::kOuts, M::keep_all(c)  (best, cell) a problem writes; whether a result that is not positive is kept
+//   M::path(c), M::name(c)    the two name strings of a launch (path_note, mi355_sw_last_kernel)
+//   M::ops(c, R)              the op count per cell of the compiled row loop
+//   M::kNoInstance            the message of a missing instance
+template <class M>
 struct AffinePairFamily {
-  typedef AffinePairProblem Problem; typedef uint32_t Item;
-  const AffineCall &c; const AffinePairList &pl;
-  static constexpr const char *kNoInstance = "internal: no sw_affine_pair_kernel instance for this query";
-  static constexpr int kOuts = 1;                                  // (best, cell) a problem writes
-  bool keep_all() const { return c.e2e(); }                        // end-to-end: a score may be <= 0
-  static uint32_t id(Item a) { return a; }
-  int R(Item a) const { return affine_pair_R(c.q.len[pl.qid[a]]); }
+  typedef AffinePairProblem Problem; typedef typename M::Source Source; typedef typename Source::Item Item;
+  const AffineCall &c; Source src;
+  static constexpr const char *kNoInstance = M::kNoInstance;
+  static constexpr int kOuts = M::kOuts;
+  bool keep_all() const { return M::keep_all(c); }
+  static uint32_t id(const Item &a) { return Source::id(a); }
+  int R(const Item &a) const { return affine_pair_R(src.rows(c, a)); }
   static int R(const Problem &p) { return affine_pair_R(p.m); }
-  int64_t size(Item a) const { return pl.cols(a); }                // longest window first: the slots of a wavefront run similar step counts
-  void fill(Item a, Problem &p) const { affine_pair_fill(c, pl, a, p); }
+  int64_t size(const Item &a) const { return src.cols(a); }        // longest window first: the slots of a wavefront run similar step counts
+  void fill(const Item &a, Problem &p) const { src.fill(c, a, p); }
   static double cells(const Problem &p) { return (double)p.m * (double)p.n; }
   auto kernel(int R) const {
     void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
-    with_listed_R<kPairR>(R, [&](auto r) {
-      kern = c.e2e() ? &sw_affine_pair_e2e_kernel<decltype(r)::value> : &sw_affine_pair_kernel<decltype(r)::value>;
-    });
+    with_listed_R<kPairR>(R, [&](auto r) { kern = M::template kernel<decltype(r)::value>(c); });
     return kern;
   }
   void note(double cells, int R, const Problem &first) const {
-    // end-to-end, per step and lane: seven ops, the table address' v_add and the winner row's select per cell, and eleven of overhead
-    // (the local instance's twelve without the key's v_or); no key, no maximum3 fold.  The 16 border steps of a slot are not counted
-    // local, per step and lane: seven ops, the table address' v_add and the key's v_or per cell, a maximum3 per two cells for the
-    // step's best key, and twelve of overhead as compiled (two DPP moves and their two copies, the row pointer's multiply
-    // and add, the column, the code's address, and compare, two selects and the v_or of the value-only key update)
-    const double ops = c.e2e() ? (9.0 * R + 11.0) / (double)R : (9.0 * R + (R + 1) / 2 + 12.0) / (double)R;
-    path_note(c.ctx, c.e2e() ? "affine_pair_e2e[R=%d]" : "affine_pair[R=%d]", R);
-    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, first.n, first.n, 0, ops,
-                       c.e2e() ? "sw_affine_pair_e2e_kernel<R=%d>" : "sw_affine_pair_kernel<R=%d>", R);
+    path_note(c.ctx, M::path(c), R);
+    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, first.n, first.n, 0, M::ops(c, R), M::name(c), R);
+  }
+};
+template <class M>
+struct AffineBandFamily {
+  typedef AffineBandProblem Problem; typedef typename M::Source Source; typedef typename Source::Item Item;
+  const AffineCall &c; Source src;
+  static constexpr const char *kNoInstance = M::kNoInstance;
+  static constexpr int kOuts = M::kOuts;
+  bool keep_all() const { return M::keep_all(c); }
+  static uint32_t id(const Item &a) { return Source::id(a); }
+  static int R(const Item &a) { return affine_band_R(a.W); }
+  static int R(const Problem &p) { return affine_band_R(p.W); }
+  int64_t size(const Item &a) const { return src.rows(c, a); }     // longest query first: the slots of a wavefront leave the row loop at similar steps
+  void fill(const Item &a, Problem &p) const { src.fill(c, a, p); }
+  static double cells(const Problem &p) { return (double)p.m * (double)p.W; }
+  auto kernel(int R) const {
+    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
+    with_listed_R<kBandR>(R, [&](auto r) { kern = M::template kernel<decltype(r)::value>(c); });
+    return kern;
+  }
+  void note(double cells, int R, const Problem &) const {          // all 16 R registers of a lane row work whatever W is: the model's time is rows x 16 R
+    path_note(c.ctx, M::path(c), R);
+    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, 16 * R, 16 * R, 0, M::ops(c, R), M::name(c), R);
   }
 };
 
 // One banded pair as the band kernel takes it: the band clipped to the matrix, its lowest diagonal and its width.
 struct AffineBandPair { uint32_t id; int32_t lo, W; };
 
-// sw_affine_band_kernel (sw_affine_band_kernel.h): pairs with a diagonal band; the table is the pair kernel's.
-struct AffineBandFamily {
-  typedef AffineBandProblem Problem; typedef AffineBandPair Item;
-  const AffineCall &c; const AffinePairList &pl;
+// Items of the caller's pair list (affine_pairs): the pair's index, for the band kernel with its band
+struct AffineListedPair {
+  typedef uint32_t Item;
+  const AffinePairList &pl;
+  static uint32_t id(Item a) { return a; }
+  int rows(const AffineCall &c, Item a) const { return c.q.len[pl.qid[a]]; }
+  int64_t cols(Item a) const { return pl.cols(a); }
+  void fill(const AffineCall &c, Item a, AffinePairProblem &p) const { affine_pair_fill(c, pl, a, p); }
+};
+struct AffineListedBandPair {
+  typedef AffineBandPair Item;
+  const AffinePairList &pl;
+  static uint32_t id(const Item &a) { return a.id; }
+  int rows(const AffineCall &c, const Item &a) const { return c.q.len[pl.qid[a.id]]; }
+  void fill(const AffineCall &c, const Item &a, AffineBandProblem &p) const { affine_pair_fill(c, pl, a.id, p); p.lo = a.lo; p.W = a.W; }
+};
+
+// sw_affine_pair_kernel / sw_affine_pair_e2e_kernel, by the call's mode
+struct AffinePairMode {
+  typedef AffineListedPair Source;
+  static constexpr const char *kNoInstance = "internal: no sw_affine_pair_kernel instance for this query";
+  static constexpr int kOuts = 1;
+  static bool keep_all(const AffineCall &c) { return c.e2e(); }    // end-to-end: a score may be <= 0
+  template <int R> static auto kernel(const AffineCall &c) { return c.e2e() ? &sw_affine_pair_e2e_kernel<R> : &sw_affine_pair_kernel<R>; }
+  static const char *path(const AffineCall &c) { return c.e2e() ? "affine_pair_e2e[R=%d]" : "affine_pair[R=%d]"; }
+  static const char *name(const AffineCall &c) { return c.e2e() ? "sw_affine_pair_e2e_kernel<R=%d>" : "sw_affine_pair_kernel<R=%d>"; }
+  static double ops(const AffineCall &c, int R) {
+    // end-to-end, per step and lane: seven ops, the table address' v_add and the winner row's select per cell, and eleven of overhead
+    // (the local instance's twelve without the key's v_or); no key, no maximum3 fold.  The 16 border steps of a slot are not counted
+    // local, per step and lane: seven ops, the table address' v_add and the key's v_or per cell, a maximum3 per two cells for the
+    // step's best key, and twelve of overhead as compiled (two DPP moves and their two copies, the row pointer's multiply
+    // and add, the column, the code's address, and compare, two selects and the v_or of the value-only key update)
+    return c.e2e() ? (9.0 * R + 11.0) / (double)R : (9.0 * R + (R + 1) / 2 + 12.0) / (double)R;
+  }
+};
+
+// sw_affine_band_kernel: pairs with a diagonal band; the table is the pair kernel's.
+struct AffineBandMode {
+  typedef AffineListedBandPair Source;
   static constexpr const char *kNoInstance = "internal: no sw_affine_band_kernel instance for this band";
   static constexpr int kOuts = 1;
-  bool keep_all() const { return false; }
-  static uint32_t id(const Item &a) { return a.id; }
-  static int R(const Item &a) { return affine_band_R(a.W); }
-  static int R(const Problem &p) { return affine_band_R(p.W); }
-  int64_t size(const Item &a) const { return c.q.len[pl.qid[a.id]]; }   // longest query first: the slots of a wavefront leave the row loop at similar steps
-  void fill(const Item &a, Problem &p) const { affine_pair_fill(c, pl, a.id, p); p.lo = a.lo; p.W = a.W; }
-  static double cells(const Problem &p) { return (double)p.m * (double)p.W; }
-  auto kernel(int R) const {
-    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
-    with_listed_R<kBandR>(R, [&](auto r) { kern = &sw_affine_band_kernel<decltype(r)::value>; });
-    return kern;
-  }
-  void note(double cells, int R, const Problem &) const {
-    path_note(c.ctx, "affine_band[R=%d]", R);
+  static bool keep_all(const AffineCall &) { return false; }
+  template <int R> static auto kernel(const AffineCall &) { return &sw_affine_band_kernel<R>; }
+  static const char *path(const AffineCall &) { return "affine_band[R=%d]"; }
+  static const char *name(const AffineCall &) { return "sw_affine_band_kernel<R=%d>"; }
+  static double ops(const AffineCall &, int R) {
     // per step and lane, as compiled: fourteen ops per register — the table address' multiply-add, the clamped add,
     // sub / max for F, max for Ht, Ht - o, sub / max of the lane's scan, maximum3 for H, the cap's min, the key's v_or, H - o, the
     // carry's sub and one move — a maximum3 per two registers for the step's key, and 29 of overhead: two DPP moves for F, five DPP
     // moves (each with the move of its `old`) and four sub / max pairs for the lanes' scan, the explicit (value, column) compare
-    // with its selects, the window addresses.  All 16 R registers of a lane row work whatever W is: the model's time is rows x 16 R
-    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, 16 * R, 16 * R, 0, (14.0 * R + (R + 1) / 2 + 29.0) / (double)R,
-                       "sw_affine_band_kernel<R=%d>", R);
+    // with its selects, the window addresses
+    return (14.0 * R + (R + 1) / 2 + 29.0) / (double)R;
   }
 };
 
@@ -1050,8 +1103,8 @@ int affine_pairs(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, int
   }
 
   // (one class table per list stage, each for its own tallest query)
-  rc = affine_list_stage(AffinePairFamily{c, pl}, plan, fast, mmax, score, ends);
-  if (!rc) rc = affine_list_stage(AffineBandFamily{c, pl}, plan, band, band_mmax, score, ends);
+  rc = affine_list_stage(AffinePairFamily<AffinePairMode>{c, {pl}}, plan, fast, mmax, score, ends);
+  if (!rc) rc = affine_list_stage(AffineBandFamily<AffineBandMode>{c, {pl}}, plan, band, band_mmax, score, ends);
   if (!rc) rc = affine_exact_stage(c, jobs);
   if (!rc) rc = affine_exact_stage(c, bjobs);
   if (rc) return rc;
@@ -1191,62 +1244,50 @@ AffineExtItem affine_ext_item(const AffineCall &c, const AffineExtList &el, size
   return it;
 }
 
-// sw_affine_pair_ext_kernel for affine_list_stage: an item carries its own pointers; two results per problem (best extension, to
-// the end).
-struct AffineExtFamily {
-  typedef AffinePairProblem Problem; typedef AffineExtItem Item;
-  const AffineCall &c;
-  static constexpr const char *kNoInstance = "internal: no sw_affine_pair_ext_kernel instance for this query";
-  static constexpr int kOuts = 2;
-  bool keep_all() const { return true; }                           // a to-end score may be <= 0, a best extension is 0 at least
+// An item that carries its own pointers, its rows, its window and its band (AffineExtItem: affine_extend, affine_global)
+struct AffineOwnItem {
+  typedef AffineExtItem Item;
   static uint32_t id(const Item &a) { return a.id; }
-  static int R(const Item &a) { return affine_pair_R(a.m); }
-  static int R(const Problem &p) { return affine_pair_R(p.m); }
-  int64_t size(const Item &a) const { return a.n; }                // longest window first, as AffinePairFamily
-  void fill(const Item &a, Problem &p) const { p.x = a.x; p.y = a.ycodes; p.m = a.m; p.n = (int32_t)a.n; }
-  static double cells(const Problem &p) { return (double)p.m * (double)p.n; }
-  auto kernel(int R) const {
-    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
-    with_listed_R<kPairR>(R, [&](auto r) { kern = &sw_affine_pair_ext_kernel<decltype(r)::value>; });
-    return kern;
-  }
-  void note(double cells, int R, const Problem &first) const {
-    // per step and lane: the local instance's count (AffinePairFamily::note) and two more per cell: the max with 0 in front of the
-    // key and the row-m select; the row-0 subtract and max, the second compare and its selects are three more of overhead.  The 16
-    // border steps of a slot are not counted
-    path_note(c.ctx, "affine_pair_ext[R=%d]", R);
-    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, first.n, first.n, 0, (11.0 * R + (R + 1) / 2 + 15.0) / (double)R,
-                       "sw_affine_pair_ext_kernel<R=%d>", R);
+  static int rows(const AffineCall &, const Item &a) { return a.m; }
+  static int64_t cols(const Item &a) { return a.n; }
+  static void fill(const AffineCall &, const Item &a, AffinePairProblem &p) { p.x = a.x; p.y = a.ycodes; p.m = a.m; p.n = (int32_t)a.n; }
+  static void fill(const AffineCall &, const Item &a, AffineBandProblem &p) {   // the clipped window and the effective band
+    p.x = a.x; p.y = a.ycodes; p.m = a.m; p.n = (int32_t)a.n; p.lo = a.blo; p.W = a.W;
   }
 };
 
-// sw_affine_band_ext_kernel (sw_affine_band_kernel.h) for affine_list_stage: the banded pairs of the extension calls, an item with its
-// own pointers, its clipped window and its effective band; two results per problem, as AffineExtFamily.
-struct AffineBandExtFamily {
-  typedef AffineBandProblem Problem; typedef AffineExtItem Item;
-  const AffineCall &c;
+// sw_affine_pair_ext_kernel: two results per problem (best extension, to the end).
+struct AffineExtMode {
+  typedef AffineOwnItem Source;
+  static constexpr const char *kNoInstance = "internal: no sw_affine_pair_ext_kernel instance for this query";
+  static constexpr int kOuts = 2;
+  static bool keep_all(const AffineCall &) { return true; }        // a to-end score may be <= 0, a best extension is 0 at least
+  template <int R> static auto kernel(const AffineCall &) { return &sw_affine_pair_ext_kernel<R>; }
+  static const char *path(const AffineCall &) { return "affine_pair_ext[R=%d]"; }
+  static const char *name(const AffineCall &) { return "sw_affine_pair_ext_kernel<R=%d>"; }
+  static double ops(const AffineCall &, int R) {
+    // per step and lane: the local instance's count (AffinePairMode::ops) and two more per cell: the max with 0 in front of the
+    // key and the row-m select; the row-0 subtract and max, the second compare and its selects are three more of overhead.  The 16
+    // border steps of a slot are not counted
+    return (11.0 * R + (R + 1) / 2 + 15.0) / (double)R;
+  }
+};
+
+// sw_affine_band_ext_kernel: the banded pairs of the extension calls; two results per problem, as AffineExtMode.
+struct AffineBandExtMode {
+  typedef AffineOwnItem Source;
   static constexpr const char *kNoInstance = "internal: no sw_affine_band_ext_kernel instance for this band";
   static constexpr int kOuts = 2;
-  bool keep_all() const { return true; }
-  static uint32_t id(const Item &a) { return a.id; }
-  static int R(const Item &a) { return affine_band_R(a.W); }
-  static int R(const Problem &p) { return affine_band_R(p.W); }
-  int64_t size(const Item &a) const { return a.m; }                // longest query first, as AffineBandFamily
-  void fill(const Item &a, Problem &p) const { p.x = a.x; p.y = a.ycodes; p.m = a.m; p.n = (int32_t)a.n; p.lo = a.blo; p.W = a.W; }
-  static double cells(const Problem &p) { return (double)p.m * (double)p.W; }
-  auto kernel(int R) const {
-    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
-    with_listed_R<kBandR>(R, [&](auto r) { kern = &sw_affine_band_ext_kernel<decltype(r)::value>; });
-    return kern;
-  }
-  void note(double cells, int R, const Problem &) const {
-    path_note(c.ctx, "affine_band_ext[R=%d]", R);
-    // per step and lane, as compiled: the local band instance's count (AffineBandFamily::note), one more per register — the max with
+  static bool keep_all(const AffineCall &) { return true; }
+  template <int R> static auto kernel(const AffineCall &) { return &sw_affine_band_ext_kernel<R>; }
+  static const char *path(const AffineCall &) { return "affine_band_ext[R=%d]"; }
+  static const char *name(const AffineCall &) { return "sw_affine_band_ext_kernel<R=%d>"; }
+  static double ops(const AffineCall &, int R) {
+    // per step and lane, as compiled: the local band instance's count (AffineBandMode::ops), one more per register — the max with
     // 0 in front of the key — and four more of overhead (the compare of the step's row with the slot's m in front of the to-end
     // branch, and moves of the -inf operands).  The branch's four scalar compares are no vector ops, and its fold (six ops per
-    // register) runs at one step of a slot's rows: not counted.  All 16 R registers of a lane row work whatever W is
-    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, 16 * R, 16 * R, 0, (15.0 * R + (R + 1) / 2 + 33.0) / (double)R,
-                       "sw_affine_band_ext_kernel<R=%d>", R);
+    // register) runs at one step of a slot's rows: not counted
+    return (15.0 * R + (R + 1) / 2 + 33.0) / (double)R;
   }
 };
 
@@ -1496,8 +1537,8 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     }
     jobs.push_back(it);
   }
-  rc = affine_list_stage(AffineExtFamily{c}, plan, fast, mmax, score, ends);
-  if (!rc) rc = affine_list_stage(AffineBandExtFamily{c}, plan, bfast, band_mmax, score, ends);
+  rc = affine_list_stage(AffinePairFamily<AffineExtMode>{c, {}}, plan, fast, mmax, score, ends);
+  if (!rc) rc = affine_list_stage(AffineBandFamily<AffineBandExtMode>{c, {}}, plan, bfast, band_mmax, score, ends);
   if (!rc) rc = affine_ext_exact_stage(c, jobs, score, ends);
   if (!rc) rc = affine_ext_exact_stage<true>(c, bjobs, score, ends);
   if (rc) return rc;
@@ -1524,64 +1565,42 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
 }
 
 // ---- global alignment between two anchors (include/mi355_sw.h "global alignment between two anchors", DESIGN.md §3.8 lemma L23) ----
-// sw_affine_pair_glob_kernel for affine_list_stage: AffineExtFamily's items, one result per problem, the corner H(m, n).
-struct AffineGlobFamily {
-  typedef AffinePairProblem Problem; typedef AffineExtItem Item;
-  const AffineCall &c;
+// sw_affine_pair_glob_kernel: AffineExtMode's items, one result per problem, the corner H(m, n).
+struct AffineGlobMode {
+  typedef AffineOwnItem Source;
   static constexpr const char *kNoInstance = "internal: no sw_affine_pair_glob_kernel instance for this query";
   static constexpr int kOuts = 1;
-  bool keep_all() const { return true; }                           // the corner's value may have any sign
-  static uint32_t id(const Item &a) { return a.id; }
-  static int R(const Item &a) { return affine_pair_R(a.m); }
-  static int R(const Problem &p) { return affine_pair_R(p.m); }
-  int64_t size(const Item &a) const { return a.n; }                // longest window first, as AffinePairFamily
-  void fill(const Item &a, Problem &p) const { p.x = a.x; p.y = a.ycodes; p.m = a.m; p.n = (int32_t)a.n; }
-  static double cells(const Problem &p) { return (double)p.m * (double)p.n; }
-  auto kernel(int R) const {
-    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
-    with_listed_R<kPairR>(R, [&](auto r) { kern = &sw_affine_pair_glob_kernel<decltype(r)::value>; });
-    return kern;
-  }
-  void note(double cells, int R, const Problem &first) const {
+  static bool keep_all(const AffineCall &) { return true; }        // the corner's value may have any sign
+  template <int R> static auto kernel(const AffineCall &) { return &sw_affine_pair_glob_kernel<R>; }
+  static const char *path(const AffineCall &) { return "affine_pair_glob[R=%d]"; }
+  static const char *name(const AffineCall &) { return "sw_affine_pair_glob_kernel<R=%d>"; }
+  static double ops(const AffineCall &, int R) {
     // per step and lane, counted in the compiled steady-state loop (four steps, every R of kPairR): the extension instance's count
-    // (AffineExtFamily::note) without the max with 0, the key's v_or and the maximum3 fold — seven ops, the table address' v_add and
+    // (AffineExtMode::ops) without the max with 0, the key's v_or and the maximum3 fold — seven ops, the table address' v_add and
     // the row-m select per cell — and 10.5 of overhead: the two DPP moves and their copies, the row pointer's multiply and add, the
     // code's address, the row-0 subtract and max, the capture's compare.  The compiler puts the capture behind an exec-mask branch
     // that a wavefront takes when one of its lanes stands on its column n, and moves a quarter of the selects out of line with it:
     // 8.75 R + 10.5 fits all six instances to within half an op.  The 16 border steps of a slot are not counted
-    path_note(c.ctx, "affine_pair_glob[R=%d]", R);
-    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, first.n, first.n, 0, (8.75 * R + 10.5) / (double)R,
-                       "sw_affine_pair_glob_kernel<R=%d>", R);
+    return (8.75 * R + 10.5) / (double)R;
   }
 };
 
-// sw_affine_band_glob_kernel for affine_list_stage: AffineBandExtFamily's items (the window is never clipped: a band that holds the
-// corner has n <= m + hi_e), one result per problem.
-struct AffineBandGlobFamily {
-  typedef AffineBandProblem Problem; typedef AffineExtItem Item;
-  const AffineCall &c;
+// sw_affine_band_glob_kernel: AffineBandExtMode's items (the window is never clipped: a band that holds the corner has
+// n <= m + hi_e), one result per problem.
+struct AffineBandGlobMode {
+  typedef AffineOwnItem Source;
   static constexpr const char *kNoInstance = "internal: no sw_affine_band_glob_kernel instance for this band";
   static constexpr int kOuts = 1;
-  bool keep_all() const { return true; }
-  static uint32_t id(const Item &a) { return a.id; }
-  static int R(const Item &a) { return affine_band_R(a.W); }
-  static int R(const Problem &p) { return affine_band_R(p.W); }
-  int64_t size(const Item &a) const { return a.m; }                // longest query first, as AffineBandFamily
-  void fill(const Item &a, Problem &p) const { p.x = a.x; p.y = a.ycodes; p.m = a.m; p.n = (int32_t)a.n; p.lo = a.blo; p.W = a.W; }
-  static double cells(const Problem &p) { return (double)p.m * (double)p.W; }
-  auto kernel(int R) const {
-    void (*kern)(const Problem *, int, const AffinePairArgs) = nullptr;
-    with_listed_R<kBandR>(R, [&](auto r) { kern = &sw_affine_band_glob_kernel<decltype(r)::value>; });
-    return kern;
-  }
-  void note(double cells, int R, const Problem &) const {
-    path_note(c.ctx, "affine_band_glob[R=%d]", R);
+  static bool keep_all(const AffineCall &) { return true; }
+  template <int R> static auto kernel(const AffineCall &) { return &sw_affine_band_glob_kernel<R>; }
+  static const char *path(const AffineCall &) { return "affine_band_glob[R=%d]"; }
+  static const char *name(const AffineCall &) { return "sw_affine_band_glob_kernel<R=%d>"; }
+  static double ops(const AffineCall &, int R) {
     // per step and lane, counted in the compiled loop (every R of kBandR, to within five ops of a step): the extension instance's
-    // count (AffineBandExtFamily::note) without the max with 0 and the key's v_or per register and without the step's (value, column)
+    // count (AffineBandExtMode::ops) without the max with 0 and the key's v_or per register and without the step's (value, column)
     // compare — thirteen ops per register, a move per two registers, and 26 of overhead.  The corner's read (one compare and one
     // select per register) runs behind the branch, at one step of a slot's rows: not counted
-    affine_note_kernel(c.ctx, cells, MI355_SW_CELL_F32, 16, R, 16 * R, 16 * R, 0, (13.0 * R + (R + 1) / 2 + 26.0) / (double)R,
-                       "sw_affine_band_glob_kernel<R=%d>", R);
+    return (13.0 * R + (R + 1) / 2 + 26.0) / (double)R;
   }
 };
 
@@ -1690,8 +1709,8 @@ int affine_global(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     }
     jobs.push_back(it);
   }
-  rc = affine_list_stage(AffineGlobFamily{c}, plan, fast, mmax, score, ends.data());
-  if (!rc) rc = affine_list_stage(AffineBandGlobFamily{c}, plan, bfast, band_mmax, score, ends.data());
+  rc = affine_list_stage(AffinePairFamily<AffineGlobMode>{c, {}}, plan, fast, mmax, score, ends.data());
+  if (!rc) rc = affine_list_stage(AffineBandFamily<AffineBandGlobMode>{c, {}}, plan, bfast, band_mmax, score, ends.data());
   if (!rc) rc = affine_ext_exact_stage<false, true>(c, jobs, score, ends.data());
   if (!rc) rc = affine_ext_exact_stage<true, true>(c, bjobs, score, ends.data());
   if (rc) return rc;

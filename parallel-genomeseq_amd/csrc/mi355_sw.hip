@@ -13,7 +13,10 @@
 //                      sw_affine_pair_kernel (end-to-end: sw_affine_pair_e2e_kernel) for lists of (query, window)
 //                      pairs, sw_affine_band_kernel for those with a diagonal band and sw_affine_pair_ext_kernel
 //                      for the anchored seed extension, forward and backward (inside a band per pair:
-//                      sw_affine_band_ext_kernel)                                                      host_affine.h
+//                      sw_affine_band_ext_kernel) and, anchored at both ends, sw_affine_pair_glob_kernel /
+//                      sw_affine_band_glob_kernel.  Seven names on two geometries: the local pair kernel, one body for
+//                      the other three pair kernels (sw_affine_pair_body.inc) and one for the three band kernels
+//                      (sw_affine_band_body.inc); a name is an entry point that names its mode            host_affine.h
 //                      (entry points: affine_align_any, affine_batch_any, affine_pairs_any, affine_extend_any — one body
 //                      per run / trace twin)
 // Problems the score kernel does not cover (see bucket_fast_ok) run 2+3 on the whole matrix.

@@ -38,6 +38,9 @@
 //
 // A slot writes only best[pid] / cell[2 pid ..]; no slot communicates with another, no workgroup waits, no atomics.  A slot whose
 // window ends early idles on `outside` codes until the longest window of its wavefront is done (wave_steps).
+//
+// The file holds the local kernel, described above, and behind it ONE BODY for the three other modes of the same geometry — end to
+// end, anchored extension, global — whose entry points only name their mode (the comment in front of them).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -180,483 +183,105 @@ __global__ __launch_bounds__(256) void sw_affine_pair_kernel(const AffinePairPro
   }
 }
 
-// sw_affine_pair_e2e_kernel — the END-TO-END sibling (include/mi355_sw.h "end-to-end mode", DESIGN.md §3.8 lemma L19): every row of
-// x is aligned, the window's flanks are free, the score may be negative.  A sibling and not a flag of the kernel above, so that the
-// local instances stay the code they were; slots, stream window, table and the per-cell chain are copies of the kernel above, which a
-// change of the scaffold must visit as well.  What differs:
-//   * no floor: the diagonal term is a plain v_add_f32;
-//   * left border H(i,0) = F(i,0) = -(o + (i-1) e), E(i,0) = -inf.  Lane l stands on column 0 at its step with t == -1 (step l - 1;
-//     lane 0: in front of the loop).  There its rows take Ho[r] = E[r] = H(i,0) - o: E(i,1) = max(E[r] - e, Ho[r]) = H(i,0) - o, the
-//     value -inf gives.  What the lane computed on `outside` codes before that step is overwritten.  At the same step the lane's DPP
-//     move reads the previous lane's Ho[R - 1] as that lane left it at ITS border step, one step earlier: Ho(i0 - 1, 0), which
-//     becomes up_prev; one step later it reads Ho(i0 - 1, 1) and the real F(i0, 1).  The chain needs no further change, and the
-//     slot's first lane keeps `old` = -o (H(0,j) = 0, F(1,j) = -o).  The selects live in a prologue of the first 16 steps (every
-//     border step is one of steps 0..14); the steady-state loop has none of them;
-//   * winner: only row m competes — lane (m-1)/R, row (m-1)%R: one select per cell under masks fixed before the loop — and only a
-//     strictly greater value replaces the lane's best, so the smallest column stays.  The best restarts at the border step: nothing
-//     left of column 1 competes.  No key, no WaveKeyFold; at the end the slot takes value and column from that one lane.
-// Columns beyond n and rows beyond m keep the `outside` code and the last class.  A padding row never feeds a real one (F and the
-// diagonal run downwards).  A padding column has E and F only: H(m, j > n) <= max over j <= n of H(m, j), with equality only for the
-// all-F path from the free row 0, and the strict compare keeps the real column (L19 (c)).  kPadScoreF enters one sum per cell, whose
-// other operand is an Ho = max(.., E, F) - o, and E and F never hold such a sum alone: every register stays finite (L19 (d)).
-// Exactness: nothing is floored and no mantissa bit is reserved; the host admits integer scores whose every value is below 2^24 in
-// magnitude (host_affine.h: affine_e2e_exact); the scale 2^-k moves no mantissa bit.
-// best[pid] = max over j of H(m, j), of any sign; cell[2 pid ..] = m and the smallest such column (1-based).
-template <int R>
-__global__ __launch_bounds__(256) void sw_affine_pair_e2e_kernel(const AffinePairProblem *probs, int nprob, const AffinePairArgs sa) {
-  static_assert(R >= 1 && R <= 32, "instances of kPairR");
-  extern __shared__ __attribute__((aligned(16))) uint32_t pairsmem[];
-  __shared__ __attribute__((aligned(16))) uint8_t win[16 * kWaveBuf];
-  float *tab = reinterpret_cast<float *>(pairsmem);                // [nrows][ncls]
-  const int tid = threadIdx.x;
-  const int l = tid & 15;
-  const int slot = tid >> 4;
-  const int pid = blockIdx.x * 16 + slot;
-  const bool active = pid < nprob;
-  const uint8_t *xb = nullptr, *yc = nullptr;
-  int m = 0, n = 0;
-  if (active) { xb = probs[pid].x; yc = probs[pid].y; m = probs[pid].m; n = probs[pid].n; }
-  for (int e = tid; e < sa.nrows * sa.ncls; e += 256) tab[e] = sa.tab[e];
-  uint32_t boff[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int i = l * R + r;
-    boff[r] = 4u * (i < m ? (uint32_t)sa.cls[xb[i]] : (uint32_t)(sa.ncls - 1));
-  }
-  __syncthreads();
+// ---- The non-local modes: ONE BODY (sw_affine_pair_body.inc), a mode is a set of traits, an entry point only names its mode ----
+// End to end, anchored extension and global alignment share slots, stream window, table, the per-cell chain and the row loop of the
+// kernel above; what a mode adds is written once, under the trait that asks for it.  Every one of them has no zero floor — the
+// diagonal term is a plain v_add_f32, scores may be negative — and the column-0 border:
+//   column 0   H(i,0) = F(i,0) = -(o + (i-1) e), E(i,0) = -inf.  Lane l stands on column 0 at its step with t == -1 (step l - 1;
+//              lane 0: in front of the loop).  There its rows take Ho[r] = E[r] = H(i,0) - o: E(i,1) = max(E[r] - e, Ho[r]) = H(i,0) - o,
+//              the value -inf gives.  What the lane computed on `outside` codes before that step is overwritten.  At the same step the
+//              lane's DPP move reads the previous lane's Ho[R - 1] as that lane left it at ITS border step, one step earlier:
+//              Ho(i0 - 1, 0), which becomes up_prev; one step later it reads Ho(i0 - 1, 1) and the real F(i0, 1).  The chain needs no
+//              further change.  The selects live in a prologue of the first 16 steps (every border step is one of steps 0..14); the
+//              steady-state loop has none of them.  Every fold restarts at the border step: nothing computed left of column 1
+//              competes.  The step's R table values are all requested in front of the row loop (sv[]): left to itself the scheduler
+//              issued each ds_read_b32 next to its use and waited for it (lgkmcnt(0) after nearly every load at R >= 16: twice the
+//              local instance's time at R = 32).
+// The traits:
+//   kRow0      the row-0 border H(0,j) = E(0,j) = -(o + (j-1) e), F(0,j) = -inf.  The slot's first lane takes Ho(0,j) = H(0,j) - o and
+//              F(1,j) = H(0,j) - o — the same number, -(2 o + (j-1) e) — from the `old` operand of its two DPP moves: `rowo`, -2 o at
+//              step 0 (lane 0 stands on column 1 there) and e lower every step: one subtract per step, not per cell.  Cell (1,1) takes
+//              its diagonal from up_prev = -o: H(0,0) = 0.  Beyond the window the value stays at that of column n (`rowmin`, one max
+//              per step), so that no register leaves the admitted range while the slot idles behind a longer window of its wavefront.
+//              Off: row 0 is free, `old` = -o (H(0,j) = 0, F(1,j) = -o), as in the kernel above.
+//   kKey       the best over all cells: the kernel's key fold (WaveKeyFold: value bits | 31 - row, a later column only with a greater
+//              VALUE, then slot_first_max) over max(H, 0) — one more max per cell, the floor on the answer, since H has none.
+//   kRowM      the strict row-m fold: only row m competes — lane (m-1)/R, row (m-1)%R: one select per cell (`hm`) under masks fixed
+//              before the loop — and only a strictly greater value replaces the lane's best, so the smallest column stays.  At the
+//              end the slot takes value and column from that one lane.
+//   kCorner    the corner capture: the row-m select again, and the step's value replaces the lane's result at the one step with
+//              t == n - 1, the lane's column n — one integer compare and one select per step.  The four slots of a wavefront have
+//              different n and run to the longest: the compare is with the slot's own n, so a slot takes its value once, at its own
+//              step, and no padding step behind column n can overwrite it (t only rises; it equals n - 1 once).  "The last value
+//              seen" would be wrong for every slot but the longest.
+//   kOuts      results (best, cell) a problem writes: one per fold or capture.
+// The modes:
+// AffinePairE2E — sw_affine_pair_e2e_kernel, END TO END (include/mi355_sw.h "end-to-end mode", DESIGN.md §3.8 lemma L19): every row of
+//   x is aligned, the window's flanks are free, the score may be negative: the row-m fold and nothing else; no key, no WaveKeyFold.
+//   Columns beyond n and rows beyond m keep the `outside` code and the last class.  A padding row never feeds a real one (F and the
+//   diagonal run downwards).  A padding column has E and F only: H(m, j > n) <= max over j <= n of H(m, j), with equality only for
+//   the all-F path from the free row 0, and the strict compare keeps the real column (L19 (c)).  kPadScoreF enters one sum per cell,
+//   whose other operand is an Ho = max(.., E, F) - o, and E and F never hold such a sum alone: every register stays finite (L19 (d)).
+//   Exactness: nothing is floored and no mantissa bit is reserved; the host admits integer scores whose every value is below 2^24
+//   in magnitude (host_affine.h: affine_e2e_exact); the scale 2^-k moves no mantissa bit.
+//   best[pid] = max over j of H(m, j), of any sign; cell[2 pid ..] = m and the smallest such column (1-based).
+// AffinePairExt — sw_affine_pair_ext_kernel, ANCHORED (include/mi355_sw.h "anchored seed extension", lemma L21): the alignment starts
+//   at cell (0,0), in front of x[1] and y[1], both flanks are gaps, and it ends where the score peaks (the best extension, over all
+//   cells: kKey) or in row m (to the end: kRowM), under the row-0 border.  Cell (0,0) = 0 always competes and every border cell is
+//   negative, so the winner of the key fold is a positive cell or 0 / 0 / 0, and a negative cell never wins.  To the end: after the
+//   slot's result H(m,0) = -(o + (m-1) e) is folded in, and column 0 wins a tie.  Padding (L21 (c), restating L19 (c) / (d) for the
+//   row-0 border): a padding row (> m) or column (> n) has E and F only, since kPadScoreF enters its diagonal term.  Its E and F
+//   derive, by opening or extending a gap, from a real cell in the same row or column — strictly below that cell, which lies in no
+//   later column — or from a border cell, which is negative; inductively every padding cell is negative or strictly below a real
+//   cell of no later column: it wins neither fold (max(H, 0) and the value-only compare; the strict compare of row m, where the
+//   frozen row 0 repeats the all-F value of column n at most).  A padding row never feeds a real one.  Every register stays finite:
+//   kPadScoreF enters one sum per cell, whose other operand is an Ho.  Exactness: every value of a real cell is an integer of
+//   magnitude below 2^24 and every positive H is below 2^19, so that the key's five mantissa bits are free (host_affine.h:
+//   affine_ext_exact); the scale 2^-k moves no mantissa bit.
+//   best[2 pid] = the best extension, cell[4 pid ..] = end_x, end_y (lengths; 0 / 0 at score 0); best[2 pid + 1] = max over
+//   0 <= j <= n of H(m, j), cell[4 pid + 2 ..] = m and the smallest such column (0: the whole of x as one insertion).
+// AffinePairGlob — sw_affine_pair_glob_kernel, ANCHORED AT BOTH ENDS (include/mi355_sw.h "global alignment between two anchors", lemma
+//   L23): the anchored model, whose answer is the one cell H(m, n): the row-0 border and the corner capture.  Nothing competes: kKey
+//   and kRowM are off — no max(H, 0), no key, no WaveKeyFold, no (blk, tl), no (best, te) and no compare of values.  Padding: a
+//   padding row (> m) or column (> n) never feeds a real cell (F and the diagonal run downwards, E to the right), and the capture
+//   reads a real cell by construction; every register stays finite as in the extension (kPadScoreF enters one sum per cell, whose
+//   other operand is an Ho; row 0 is frozen at column n's value).  Exactness: every value of a real cell is an integer below 2^24 in
+//   magnitude (host_affine.h: affine_glob_exact).  No key is formed, so no mantissa bit is reserved: the extension's
+//   smax (rows + 1) < 2^18 has no counterpart here.  The scale 2^-k moves no bit.
+//   best[pid] = H(m, n), of any sign; cell[2 pid ..] = m, n.
+// A further mode is a trait set, its paragraph here and its entry point.
+//
+// Why the body is a file that an entry point includes, and why the local kernel above is not one of its modes: the compiled kernels
+// are to stay what they are (profiles/affine_list_merge_isa_identity.txt).  Behind a call — a __forceinline__ function, by reference or
+// by value — the optimiser meets the kernel's arguments and loops in another order, and local R = 24 went from 127 to 129 VGPRs, a
+// wave per SIMD, global R = 5 from 60 to 68; included, the 18 instances below are the parent's instruction for instruction.  The
+// local kernel's row loop through the body's `step` lambda schedules differently at R >= 24 (the same two VGPRs) whatever else is
+// done, so it keeps its own text; a change of the scaffold visits the kernel above and the body, no longer four kernels.
+struct AffinePairE2E {
+  static constexpr bool kRow0 = false, kKey = false, kRowM = true, kCorner = false;
+  static constexpr int kOuts = 1;
+};
+struct AffinePairExt {
+  static constexpr bool kRow0 = true, kKey = true, kRowM = true, kCorner = false;
+  static constexpr int kOuts = 2;
+};
+struct AffinePairGlob {
+  static constexpr bool kRow0 = true, kKey = false, kRowM = false, kCorner = true;
+  static constexpr int kOuts = 1;
+};
 
-  const uint32_t outside = (uint32_t)(sa.nrows - 1);
-  auto stage_load = [&](int seg) -> uint32_t {
-    return wave_stage_word(yc, n, seg * kWaveSeg + 4 * l, [&](bool in, uint32_t byte) { return in ? byte : outside; });
-  };
-  int nseg, steps4;
-  wave_steps(n, 16, nseg, steps4);
-  uint8_t *buf = win + slot * kWaveBuf;
-  uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
-  const uint8_t *buf_lane = buf + 16 - l;
-  uint32_t nextc = stage_load(0);
-  if (l < 4) buf32[l] = outside * 0x01010101u;
-  buf32[4 + l] = nextc;
-  nextc = stage_load(1);
-
-  float ov = sa.open_s, ev = sa.ext_s;
-  asm volatile("" : "+v"(ov), "+v"(ev));
-  const int nopen = (int)__float_as_uint(-sa.open_s);              // row 0: H = 0 is Ho = -o, and F(1, j) = -o
-  // Ho = E = H(i,0) - o = -(2 o + (i - 1) e) of the lane's first row, i - 1 = l R (integers below 2^24 units: exact)
-  const float bord0 = -(2.0f * sa.open_s + (float)(l * R) * sa.ext_s);
-  float E[R], Ho[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) { E[r] = bord0 - (float)r * sa.ext_s; Ho[r] = E[r]; }   // lane 0 stands on column 0 here
-  float up_prev = -ov;                                             // Ho(i0 - 1, 0) of lane 0: row 0
-  float fout = -ov;
-  const float ninf = -__builtin_inff();
-  float best = ninf;                                               // the greatest H(m, j) so far, first seen at column tl (0-based)
-  int tl = 0;
-  const uint32_t row_bytes = 4u * (uint32_t)sa.ncls;
-  const char *tab_b = reinterpret_cast<const char *>(tab);
-  // the one cell of a column that competes, row m: lane (m - 1) / R, row (m - 1) % R (no lane of an idle slot)
-  const int wrow = (m > 0 && (m - 1) / R == l) ? (m - 1) % R : -1;
-  bool wsel[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) wsel[r] = wrow == r;
-
-  // one step of the lane: column t = gstep - l of the window, code at buf_lane[k].  BORDER (the first 16 steps): the lane whose t is
-  // -1 stands on column 0 and takes the border instead of what it computed
-  auto step = [&](auto border, const int gstep, const int k) {
-    constexpr bool BORDER = decltype(border)::value;
-    const int t = gstep - l;
-    const uint32_t c = (uint32_t)buf_lane[k];
-    const char *rowp = tab_b + c * row_bytes;
-    const float up = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(nopen, (int)__float_as_uint(Ho[R - 1]), 0x111, 0xf, 0xf, false));
-    float frun = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(nopen, (int)__float_as_uint(fout), 0x111, 0xf, 0xf, false));
-    float diag = up_prev;                                          // H(i-1, j-1) - o
-    up_prev = up;
-    float hm = ninf;                                               // H(m, t + 1) in the lane that holds row m
-    const bool on_border = BORDER && t == -1;
-    float bord = bord0;
-    // the step's R table values, all requested in front of the row loop: left to itself the scheduler issued each ds_read_b32 next to
-    // its use and waited for it (lgkmcnt(0) after nearly every load at R >= 16: twice the local instance's time at R = 32)
-    float sv[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) sv[r] = *reinterpret_cast<const float *>(rowp + boff[r]);
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const float w = Ho[r];                                       // H(i, j-1) - o
-      const float s = sv[r];
-      float x, g, h, ho, fs;
-      asm("v_add_f32 %0, %1, %2" : "=v"(x) : "v"(diag), "v"(s));   // no clamp: no floor
-      asm("v_sub_f32 %0, %1, %2" : "=v"(g) : "v"(E[r]), "v"(ev));
-      asm("v_max_f32 %0, %1, %2" : "=v"(g) : "v"(g), "v"(w));
-      asm("v_max3_f32 %0, %1, %2, %3" : "=v"(h) : "v"(x), "v"(g), "v"(frun));
-      hm = wsel[r] ? h : hm;
-      asm("v_sub_f32 %0, %1, %2" : "=v"(ho) : "v"(h), "v"(ov));
-      asm("v_sub_f32 %0, %1, %2" : "=v"(fs) : "v"(frun), "v"(ev));
-      asm("v_max_f32 %0, %1, %2" : "=v"(frun) : "v"(fs), "v"(ho));
-      if constexpr (BORDER) { g = on_border ? bord : g; ho = on_border ? bord : ho; bord -= ev; }
-      E[r] = g;
-      Ho[r] = ho;
-      diag = w;
-    }
-    fout = frun;
-    // only a strictly greater value: the smallest column stays; at the border step the best restarts
-    const bool take = hm > best;
-    tl = take ? t : tl;
-    best = take ? hm : best;
-    if constexpr (BORDER) best = on_border ? ninf : best;
-  };
-
-  for (int seg = 0; seg < nseg; ++seg) {
-    const int kq = min(kWaveSeg, steps4 - seg * kWaveSeg) >> 2;
-    int k4 = 0;
-    if (seg == 0) {                                                // the 16 steps that hold every lane's border step (steps4 >= 16)
-#pragma unroll 1
-      for (int k = 0; k < 16; ++k) step(std::true_type(), k, k);
-      k4 = 4;
-    }
-    for (; k4 < kq; ++k4) {
-#pragma unroll
-      for (int ku = 0; ku < 4; ++ku) step(std::false_type(), seg * kWaveSeg + 4 * k4 + ku, 4 * k4 + ku);
-    }
-    const uint32_t hist = buf32[kWaveSeg / 4 + (l & 3)];
-    if (l < 4) buf32[l] = hist;
-    buf32[4 + l] = nextc;
-    nextc = stage_load(seg + 2);
-  }
-
-  // the slot's result: value and column of the lane that holds row m
-  const int wl = m > 0 ? (m - 1) / R : 0;
-  const float bv = __shfl(best, wl, 16) * sa.unscale;
-  const int bt = __shfl(tl, wl, 16);
-  if (l == 0 && active) {
-    sa.best[pid] = bv;
-    sa.cell[2 * (size_t)pid] = m;
-    sa.cell[2 * (size_t)pid + 1] = (long long)bt + 1;
-  }
+// The entry points: a name per mode (public: include/mi355_sw.h documents them, mi355_sw_last_kernel reports them).
+template <int R> __global__ __launch_bounds__(256) void sw_affine_pair_e2e_kernel(const AffinePairProblem *probs, int nprob, const AffinePairArgs sa) {
+  using MODE = AffinePairE2E;
+#include "sw_affine_pair_body.inc"
 }
-
-// sw_affine_pair_ext_kernel — the ANCHORED sibling (include/mi355_sw.h "anchored seed extension", DESIGN.md §3.8 lemma L21): the
-// alignment starts at cell (0,0), in front of x[1] and y[1], both flanks are gaps, and it ends where the score peaks (the best
-// extension, over all cells) or in row m (to the end).  A sibling and not a flag, as the end-to-end kernel above, whose geometry,
-// stream window, table, cell chain, column-0 border (the 16-step prologue) and row-m select it copies; a change of the scaffold must
-// visit all three.  What differs from the end-to-end kernel:
-//   * row 0: H(0,j) = E(0,j) = -(o + (j-1) e), F(0,j) = -inf.  The slot's first lane takes Ho(0,j) = H(0,j) - o and F(1,j) =
-//     H(0,j) - o — the same number, -(2 o + (j-1) e) — from the `old` operand of its two DPP moves: `rowo`, -2 o at step 0 (lane 0
-//     stands on column 1 there) and e lower every step: one subtract per step, not per cell.  Cell (1,1) takes its diagonal from
-//     up_prev = -o: H(0,0) = 0.  Beyond the window the value stays at that of column n (one max per step), so that no register
-//     leaves the admitted range while the slot idles behind a longer window of its wavefront;
-//   * best extension: the local kernel's key fold (WaveKeyFold: value bits | 31 - row, a later column only with a greater VALUE) over
-//     max(H, 0) — one more max per cell.  Cell (0,0) = 0 always competes and every border cell is negative, so the winner is a
-//     positive cell or 0 / 0 / 0, and a negative cell never wins.  The lane's best restarts at its border step: nothing computed left
-//     of column 1 competes;
-//   * to the end: the end-to-end kernel's row-m select and strict compare; after the slot's result H(m,0) = -(o + (m-1) e) is folded
-//     in, and column 0 wins a tie.
-// Padding (L21 (c), restating L19 (c) / (d) for the row-0 border): a padding row (> m) or column (> n) has E and F only, since
-// kPadScoreF enters its diagonal term.  Its E and F derive, by opening or extending a gap, from a real cell in the same row or
-// column — strictly below that cell, which lies in no later column — or from a border cell, which is negative; inductively every
-// padding cell is negative or strictly below a real cell of no later column: it wins neither fold (max(H, 0) and the value-only
-// compare; the strict compare of row m, where the frozen row 0 repeats the all-F value of column n at most).  A padding row never
-// feeds a real one.  Every register stays finite: kPadScoreF enters one sum per cell, whose other operand is an Ho.
-// Exactness: every value of a real cell is an integer of magnitude below 2^24 and every positive H is below 2^19, so that the key's
-// five mantissa bits are free (host_affine.h: affine_ext_exact); the scale 2^-k moves no mantissa bit.
-// best[2 pid] = the best extension, cell[4 pid ..] = end_x, end_y (lengths; 0 / 0 at score 0); best[2 pid + 1] = max over 0 <= j <= n
-// of H(m, j), cell[4 pid + 2 ..] = m and the smallest such column (0: the whole of x as one insertion).
-template <int R>
-__global__ __launch_bounds__(256) void sw_affine_pair_ext_kernel(const AffinePairProblem *probs, int nprob, const AffinePairArgs sa) {
-  static_assert(R >= 1 && R <= 32, "the key holds the row within the lane in five bits");
-  extern __shared__ __attribute__((aligned(16))) uint32_t pairsmem[];
-  __shared__ __attribute__((aligned(16))) uint8_t win[16 * kWaveBuf];
-  float *tab = reinterpret_cast<float *>(pairsmem);                // [nrows][ncls]
-  const int tid = threadIdx.x;
-  const int l = tid & 15;
-  const int slot = tid >> 4;
-  const int pid = blockIdx.x * 16 + slot;
-  const bool active = pid < nprob;
-  const uint8_t *xb = nullptr, *yc = nullptr;
-  int m = 0, n = 0;
-  if (active) { xb = probs[pid].x; yc = probs[pid].y; m = probs[pid].m; n = probs[pid].n; }
-  for (int e = tid; e < sa.nrows * sa.ncls; e += 256) tab[e] = sa.tab[e];
-  uint32_t boff[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int i = l * R + r;
-    boff[r] = 4u * (i < m ? (uint32_t)sa.cls[xb[i]] : (uint32_t)(sa.ncls - 1));
-  }
-  __syncthreads();
-
-  const uint32_t outside = (uint32_t)(sa.nrows - 1);
-  auto stage_load = [&](int seg) -> uint32_t {
-    return wave_stage_word(yc, n, seg * kWaveSeg + 4 * l, [&](bool in, uint32_t byte) { return in ? byte : outside; });
-  };
-  int nseg, steps4;
-  wave_steps(n, 16, nseg, steps4);
-  uint8_t *buf = win + slot * kWaveBuf;
-  uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
-  const uint8_t *buf_lane = buf + 16 - l;
-  uint32_t nextc = stage_load(0);
-  if (l < 4) buf32[l] = outside * 0x01010101u;
-  buf32[4 + l] = nextc;
-  nextc = stage_load(1);
-
-  float ov = sa.open_s, ev = sa.ext_s;
-  asm volatile("" : "+v"(ov), "+v"(ev));
-  // row 0 as the slot's first lane sees it: Ho(0, j) = F(1, j) = -(2 o + (j - 1) e), column j = step + 1; never below column n's
-  float rowo = -2.0f * sa.open_s;
-  const float rowmin = -(2.0f * sa.open_s + (float)max(n - 1, 0) * sa.ext_s);
-  // Ho = E = H(i,0) - o = -(2 o + (i - 1) e) of the lane's first row, i - 1 = l R (integers below 2^24 units: exact)
-  const float bord0 = -(2.0f * sa.open_s + (float)(l * R) * sa.ext_s);
-  float E[R], Ho[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) { E[r] = bord0 - (float)r * sa.ext_s; Ho[r] = E[r]; }   // lane 0 stands on column 0 here
-  float up_prev = -ov;                                             // Ho(0, 0) of lane 0: H(0,0) = 0
-  float fout = -ov;
-  const float ninf = -__builtin_inff();
-  float blk = 0.0f, blk31 = __uint_as_float(31u);                  // best extension: the lane's best key, and the same with its row bits set
-  int tl = 0;                                                      // the column (0-based) blk was first seen at
-  float best = ninf;                                               // to the end: the greatest H(m, j) so far, first seen at column te
-  int te = 0;
-  const uint32_t row_bytes = 4u * (uint32_t)sa.ncls;
-  const char *tab_b = reinterpret_cast<const char *>(tab);
-  const int wrow = (m > 0 && (m - 1) / R == l) ? (m - 1) % R : -1;
-  bool wsel[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) wsel[r] = wrow == r;
-
-  auto step = [&](auto border, const int gstep, const int k) {
-    constexpr bool BORDER = decltype(border)::value;
-    const int t = gstep - l;
-    const uint32_t c = (uint32_t)buf_lane[k];
-    const char *rowp = tab_b + c * row_bytes;
-    const int rowo_i = (int)__float_as_uint(rowo);
-    const float up = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(rowo_i, (int)__float_as_uint(Ho[R - 1]), 0x111, 0xf, 0xf, false));
-    float frun = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(rowo_i, (int)__float_as_uint(fout), 0x111, 0xf, 0xf, false));
-    rowo = fmaxf(rowo - ev, rowmin);
-    float diag = up_prev;                                          // H(i-1, j-1) - o
-    up_prev = up;
-    float hm = ninf;                                               // H(m, t + 1) in the lane that holds row m
-    float mx = 0.0f, tpend = 0.0f;
-    (void)tpend;
-    const bool on_border = BORDER && t == -1;
-    float bord = bord0;
-    float sv[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) sv[r] = *reinterpret_cast<const float *>(rowp + boff[r]);
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const float w = Ho[r];                                       // H(i, j-1) - o
-      const float s = sv[r];
-      float x, g, h, hp, ho, fs;
-      asm("v_add_f32 %0, %1, %2" : "=v"(x) : "v"(diag), "v"(s));   // no clamp: no floor
-      asm("v_sub_f32 %0, %1, %2" : "=v"(g) : "v"(E[r]), "v"(ev));
-      asm("v_max_f32 %0, %1, %2" : "=v"(g) : "v"(g), "v"(w));
-      asm("v_max3_f32 %0, %1, %2, %3" : "=v"(h) : "v"(x), "v"(g), "v"(frun));
-      hm = wsel[r] ? h : hm;
-      asm("v_max_f32 %0, 0, %1" : "=v"(hp) : "v"(h));              // the floor on the answer: cell (0,0) competes
-      WaveKeyFold::cell<R>(r, hp, mx, tpend);
-      asm("v_sub_f32 %0, %1, %2" : "=v"(ho) : "v"(h), "v"(ov));
-      asm("v_sub_f32 %0, %1, %2" : "=v"(fs) : "v"(frun), "v"(ev));
-      asm("v_max_f32 %0, %1, %2" : "=v"(frun) : "v"(fs), "v"(ho));
-      if constexpr (BORDER) { g = on_border ? bord : g; ho = on_border ? bord : ho; bord -= ev; }
-      E[r] = g;
-      Ho[r] = ho;
-      diag = w;
-    }
-    fout = frun;
-    // best extension: a later column wins only with a greater VALUE; to the end: only a strictly greater value
-    const bool take = mx > blk31;
-    tl = take ? t : tl;
-    blk = take ? mx : blk;
-    const bool take_e = hm > best;
-    te = take_e ? t : te;
-    best = take_e ? hm : best;
-    if constexpr (BORDER) { blk = on_border ? 0.0f : blk; best = on_border ? ninf : best; }   // at the border step both restart
-    blk31 = __uint_as_float(__float_as_uint(blk) | 31u);
-  };
-
-  for (int seg = 0; seg < nseg; ++seg) {
-    const int kq = min(kWaveSeg, steps4 - seg * kWaveSeg) >> 2;
-    int k4 = 0;
-    if (seg == 0) {                                                // the 16 steps that hold every lane's border step (steps4 >= 16)
-#pragma unroll 1
-      for (int k = 0; k < 16; ++k) step(std::true_type(), k, k);
-      k4 = 4;
-    }
-    for (; k4 < kq; ++k4) {
-#pragma unroll
-      for (int ku = 0; ku < 4; ++ku) step(std::false_type(), seg * kWaveSeg + 4 * k4 + ku, 4 * k4 + ku);
-    }
-    const uint32_t hist = buf32[kWaveSeg / 4 + (l & 3)];
-    if (l < 4) buf32[l] = hist;
-    buf32[4 + l] = nextc;
-    nextc = stage_load(seg + 2);
-  }
-
-  // the best extension: the lane's winner, then the slot's (value, smaller column, smaller row)
-  const uint32_t kb = __float_as_uint(blk);
-  float bv = __uint_as_float(kb & ~31u) * sa.unscale;
-  long long bi = (long long)l * R + (31 - (int)(kb & 31u)) + 1;
-  long long bj = (long long)tl + 1;
-  if (!(bv > 0.0f)) { bv = 0.0f; bi = 0; bj = 0; }
-  slot_first_max(bv, bi, bj);
-  // to the end: value and column of the lane that holds row m, then column 0, which wins a tie
-  const int wl = m > 0 ? (m - 1) / R : 0;
-  float ev_best = __shfl(best, wl, 16);
-  long long ej = (long long)__shfl(te, wl, 16) + 1;
-  const float col0 = -(sa.open_s + (float)max(m - 1, 0) * sa.ext_s);
-  if (col0 >= ev_best) { ev_best = col0; ej = 0; }
-  if (l == 0 && active) {
-    sa.best[2 * (size_t)pid] = bv;
-    sa.best[2 * (size_t)pid + 1] = ev_best * sa.unscale;
-    sa.cell[4 * (size_t)pid] = bv > 0.0f ? bi : 0;
-    sa.cell[4 * (size_t)pid + 1] = bv > 0.0f ? bj : 0;
-    sa.cell[4 * (size_t)pid + 2] = m;
-    sa.cell[4 * (size_t)pid + 3] = ej;
-  }
+template <int R> __global__ __launch_bounds__(256) void sw_affine_pair_ext_kernel(const AffinePairProblem *probs, int nprob, const AffinePairArgs sa) {
+  using MODE = AffinePairExt;
+#include "sw_affine_pair_body.inc"
 }
-
-// sw_affine_pair_glob_kernel — the sibling ANCHORED AT BOTH ENDS (include/mi355_sw.h "global alignment between two anchors", DESIGN.md
-// §3.8 lemma L23): the anchored model of the kernel above, whose answer is the one cell H(m, n).  A sibling and not a flag, as its
-// neighbours; geometry, stream window, table, cell chain, the column-0 border (the 16-step prologue), the row-0 border (`rowo`, frozen
-// at column n's value: `rowmin`) and the row-m select are copies of the kernel above, and a change of the scaffold must visit all
-// four.  What differs from the extension kernel: less.
-//   * nothing competes: no max(H, 0), no key, no WaveKeyFold, no (blk, tl), no (best, te) and no compare of values;
-//   * the answer is CAPTURED, not folded: the lane that holds row m keeps the row-m select of the kernel above (one select per cell,
-//     masks fixed before the loop), and the step's value replaces the lane's result at the one step with t == n - 1, the lane's
-//     column n — one integer compare and one select per step.  The four slots of a wavefront have different n and run to the longest:
-//     the compare is with the slot's own n, so a slot takes its value once, at its own step, and no padding step behind column n can
-//     overwrite it (t only rises; it equals n - 1 once).  "The last value seen" would be wrong for every slot but the longest.
-// Padding: a padding row (> m) or column (> n) never feeds a real cell (F and the diagonal run downwards, E to the right), and the
-// capture reads a real cell by construction; every register stays finite as in the kernel above (kPadScoreF enters one sum per cell,
-// whose other operand is an Ho; row 0 is frozen at column n's value).
-// Exactness: every value of a real cell is an integer below 2^24 in magnitude (host_affine.h: affine_glob_exact).  No key is formed, so
-// no mantissa bit is reserved: the extension kernel's smax (rows + 1) < 2^18 has no counterpart here.  The scale 2^-k moves no bit.
-// best[pid] = H(m, n), of any sign; cell[2 pid ..] = m, n.
-template <int R>
-__global__ __launch_bounds__(256) void sw_affine_pair_glob_kernel(const AffinePairProblem *probs, int nprob, const AffinePairArgs sa) {
-  static_assert(R >= 1 && R <= 32, "instances of kPairR");
-  extern __shared__ __attribute__((aligned(16))) uint32_t pairsmem[];
-  __shared__ __attribute__((aligned(16))) uint8_t win[16 * kWaveBuf];
-  float *tab = reinterpret_cast<float *>(pairsmem);                // [nrows][ncls]
-  const int tid = threadIdx.x;
-  const int l = tid & 15;
-  const int slot = tid >> 4;
-  const int pid = blockIdx.x * 16 + slot;
-  const bool active = pid < nprob;
-  const uint8_t *xb = nullptr, *yc = nullptr;
-  int m = 0, n = 0;
-  if (active) { xb = probs[pid].x; yc = probs[pid].y; m = probs[pid].m; n = probs[pid].n; }
-  for (int e = tid; e < sa.nrows * sa.ncls; e += 256) tab[e] = sa.tab[e];
-  uint32_t boff[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int i = l * R + r;
-    boff[r] = 4u * (i < m ? (uint32_t)sa.cls[xb[i]] : (uint32_t)(sa.ncls - 1));
-  }
-  __syncthreads();
-
-  const uint32_t outside = (uint32_t)(sa.nrows - 1);
-  auto stage_load = [&](int seg) -> uint32_t {
-    return wave_stage_word(yc, n, seg * kWaveSeg + 4 * l, [&](bool in, uint32_t byte) { return in ? byte : outside; });
-  };
-  int nseg, steps4;
-  wave_steps(n, 16, nseg, steps4);
-  uint8_t *buf = win + slot * kWaveBuf;
-  uint32_t *buf32 = reinterpret_cast<uint32_t *>(buf);
-  const uint8_t *buf_lane = buf + 16 - l;
-  uint32_t nextc = stage_load(0);
-  if (l < 4) buf32[l] = outside * 0x01010101u;
-  buf32[4 + l] = nextc;
-  nextc = stage_load(1);
-
-  float ov = sa.open_s, ev = sa.ext_s;
-  asm volatile("" : "+v"(ov), "+v"(ev));
-  // row 0 as the slot's first lane sees it: Ho(0, j) = F(1, j) = -(2 o + (j - 1) e), column j = step + 1; never below column n's
-  float rowo = -2.0f * sa.open_s;
-  const float rowmin = -(2.0f * sa.open_s + (float)max(n - 1, 0) * sa.ext_s);
-  // Ho = E = H(i,0) - o = -(2 o + (i - 1) e) of the lane's first row, i - 1 = l R (integers below 2^24 units: exact)
-  const float bord0 = -(2.0f * sa.open_s + (float)(l * R) * sa.ext_s);
-  float E[R], Ho[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) { E[r] = bord0 - (float)r * sa.ext_s; Ho[r] = E[r]; }   // lane 0 stands on column 0 here
-  float up_prev = -ov;                                             // Ho(0, 0) of lane 0: H(0,0) = 0
-  float fout = -ov;
-  const float ninf = -__builtin_inff();
-  float corner = ninf;                                             // H(m, n), in the lane that holds row m
-  const int tcap = n - 1;                                          // the lane's column n (0-based): the one step that is captured
-  const uint32_t row_bytes = 4u * (uint32_t)sa.ncls;
-  const char *tab_b = reinterpret_cast<const char *>(tab);
-  const int wrow = (m > 0 && (m - 1) / R == l) ? (m - 1) % R : -1;
-  bool wsel[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) wsel[r] = wrow == r;
-
-  auto step = [&](auto border, const int gstep, const int k) {
-    constexpr bool BORDER = decltype(border)::value;
-    const int t = gstep - l;
-    const uint32_t c = (uint32_t)buf_lane[k];
-    const char *rowp = tab_b + c * row_bytes;
-    const int rowo_i = (int)__float_as_uint(rowo);
-    const float up = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(rowo_i, (int)__float_as_uint(Ho[R - 1]), 0x111, 0xf, 0xf, false));
-    float frun = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(rowo_i, (int)__float_as_uint(fout), 0x111, 0xf, 0xf, false));
-    rowo = fmaxf(rowo - ev, rowmin);
-    float diag = up_prev;                                          // H(i-1, j-1) - o
-    up_prev = up;
-    float hm = ninf;                                               // H(m, t + 1) in the lane that holds row m
-    const bool on_border = BORDER && t == -1;
-    float bord = bord0;
-    float sv[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) sv[r] = *reinterpret_cast<const float *>(rowp + boff[r]);
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const float w = Ho[r];                                       // H(i, j-1) - o
-      const float s = sv[r];
-      float x, g, h, ho, fs;
-      asm("v_add_f32 %0, %1, %2" : "=v"(x) : "v"(diag), "v"(s));   // no clamp: no floor
-      asm("v_sub_f32 %0, %1, %2" : "=v"(g) : "v"(E[r]), "v"(ev));
-      asm("v_max_f32 %0, %1, %2" : "=v"(g) : "v"(g), "v"(w));
-      asm("v_max3_f32 %0, %1, %2, %3" : "=v"(h) : "v"(x), "v"(g), "v"(frun));
-      hm = wsel[r] ? h : hm;
-      asm("v_sub_f32 %0, %1, %2" : "=v"(ho) : "v"(h), "v"(ov));
-      asm("v_sub_f32 %0, %1, %2" : "=v"(fs) : "v"(frun), "v"(ev));
-      asm("v_max_f32 %0, %1, %2" : "=v"(frun) : "v"(fs), "v"(ho));
-      if constexpr (BORDER) { g = on_border ? bord : g; ho = on_border ? bord : ho; bord -= ev; }
-      E[r] = g;
-      Ho[r] = ho;
-      diag = w;
-    }
-    fout = frun;
-    corner = t == tcap ? hm : corner;                              // the capture: the slot's own column n, once
-  };
-
-  for (int seg = 0; seg < nseg; ++seg) {
-    const int kq = min(kWaveSeg, steps4 - seg * kWaveSeg) >> 2;
-    int k4 = 0;
-    if (seg == 0) {                                                // the 16 steps that hold every lane's border step (steps4 >= 16)
-#pragma unroll 1
-      for (int k = 0; k < 16; ++k) step(std::true_type(), k, k);
-      k4 = 4;
-    }
-    for (; k4 < kq; ++k4) {
-#pragma unroll
-      for (int ku = 0; ku < 4; ++ku) step(std::false_type(), seg * kWaveSeg + 4 * k4 + ku, 4 * k4 + ku);
-    }
-    const uint32_t hist = buf32[kWaveSeg / 4 + (l & 3)];
-    if (l < 4) buf32[l] = hist;
-    buf32[4 + l] = nextc;
-    nextc = stage_load(seg + 2);
-  }
-
-  // the slot's result: the value the lane that holds row m captured
-  const int wl = m > 0 ? (m - 1) / R : 0;
-  const float bv = __shfl(corner, wl, 16) * sa.unscale;
-  if (l == 0 && active) {
-    sa.best[pid] = bv;
-    sa.cell[2 * (size_t)pid] = m;
-    sa.cell[2 * (size_t)pid + 1] = n;
-  }
+template <int R> __global__ __launch_bounds__(256) void sw_affine_pair_glob_kernel(const AffinePairProblem *probs, int nprob, const AffinePairArgs sa) {
+  using MODE = AffinePairGlob;
+#include "sw_affine_pair_body.inc"
 }
 
 // dst[k] = src[n - 1 - k]: the reversed copies behind the backward pairs of the extension calls (no kernel above knows a direction)

@@ -82,9 +82,12 @@ def test_there_is_an_instance_list_and_it_is_dispatched():
     assert Rs == sorted(set(Rs)) and len(Rs) >= 3 and 16 * Rs[-1] >= 256 and 16 * Rs[0] <= 32      # W <= 256, a narrow band pays little
     assert re.search(r"template\s*<\s*int\s+R\s*>\s*__global__[^\n]*\bsw_affine_band_kernel\(", kernel)
     host = _read(CSRC, "host_affine.h")
-    assert re.search(r"with_listed_R<kBandR>\(R,[^;]*&sw_affine_band_kernel<decltype\(r\)::value>", host, re.S)
+    # one dispatch over kBandR (the band family's) asks the mode for the instance of an R; the local mode names its kernel once
+    assert len(re.findall(r"with_listed_R<kBandR>\(R,[^;]*M::template kernel<decltype\(r\)::value>\(c\)", host, re.S)) == 1
+    m = re.search(r"struct\s+AffineBandMode\s*\{(.*?)\n\};", host, re.S)
+    assert m and re.search(r"template\s*<\s*int\s+R\s*>[^;]*return\s+&sw_affine_band_kernel<R>\s*;", m.group(1)) and host.count("&sw_affine_band_kernel<R>") == 1
     # the band kernel's family runs on the list stage it shares with the pair kernel
-    assert re.search(r"int\s+affine_list_stage\(", host) and re.search(r"affine_list_stage\(AffineBandFamily\b", host) and "affine_band[R=%d]" in host
+    assert re.search(r"int\s+affine_list_stage\(", host) and re.search(r"affine_list_stage\(AffineBandFamily<AffineBandMode>\{", host) and "affine_band[R=%d]" in host
     # the shared fill takes the band as a template parameter whose default is the unbanded code
     assert re.search(r"template\s*<\s*bool\s+TRACE\s*,\s*bool\s+E2E\s*=\s*false\s*,\s*bool\s+BAND\s*=\s*false\s*>", _read(CSRC, "sw_affine_kernel.h"))
     assert '#include "sw_affine_band_kernel.h"' in _read(CSRC, "mi355_sw.hip")

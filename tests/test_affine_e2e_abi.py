@@ -73,5 +73,8 @@ def test_every_instance_is_compiled_for_both_modes():
     assert re.search(r"template\s*<\s*int\s+R\s*>\s*__global__[^\n]*\bsw_affine_pair_e2e_kernel\(", kernel)
     with open(os.path.join(base, "host_affine.h")) as f:
         host = f.read()
-    # one dispatch over kPairR picks both instances of an R
-    assert re.search(r"with_listed_R<kPairR>\(R,[^;]*&sw_affine_pair_e2e_kernel<decltype\(r\)::value>[^;]*&sw_affine_pair_kernel<decltype\(r\)::value>", host, re.S)
+    # one dispatch over kPairR (the pair family's) asks the mode for the instance of an R, and the call's mode picks both in one place
+    assert len(re.findall(r"with_listed_R<kPairR>\(R,[^;]*M::template kernel<decltype\(r\)::value>\(c\)", host, re.S)) == 1
+    m = re.search(r"struct\s+AffinePairMode\s*\{(.*?)\n\};", host, re.S)
+    assert m and re.search(r"template\s*<\s*int\s+R\s*>[^;]*c\.e2e\(\)\s*\?\s*&sw_affine_pair_e2e_kernel<R>\s*:\s*&sw_affine_pair_kernel<R>\s*;", m.group(1))
+    assert host.count("&sw_affine_pair_e2e_kernel<R>") == 1 and host.count("&sw_affine_pair_kernel<R>") == 1

@@ -93,9 +93,11 @@ def test_every_instance_has_its_extension_sibling():
     kernel = _read(CSRC, "sw_affine_pair_kernel.h")
     assert re.search(r"template\s*<\s*int\s+R\s*>\s*__global__[^\n]*\bsw_affine_pair_ext_kernel\(", kernel)
     host = _read(CSRC, "host_affine.h")
-    # one dispatch over kPairR picks the extension instance of an R
-    assert re.search(r"with_listed_R<kPairR>\(R,[^;]*&sw_affine_pair_ext_kernel<decltype\(r\)::value>", host, re.S)
-    assert re.search(r"affine_list_stage\(AffineExtFamily\b", host) and "affine_pair_ext[R=%d]" in host
+    # one dispatch over kPairR (the pair family's) asks the mode for the instance of an R; the extension mode names its kernel once
+    assert len(re.findall(r"with_listed_R<kPairR>\(R,[^;]*M::template kernel<decltype\(r\)::value>\(c\)", host, re.S)) == 1
+    m = re.search(r"struct\s+AffineExtMode\s*\{(.*?)\n\};", host, re.S)
+    assert m and re.search(r"template\s*<\s*int\s+R\s*>[^;]*return\s+&sw_affine_pair_ext_kernel<R>\s*;", m.group(1)) and host.count("&sw_affine_pair_ext_kernel<R>") == 1
+    assert re.search(r"affine_list_stage\(AffinePairFamily<AffineExtMode>\{", host) and "affine_pair_ext[R=%d]" in host
     # the anchored model is a third model of the exact fill; the template head the other models are named by stays
     fill = _read(CSRC, "sw_affine_kernel.h")
     assert re.search(r"template\s*<\s*bool\s+TRACE\s*,\s*bool\s+E2E\s*=\s*false\s*,\s*bool\s+BAND\s*=\s*false\s*>", fill)

@@ -97,14 +97,23 @@ def test_argument_errors_come_before_any_device_work(pgs):
 def test_every_band_instance_has_its_extension_sibling():
     kernel = _read(CSRC, "sw_affine_band_kernel.h")
     assert re.search(r"template\s*<\s*int\s+R\s*>\s*__global__[^\n]*\bsw_affine_band_ext_kernel\(", kernel)
-    assert re.search(r"template\s*<\s*int\s+R\s*>\s*__global__[^\n]*\bsw_affine_band_kernel\(", kernel)   # a sibling, not a flag
+    assert re.search(r"template\s*<\s*int\s+R\s*>\s*__global__[^\n]*\bsw_affine_band_kernel\(", kernel)   # an entry point of its own, not a flag
+    # each entry point only names its mode and includes the one body; the extension's traits: no floor, the key, the row-m fold, two results
+    for name, mode in (("sw_affine_band_kernel", "AffineBandLocal"), ("sw_affine_band_ext_kernel", "AffineBandExt")):
+        assert re.search(r"void %s\([^)]*\)\s*\{\s*using MODE = %s;\s*#include \"sw_affine_band_body\.inc\"\s*\}" % (name, mode), kernel), name
+    m = re.search(r"struct\s+AffineBandExt\s*\{(.*?)\n\};", kernel, re.S)
+    assert m and re.search(r"kFloor = false, kKey = true, kRowM = true, kCorner = false;", m.group(1)) and re.search(r"kOuts = 2;", m.group(1))
+    m = re.search(r"struct\s+AffineBandLocal\s*\{(.*?)\n\};", kernel, re.S)
+    assert m and re.search(r"kFloor = true, kKey = true, kRowM = false, kCorner = false;", m.group(1)) and re.search(r"kOuts = 1;", m.group(1))
     assert len(re.findall(r"constexpr\s+int\s+kBandR\[\]", kernel)) == 1
     host = _read(CSRC, "host_affine.h")
-    # one dispatch over kBandR picks the extension instance of an R
-    assert len(re.findall(r"with_listed_R<kBandR>\(R,[^;]*&sw_affine_band_ext_kernel<decltype\(r\)::value>", host, re.S)) == 1
-    assert host.count("sw_affine_band_ext_kernel<") == 2             # that dispatch and the kernel's name in note()
-    assert re.search(r"affine_list_stage\(AffineBandExtFamily\b", host) and "affine_band_ext[R=%d]" in host
-    assert re.search(r"struct\s+AffineBandExtFamily\s*\{.*?kOuts\s*=\s*2\s*;.*?keep_all\(\)\s*const\s*\{\s*return\s+true;", host, re.S)
+    # one dispatch over kBandR (the band family's) asks the mode for the instance of an R; the extension mode names its kernel once
+    assert len(re.findall(r"with_listed_R<kBandR>\(R,[^;]*M::template kernel<decltype\(r\)::value>\(c\)", host, re.S)) == 1
+    m = re.search(r"struct\s+AffineBandExtMode\s*\{(.*?)\n\};", host, re.S)
+    assert m and re.search(r"template\s*<\s*int\s+R\s*>[^;]*return\s+&sw_affine_band_ext_kernel<R>\s*;", m.group(1))
+    assert host.count("sw_affine_band_ext_kernel<") == 2             # that pick and the kernel's name
+    assert re.search(r"affine_list_stage\(AffineBandFamily<AffineBandExtMode>\{", host) and "affine_band_ext[R=%d]" in host
+    assert re.search(r"kOuts\s*=\s*2\s*;.*?keep_all\(const AffineCall &\)\s*\{\s*return\s+true;", m.group(1), re.S)
     assert "affine_band_ext_exact" in host and re.search(r"bool\s+affine_ext_exact\(", host)
     # the anchored model under a band is an instance of the exact fill; the end-to-end guard stays
     fill = _read(CSRC, "sw_affine_kernel.h")

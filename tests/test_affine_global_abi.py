@@ -103,31 +103,56 @@ def test_every_instance_has_its_global_sibling():
     pair, band = _read(CSRC, "sw_affine_pair_kernel.h"), _read(CSRC, "sw_affine_band_kernel.h")
     for text, names in ((pair, ("sw_affine_pair_glob_kernel", "sw_affine_pair_ext_kernel", "sw_affine_pair_e2e_kernel", "sw_affine_pair_kernel")),
                         (band, ("sw_affine_band_glob_kernel", "sw_affine_band_ext_kernel", "sw_affine_band_kernel"))):
-        for name in names:                                            # siblings, not flags
+        for name in names:                                            # entry points of their own, not flags
             assert re.search(r"template\s*<\s*int\s+R\s*>\s*__global__[^\n]*\b%s\(" % name, text), name
     assert len(re.findall(r"constexpr\s+int\s+kPairR\[\]", pair)) == 1 and len(re.findall(r"constexpr\s+int\s+kBandR\[\]", band)) == 1
 
-    def body(text, name):
-        at = text.index("void %s(" % name)
-        return text[at:text.index("\n}\n", at)]
-    for text, name in ((pair, "sw_affine_pair_glob_kernel"), (band, "sw_affine_band_glob_kernel")):
-        b = body(text, name)
-        assert "WaveKeyFold" not in b and "slot_first_max" not in b                          # no key, no fold
-        assert not re.search(r"v_add_f32_e64|fmed3f|v_max_f32 %0, 0,|fmaxf\(h, 0\.0f\)", b)   # no floor, in the cell or on the answer
-        assert "sa.best[pid] = bv;" in b
-    b = body(pair, "sw_affine_pair_glob_kernel")
-    assert "hm = wsel[r] ? h : hm;" in b and re.search(r"corner = t == tcap \? hm : corner;", b) and "const int tcap = n - 1;" in b
-    b = body(band, "sw_affine_band_glob_kernel")
-    assert "if (it + 1 == m)" in b and "n - m - lo" in b
+    def code(name):                                                   # a body file without its comments
+        return re.sub(r"//[^\n]*", "", _read(CSRC, name))
+    def mode(text, name):
+        m = re.search(r"struct\s+%s\s*\{(.*?)\n\};" % name, text, re.S)
+        assert m, name
+        return m.group(1)
+    # the global entry points only name their mode and include the one body of their geometry
+    for text, name, md, inc in ((pair, "sw_affine_pair_glob_kernel", "AffinePairGlob", "sw_affine_pair_body.inc"),
+                                (band, "sw_affine_band_glob_kernel", "AffineBandGlob", "sw_affine_band_body.inc")):
+        assert re.search(r"void %s\([^)]*\)\s*\{\s*using MODE = %s;\s*#include \"%s\"\s*\}" % (name, md, re.escape(inc)), text), name
+    # the global modes' traits: no key, no floor, no row-m fold; the corner and one result
+    assert re.search(r"kRow0 = true, kKey = false, kRowM = false, kCorner = true;", mode(pair, "AffinePairGlob")) and "kOuts = 1;" in mode(pair, "AffinePairGlob")
+    assert re.search(r"kFloor = false, kKey = false, kRowM = false, kCorner = true;", mode(band, "AffineBandGlob")) and "kOuts = 1;" in mode(band, "AffineBandGlob")
+    # the key, the floors and the folds of the bodies stand under exactly those traits: no key, no fold ...
+    pb, bb = code("sw_affine_pair_body.inc"), code("sw_affine_band_body.inc")
+    assert pb.count("WaveKeyFold") == 1 and pb.count("slot_first_max") == 1 and bb.count("WaveKeyFold") == 1 and bb.count("slot_first_max") == 1
+    assert re.search(r"if constexpr \(MODE::kKey\) \{\s*asm\(\"v_max_f32 %0, 0, %1\" : \"=v\"\(hp\) : \"v\"\(h\)\);\s*WaveKeyFold::cell<R>\(r, hp, mx, tpend\);\s*\}", pb)
+    assert re.search(r"if constexpr \(MODE::kKey\) WaveKeyFold::cell<R>\(r, MODE::kFloor \? h : fmaxf\(h, 0\.0f\), mx, tpend\);", bb)
+    for b in (pb, bb):
+        assert re.search(r"if constexpr \(MODE::kKey\) \{[^}]*\{[^}]*\}[^}]*slot_first_max\(bv, bi, bj\);\s*\}", b)
+        assert re.search(r"static_assert\(MODE::kOuts == \(MODE::kKey \? 1 : 0\) \+ \(MODE::kRowM \? 1 : 0\) \+ \(MODE::kCorner \? 1 : 0\)", b)
+    # ... no floor, in the cell or on the answer: the pair body has none in the cell at all, the band body's stands under kFloor
+    assert not re.search(r"v_add_f32_e64|fmed3f|clamp", pb) and pb.count("v_max_f32 %0, 0,") == 1
+    assert bb.count("fmed3f") == 1 and "MODE::kFloor ? __builtin_amdgcn_fmed3f(Ho[r] + s, 0.0f, 1.0f) : Ho[r] + s;" in bb and bb.count("fmaxf(h, 0.0f)") == 1
+    # ... the row-m fold under kRowM
+    assert re.search(r"if constexpr \(MODE::kRowM\) \{\s*const bool take_e = hm > best;", pb) and pb.count("hm > best") == 1
+    assert re.search(r"if constexpr \(MODE::kRowM\) \{\s*#pragma unroll\s*for \(int r = 0; r < R; \+\+r\) \{\s*const int j = col0 \+ it \+ r;", bb) and bb.count("h > eval") == 1
+    # the capture statements, under the corner's trait, and the one result where a problem's last result goes
+    assert "if constexpr (kSelM) hm = wsel[r] ? h : hm;" in pb and "constexpr bool kSelM = MODE::kRowM || MODE::kCorner;" in pb
+    assert "if constexpr (MODE::kCorner) corner = t == tcap ? hm : corner;" in pb and "const int tcap = n - 1;" in pb
+    assert "if (it + 1 == m)" in bb and "n - m - lo" in bb
+    assert re.search(r"if constexpr \(MODE::kCorner\) \{\s*#pragma unroll\s*for \(int r = 0; r < R; \+\+r\) corner = dsel == r \? Ho\[r\] \+ ov : corner;", bb)
+    for b in (pb, bb):
+        assert "sa.best[NO * (size_t)pid + NO - 1] =" in b and "constexpr size_t NO = MODE::kOuts;" in b
 
     host = _read(CSRC, "host_affine.h")
-    # one dispatch over kPairR and one over kBandR pick the global instance of an R
-    assert len(re.findall(r"with_listed_R<kPairR>\(R,[^;]*&sw_affine_pair_glob_kernel<decltype\(r\)::value>", host, re.S)) == 1
-    assert len(re.findall(r"with_listed_R<kBandR>\(R,[^;]*&sw_affine_band_glob_kernel<decltype\(r\)::value>", host, re.S)) == 1
-    assert host.count("sw_affine_pair_glob_kernel<") == 2 and host.count("sw_affine_band_glob_kernel<") == 2   # dispatch and note()
-    for fam in ("AffineGlobFamily", "AffineBandGlobFamily"):
-        assert re.search(r"affine_list_stage\(%s\b" % fam, host)
-        assert re.search(r"struct\s+%s\s*\{.*?kOuts\s*=\s*1\s*;.*?keep_all\(\)\s*const\s*\{\s*return\s+true;" % fam, host, re.S)
+    # one dispatch over kPairR and one over kBandR (the two families') ask the mode for the instance of an R; each global name is
+    # picked in exactly one place and named in exactly one
+    assert len(re.findall(r"with_listed_R<kPairR>\(R,[^;]*M::template kernel<decltype\(r\)::value>\(c\)", host, re.S)) == 1
+    assert len(re.findall(r"with_listed_R<kBandR>\(R,[^;]*M::template kernel<decltype\(r\)::value>\(c\)", host, re.S)) == 1
+    assert host.count("sw_affine_pair_glob_kernel<") == 2 and host.count("sw_affine_band_glob_kernel<") == 2   # the pick and the name
+    for fam, md, kern in (("AffinePairFamily", "AffineGlobMode", "sw_affine_pair_glob_kernel"), ("AffineBandFamily", "AffineBandGlobMode", "sw_affine_band_glob_kernel")):
+        assert re.search(r"affine_list_stage\(%s<%s>\{" % (fam, md), host)
+        m = mode(host, md)
+        assert re.search(r"template\s*<\s*int\s+R\s*>[^;]*return\s+&%s<R>\s*;" % kern, m) and ('return "%s<R=%%d>";' % kern) in m
+        assert re.search(r"kOuts\s*=\s*1\s*;.*?keep_all\(const AffineCall &\)\s*\{\s*return\s+true;", m, re.S)
     assert "affine_pair_glob[R=%d]" in host and "affine_band_glob[R=%d]" in host
     # the extension's item building and class table are shared, not copied
     assert len(re.findall(r"\brev_q_total - q\.off\[qi\]", host)) == 1 and host.count("affine_ext_item(c, el, k)") == 2

@@ -47,6 +47,9 @@ clock around the call.
     python tools/affine_pairs_bench.py --extend --band 8,16,32,64
     python tools/affine_pairs_bench.py --global
     python tools/affine_pairs_bench.py --global --band 8,16,32,64
+
+--read-len N (default 150, the instance R = 10 of the pair kernels) times another instance of kPairR: 30 / 80 / 150 / 250 / 380 / 500
+rows reach R = 2 / 5 / 10 / 16 / 24 / 32; the windows grow with the read.
 """
 import argparse
 import json
@@ -65,6 +68,7 @@ SCORING = dict(match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0)
 
 
 def main(argv=None):
+    global READ_LEN
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=100_000)
     ap.add_argument("--ref-len", type=int, default=5_000_000)
@@ -74,8 +78,10 @@ def main(argv=None):
     ap.add_argument("--band", default=None, help="half widths of the band around the read's diagonal, comma separated")
     ap.add_argument("--extend", action="store_true", help="the anchored extension call against the local instance")
     ap.add_argument("--global", dest="glob", action="store_true", help="the call anchored at both ends against the extension call")
+    ap.add_argument("--read-len", type=int, default=READ_LEN, help="rows of a read: picks the instance of the pair kernels")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    READ_LEN = args.read_len
     if args.glob and (args.extend or args.mode != "local"):
         ap.error("--global stands alone (with --band or without)")
     if args.extend and args.mode != "local":
