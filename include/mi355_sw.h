@@ -657,7 +657,21 @@ int mi355_sw_prefix_thin_items(mi355_sw_ctx *ctx, size_t n_items, const uint32_t
  * letters (0: the rule above on the batch's shortest read; the k used goes to *k_used).  counts[q] = hits of query q, exact;
  * the first 32 of them, in no particular order, as starts[q * 32 + j] = position - offset relative to `left` (may be negative) and
  * offsets[q * 32 + j].  A seed with a letter the reference does not hold is left out, and so is a seed that repeats itself with a
- * period of at most k / 2 letters (poly-A, a microsatellite). */
+ * period of at most k / 2 letters (poly-A, a microsatellite).
+ *
+ * Reads an intact seed must find: a seeded read whose hits are all listed and whose deficit d = smax m - B0
+ * satisfies floor(d / min(gap, smax)) < u — u the read's seeds in the table — keeps an intact seed in every alignment of score >= B0,
+ * so the windows of all its hits give its result and it takes no pass: path tag "seed_certify[n=..,windows=..]", counter
+ * "seed_certified" (apart from "prefix_certified").  "no_seed_certify" gives the flow without it (the A/B), "seed_certify_min_cols"
+ * moves its size gate (default 4 Mi columns, independent of "prefix_seed_min_cols"); "seed_ride" = 1 / 2 / 3 picks how a small group
+ * of the remaining reads rides with a taller one (cascade / near heights only / not at all).  Results are the same either way.
+ * Host functions behind it, none needs a device (test hooks): mi355_sw_seed_usable — u of one read for seeds of k letters, `letters`
+ * the bytes the reference holds; mi355_sw_seed_certify_ok — the rule, 1 or 0; mi355_sw_seed_certify_window — the 0-based end columns
+ * [*lo, *hi] inside [0, n) of an alignment of score >= B0 through the intact seed of a hit with start = position - offset,
+ * start + m - 1 - floor(d / min(gap, smax)) .. start + m - 1 + floor(d / gap); returns 1, or 0 when no column of the range is left. */
+int mi355_sw_seed_usable(const uint8_t *read, int32_t len, int k, const uint8_t *letters, size_t n_letters);
+int mi355_sw_seed_certify_ok(int64_t d, int64_t smax, int64_t g, int64_t u);
+int mi355_sw_seed_certify_window(int64_t start, int64_t m, int64_t d, int64_t smax, int64_t g, int64_t n, int64_t *lo, int64_t *hi);
 int mi355_sw_seed_k(int letters, int min_len, int64_t n);
 uint32_t mi355_sw_seed_hash(const uint8_t *codes, int k);
 int mi355_sw_seed_cluster(size_t n_hits, const int64_t *starts, const int32_t *offsets, int64_t width, int64_t *lo, int64_t *hi, int *distinct);

@@ -30,6 +30,7 @@ EXPORTS = [
     "mi355_sw_affine_extend_run_band", "mi355_sw_affine_extend_trace_band",
     "mi355_sw_affine_global_run", "mi355_sw_affine_global_trace",
     "mi355_sw_seed_k", "mi355_sw_seed_hash", "mi355_sw_seed_cluster", "mi355_sw_seed_hits",
+    "mi355_sw_seed_usable", "mi355_sw_seed_certify_ok", "mi355_sw_seed_certify_window",
 ]
 SEED_HIT_CAP = 32                                       # hits listed per read by the seed scan (kSeedHitCap of sw_seed_kernel.h)
 AFFINE_LOCAL, AFFINE_END_TO_END = 0, 1                 # mode of the affine pairs calls (include/mi355_sw.h)
@@ -663,7 +664,7 @@ class Context:
         self._L.mi355_sw_last_counters(self._ctx, c)
         out = dict(requeried=int(c[0]), whole_batch_again=int(c[1]), candidates=int(c[2]), left_window=int(c[3]))
         for name in ("first_settled", "saved_locates", "saved_traces", "saved_fallbacks", "walk_widened", "wait_retries", "early_settled", "beyond_f16", "prefix_certified",
-                     "prefix_second_pass", "prefix_thinned", "prefix_thin_items", "pooled_loops", "prefix_seeded", "prefix_seed_hits", "prefix_calibrated"):
+                     "prefix_second_pass", "prefix_thinned", "prefix_thin_items", "pooled_loops", "prefix_seeded", "prefix_seed_hits", "prefix_calibrated", "seed_certified"):
             v = C.c_uint64(0)
             rc = self._L.mi355_sw_last_counter(self._ctx, name.encode(), C.byref(v))
             if rc:
@@ -842,6 +843,34 @@ def seed_hash(codes):
     """mi355_sw_seed_hash: the rolling hash of the code bytes `codes` (no device needed)."""
     a = np.ascontiguousarray(np.frombuffer(bytes(codes), dtype=np.uint8))
     return int(lib().mi355_sw_seed_hash(a.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int(len(a))))
+
+
+def seed_usable(read, k, letters=b"ACGT"):
+    """mi355_sw_seed_usable: the seeds of `read` (k letters at offsets 0, k, 2k, ...) that enter the seed table — every letter among
+    `letters`, not periodic (no device needed)."""
+    x = np.ascontiguousarray(np.frombuffer(bytes(read), dtype=np.uint8))
+    a = np.ascontiguousarray(np.frombuffer(bytes(letters), dtype=np.uint8))
+    rc = lib().mi355_sw_seed_usable(x.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int32(len(x)), C.c_int(k),
+                                    a.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_size_t(len(a)))
+    if rc < 0:
+        raise MI355Error(rc, "mi355_sw_seed_usable")
+    return int(rc)
+
+
+def seed_certify_ok(d, smax, g, u):
+    """mi355_sw_seed_certify_ok: does a read of deficit d with u seeds in the table keep an intact seed in every alignment of score
+    >= B0?"""
+    return bool(lib().mi355_sw_seed_certify_ok(C.c_int64(d), C.c_int64(smax), C.c_int64(g), C.c_int64(u)))
+
+
+def seed_certify_window(start, m, d, smax, g, n):
+    """mi355_sw_seed_certify_window: (lo, hi), the 0-based end columns inside [0, n) that L21 leaves to the hit `start`, or None."""
+    lo, hi = C.c_int64(0), C.c_int64(0)
+    rc = lib().mi355_sw_seed_certify_window(C.c_int64(start), C.c_int64(m), C.c_int64(d), C.c_int64(smax), C.c_int64(g), C.c_int64(n),
+                                            C.byref(lo), C.byref(hi))
+    if rc < 0:
+        raise MI355Error(rc, "mi355_sw_seed_certify_window")
+    return (lo.value, hi.value) if rc == 1 else None
 
 
 def seed_cluster(hits, width):

@@ -967,12 +967,14 @@ int batch_host_bytes(mi355_sw_ctx *ctx, const QueryBatch &q, const uint8_t *&byt
 
 // sw_seed_scan_kernel over the range for the seeds of the reads `ids`: count[id] hits (exact), the first kSeedHitCap of them as
 // start[id * kSeedHitCap + j] (position - offset, relative to the range) and hoff[...] (the seed's offset in the read).
+// usable (may be null): the seeds of every read that entered the table, by read id (u of lemma L21).
 int seed_scan(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const std::vector<int32_t> &ids, int k,
-              std::vector<uint32_t> &count, std::vector<int64_t> &start, std::vector<int32_t> &hoff) {
+              std::vector<uint32_t> &count, std::vector<int64_t> &start, std::vector<int32_t> &hoff, std::vector<uint32_t> *usable = nullptr) {
   HostTrace trace_("seed_scan");
   const size_t nq = q.nq;
   const int64_t n = rg.hi - rg.lo;
   count.assign(nq, 0u); start.assign(nq * kSeedHitCap, 0); hoff.assign(nq * kSeedHitCap, 0);
+  if (usable) usable->assign(nq, 0u);
   if (k < 1 || k > kSeedMaxK) return fail(ctx, MI355_SW_EINVAL, "seed length outside 1 .. 32");
   const uint8_t *bytes = nullptr;
   int rc = batch_host_bytes(ctx, q, bytes);
@@ -980,6 +982,7 @@ int seed_scan(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const 
   SeedTable t;
   if (!seed_table_build(t, k, bytes, q.off.data(), q.len.data(), ids.data(), ids.size(), ref.code_of))
     return fail(ctx, MI355_SW_ENOTSUP, "too many seeds for the seed table");
+  if (usable) seed_usable(t, nq, *usable);
   const size_t ns = t.nseeds();
   if (ns == 0 || n < k) return 0;
   const int64_t threads = (n - k + 1 + kSeedStretch - 1) / kSeedStretch, blocks = (threads + kSeedThreads - 1) / kSeedThreads;
@@ -1136,10 +1139,16 @@ double background_flags(const PrefixBackground &g, int R, long d) {
 //            with more than kSeedHitCap, has no seed (a repeat family would steer by the order of the atomics);
 //   B0:      the sub-chunks that hold the end columns of the cluster go through locate_flagged as round 1's list does in prefix_bucket:
 //            the located score is an exact alignment score, B0 <= B, which is all L19 and L20 ask of it;
-//   height:  every seeded read takes the lowest height P of prefix_heights_seeded with B0 > prefix_bound(P) whose background table
+//   settled: a read whose hits are all listed and whose deficit d = smax m - B0 breaks fewer seeds than it has in the table,
+//            floor(d / min(g, smax)) < u, has an intact seed in every alignment of score >= B0: the windows of ALL
+//            its hits go through one more locate, the first maximum over them and the seed windows is its result, and it joins no
+//            pass (seed_certify[n=..,windows=..]; option no_seed_certify, size gate seed_certify_min_cols).  A bucket settled whole
+//            launches no score kernel at all;
+//   height:  every other seeded read takes the lowest height P of prefix_heights_seeded with B0 > prefix_bound(P) whose background table
 //            (prefix_background) expects at most query_flag_cap flags at the read's deficit; none: the full sweep, at once;
-//   groups:  one pass per height, ascending, B0 given (PrefixAsk::given).  A group of fewer than kSeedGroupMin reads rides with the next
-//            taller group; the reads without a seed ride at the chain's lowest height with B0 from their prefix key, as in prefix_chain;
+//   groups:  one pass per height that has a read, ascending, B0 given (PrefixAsk::given); whether a group of fewer than kSeedGroupMin
+//            reads rides with a taller one is kSeedRideDefault's business (below: it does not).  The reads without a seed take the
+//            chain's lowest height with B0 from their prefix key, as in prefix_chain;
 //   after:   an offender of a pass takes ONE more pass, at the next height whose bound and table admit it, else it is an offender of
 //            the bucket (requery).
 // used = false: the stage did not apply (gates) or failed — more than half of the bucket without a seed B0, path note
@@ -1150,6 +1159,34 @@ double background_flags(const PrefixBackground &g, int R, long d) {
 // 960 reads has been measured; 256 is where a pass fills the chip with one tile per slot several times over and is taken as bulk.
 constexpr int64_t kPrefixSeedMinCols = (int64_t)4 << 20;
 constexpr size_t kSeedGroupMin = 256;
+// The size gate of the settled reads (option seed_certify_min_cols), apart from prefix_seed_min_cols.  It has no performance reason:
+// L21 holds at any size.  tests/test_gpu_prefix_seed_flow.py lowers prefix_seed_min_cols to 1 on a reference of 1 Mi columns and pins
+// the group passes it sees there, three heights with the lowest on a low tile; with this gate left alone that file goes on testing
+// the group passes, which a batch of mostly settled reads would no longer run.
+constexpr int64_t kSeedCertifyMinCols = kPrefixSeedMinCols;
+// How a group below kSeedGroupMin rides (option seed_ride): with the next taller group whatever its own height (cascade: 26 -> 32 ->
+// 38), only while its OWN height is above kSeedRideRatio of the host's (near: the 0.74 of the argument above, which 26 / 38 = 0.68
+// misses), or not at all (none: one pass per height that has a read).  Measured on the bench batch's residual, 121 / 39 / 3 reads at
+// P = 26 / 32 / 38 after 1885 settled (bench.py, 20 steps, each rule twice, ms per step and score kernels alone): cascade 18.95 and
+// 19.34 (14.6), near 18.26 and 18.35 (13.5), none 18.25 and 17.81 (11.9; 17.65 - 17.67 in three further runs).  The kernels follow
+// the read-rows, 6194 / 5468 / 4508, at 2.4 - 2.6 us each whatever the pass's size: the small passes' rate that kSeedGroupMin's
+// argument charges a pass of its own is paid by the riders too once every pass is small, and a further pass costs 0.3 - 0.4 ms of
+// thin and locate launches.  So: none.
+constexpr long kSeedRideCascade = 1, kSeedRideNear = 2, kSeedRideNone = 3;
+constexpr double kSeedRideRatio = 0.74;
+constexpr long kSeedRideDefault = kSeedRideNone;
+// L21 charges every broken seed c = min(g, smax) or more; a substitution costs smax - s(a, b), so the rule is used only with tables
+// whose mismatches of letters the reference holds all score smax - c or less (match / mismatch scoring with mismatch <= 0 always).
+bool seed_certify_table_ok(const RefData &ref, const ScoreTable &t) {
+  if (!t.integral || t.gap <= 0 || t.smax <= 0) return false;
+  const int nc = ref.ncodes, c = std::min(t.gap, t.smax);
+  for (int a = 0; a < 256; ++a) {
+    if (ref.code_of[a] < 0) continue;
+    for (int y = 0; y < nc - 1; ++y)
+      if (y != ref.code_of[a] && (int)t.stab[(size_t)a * nc + y] > t.smax - c) return false;
+  }
+  return true;
+}
 constexpr int64_t kSeedEndPad = 16;                                    // columns an indel behind the last hit may move the end cell
 int prefix_seeded(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const Range &rg, const mi355_sw_params &p,
                   const ScoreTable &table, const Bucket &b, std::vector<int64_t> &qchunk, std::vector<int64_t> &qwarm,
@@ -1169,8 +1206,9 @@ int prefix_seeded(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   std::vector<uint32_t> count;
   std::vector<int64_t> start;
   std::vector<int32_t> hoff;
+  std::vector<uint32_t> usable;
   HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-  int rc = seed_scan(ctx, ref, q, rg, ids, k, count, start, hoff);
+  int rc = seed_scan(ctx, ref, q, rg, ids, k, count, start, hoff, &usable);
   if (rc) return rc;
   HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
   const float scan_us = elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
@@ -1222,9 +1260,23 @@ int prefix_seeded(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     else given[id] = 0;
   }
   if (2 * ((size_t)b.count - nseeded) > (size_t)b.count) { path_note(ctx, "prefix_seed_failed"); return 0; }
-  rc = prefix_background(ctx, ref, rg, p, table, b, hs);
-  if (rc) return rc;
-  if (!ctx->pbg.valid || ctx->pbg.E != E) { path_note(ctx, "prefix_seed_failed"); return 0; }
+  // settled: the reads an intact seed must find (L21) — B0 from the seed windows, every hit listed, floor(d / c) < u.  Chosen here on
+  // the host; their windows are evaluated below, once the flow is known to go on.
+  std::vector<char> settled(nq, 0);
+  size_t nsettled = 0;
+  const long cgate = opt().seed_certify_min_cols;
+  if (!opt().no_seed_certify && n >= (cgate > 0 ? (int64_t)cgate : kSeedCertifyMinCols) && seed_certify_table_ok(ref, table)) {
+    for (int id : ids) {
+      if (!given[id] || count[id] > (uint32_t)kSeedHitCap) continue;
+      const int64_t d = (int64_t)table.smax * q.len[id] - (int64_t)std::lround((double)B0[id]);
+      if (seed_certify_ok(d, table.smax, table.gap, usable[id])) { settled[id] = 1; ++nsettled; }
+    }
+  }
+  if (nsettled < (size_t)b.count) {                                     // (a bucket that is settled whole asks no height of anybody)
+    rc = prefix_background(ctx, ref, rg, p, table, b, hs);
+    if (rc) return rc;
+    if (!ctx->pbg.valid || ctx->pbg.E != E) { path_note(ctx, "prefix_seed_failed"); return 0; }
+  }
   ctx->candidates += f0.size();
   ctx->prefix_seeded += nseeded;
   // heights and groups
@@ -1237,6 +1289,7 @@ int prefix_seeded(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   std::map<int, std::vector<int>> groups;
   std::vector<int> none;                                                // no height can certify them: they pay for no pass
   for (int id : ids) {
+    if (settled[id]) continue;                                          // (joins no group)
     if (!given[id]) { groups[chainR].push_back(id); continue; }
     int R = 0;
     for (int r : hs) if (admits(r, id)) { R = r; break; }
@@ -1254,10 +1307,61 @@ int prefix_seeded(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     return 0;
   }
   offenders.insert(offenders.end(), none.begin(), none.end());
-  for (auto it = groups.begin(); it != groups.end();) {
+  // (The "more than half" tests above — seedless, no seed B0, beyond every height — all count over the whole bucket with the settled
+  // reads on the side that is served: a settled read has a seed, a B0, and needs no height.  A hopeless batch is swept whole, so it
+  // returned before anything was settled.)
+  if (nsettled) {
+    // L21: every cell with H >= B0 ends in the window of one of the read's hits.  The sub-chunks of ALL hits' windows, less what the
+    // seed windows above evaluated, go through one more locate with B0 as the lower bound (as round 2 of prefix_bucket); the read's
+    // result is the first maximum over both, and it is final.
+    std::vector<std::pair<uint32_t, uint32_t>> fc, fcnew;
+    for (int id : ids) {
+      if (!settled[id]) continue;
+      const int64_t m = q.len[id], d = (int64_t)table.smax * m - (int64_t)std::lround((double)B0[id]);
+      for (uint32_t j = 0; j < count[id]; ++j) {
+        int64_t c_lo = 0, c_hi = 0;
+        if (!seed_certify_window(start[(size_t)id * kSeedHitCap + j], m, d, table.smax, table.gap, n, c_lo, c_hi)) continue;
+        for (int64_t s = c_lo / E; s <= c_hi / E; ++s) fc.push_back({(uint32_t)id, (uint32_t)s});
+      }
+    }
+    std::sort(fc.begin(), fc.end());
+    fc.erase(std::unique(fc.begin(), fc.end()), fc.end());
+    std::set_difference(fc.begin(), fc.end(), f0.begin(), f0.end(), std::back_inserter(fcnew));
+    std::vector<Located> locc(nq);
+    std::vector<char> donec(nq, 0);
+    if (!fcnew.empty()) {
+      HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+      rc = locate_flagged(ctx, ref, q, rg, p, qchunk, qwarm, B0, table, fcnew, locc, donec);
+      if (rc) return rc;
+      HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+      ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+    }
+    for (int id : ids) {
+      if (!settled[id]) continue;
+      Located best = loc0[id];                                          // (B0 came from it)
+      const int64_t m = q.len[id];
+      if (donec[id] && (locc[id].score > best.score ||
+                        (locc[id].score == best.score && host_order_key(p.semantics, locc[id].ix, locc[id].iy, m, n) < host_order_key(p.semantics, best.ix, best.iy, m, n))))
+        best = locc[id];
+      loc[id] = best; qdone[id] = 1;                                    // (qchunk / qwarm: set for the seed windows above)
+    }
+    ctx->candidates += fcnew.size();
+    ctx->seed_certified += nsettled;
+    path_note(ctx, "seed_certify[n=%zu,windows=%zu]", nsettled, fcnew.size());
+  }
+  const long ride = opt().seed_ride > 0 ? opt().seed_ride : kSeedRideDefault;
+  std::vector<int> ownR(nq, 0);                                         // the height the read was given, wherever it rides
+  for (const auto &gr : groups) for (int id : gr.second) ownR[id] = gr.first;
+  for (auto it = groups.begin(); it != groups.end() && ride != kSeedRideNone;) {
     auto nx = std::next(it);
-    if (nx != groups.end() && it->second.size() < kSeedGroupMin) { nx->second.insert(nx->second.end(), it->second.begin(), it->second.end()); it = groups.erase(it); }
-    else ++it;
+    if (nx == groups.end() || it->second.size() >= kSeedGroupMin) { ++it; continue; }
+    std::vector<int> stay;
+    for (int id : it->second) {
+      if (ride == kSeedRideNear && !((double)ownR[id] > kSeedRideRatio * (double)nx->first)) stay.push_back(id);
+      else nx->second.push_back(id);
+    }
+    if (stay.empty()) it = groups.erase(it);
+    else { it->second.swap(stay); ++it; }
   }
   size_t biggest = 0;
   for (const auto &gr : groups) biggest = std::max(biggest, gr.second.size());
@@ -1518,7 +1622,7 @@ int align_range_core(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q,
       if (ntried && (2 * offenders.size() > ntried || (opt().no_requery && !offenders.empty()))) {
         // most reads cannot be certified by their prefix (no hit, or a repeat family over the cap): the sweep decides for everybody
         for (size_t k = 0; k < nq; ++k) if (tried[k]) { loc[k] = Located(); qdone[k] = 0; }
-        ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->prefix_named = false; ctx->candidates = candidates_before;
+        ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->seed_certified = 0; ctx->prefix_named = false; ctx->candidates = candidates_before;
         ctx->last_kernel.cells = 0; ctx->timings[4] = 0; ctx->timings[5] = 0;
         ctx->whole_again += 1;
         path_note(ctx, "whole_again");
@@ -2100,7 +2204,7 @@ void reset_timings(mi355_sw_ctx *ctx) {
   for (double &t : ctx->timings) t = 0;
   ctx->score_ev_used = 0; ctx->arenas.clear(); ctx->cons_used = 0;
   ctx->last_kernel = mi355_sw_kernel_info{};
-  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->prefix_seeded = 0; ctx->prefix_seed_hits = 0; ctx->prefix_calibrated = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
+  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->prefix_seeded = 0; ctx->prefix_seed_hits = 0; ctx->seed_certified = 0; ctx->prefix_calibrated = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
   ctx->hook_ids.clear(); ctx->hook_nsub = 0;
   ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->walk_widened = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
   ctx->path.clear();

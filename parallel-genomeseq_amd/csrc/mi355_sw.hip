@@ -798,6 +798,7 @@ int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *o
   else if (k == "prefix_thin_items") *out = ctx->prefix_thin_items;
   else if (k == "prefix_seeded") *out = ctx->prefix_seeded;
   else if (k == "prefix_seed_hits") *out = ctx->prefix_seed_hits;
+  else if (k == "seed_certified") *out = ctx->seed_certified;
   else if (k == "prefix_calibrated") *out = ctx->prefix_calibrated;
   else if (k == "left_window") *out = ctx->left_window;
   else if (k == "beyond_f16") *out = ctx->beyond_f16;
@@ -878,6 +879,31 @@ int mi355_sw_seed_cluster(size_t n_hits, const int64_t *starts, const int32_t *o
   for (size_t k = 0; k < n_hits; ++k) hits[k] = SeedHit{starts[k], offsets[k]};
   *lo = 0; *hi = 0; *distinct = 0;
   return seed_cluster(hits, width, *lo, *hi, *distinct) ? 1 : 0;
+}
+
+int mi355_sw_seed_usable(const uint8_t *read, int32_t len, int k, const uint8_t *letters, size_t n_letters) {
+  if (!read || len < 0 || k < 1 || k > kSeedMaxK || (n_letters && !letters)) return MI355_SW_EINVAL;
+  int code_of[256];
+  for (int b = 0; b < 256; ++b) code_of[b] = -1;
+  for (size_t i = 0; i < n_letters; ++i) code_of[letters[i]] = 0;     // (known or not is all the count asks)
+  const int64_t off = 0;
+  const int32_t id = 0;
+  SeedTable t;
+  if (!seed_table_build(t, k, read, &off, &len, &id, 1, code_of)) return MI355_SW_ENOTSUP;
+  std::vector<uint32_t> u;
+  seed_usable(t, 1, u);
+  return (int)u[0];
+}
+
+int mi355_sw_seed_certify_ok(int64_t d, int64_t smax, int64_t g, int64_t u) { return seed_certify_ok(d, smax, g, u) ? 1 : 0; }
+
+int mi355_sw_seed_certify_window(int64_t start, int64_t m, int64_t d, int64_t smax, int64_t g, int64_t n, int64_t *lo, int64_t *hi) {
+  if (!lo || !hi) return MI355_SW_EINVAL;
+  *lo = 0; *hi = -1;
+  int64_t a = 0, b = -1;
+  if (!seed_certify_window(start, m, d, smax, g, n, a, b)) return 0;
+  *lo = a; *hi = b;
+  return 1;
 }
 
 int mi355_sw_seed_hits(mi355_sw_ctx *ctx, int64_t left, int64_t right, int k, uint32_t *counts, int64_t *starts, int32_t *offsets, int *k_used) {

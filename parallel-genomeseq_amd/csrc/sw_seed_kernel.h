@@ -141,6 +141,30 @@ inline bool seed_cluster(std::vector<SeedHit> hits, int64_t width, int64_t &lo, 
   return true;
 }
 
+// u of lemma L21: the seeds of every read that entered the table, by read id.  Seeds with a letter the reference
+// does not hold and periodic seeds are not in it, which only lowers u.
+inline void seed_usable(const SeedTable &t, size_t nq, std::vector<uint32_t> &u) {
+  u.assign(nq, 0u);
+  for (int32_t r : t.read) if (r >= 0 && (size_t)r < nq) ++u[(size_t)r];
+}
+// The rule of L21 for a read of deficit d = smax m - B0 with u seeds in the table: every alignment of score >= B0 breaks at most
+// floor(d / c) seeds, c = min(g, smax), so it keeps an intact one while that is below u.  (Each way to break a seed must cost c or
+// more; a table whose mismatches can score above smax - c is the caller's to leave out.)
+inline bool seed_certify_ok(int64_t d, int64_t smax, int64_t g, int64_t u) {
+  if (d < 0 || smax <= 0 || g <= 0 || u <= 0) return false;
+  return d / std::min(g, smax) < u;
+}
+// ... and the end columns (0-based, inside [0, n)) of such an alignment through the intact seed of the hit `start` (position - offset):
+// start + m - 1, moved left by at most floor(d / c) clipped or inserted read letters and right by at most floor(d / g) reference
+// letters against a gap.  false: the interval has no column of the range.
+inline bool seed_certify_window(int64_t start, int64_t m, int64_t d, int64_t smax, int64_t g, int64_t n, int64_t &lo, int64_t &hi) {
+  if (d < 0 || smax <= 0 || g <= 0 || m <= 0 || n <= 0) return false;
+  const int64_t end = start + m - 1;
+  lo = std::max<int64_t>(0, end - d / std::min(g, smax));
+  hi = std::min<int64_t>(n - 1, end + d / g);
+  return lo <= hi;
+}
+
 struct SeedArgs {
   const uint8_t *codes;      // reference codes of the RANGE's first column
   int64_t n;                 // columns of the range

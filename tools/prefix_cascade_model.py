@@ -20,6 +20,9 @@ swept per batch, a full sweep counted as read-len rows, by a chain that starts a
 --per-read takes sets of prefix rows, ';' between the sets (their union goes to --heights): the seeded flow (prefix_seeded), where B0
 is known before any sweep and every read takes the lowest height of the set that can certify it — `per_read`: flags by deficit, rows
 swept per read, reads per height (--per-read "26,32,38;16,20,26,32,38" --heights 16,20,26,32,38).
+
+--certify adds `certify`: the reads of the batch that lemma L21 settles from the windows of their seed hits (floor(d / min(g, smax))
+below the read's seeds in the table) and the heights the residual reads take (of the last --per-read set, else of --heights).
 """
 import argparse
 import json
@@ -96,6 +99,8 @@ def main(argv=None):
     ap.add_argument("--thin-cap", type=int, default=1024, help="flags a read may list for the thin stage (host_score.h thin_flag_cap)")
     ap.add_argument("--per-read", type=lambda v: [[int(t) for t in s.split(",")] for s in v.split(";")], default=None,
                     help="sets of prefix rows for a height per read, e.g. '26,32,38;16,20,26,32,38' (give the union to --heights)")
+    ap.add_argument("--certify", action="store_true",
+                    help="the reads settled by the windows of their seed hits (L21) and the residual reads per height (of the last --per-read set)")
     args = ap.parse_args(argv)
     import __graft_entry__ as entry
     pgs = entry._load_package()
@@ -140,7 +145,27 @@ def main(argv=None):
         line["flows"].update({"%d" % a: args.reads * a + off[a] * m for a in sorted(flags)})
     if args.per_read:
         line["per_read"] = per_read(flags, d, m, args.per_read)
+    if args.certify:
+        line["certify"] = certify(pgs, flags, d, args, args.per_read[-1] if args.per_read else sorted(flags))
     print(json.dumps(line))
+
+
+def certify(pgs, flags, d, args, heights):
+    """Reads an intact seed must find: a read with u seeds in the table (disjoint k-mers, none periodic; k by the
+    library's rule) and deficit d is settled by the windows of its hits when floor(d / min(g, smax)) < u — its hits taken to be within
+    the cap, as all but a repeat's are.  The others keep their height of `heights` (per_read's rule)."""
+    m = args.read_len
+    k = pgs.capi.seed_k(4, m, args.ref_len)
+    ref = pgs.synth.dna(3, args.ref_len)
+    batch = pgs.synth.reads_from_ref(ref, 4, args.reads, m)[0]
+    u = np.array([pgs.capi.seed_usable(r.tobytes(), k) for r in batch], dtype=np.int64) if k else np.zeros(len(d), dtype=np.int64)
+    settled = (d // int(min(GAP, MATCH)) < u) & (u > 0)
+    rest = d[~settled]
+    residual = per_read(flags, rest, m, [heights]) if len(rest) else {}
+    residual.pop("flags_by_deficit", None)
+    return dict(k=k, seeds_per_read=dict(min=int(u.min()), max=int(u.max())), settled=int(settled.sum()), reads=len(d),
+                residual_reads=int(len(rest)), residual_deficits=dict(min=int(rest.min()), max=int(rest.max())) if len(rest) else None,
+                residual=residual)
 
 
 def per_read(flags, d, m, height_sets):
