@@ -554,6 +554,63 @@ int mi355_sw_affine_global_run(mi355_sw_ctx *ctx, const mi355_sw_extend_list *li
 int mi355_sw_affine_global_trace(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo, const int64_t *band_hi,
                                  const mi355_sw_affine_params *params, mi355_sw_result *outs);
 
+/* ---- lists of pairs, banded extension with a z-drop stop rule (BWA-MEM ksw_extend zdrop, minimap2 ksw_extz zdrop) ----------------
+ * A mapper stops an extension that has run into junk: a chimeric read, or a seed at a false position, is not extended over all its
+ * rows, and its best extension cannot jump across a stretch of mismatches to an unrelated match further down.  Pair k is a pair of
+ * mi355_sw_affine_extend_run_band, unchanged — x with m rows, y with n columns, forward or backward, the band band_lo[k] <= j - i <=
+ * band_hi[k] with band_lo <= 0 <= band_hi, the anchored recurrence and its borders, -infinity outside the band.  New is one scalar
+ * per call, zdrop >= 0.
+ *
+ * Stop rule.  It runs over the rows i = 1, 2, ..., m - 1 in order; its running best starts at (B, bi, bj) = (0, 0, 0), the anchor.
+ * For row i: r_i = the maximum of H(i, j) over the in-band real columns 0 <= j <= n of row i (column 0 is the border cell where it
+ * lies in the band; columns beyond n never count), c_i = the smallest such column; a row with no such column (i + band_lo > n) has
+ * r_i = -infinity.  If r_i > B then (B, bi, bj) = (r_i, i, c_i) — strictly greater: the earliest row that attains the running
+ * maximum, at its smallest column.  Otherwise let d = |(i - bi) - (c_i - bj)|, the diagonal offset between the two cells; the
+ * extension stops after row i when
+ *     B - r_i - d gap_extend > zdrop
+ * and an r_i of -infinity stops for every finite zdrop.  Row m is never tested: a stop there would leave nothing to skip.
+ * rows_done[k] = the stop row s (1 <= s < m), or m when no row stopped; 0 for m = 0.  Rows beyond rows_done are not part of the
+ * matrix.
+ *
+ * Definition by truncation: the results of pair k are those of mi355_sw_affine_extend_run_band on the first
+ * rows_done[k] letters of x — for a backward pair, letters of the reversed string — same window, same band.  One exception: when
+ * rows_done < m the read's end was not reached, so to_end_score = -INFINITY and to_end_y = -1, and a trace with to_end[k] != 0 on
+ * such a pair is the empty alignment of the banded call's unreachable case.  Rows <= s do not depend on later rows, so the cells
+ * are those of the full matrix; row s itself cannot hold the best, because r_s < B.  The best extension keeps the tie rule of the
+ * extension calls (the first maximum in column-major order); the rule's (bi, bj) is only the stop test's own bookkeeping.
+ * This is the library's own statement of the rule, not a port: it differs from BWA-MEM's loop in its tie choices (which row and
+ * which column hold a repeated maximum).
+ *
+ * Degenerate pairs.  n = 0, m >= 1: the same rule on the border column, evaluated by the host (B stays 0 and d = i, so a row in
+ * the band stops exactly when gap_open - gap_extend > zdrop, and the first row below the band stops).  m = 0: rows_done = 0.
+ * zdrop = +INFINITY: the call IS mi355_sw_affine_extend_run_band / _trace_band — same path, same bytes, same mi355_sw_last_path —
+ * and rows_done = m.  With a finite zdrop a band that covers the matrix does not re-route the pair to the pair kernel: every pair
+ * with m, n >= 1 is a banded pair.
+ *
+ * Arguments, their checks and the order of those checks are those of the _band calls; then: band_lo == NULL and band_hi == NULL is
+ * MI355_SW_EINVAL (bands are required: an unbanded z-drop has no kernel), and last, zdrop negative or NaN is MI355_SW_EINVAL.
+ * rows_done may be NULL.  After any error the context stays usable.
+ *
+ * Dispatch.  The z-drop instance of the band kernel (a fourth mode of its body; the wavefront leaves its row loop when none of
+ * its four pairs is still alive) where the banded extension call dispatches to the band kernel and zdrop < 2^24: the test is
+ * formed as r_i + d gap_extend < B - floor(zdrop), both sides integers below 2^24 in magnitude (L24).  Every other pair takes the
+ * exact path, which carries out the definition in two steps: the rows instance of the exact kernel under the band writes r_i and
+ * c_i of every row, the host runs the rule, and the exact kernel under the band runs on the first rows_done letters.  The rows
+ * instance holds at most 4 398 rows (two more words of LDS per row); a pair beyond that fails the call with MI355_SW_ENOTSUP,
+ * naming the bound.  Options no_affine_band and no_affine_pairs send every pair to the exact path.
+ * mi355_sw_last_path: "affine_band_extz[R=..]" once per instance that ran, "affine_exact_band_rows" and "affine_exact_band" for the
+ * exact path's two steps, "affine_trace" as before.  mi355_sw_last_kernel names "sw_affine_band_extz_kernel<R=..>" with its ops
+ * per cell.  mi355_sw_last_counter: "zdrop_stopped" = pairs with rows_done < m; "zdrop_rows_run" = the sum over the z-drop
+ * instance's wavefronts of the rows their loops ran (four pairs share a wavefront, which leaves when all four are done). */
+int mi355_sw_affine_extend_run_zdrop(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo,
+                                     const int64_t *band_hi, float zdrop, const mi355_sw_affine_params *params, float *score,
+                                     int64_t *end_x, int64_t *end_y, float *to_end_score, int64_t *to_end_y,
+                                     int64_t *rows_done /* may be NULL */);
+int mi355_sw_affine_extend_trace_zdrop(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo,
+                                       const int64_t *band_hi, float zdrop, const mi355_sw_affine_params *params,
+                                       const uint8_t *to_end /* NULL: best extension for every pair */,
+                                       mi355_sw_result *outs, float *to_end_score, int64_t *to_end_y, int64_t *rows_done);
+
 /* Host-only helper: piece ranges [left,right). Returns MI355_SW_ERANGE where the reference asserts. */
 int mi355_sw_make_string_range(int npiece, int64_t shortlen, int64_t longlen, float overlap_ratio,
                                int64_t *lefts, int64_t *rights);

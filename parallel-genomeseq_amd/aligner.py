@@ -201,6 +201,26 @@ class AffineSWAligner:
         return ctx.affine_extend_run(query, lefts, rights, **kw)
 
     @staticmethod
+    def extend_pairs_zdrop(query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0,
+                           scoring=None, context=None, traceback=False, to_end=None, band=None, zdrop=float("inf")):
+        """extend_pairs inside a band under a z-drop stop rule (Context.affine_extend_zdrop_run, or affine_extend_zdrop_trace with
+        traceback=True): the extension of a pair stops after the first row whose in-band maximum falls more than zdrop below the
+        running best (B - r_i - d gap_extend > zdrop, d the distance of the two cells' diagonals), as BWA-MEM's and minimap2's
+        extensions do when they run into junk.  band=(lo, hi) is required.  The dict gains rows_done; a pair that stopped has
+        to_end_score float("-inf") and to_end_y -1, and its other results are those of extend_pairs on its first rows_done letters."""
+        if band is None:
+            raise ValueError("extend_pairs_zdrop needs a band: band=(lo, hi)")
+        ctx = context if context is not None else default_context()
+        lut = None
+        if scoring is not None:
+            lut = _lut_from_function(scoring) if callable(scoring) else np.asarray(scoring, dtype=np.float32)
+        kw = dict(q_lo=q_lo, q_hi=q_hi, backward=backward, match=float(match), mismatch=float(mismatch), gap_open=float(gap_open),
+                  gap_extend=float(gap_extend), lut=lut, band_lo=band[0], band_hi=band[1], zdrop=float(zdrop))
+        if traceback:
+            return ctx.affine_extend_zdrop_trace(query, lefts, rights, to_end=to_end, **kw)
+        return ctx.affine_extend_zdrop_run(query, lefts, rights, **kw)
+
+    @staticmethod
     def global_pairs(query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0, gap_extend=1.0,
                      scoring=None, traceback=False, context=None, band=None):
         """A mapper's gap fill: pair k = the letters [q_lo[k], q_hi[k]) of query[k] against the window [lefts[k], rights[k]), anchored

@@ -29,6 +29,7 @@ EXPORTS = [
     "mi355_sw_affine_extend_run", "mi355_sw_affine_extend_trace",
     "mi355_sw_affine_extend_run_band", "mi355_sw_affine_extend_trace_band",
     "mi355_sw_affine_global_run", "mi355_sw_affine_global_trace",
+    "mi355_sw_affine_extend_run_zdrop", "mi355_sw_affine_extend_trace_zdrop",
     "mi355_sw_seed_k", "mi355_sw_seed_hash", "mi355_sw_seed_cluster", "mi355_sw_seed_hits",
     "mi355_sw_seed_usable", "mi355_sw_seed_certify_ok", "mi355_sw_seed_certify_window",
 ]
@@ -551,6 +552,11 @@ class Context:
         band_lo / band_hi (mi355_sw_affine_extend_run_band; a scalar or an array per pair, band_lo <= 0 <= band_hi): only cells with
         band_lo <= j - i <= band_hi count, i and j the letters and columns consumed from the anchor.  A read end the band cannot
         reach comes back as to_end_score = float("-inf") and to_end_y = -1."""
+        return self._extend_run(query, lefts, rights, q_lo, q_hi, backward, match, mismatch, gap_open, gap_extend, lut, band_lo, band_hi)
+
+    def _extend_run(self, query, lefts, rights, q_lo, q_hi, backward, match, mismatch, gap_open, gap_extend, lut, band_lo, band_hi,
+                    zdrop=None):
+        """affine_extend_run, and with zdrop (not None) affine_extend_zdrop_run: the _zdrop entry point, which also fills rows_done."""
         p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
         el, n, arrays = self._extend_list(query, lefts, rights, q_lo, q_hi, backward)
         blo, bhi = self._extend_bands(band_lo, band_hi, n)
@@ -558,12 +564,28 @@ class Context:
         ex, ey, ty = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
         f32, i64 = C.POINTER(C.c_float), C.POINTER(C.c_int64)
         outs = (score.ctypes.data_as(f32), ex.ctypes.data_as(i64), ey.ctypes.data_as(i64), tscore.ctypes.data_as(f32), ty.ctypes.data_as(i64))
-        if blo is None:
+        out = dict(score=score, end_x=ex, end_y=ey, to_end_score=tscore, to_end_y=ty)
+        if zdrop is not None:
+            out["rows_done"] = np.zeros(n, dtype=np.int64)
+            self._chk(self._L.mi355_sw_affine_extend_run_zdrop(self._ctx, C.byref(el), None if blo is None else blo.ctypes.data_as(i64),
+                                                               None if bhi is None else bhi.ctypes.data_as(i64), C.c_float(zdrop),
+                                                               C.byref(p), *outs, out["rows_done"].ctypes.data_as(i64)))
+        elif blo is None:
             self._chk(self._L.mi355_sw_affine_extend_run(self._ctx, C.byref(el), C.byref(p), *outs))
         else:
             self._chk(self._L.mi355_sw_affine_extend_run_band(self._ctx, C.byref(el), blo.ctypes.data_as(i64), bhi.ctypes.data_as(i64),
                                                               C.byref(p), *outs))
-        return dict(score=score, end_x=ex, end_y=ey, to_end_score=tscore, to_end_y=ty)
+        return out
+
+    def affine_extend_zdrop_run(self, query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0,
+                                gap_extend=1.0, lut=None, band_lo=None, band_hi=None, zdrop=float("inf")):
+        """affine_extend_run inside a band under the z-drop stop rule (mi355_sw_affine_extend_run_zdrop): the extension of pair k
+        stops after the first row i < m whose in-band maximum r_i falls more than zdrop below the running best B, the gap between
+        their diagonals allowed for: B - r_i - d gap_extend > zdrop.  The results are those of affine_extend_run with the same band on
+        the first rows_done[k] letters, and a pair that stopped has to_end_score = float("-inf") and to_end_y = -1.  The dict gains
+        rows_done (the stop row, or m).  Bands are required; zdrop = inf is affine_extend_run with these bands."""
+        return self._extend_run(query, lefts, rights, q_lo, q_hi, backward, match, mismatch, gap_open, gap_extend, lut, band_lo, band_hi,
+                                zdrop=float(zdrop))
 
     def affine_extend_trace(self, query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0,
                             gap_extend=1.0, lut=None, to_end=None, band_lo=None, band_hi=None):
@@ -573,16 +595,33 @@ class Context:
         anchor: reversed for a forward pair, left to right in the original strings for a backward pair.  The CIGAR is in reading
         order for both directions.  band_lo / band_hi (mi355_sw_affine_extend_trace_band): as affine_extend_run; every emitted cell
         lies in the band, and a pair traced to an end the band cannot reach has score float("-inf"), end 0 / 0 and empty strings."""
+        return self._extend_trace(query, lefts, rights, q_lo, q_hi, backward, match, mismatch, gap_open, gap_extend, lut, to_end, band_lo, band_hi)
+
+    def affine_extend_zdrop_trace(self, query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0,
+                                  gap_extend=1.0, lut=None, to_end=None, band_lo=None, band_hi=None, zdrop=float("inf")):
+        """affine_extend_zdrop_run with the traceback (mi355_sw_affine_extend_trace_zdrop): affine_extend_trace's dict and rows_done.
+        Every emitted cell lies in the band and in rows <= rows_done; a pair that stopped, traced to_end, is the empty alignment."""
+        return self._extend_trace(query, lefts, rights, q_lo, q_hi, backward, match, mismatch, gap_open, gap_extend, lut, to_end, band_lo, band_hi,
+                                  zdrop=float(zdrop))
+
+    def _extend_trace(self, query, lefts, rights, q_lo, q_hi, backward, match, mismatch, gap_open, gap_extend, lut, to_end, band_lo, band_hi,
+                      zdrop=None):
+        """affine_extend_trace, and with zdrop (not None) affine_extend_zdrop_trace."""
         p, keep = make_affine_params(match, mismatch, gap_open, gap_extend, lut)
         el, n, arrays = self._extend_list(query, lefts, rights, q_lo, q_hi, backward)
         blo, bhi = self._extend_bands(band_lo, band_hi, n)
         te = self._per_pair(None if to_end is None else np.asarray(to_end).astype(bool), n, np.uint8, "to_end")
         res = (Result * max(1, n))()
         tscore, ty = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int64)
+        rows_done = np.zeros(n, dtype=np.int64)
         i64 = C.POINTER(C.c_int64)
         tail = (te.ctypes.data_as(C.POINTER(C.c_uint8)) if te is not None else None, res,
                 tscore.ctypes.data_as(C.POINTER(C.c_float)), ty.ctypes.data_as(i64))
-        if blo is None:
+        if zdrop is not None:
+            self._chk(self._L.mi355_sw_affine_extend_trace_zdrop(self._ctx, C.byref(el), None if blo is None else blo.ctypes.data_as(i64),
+                                                                 None if bhi is None else bhi.ctypes.data_as(i64), C.c_float(zdrop),
+                                                                 C.byref(p), *tail, rows_done.ctypes.data_as(i64)))
+        elif blo is None:
             self._chk(self._L.mi355_sw_affine_extend_trace(self._ctx, C.byref(el), C.byref(p), *tail))
         else:
             self._chk(self._L.mi355_sw_affine_extend_trace_band(self._ctx, C.byref(el), blo.ctypes.data_as(i64), bhi.ctypes.data_as(i64),
@@ -600,6 +639,8 @@ class Context:
             out[k] = np.array([r[k] for r in rows], dtype=np.int64)
         for k in ("cons_x", "cons_y", "cigar"):
             out[k] = [r[k] for r in rows]
+        if zdrop is not None:
+            out["rows_done"] = rows_done
         return out
 
     def affine_global_run(self, query, lefts, rights, q_lo=None, q_hi=None, backward=None, match=3.0, mismatch=-3.0, gap_open=5.0,
@@ -664,7 +705,8 @@ class Context:
         self._L.mi355_sw_last_counters(self._ctx, c)
         out = dict(requeried=int(c[0]), whole_batch_again=int(c[1]), candidates=int(c[2]), left_window=int(c[3]))
         for name in ("first_settled", "saved_locates", "saved_traces", "saved_fallbacks", "walk_widened", "wait_retries", "early_settled", "beyond_f16", "prefix_certified",
-                     "prefix_second_pass", "prefix_thinned", "prefix_thin_items", "pooled_loops", "prefix_seeded", "prefix_seed_hits", "prefix_calibrated", "seed_certified"):
+                     "prefix_second_pass", "prefix_thinned", "prefix_thin_items", "pooled_loops", "prefix_seeded", "prefix_seed_hits", "prefix_calibrated", "seed_certified",
+                     "zdrop_stopped", "zdrop_rows_run"):
             v = C.c_uint64(0)
             rc = self._L.mi355_sw_last_counter(self._ctx, name.encode(), C.byref(v))
             if rc:

@@ -94,6 +94,8 @@ struct AffineCall {
   int mode = MI355_SW_AFFINE_LOCAL;          // pairs calls: MI355_SW_AFFINE_END_TO_END (no floor, row m wins; include/mi355_sw.h)
   bool e2e() const { return mode == MI355_SW_AFFINE_END_TO_END; }
   bool ext() const { return mode == kAffineModeExt; }              // the anchored model of the extension calls (affine_extend)
+  float zdrop = INFINITY;                    // the extension calls' z-drop (include/mi355_sw.h "z-drop"); +inf: no stop rule
+  bool zd() const { return zdrop < INFINITY; }
 };
 
 // End-to-end mode: are all values of a problem of m rows integers below 2^24 in magnitude (exact in float32, no bit reserved)?
@@ -144,6 +146,11 @@ AffineKernel affine_kernel(int SL, int R) {
 }
 
 size_t affine_exact_lds(int m) { return (size_t)7 * (m + 2) * 4 + (size_t)m + 16; }
+// the rows instance (sw_affine_exact_rows_band_kernel): the letters padded to a word, then a maximum and a column per row
+constexpr size_t affine_exact_rows_lds(int m) { return (size_t)7 * (m + 2) * 4 + (((size_t)m + 3) & ~(size_t)3) + (size_t)8 * (m + 1) + 16; }
+constexpr int kAffineExactRowsMax = 4398;    // its row limit (the other instances': 5600)
+inline size_t affine_exact_lds(int m, bool rows) { return rows ? affine_exact_rows_lds(m) : affine_exact_lds(m); }
+static_assert(affine_exact_rows_lds(kAffineExactRowsMax) <= kExactLdsMax && affine_exact_rows_lds(kAffineExactRowsMax + 1) > kExactLdsMax, "the bound the refusal names");
 
 // A job of the exact kernel under a band, blo <= j - i <= bhi in its window's local coordinates: the BAND instance takes it.
 struct ExactBandJob : ExactJob { int32_t blo = 0, bhi = 0; };
@@ -230,13 +237,14 @@ int affine_exact_stage(const AffineCall &c, std::vector<Job> &jobs) {
 
 // (best, cell) of the np problems launched since ev[0], from outs_f / outs_i through pin_out: closes the interval (ev[1]), copies,
 // waits, adds the interval to timings[0].  h_best[np], h_cell[np][2]: views into pin_out.  `nomem`: the caller's ENOMEM message.
-int affine_download(mi355_sw_ctx *ctx, size_t np, const char *nomem, const float *&h_best, const int64_t *&h_cell) {
+// tail_f: further bytes of outs_f behind the np results that ride with the same copy (the z-drop mode's row counter).
+int affine_download(mi355_sw_ctx *ctx, size_t np, const char *nomem, const float *&h_best, const int64_t *&h_cell, size_t tail_f = 0) {
   HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-  const size_t o_cell = (np * 4 + 15) & ~(size_t)15;
+  const size_t o_cell = (np * 4 + tail_f + 15) & ~(size_t)15;
   if (ctx->pin_out.ensure(o_cell + np * 16)) return fail(ctx, MI355_SW_ENOMEM, nomem);
   uint8_t *pin = ctx->pin_out.as<uint8_t>();
   h_best = reinterpret_cast<const float *>(pin); h_cell = reinterpret_cast<const int64_t *>(pin + o_cell);
-  HIPCHK(ctx, hipMemcpyAsync(pin, ctx->outs_f.p, np * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(pin, ctx->outs_f.p, np * 4 + tail_f, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(pin + o_cell, ctx->outs_i.p, np * 16, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->timings[0] += elapsed_us(ctx, ctx->ev[0], ctx->ev[1]);
@@ -821,12 +829,16 @@ int affine_band_R(int64_t W) {
 //   M::path(c), M::name(c)    the two name strings of a launch (path_note, mi355_sw_last_kernel)
 //   M::ops(c, R)              the op count per cell of the compiled row loop
 //   M::kNoInstance            the message of a missing instance
+// M::kCountsRows (optional, the z-drop mode alone): the mode's wavefronts add the rows their loops ran to AffinePairArgs::zrows
+template <class M, class = void> struct AffineModeCountsRows : std::false_type {};
+template <class M> struct AffineModeCountsRows<M, std::void_t<decltype(M::kCountsRows)>> : std::integral_constant<bool, M::kCountsRows> {};
 template <class M>
 struct AffinePairFamily {
   typedef AffinePairProblem Problem; typedef typename M::Source Source; typedef typename Source::Item Item;
   const AffineCall &c; Source src;
   static constexpr const char *kNoInstance = M::kNoInstance;
   static constexpr int kOuts = M::kOuts;
+  static constexpr bool kCountsRows = false;
   bool keep_all() const { return M::keep_all(c); }
   static uint32_t id(const Item &a) { return Source::id(a); }
   int R(const Item &a) const { return affine_pair_R(src.rows(c, a)); }
@@ -850,6 +862,7 @@ struct AffineBandFamily {
   const AffineCall &c; Source src;
   static constexpr const char *kNoInstance = M::kNoInstance;
   static constexpr int kOuts = M::kOuts;
+  static constexpr bool kCountsRows = AffineModeCountsRows<M>::value;
   bool keep_all() const { return M::keep_all(c); }
   static uint32_t id(const Item &a) { return Source::id(a); }
   static int R(const Item &a) { return affine_band_R(a.W); }
@@ -947,6 +960,8 @@ int affine_list_stage(const F &f, const AffineProfPlan &plan, std::vector<typena
   sa.nrows = nrows; sa.ncls = ncls;
   int rc = affine_class_table(c, plan, mmax, tab_floats, 1, ncls, "hipMalloc(affine pair table) failed", sa.tab, sa);
   if (rc) return rc;
+  sa.zdrop_s = std::floor(c.zdrop) / sa.unscale;                   // (a power of two: exact; read by the z-drop mode alone, as the word below)
+  sa.zrows = nullptr;
   for (size_t g0 = 0; g0 < items.size(); g0 += kAffinePairGroupProblems) {
     const size_t np = std::min(kAffinePairGroupProblems, items.size() - g0);
     const char *nomem = "affine pairs: allocation of the pair scratch failed";
@@ -955,6 +970,13 @@ int affine_list_stage(const F &f, const AffineProfPlan &plan, std::vector<typena
         ctx->pin_probs.ensure(np * sizeof(Problem)))
       return fail(ctx, MI355_SW_ENOMEM, nomem);
     Problem *pr = ctx->pin_probs.as<Problem>();
+    // the z-drop mode's row counter: a word of outs_f behind the group's results (the 64 spare bytes), zeroed in front of the
+    // launches and brought down by the results' own copy — no launch, copy or wait of its own
+    const size_t zrows_at = (NO * np * 4 + 7) & ~(size_t)7, zrows_tail = F::kCountsRows ? zrows_at + 8 - NO * np * 4 : 0;
+    if (F::kCountsRows) {
+      sa.zrows = reinterpret_cast<unsigned long long *>(ctx->outs_f.as<uint8_t>() + zrows_at);
+      HIPCHK(ctx, hipMemsetAsync(sa.zrows, 0, 8, ctx->stream));
+    }
     for (size_t i = 0; i < np; ++i) f.fill(items[g0 + i], pr[i]);  // one upload of the pair list
     HIPCHK(ctx, hipMemcpyAsync(ctx->wprobs.p, pr, np * sizeof(Problem), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
@@ -974,7 +996,12 @@ int affine_list_stage(const F &f, const AffineProfPlan &plan, std::vector<typena
       i0 = i1;
     }
     const float *h_best = nullptr; const int64_t *h_cell = nullptr;
-    rc = affine_download(ctx, NO * np, nomem, h_best, h_cell); if (rc) return rc;
+    rc = affine_download(ctx, NO * np, nomem, h_best, h_cell, zrows_tail); if (rc) return rc;
+    if (F::kCountsRows) {
+      unsigned long long ran = 0;
+      memcpy(&ran, reinterpret_cast<const uint8_t *>(h_best) + zrows_at, 8);
+      ctx->zdrop_rows_run += (size_t)ran;
+    }
     for (size_t i = 0; i < NO * np; ++i) {
       const size_t id = NO * f.id(items[g0 + i / NO]) + i % NO;
       if (!f.keep_all() && !(h_best[i] > 0)) continue;
@@ -1291,6 +1318,113 @@ struct AffineBandExtMode {
   }
 };
 
+// ---- the z-drop stop rule of the banded extension (include/mi355_sw.h "z-drop", DESIGN.md §3.8 lemma L24) ----
+// sw_affine_band_extz_kernel: AffineBandExtMode's items and results under the stop rule; the to-end half's first cell word is rows_done.
+struct AffineBandExtZMode {
+  typedef AffineOwnItem Source;
+  static constexpr const char *kNoInstance = "internal: no sw_affine_band_extz_kernel instance for this band";
+  static constexpr int kOuts = 2;
+  static constexpr bool kCountsRows = true;                        // counter zdrop_rows_run (affine_list_stage)
+  static bool keep_all(const AffineCall &) { return true; }
+  template <int R> static auto kernel(const AffineCall &) { return &sw_affine_band_extz_kernel<R>; }
+  static const char *path(const AffineCall &) { return "affine_band_extz[R=%d]"; }
+  static const char *name(const AffineCall &) { return "sw_affine_band_extz_kernel<R=%d>"; }
+  static double ops(const AffineCall &, int R) {
+    // per step and lane, counted in the compiled row loop of all eight instances against the extension instance's loop: that mode's
+    // count (AffineBandExtMode::ops), five more per register — the unsigned compare of the column against n, the compare with the
+    // lane's row maximum, their and on the scalar side, two selects and the column's add — and 53 of overhead: four rounds of move,
+    // DPP move, canonicalisation and max for the slot's row maximum (the maxima of moved values are canonicalised, those of results
+    // of arithmetic are not), compare and select of the column's candidates, four rounds of move, DPP move and min for the column,
+    // the freeze of the key, and the rule itself (row, the two diagonals, their distance and its conversion, multiply, add,
+    // subtract, three compares, three selects, the ballot's compare).  5 R + 53 fits all eight instances to within one op
+    return (20.0 * R + (R + 1) / 2 + 86.0) / (double)R;
+  }
+};
+
+// Lemma L24, what the band kernel's stop test needs beyond L22 (affine_band_ext_exact): it compares r_i + d e with B - floor(zdrop).
+// d is the distance of two in-band diagonals, at most W - 1; r_i + d e is an integer within (-2^24, smax m + (W - 1) e], and
+// smax m + (W - 1) e < 2^24 follows from L22's 3o + (W + 1) e < 2^24 and smax (m + 1) < 2^18 for W <= 256 (o >= e).  B - floor(zdrop) lies
+// in (-2^24, 2^18) where zdrop < 2^24.  B - r_i - d e is an integer, so it exceeds zdrop exactly where it exceeds floor(zdrop).
+bool affine_band_zdrop_exact(float zdrop) { return zdrop < 16777216.0f; }
+
+// The stop rule over rows 1..m-1 (include/mi355_sw.h "z-drop"): rmax[i-1] / rcol[i-1] = the maximum of row i over its in-band real
+// columns (-inf: none) and its smallest column.  Returns rows_done: the stop row, or m.  Every operand is an integer below 2^25: exact
+// in double.
+int64_t affine_zdrop_stop_row(const float *rmax, const int32_t *rcol, int64_t m, double ext, double zdrop) {
+  double B = 0.0; int64_t bdiag = 0;                               // the anchor (0, 0)
+  for (int64_t i = 1; i < m; ++i) {
+    const double r = rmax[i - 1];
+    if (r > B) { B = r; bdiag = (int64_t)rcol[i - 1] - i; continue; }
+    if (r == -INFINITY) return i;
+    const int64_t cd = (int64_t)rcol[i - 1] - i, d = bdiag > cd ? bdiag - cd : cd - bdiag;
+    if (B - r - (double)d * ext > zdrop) return i;
+  }
+  return m;
+}
+// The same on an empty window: row i is the border cell (i, 0) = -(o + (i-1) e) where -i >= band_lo, so B stays 0 at the anchor, d = i
+// and the test reads o - e > zdrop in every row; a row below the band has no cell and stops.
+int64_t affine_zdrop_stop_row_border(int64_t m, int64_t band_lo, double open, double ext, double zdrop) {
+  if (m < 2) return m;
+  if (open - ext > zdrop) return 1;
+  return band_lo > -m + 1 ? -band_lo + 1 : m;                      // the first row i with -i < band_lo, where that is below m
+}
+
+// First step of the exact path under the stop rule: sw_affine_exact_rows_band_kernel over `jobs` (banded items on their clipped
+// windows), the rule on the host, and m := rows_done in the job — the second step is affine_ext_exact_stage<true> on what is left.
+int affine_ext_rows_stage(const AffineCall &c, std::vector<AffineExtItem> &jobs, int64_t *rows_done) {
+  mi355_sw_ctx *ctx = c.ctx;
+  if (jobs.empty()) return 0;
+  path_note(ctx, "affine_exact_band_rows");
+  AffineScoring sc;
+  { int rc = affine_scoring(ctx, c.p, sc); if (rc) return rc; }
+  HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+  for (size_t lo = 0; lo < jobs.size();) {
+    size_t hi = lo, lds = 0, words = 0;                            // a launch: at most 65536 problems and 2^24 row words
+    while (hi < jobs.size() && hi - lo < 65536 && (hi == lo || words + 2 * (size_t)jobs[hi].m <= ((size_t)1 << 24))) {
+      lds = std::max(lds, affine_exact_lds(jobs[hi].m, true)); words += 2 * (size_t)jobs[hi].m; ++hi;
+    }
+    const size_t n = hi - lo;
+    if (ctx->probs.ensure(n * sizeof(ExactBandProblem)) || ctx->hmat.ensure(words * 4))
+      return fail(ctx, MI355_SW_ENOMEM, "hipMalloc(exact scratch) failed");
+    std::vector<ExactBandProblem> pr(n);
+    size_t at = 0;
+    for (size_t k = 0; k < n; ++k) {
+      const AffineExtItem &j = jobs[lo + k];
+      memset(&pr[k], 0, sizeof pr[k]);
+      pr[k].blo = j.blo; pr[k].bhi = j.bhi;
+      ExactProblem &e = pr[k].e;
+      e.x = j.x; e.y = j.ybytes; e.m = j.m; e.nw = (int32_t)j.n; e.full_n = j.n; e.own_lo = 1; e.target = -1.0f;
+      e.hout = ctx->hmat.as<float>() + at; at += 2 * (size_t)j.m;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactBandProblem), hipMemcpyHostToDevice, ctx->stream));
+    launch_dyn_lds(&sw_affine_exact_rows_band_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactBandProblem>(), sc);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<float> rows(words);
+    std::vector<int32_t> cols;
+    HIPCHK(ctx, hipMemcpyAsync(rows.data(), ctx->hmat.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    at = 0;
+    for (size_t k = 0; k < n; ++k) {
+      AffineExtItem &j = jobs[lo + k];
+      const int64_t m = j.m;
+      static_assert(sizeof(int32_t) == sizeof(float), "the columns travel as bits");
+      cols.resize((size_t)m);
+      memcpy(cols.data(), rows.data() + at + m, (size_t)m * 4);
+      const int64_t s = affine_zdrop_stop_row(rows.data() + at, cols.data(), m, (double)c.t.ext, (double)c.zdrop);
+      at += 2 * (size_t)m;
+      rows_done[j.id] = s;
+      if (s < m) {                                                 // the truncated pair: its rows, its window clipped again, the same band
+        j.m = (int32_t)s;
+        j.n = std::min<int64_t>(j.n, s + j.bhi); j.bhi = (int32_t)std::min<int64_t>(j.bhi, j.n);
+      }
+    }
+    lo = hi;
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+  ctx->timings[1] += elapsed_us(ctx, ctx->ev[2], ctx->ev[3]);
+  return 0;
+}
+
 // sw_affine_exact_ext_kernel over all of `jobs`, 65536 per launch: score[npairs][2], ends[npairs][2][2] as the list stage; its
 // interval goes to timings[1].
 // BAND: sw_affine_exact_ext_band_kernel over jobs that carry their band (AffineExtItem::blo, bhi) and their clipped window.
@@ -1467,18 +1601,29 @@ int affine_ext_trace(const AffineCall &c, const std::vector<AffineExtItem> &pair
 // clipped window — sw_affine_band_ext_kernel while rows, diagonals, table and admission (affine_band_ext_exact) allow and option
 // no_affine_band is off, else the exact kernel under the band — and never runs on an unbanded kernel.  The stages run in a fixed
 // order: the pair kernel, the band kernel, the exact kernel's unbanded and then its banded jobs, the two passes of the traceback.
+// zdrop < +inf (the z-drop calls; bands required, the caller checks): the stop rule of include/mi355_sw.h "z-drop" (DESIGN.md §3.8,
+// L24).  rows_done[npairs] (may be null): the stop row of pair k, or m.  Every pair with m, n >= 1 is then a banded pair, a band that
+// covers the matrix included: sw_affine_band_extz_kernel where the band kernel admits the pair and zdrop (affine_band_zdrop_exact),
+// else the exact path in two steps — the rows instance and the rule on the host (affine_ext_rows_stage), then the exact kernel under
+// the band on the first rows_done rows.  A pair that stopped never reached its row m: its to-end half is the `unreach` overwrite.  An
+// empty window is the rule on the border column, here.  zdrop = +inf changes nothing: rows_done = m.
 int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, const AffineExtList &el, const mi355_sw_affine_params &p,
-                  const uint8_t *to_end, float *score, int64_t *ends, std::vector<TraceOut> *tout) {
+                  const uint8_t *to_end, float *score, int64_t *ends, std::vector<TraceOut> *tout, float zdrop = INFINITY,
+                  int64_t *rows_done = nullptr) {
   const size_t npairs = el.npairs;
   for (size_t k = 0; k < 2 * npairs; ++k) { score[k] = 0.0f; ends[2 * k] = 0; ends[2 * k + 1] = 0; }
   if (tout) tout->assign(npairs, TraceOut());
   if (npairs > 0xFFFFFFFFull) return fail(ctx, MI355_SW_ENOTSUP, "affine extension: more than 2^32 pairs");
   AffineCall c{ctx, ref, q, p, AffineTable(), kAffineModeExt};
+  c.zdrop = zdrop;
   int rc = affine_begin(c);
   if (rc) return rc > 0 ? 0 : rc;
   AffineProfPlan plan;
   const bool table_ok = affine_ext_plan(c, plan);
   rc = affine_ext_any_reversed(c, el); if (rc) return rc;
+  std::vector<int64_t> own_rows_done;
+  if (!rows_done && c.zd()) { own_rows_done.resize(npairs); rows_done = own_rows_done.data(); }
+  std::vector<AffineExtItem> zfast;                                // z-drop: the banded pairs of sw_affine_band_extz_kernel
 
   std::vector<AffineExtItem> pairs(npairs), fast, jobs;
   std::vector<AffineExtItem> bfast, bjobs;                         // banded pairs of sw_affine_band_ext_kernel, and of the exact kernel under a band
@@ -1488,20 +1633,35 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
     AffineExtItem &it = pairs[k];
     it = affine_ext_item(c, el, k);
     const int64_t m = it.m, n = it.n;
+    if (rows_done) rows_done[k] = m;
     if (m < 1) continue;
     if (el.band_lo) {
       // the band clipped to the matrix; one that covers it leaves the pair unbanded: today's route below, today's bytes
       const int64_t lo_e = std::max(el.band_lo[k], -m), hi_e = std::min(el.band_hi[k], n);
-      if (lo_e != -m || hi_e != n) {
+      if (c.zd() && n < 1) {                                       // z-drop on an empty window: the rule on the border column
+        const int64_t s = affine_zdrop_stop_row_border(m, el.band_lo[k], (double)c.t.open, (double)c.t.ext, (double)c.zdrop);
+        if (s < m) { rows_done[k] = s; unreach[k] = 1; continue; } // nothing to extend, the end not reached: the zeros stand
+      }
+      if ((c.zd() && n >= 1) || lo_e != -m || hi_e != n) {         // (z-drop: a band that covers the matrix stays a band)
         const bool reach = lo_e <= n - m;                          // row m holds an in-band cell
         if (!reach) unreach[k] = 1;
         if (n < 1) continue;                                       // (lo_e > -m: unreachable) nothing to extend: the zeros stand
         // columns beyond m + hi_e are out of band in every row: the window is clipped before anything is sized
         const int64_t nc = std::min(n, m + hi_e), W = hi_e - lo_e + 1;
         it.n = nc; it.banded = true; it.blo = (int32_t)lo_e; it.bhi = (int32_t)std::min(hi_e, nc); it.W = (int32_t)std::min<int64_t>(W, 0x7fffffff);
-        if (table_ok && !opt().no_affine_band && m <= kBandRowsMax && affine_band_R(W) != 0 && affine_band_ext_exact(c.t, (double)m, (double)W)) {
-          bfast.push_back(it); band_mmax = std::max(band_mmax, (int)m);
+        if (table_ok && !opt().no_affine_band && m <= kBandRowsMax && affine_band_R(W) != 0 && affine_band_ext_exact(c.t, (double)m, (double)W) &&
+            (!c.zd() || affine_band_zdrop_exact(c.zdrop))) {
+          (c.zd() ? zfast : bfast).push_back(it); band_mmax = std::max(band_mmax, (int)m);
           continue;
+        }
+        if (c.zd() && m > kAffineExactRowsMax) {
+          char msg[480];
+          std::snprintf(msg, sizeof msg, "affine extension with z-drop: banded pair %zu (%lld rows, %lld diagonals) is outside the band kernel (1..512 rows, "
+                        "at most 256 diagonals, zdrop < 2^24%s) and has more rows than the rows instance of the exact kernel holds (at most %d rows: a "
+                        "maximum and a column per row beside the LDS diagonals)", k, (long long)m, (long long)W,
+                        opt().no_affine_band ? "; option no_affine_band is set" : opt().no_affine_pairs ? "; option no_affine_pairs is set" : "",
+                        kAffineExactRowsMax);
+          return fail(ctx, MI355_SW_ENOTSUP, msg);
         }
         if ((double)m * (double)nc > kAffineExactCellsMax || !affine_band_ext_whole_exact(c.t, (double)m, (double)W) || affine_exact_lds((int)m) > kExactLdsMax) {
           char msg[800];
@@ -1539,9 +1699,19 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
   }
   rc = affine_list_stage(AffinePairFamily<AffineExtMode>{c, {}}, plan, fast, mmax, score, ends);
   if (!rc) rc = affine_list_stage(AffineBandFamily<AffineBandExtMode>{c, {}}, plan, bfast, band_mmax, score, ends);
+  if (!rc && !zfast.empty()) {
+    // rows_done from where the other mode writes m (the stage also brings down the counter zdrop_rows_run)
+    rc = affine_list_stage(AffineBandFamily<AffineBandExtZMode>{c, {}}, plan, zfast, band_mmax, score, ends);
+    if (rc) return rc;
+    for (const AffineExtItem &it : zfast) rows_done[it.id] = ends[4 * (size_t)it.id + 2];
+  }
   if (!rc) rc = affine_ext_exact_stage(c, jobs, score, ends);
+  if (!rc && c.zd()) rc = affine_ext_rows_stage(c, bjobs, rows_done);
   if (!rc) rc = affine_ext_exact_stage<true>(c, bjobs, score, ends);
   if (rc) return rc;
+  if (c.zd())
+    for (size_t k = 0; k < npairs; ++k)
+      if (rows_done[k] < pairs[k].m) { unreach[k] = 1; ctx->zdrop_stopped += 1; }   // stopped: the read's end was not reached
   // a read whose end the band cannot reach: no kernel decides this.  Such a pair still ran on its kernel above, for the best
   // extension; what that kernel wrote for the to-end half (-inf / -1 as it happens) is deliberately ignored and overwritten here, so
   // that the header's rule band_lo > n - m alone decides.  Keep the overwrite.  Traced to the end the pair is an empty alignment
@@ -1556,7 +1726,7 @@ int affine_extend(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, co
       ts[k] = score[2 * k + w]; tx[k] = ends[4 * k + 2 * w]; ty[k] = ends[4 * k + 2 * w + 1];
     }
     rc = affine_ext_trace(c, pairs, ts.data(), tx.data(), ty.data(), *tout);
-    if (!rc && (!bfast.empty() || !bjobs.empty())) rc = affine_ext_trace<true>(c, pairs, ts.data(), tx.data(), ty.data(), *tout);
+    if (!rc && (!bfast.empty() || !zfast.empty() || !bjobs.empty())) rc = affine_ext_trace<true>(c, pairs, ts.data(), tx.data(), ty.data(), *tout);
     if (rc) return rc;
   }
   HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));

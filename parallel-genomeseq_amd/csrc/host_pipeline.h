@@ -2207,6 +2207,7 @@ void reset_timings(mi355_sw_ctx *ctx) {
   ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->prefix_seeded = 0; ctx->prefix_seed_hits = 0; ctx->seed_certified = 0; ctx->prefix_calibrated = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
   ctx->hook_ids.clear(); ctx->hook_nsub = 0;
   ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->walk_widened = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
+  ctx->zdrop_stopped = 0; ctx->zdrop_rows_run = 0;
   ctx->path.clear();
 }
 

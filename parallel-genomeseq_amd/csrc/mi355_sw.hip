@@ -552,9 +552,11 @@ int mi355_sw_affine_pairs_trace_band(mi355_sw_ctx *ctx, int mode, size_t npairs,
 
 // mi355_sw_affine_extend_run (score .. to_end_y) and, with `trace`, mi355_sw_affine_extend_trace (outs), written only after success
 // (and their _band twins: without bands the call itself; the band checks come last)
+// zcall: the _zdrop twins of the _band calls — bands are required and zdrop >= 0, checked behind the band checks; rows_done may be null
 static int affine_extend_any(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const mi355_sw_affine_params *params, bool trace,
                              const uint8_t *to_end, float *score, int64_t *end_x, int64_t *end_y, mi355_sw_result *outs, float *to_end_score,
-                             int64_t *to_end_y, const int64_t *band_lo = nullptr, const int64_t *band_hi = nullptr) {
+                             int64_t *to_end_y, const int64_t *band_lo = nullptr, const int64_t *band_hi = nullptr, bool zcall = false,
+                             float zdrop = INFINITY, int64_t *rows_done = nullptr) {
   OptScope opt_scope_(ctx);
   int rc = affine_check(ctx, params);
   if (rc) return rc;
@@ -577,12 +579,17 @@ static int affine_extend_any(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list
   if (band_lo)
     for (size_t k = 0; k < npairs; ++k)
       if (band_lo[k] > 0 || band_hi[k] < 0) return fail(ctx, MI355_SW_EINVAL, "banded extension: the band must hold the anchor's diagonal, band_lo <= 0 <= band_hi");
+  if (zcall && !band_lo) return fail(ctx, MI355_SW_EINVAL, "z-drop extension: band_lo and band_hi are required (an unbanded z-drop has no kernel)");
+  if (zcall && !(zdrop >= 0.0f)) return fail(ctx, MI355_SW_EINVAL, "z-drop extension: zdrop must be >= 0 (+INFINITY: no stop rule)");
   std::vector<float> sc(2 * npairs, 0.0f);
   std::vector<int64_t> ends(4 * npairs, 0);
   std::vector<TraceOut> tout(trace ? npairs : 0);
+  std::vector<int64_t> rows(zcall ? npairs : 0);
   const AffineExtList el{npairs, list->query, list->q_lo, list->q_hi, list->lefts, list->rights, list->backward, band_lo, band_hi};
-  rc = affine_extend(ctx, ctx->ref, ctx->batch, el, *params, trace ? to_end : nullptr, sc.data(), ends.data(), trace ? &tout : nullptr);
+  rc = affine_extend(ctx, ctx->ref, ctx->batch, el, *params, trace ? to_end : nullptr, sc.data(), ends.data(), trace ? &tout : nullptr,
+                     zcall ? zdrop : INFINITY, zcall ? rows.data() : nullptr);
   if (rc) return rc;
+  if (rows_done) for (size_t k = 0; k < npairs; ++k) rows_done[k] = rows[k];
   for (size_t k = 0; k < npairs; ++k) {
     const size_t w = (trace && to_end && to_end[k]) ? 1 : 0;         // the traced alignment: best extension, or to the end
     if (trace) {
@@ -618,6 +625,18 @@ int mi355_sw_affine_extend_trace_band(mi355_sw_ctx *ctx, const mi355_sw_extend_l
                                       const mi355_sw_affine_params *params, const uint8_t *to_end, mi355_sw_result *outs, float *to_end_score,
                                       int64_t *to_end_y) {
   return affine_extend_any(ctx, list, params, true, to_end, nullptr, nullptr, nullptr, outs, to_end_score, to_end_y, band_lo, band_hi);
+}
+
+int mi355_sw_affine_extend_run_zdrop(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo, const int64_t *band_hi, float zdrop,
+                                     const mi355_sw_affine_params *params, float *score, int64_t *end_x, int64_t *end_y, float *to_end_score,
+                                     int64_t *to_end_y, int64_t *rows_done) {
+  return affine_extend_any(ctx, list, params, false, nullptr, score, end_x, end_y, nullptr, to_end_score, to_end_y, band_lo, band_hi, true, zdrop, rows_done);
+}
+
+int mi355_sw_affine_extend_trace_zdrop(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo, const int64_t *band_hi, float zdrop,
+                                       const mi355_sw_affine_params *params, const uint8_t *to_end, mi355_sw_result *outs, float *to_end_score,
+                                       int64_t *to_end_y, int64_t *rows_done) {
+  return affine_extend_any(ctx, list, params, true, to_end, nullptr, nullptr, nullptr, outs, to_end_score, to_end_y, band_lo, band_hi, true, zdrop, rows_done);
 }
 
 // mi355_sw_affine_global_run (score) and, with `trace`, mi355_sw_affine_global_trace (outs), written only after success; the checks and
@@ -809,6 +828,8 @@ int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *o
   else if (k == "saved_traces") *out = ctx->saved_traces;
   else if (k == "saved_fallbacks") *out = ctx->saved_fallbacks;
   else if (k == "walk_widened") *out = ctx->walk_widened;
+  else if (k == "zdrop_stopped") *out = ctx->zdrop_stopped;
+  else if (k == "zdrop_rows_run") *out = ctx->zdrop_rows_run;
   else if (k == "pooled_loops") *out = tl_pooled_loops;            // (the calling thread's last call: this function opens no OptScope)
   else return MI355_SW_EINVAL;
   return 0;

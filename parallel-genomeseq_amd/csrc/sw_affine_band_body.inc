@@ -62,6 +62,10 @@
   const char *tab_b = reinterpret_cast<const char *>(tab);
   const uint8_t *yl = yw + l * R;
   [[maybe_unused]] const int col0 = lo + l * R + 1;                // column of register 0 in row 0 (it = 0 is row 1: + it)
+  // kZdrop: the rule's running best B and the diagonal bj - bi of its cell, the stop row (0: none yet) — the same in every lane of the
+  // slot — and the rows the wavefront's loop ran
+  [[maybe_unused]] float zB = 0.0f;
+  [[maybe_unused]] int zdiag = 0, zstop = 0, zrun = steps;
 
   for (int it = 0; it < steps; ++it) {
     const uint32_t xo = xw[it];
@@ -93,14 +97,23 @@
     G = fmaxf(G, band_dpp<0x118>(ninf, G) - dec8);
     float ce = band_dpp<0x111>(ninf, G);                           // E of register 0: everything left of the lane
     [[maybe_unused]] float mx = 0.0f, tpend = 0.0f;
+    [[maybe_unused]] float zr = ninf;                              // kZdrop: the lane's greatest real cell of this row at its smallest column
+    [[maybe_unused]] int zc = 0x3fffffff;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       float h = r == 0 ? fmaxf(Ht[0], ce) : fmaxf(fmaxf(Ht[r], q[r - 1]), ce);
       h = fminf(h, cap[r]);
       if constexpr (MODE::kKey) WaveKeyFold::cell<R>(r, MODE::kFloor ? h : fmaxf(h, 0.0f), mx, tpend);   // no floor in the cell: the floor on the answer, cell (0,0) competes
+      if constexpr (MODE::kZdrop) {
+        const int j = col0 + it + r;                               // 0 <= j <= n in one unsigned compare; columns rise with r: '>' keeps the smallest
+        const bool in = (uint32_t)j <= (uint32_t)n && h > zr;      // (a capped register holds -inf and never passes)
+        zr = in ? h : zr;
+        zc = in ? j : zc;
+      }
       Ho[r] = h - ov;
       if (r + 1 < R) ce = ce - ev;
     }
+    if constexpr (MODE::kZdrop) mx = zstop != 0 ? ninf : mx;       // a stopped slot: the key of -inf wins nothing, (bval, bcol, brow) freeze
     if constexpr (MODE::kKey) {
       // the step's best against the lane's: greater value, or the same value in a smaller column (header: Winner)
       const uint32_t kb = __float_as_uint(mx);
@@ -124,6 +137,10 @@
             eval = in ? h : eval;
             ecol = in ? j : ecol;
           }
+          if constexpr (MODE::kZdrop) {                            // a stopped slot never reached its row m: the fold is taken back
+            eval = zstop != 0 ? ninf : eval;
+            ecol = zstop != 0 ? 0x7fffffff : ecol;
+          }
         }
         if constexpr (MODE::kCorner) {
 #pragma unroll
@@ -131,6 +148,31 @@
         }
       }
     }
+    // the stop rule on row it + 1 (header: AffineBandExtZ; DESIGN.md §3.8, L24)
+    if constexpr (MODE::kZdrop) {
+      float rs = zr;                                               // the slot's r_i in every lane ...
+      rs = fmaxf(rs, band_dpp<0xB1>(rs, rs));
+      rs = fmaxf(rs, band_dpp<0x4E>(rs, rs));
+      rs = fmaxf(rs, band_dpp<0x141>(rs, rs));
+      rs = fmaxf(rs, band_dpp<0x140>(rs, rs));
+      int rc = zr == rs ? zc : 0x3fffffff;                         // ... and c_i, the smallest column among the lanes that hold it
+      rc = min(rc, band_dpp_i<0xB1>(rc));
+      rc = min(rc, band_dpp_i<0x4E>(rc));
+      rc = min(rc, band_dpp_i<0x141>(rc));
+      rc = min(rc, band_dpp_i<0x140>(rc));
+      const int row = it + 1, cdiag = rc - row;
+      const bool live = zstop == 0 && row < m;                     // row m is never tested; an idle slot has m = 0
+      const bool up = rs > zB;
+      const int dd = zdiag > cdiag ? zdiag - cdiag : cdiag - zdiag;
+      const bool drop = !up && rs + (float)dd * ev < zB - sa.zdrop_s;   // r_i = -inf: drops for every z
+      zB = live && up ? rs : zB;
+      zdiag = live && up ? cdiag : zdiag;
+      zstop = live && drop ? row : zstop;
+      if (__builtin_amdgcn_ballot_w64(zstop == 0 && row < m) == 0) { zrun = row; break; }   // wave-uniform: no slot of the wavefront is alive
+    }
+  }
+  if constexpr (MODE::kZdrop) {
+    if ((tid & 63) == 0) atomicAdd(sa.zrows, (unsigned long long)zrun);
   }
 
   // kKey: the lanes' winners -> the slot's
@@ -168,7 +210,7 @@
       sa.cell[2 * NO * (size_t)pid + 1] = bv > 0.0f ? bj : 0;
     }
     if constexpr (MODE::kRowM || MODE::kCorner) {
-      sa.cell[2 * NO * (size_t)pid + 2 * NO - 2] = m;
+      sa.cell[2 * NO * (size_t)pid + 2 * NO - 2] = MODE::kZdrop && zstop != 0 ? zstop : m;   // kZdrop: rows_done
       sa.cell[2 * NO * (size_t)pid + 2 * NO - 1] = MODE::kCorner ? n : ecol == 0x7fffffff ? -1 : ecol;
     }
   }

@@ -65,6 +65,9 @@ template <int CTRL>
 __device__ __forceinline__ float band_dpp(float old, float v) {
   return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp((int)__float_as_uint(old), (int)__float_as_uint(v), CTRL, 0xf, 0xf, false));
 }
+// a permutation of the slot's lanes (quad_perm, row_half_mirror, row_mirror: every lane has a source, no `old`)
+template <int CTRL>
+__device__ __forceinline__ int band_dpp_i(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
 
 // ---- ONE BODY (sw_affine_band_body.inc), a mode is a set of traits, an entry point only names its mode ----
 // Everything above is the scaffold of every mode: geometry, the two row_shl:1 moves for F, the max-plus scan for E, the windows of y
@@ -96,6 +99,7 @@ __device__ __forceinline__ float band_dpp(float old, float v) {
 //              Behind the same branch the lane that holds D takes Ho + o of that one register.  The host sends only pairs with
 //              lo <= n - m <= lo + W - 1 (the corner lies in the band), so D is one of the 16 R registers and holds a finite value.
 //              A slot reads at its own step, once; steps behind row m write nothing.
+//   kZdrop     the stop rule over the rows and the early exit (AffineBandExtZ below); off, nothing of it is compiled.
 //   kOuts      results (best, cell) a problem writes: one per fold or read.
 // The modes:
 // AffineBandLocal — sw_affine_band_kernel: the floor and the key (the file's head; exactness: DESIGN.md §3.8, L20).
@@ -115,19 +119,40 @@ __device__ __forceinline__ float band_dpp(float old, float v) {
 //   no per-step fold and no (bval, bcol, brow) state.  Padding and exactness: as the extension, without its key — every value of a
 //   real cell is an integer below 2^24 in magnitude (host_affine.h: affine_band_glob_exact), no mantissa bit is reserved.
 //   best[pid] = H(m, n), of any sign; cell[2 pid ..] = m, n.
+// AffineBandExtZ — sw_affine_band_extz_kernel, AffineBandExt under the Z-DROP STOP RULE (include/mi355_sw.h "z-drop", lemma L24): the
+//   traits of AffineBandExt and kZdrop.  Per row i (step it = i - 1) every lane folds the unfloored maximum of its registers over the
+//   REAL columns 0 <= j <= n at its smallest column (a capped register holds -inf; a padding column j > n can hold more than the
+//   row's real cells — an F chain runs down column n + 1 — and is masked as the row-m fold masks it).  Four DPP permutations inside
+//   the slot (quad_perm xor 1, xor 2, row_half_mirror, row_mirror) leave the slot's maximum r_i in all 16 lanes, four more the
+//   smallest column c_i among the lanes that hold it.  Every lane of the slot keeps the rule's state redundantly: B, the diagonal
+//   bj - bi of the cell that set it (d = |(i - bi) - (c_i - bj)| is the distance of two diagonals) and the stop row.  The test is
+//   r_i + d e < B - z: r_i + d e is an integer within (-2^24, smax m + (W - 1) e) units and B - z within (-2^24, 2^18) for z < 2^24, so
+//   no intermediate needs a 25th bit (L24); r_i = -inf (no real in-band column) stops.  Row m is not tested.  A stopped slot keeps
+//   executing: the step's key is replaced by -inf so that (bval, bcol, brow) freeze, the row-m fold is taken back (to the end: -inf /
+//   -1) and the stop row goes where AffineBandExt writes m.  The wavefront leaves the row loop by a `break` under a ballot: none of
+//   its four slots is alive (not stopped, row below m).  The loop stays `for (it < steps)`, so it ends whatever the data hold, and
+//   there is no barrier in or behind it: the four wavefronts of a workgroup leave at different steps.  At its exit a wavefront adds
+//   the rows its loop ran to *sa.zrows, one vector atomic.
+//   best / cell: as AffineBandExt, with cell[4 pid + 2] = rows_done (the stop row, or m).
 // A further mode is a trait set, its paragraph here and its entry point.  The compiled instances are the ones the three kernels were
 // before they shared a body (profiles/affine_list_merge_isa_identity.txt).
 struct AffineBandLocal {
   static constexpr bool kFloor = true, kKey = true, kRowM = false, kCorner = false;
+  static constexpr bool kZdrop = false;
   static constexpr int kOuts = 1;
 };
 struct AffineBandExt {
   static constexpr bool kFloor = false, kKey = true, kRowM = true, kCorner = false;
+  static constexpr bool kZdrop = false;
   static constexpr int kOuts = 2;
 };
 struct AffineBandGlob {
   static constexpr bool kFloor = false, kKey = false, kRowM = false, kCorner = true;
+  static constexpr bool kZdrop = false;
   static constexpr int kOuts = 1;
+};
+struct AffineBandExtZ : AffineBandExt {
+  static constexpr bool kZdrop = true;
 };
 
 // The entry points: a name per mode (public: include/mi355_sw.h documents them, mi355_sw_last_kernel reports them).  sa: as for
@@ -142,6 +167,10 @@ template <int R> __global__ __launch_bounds__(256) void sw_affine_band_ext_kerne
 }
 template <int R> __global__ __launch_bounds__(256) void sw_affine_band_glob_kernel(const AffineBandProblem *probs, int nprob, const AffinePairArgs sa) {
   using MODE = AffineBandGlob;
+#include "sw_affine_band_body.inc"
+}
+template <int R> __global__ __launch_bounds__(256) void sw_affine_band_extz_kernel(const AffineBandProblem *probs, int nprob, const AffinePairArgs sa) {
+  using MODE = AffineBandExtZ;
 #include "sw_affine_band_body.inc"
 }
 

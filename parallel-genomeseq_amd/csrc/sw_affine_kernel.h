@@ -257,12 +257,17 @@ enum : int { kAffStop = 0, kAffDiag = 1, kAffE = 2, kAffF = 3, kAffEExt = 4, kAf
 // where it lies in the band, else it is -inf as well.  The loop is the banded one, so both folds see in-band cells only, all finite;
 // a row m without an in-band cell leaves end = -inf (the host reports the pair as unreachable).  TRACE: an equality with -inf never
 // holds, so the walk stays in the band; it meets row 0 or column 0 on an in-band cell, and the rest of that border towards (0,0) is.
+// ROWS (EXT with BAND, score pass): the rows instance of the z-drop stop rule (include/mi355_sw.h "z-drop").  Beside
+// the two winners it keeps, per row i = 1..m, the maximum of H(i, jl) over the in-band real columns 0 <= jl <= nw and its smallest
+// column, in two more LDS arrays behind the letters of x: the border cell (i, 0) initialises them where it lies in the band (else -inf),
+// and the one cell of row i on a diagonal replaces them where it is greater — a row meets its columns in rising order, so '>' keeps the
+// smallest.  They are stored at the end: P.hout[i-1] = the maximum, P.hout[m + i-1] = the column's bits.  The host runs the rule.
 // GLOB (kAffineModelGlob): the anchored model again — EXT's borders, EXT's cells, with or without BAND — whose answer is the corner:
 // nothing competes, `best` is the value of cell (m, nw) (the lane that computes it; -inf in the others, and where the band misses the
 // corner, which the host never sends).  It has no TRACE instance of its own: the traceback of a corner is EXT's walk from (m, nw).
 struct AffineBest { float best; int64_t i, j; float end; int64_t end_j; };
 enum : int { kAffineModelLocal = 0, kAffineModelE2E = 1, kAffineModelExt = 2, kAffineModelGlob = 3 };
-template <bool TRACE, int MODEL, bool BAND>
+template <bool TRACE, int MODEL, bool BAND, bool ROWS = false>
 __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem P, const AffineScoring sc, uint8_t *smem_raw, const int blo,
                                                               const int bhi) {
   constexpr bool GLOB = MODEL == kAffineModelGlob;                 // EXT's matrix, the corner for an answer
@@ -271,6 +276,7 @@ __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem
   constexpr bool E2E = MODEL != kAffineModelLocal;                 // no floor and the column-0 border: every floor-free model
   static_assert(!(BAND && MODEL == kAffineModelE2E), "the banded end-to-end model is not defined");
   constexpr bool XB = EXT && BAND;                                 // the anchored model under a band: outside is -inf, borders only in the band
+  static_assert(!ROWS || (MODEL == kAffineModelExt && BAND && !TRACE), "the rows instance is the banded anchored score pass");
   const int lane = threadIdx.x;
   const int m = P.m, nw = P.nw;
   const int plen = m + 2;
@@ -278,10 +284,14 @@ __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem
   float *H0 = Hb, *H1 = Hb + plen, *H2 = Hb + 2 * plen;
   float *E0 = Hb + 3 * plen, *E1 = Hb + 4 * plen, *F0 = Hb + 5 * plen, *F1 = Hb + 6 * plen;
   uint8_t *xs = reinterpret_cast<uint8_t *>(Hb + 7 * plen);
+  [[maybe_unused]] float *rmax = reinterpret_cast<float *>(xs + ((m + 3) & ~3));   // ROWS: [m + 1] the row's maximum ...
+  [[maybe_unused]] int *rcol = reinterpret_cast<int *>(rmax + (m + 1));            // ... and [m + 1] its smallest column
   const float ninf = -__builtin_inff();
   for (int k = lane; k < 3 * plen; k += 64) Hb[k] = 0.0f;
   for (int k = lane; k < 4 * plen; k += 64) E0[k] = ninf;
   for (int k = lane; k < m; k += 64) xs[k] = P.x[k];
+  if constexpr (ROWS)
+    for (int i = 1 + lane; i <= m; i += 64) { rmax[i] = -i >= blo ? -(sc.gap_open + (float)(i - 1) * sc.gap_extend) : -__builtin_inff(); rcol[i] = 0; }
   if (E2E && lane == 0 && m >= 1) { H0[1] = -sc.gap_open; F0[1] = -sc.gap_open; }   // diagonal 1: cell (1, 0)
   if (EXT && lane == 0) { H0[0] = -sc.gap_open; E0[0] = -sc.gap_open; }             // and cell (0, 1)
   if (XB && lane == 0) {                                           // the two border cells of diagonal 1 where they miss the band
@@ -335,6 +345,9 @@ __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem
       const float x = Hpp[i - 1] + s;
       const float h = E2E ? fmaxf(x, fmaxf(e, f)) : fmaxf(fmaxf(x, 0.0f), fmaxf(e, f));
       Hc[i] = h; Ec[i] = e; Fc[i] = f;
+      // (row i is another lane's on the next diagonal, and the store loop behind reads it from yet another: one wavefront executes its
+      // LDS operations in order, as for Hc / Hp above — no barrier)
+      if constexpr (ROWS) { if (h > rmax[i]) { rmax[i] = h; rcol[i] = jl; } }
       if (TRACE) {
         const int src = (!E2E && h == 0.0f) ? kAffStop : h == x ? kAffDiag : h == e ? kAffE : kAffF;
         P.dirs[(size_t)d * (size_t)dstride + (size_t)(i - ilo)] = (uint8_t)(src | (e != eo ? kAffEExt : 0) | (f != fo ? kAffFExt : 0));
@@ -374,6 +387,8 @@ __device__ __forceinline__ AffineBest affine_exact_fill_model(const ExactProblem
       if (oe > end || (oe == end && oej < end_j)) { end = oe; end_j = oej; }
     }
   }
+  if constexpr (ROWS)
+    for (int i = 1 + lane; i <= m; i += 64) { P.hout[i - 1] = rmax[i]; P.hout[m + i - 1] = __int_as_float(rcol[i]); }
   return AffineBest{best, bi, bj, end, end_j};
 }
 
@@ -443,6 +458,14 @@ __global__ __launch_bounds__(64) void sw_affine_exact_ext_band_kernel(const Exac
     P.cell[0] = pos ? r.i : 0; P.cell[1] = pos ? r.j : 0;
     P.cell[2] = P.m; P.cell[3] = at0 ? 0 : (end == -__builtin_inff() ? -1 : r.end_j);
   }
+}
+
+// The rows instance under a band (ROWS of affine_exact_fill_model): P.hout[0 .. 2 m) = the rows' maxima and, as bits, their smallest
+// columns; P.best and P.cell are not written — the pair's results come from sw_affine_exact_ext_band_kernel on its first rows_done rows.
+__global__ __launch_bounds__(64) void sw_affine_exact_rows_band_kernel(const ExactBandProblem *probs, const AffineScoring sc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  const ExactProblem P = probs[blockIdx.x].e;
+  (void)affine_exact_fill_model<false, kAffineModelExt, true, true>(P, sc, smem_raw, probs[blockIdx.x].blo, probs[blockIdx.x].bhi);
 }
 
 // The anchored model's corner (GLOB of affine_exact_fill_model) on whole problems of at least one row and one column, with or without a

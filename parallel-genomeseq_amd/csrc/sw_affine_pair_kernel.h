@@ -66,8 +66,10 @@ struct AffinePairArgs {
   int32_t nrows, ncls;       // letters of the reference + 1, classes of x's bytes + 1
   float open_s, ext_s;       // o and e * 2^-k
   float unscale;             // 2^k
+  float zdrop_s;             // sw_affine_band_extz_kernel only: floor(zdrop) * 2^-k, below 2^24 units; in what was padding
   float *best;               // [nprob] maximum (0 when no positive cell)
   int64_t *cell;             // [nprob][2] = row (into x), column (into the window), 1-based, of the first maximum
+  unsigned long long *zrows; // sw_affine_band_extz_kernel only: the word its wavefronts add the rows of their loops to (null for every other kernel)
 };
 
 template <int R>

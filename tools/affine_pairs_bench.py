@@ -29,6 +29,15 @@
     is the exact kernel under the band (option no_affine_band), once per width; kernel time, ratio and the ratio the row loop's op
     count predicts come side by side.  Default --out: profiles/affine_extend_band_n1.json.
 
+  * --extend --band W_HALF[,W_HALF..] --zdrop Z[,Z..] [--chimeric F] [--scoring M,X,O,E]: the pairs of --extend --band under the z-drop stop
+    rule, Context.affine_extend_zdrop_run on sw_affine_band_extz_kernel, against the banded extension call (sw_affine_band_ext_kernel)
+    on the same pairs and bands, alternating in one process, medians and the spread of the steps.  --chimeric F replaces the tail of
+    that share of the reads, from a random point between 20 % and 80 % of the read, by random letters: the reads a stop rule is for.
+    Beside the times: the share of pairs that stopped, the rows the wavefronts ran (counter zdrop_rows_run) against the rows of the
+    list and against rows_done, and the ratio the row loops' op counts predict for a zdrop that never fires.  The z-drop result is
+    checked once per width against the exact path (option no_affine_band).  Default --out: profiles/affine_extend_zdrop_n1.json
+    (with --chimeric: affine_extend_zdrop_chimeric_n1.json).
+
   * --global [--band W_HALF[,W_HALF..]]: the reads of --extend, each against the window [at, at + 150) behind its true start, anchored at
     both ends: Context.affine_global_run on sw_affine_pair_glob_kernel (with --band: under [-w, w] on sw_affine_band_glob_kernel)
     alternating with Context.affine_extend_run (with --band: the banded extension call) on the same pairs in one process, medians
@@ -45,6 +54,8 @@ clock around the call.
     python tools/affine_pairs_bench.py --band 8,16,32,64
     python tools/affine_pairs_bench.py --extend
     python tools/affine_pairs_bench.py --extend --band 8,16,32,64
+    python tools/affine_pairs_bench.py --extend --band 8,16,32,64 --zdrop 1048576
+    python tools/affine_pairs_bench.py --extend --band 8,16,32,64 --zdrop 20,100 --chimeric 0.5 --scoring 1,-4,7,1
     python tools/affine_pairs_bench.py --global
     python tools/affine_pairs_bench.py --global --band 8,16,32,64
 
@@ -79,15 +90,24 @@ def main(argv=None):
     ap.add_argument("--extend", action="store_true", help="the anchored extension call against the local instance")
     ap.add_argument("--global", dest="glob", action="store_true", help="the call anchored at both ends against the extension call")
     ap.add_argument("--read-len", type=int, default=READ_LEN, help="rows of a read: picks the instance of the pair kernels")
+    ap.add_argument("--zdrop", default=None, help="with --extend --band: z-drop values, comma separated; the stop rule against the banded call")
+    ap.add_argument("--chimeric", type=float, default=0.0, help="with --zdrop: share of the reads whose tail is replaced by random letters")
+    ap.add_argument("--scoring", default=None, help="with --zdrop: match,mismatch,gap_open,gap_extend instead of 3,-3,5,1")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     READ_LEN = args.read_len
+    if args.zdrop is not None and not (args.extend and args.band is not None):
+        ap.error("--zdrop needs --extend --band")
+    if (args.chimeric or args.scoring is not None) and args.zdrop is None:
+        ap.error("--chimeric and --scoring belong to --zdrop")
     if args.glob and (args.extend or args.mode != "local"):
         ap.error("--global stands alone (with --band or without)")
     if args.extend and args.mode != "local":
         ap.error("--extend needs the local mode")
     if args.band is not None and args.mode != "local":
         ap.error("--band needs the local mode")
+    if args.out is None and args.zdrop is not None:
+        args.out = os.path.join(ROOT, "profiles", "affine_extend_zdrop_chimeric_n1.json" if args.chimeric else "affine_extend_zdrop_n1.json")
     if args.out is None:
         name = "affine_global_band_n1.json" if args.glob and args.band is not None else "affine_global_n1.json" if args.glob else "affine_extend_band_n1.json" if args.extend and args.band is not None else "affine_pairs_extend_n1.json" if args.extend else "affine_pairs_band_n1.json" if args.band is not None else "affine_pairs_e2e_n1.json" if args.mode == "end_to_end" else "affine_pairs_n1.json"
         args.out = os.path.join(ROOT, "profiles", name)
@@ -98,6 +118,11 @@ def main(argv=None):
     diag = np.zeros(args.pairs, dtype=np.int64)                       # the diagonal j - i of the read's true locus in its window
     for k in range(args.pairs):
         read, at = pgs.synth.read_from_ref(ref, 1000 + k, READ_LEN, sub_rate=0.03, indel_rate=0.02)[:2]
+        if args.chimeric and k < args.chimeric * args.pairs:          # a chimeric read: the tail from a random point is junk
+            rng = np.random.default_rng(7000 + k)
+            cut = int(rng.integers(READ_LEN // 5, 4 * READ_LEN // 5))
+            read = read.copy()
+            read[cut:] = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, len(read) - cut)]
         reads.append(read.tobytes())
         lefts[k] = int(at) if args.extend or args.glob else max(0, int(at) - FLANK)
         rights[k] = min(args.ref_len, int(at) + READ_LEN + (0 if args.glob else FLANK))
@@ -108,6 +133,8 @@ def main(argv=None):
     ctx.batch_upload(reads)
     if args.glob:
         return global_against_extend(args, ctx, reads, query, lefts, rights)
+    if args.zdrop is not None:
+        return zdrop_against_banded_extend(args, ctx, reads, query, lefts, rights)
     if args.extend and args.band is not None:
         return banded_extend_against_extend(args, ctx, reads, query, lefts, rights)
     if args.extend:
@@ -367,6 +394,75 @@ def banded_extend_against_extend(args, ctx, reads, query, lefts, rights):
         f.write(text + "\n")
     print(text)
     return 0 if all(equal.values()) and all(line[s]["not_above_unbanded"] for s in bands) else 1
+
+
+def zdrop_against_banded_extend(args, ctx, reads, query, lefts, rights):
+    """The banded extension call and the z-drop call at every value of --zdrop, at every half width of --band, on the same pairs,
+    alternating; one JSON line."""
+    widths = [int(w) for w in str(args.band).split(",")]
+    zdrops = [float(z) for z in str(args.zdrop).split(",")]
+    scoring = dict(SCORING)
+    if args.scoring is not None:
+        scoring = dict(zip(("match", "mismatch", "gap_open", "gap_extend"), (float(v) for v in args.scoring.split(","))))
+    sides = []
+    for w in widths:
+        sides.append(("band_w%d" % w, w, None))
+        sides += [("zdrop_w%d_z%g" % (w, z), w, z) for z in zdrops]
+    fields = ("score", "end_x", "end_y", "to_end_score", "to_end_y")
+    t = {s[0]: dict(kernel_us=[], call_ms=[]) for s in sides}
+    info, results = {}, {}
+    for step in range(args.warmup + args.steps):
+        for side, w, z in sides:                                    # alternating: all sides see the same clocks
+            t0 = time.perf_counter()
+            if z is None:
+                got = ctx.affine_extend_run(query, lefts, rights, band_lo=-w, band_hi=w, **scoring)
+            else:
+                got = ctx.affine_extend_zdrop_run(query, lefts, rights, band_lo=-w, band_hi=w, zdrop=z, **scoring)
+            wall = time.perf_counter() - t0
+            lt, ki, c = ctx.last_timings(), ctx.last_kernel(), ctx.last_counters()
+            info[side] = dict(path=ctx.last_path(), kernel=ki["name"], launches=lt["score_launches"], valu_ops_per_cell=ki["valu_ops_per_cell"],
+                              rows_per_lane=ki["rows_per_lane"], cells=lt["cells"], zdrop_stopped=c["zdrop_stopped"], zdrop_rows_run=c["zdrop_rows_run"])
+            results[side] = got
+            if step >= args.warmup:
+                t[side]["kernel_us"].append(lt["score_us"])
+                t[side]["call_ms"].append(wall * 1e3)
+    equal = {}
+    ctx.set_option("no_affine_band", 1)
+    try:
+        for w in widths:                                            # once per width, at the first zdrop: the exact path's two steps
+            side = "zdrop_w%d_z%g" % (w, zdrops[0])
+            exact = ctx.affine_extend_zdrop_run(query, lefts, rights, band_lo=-w, band_hi=w, zdrop=zdrops[0], **scoring)
+            equal[side] = all(np.array_equal(results[side][f], exact[f]) for f in fields + ("rows_done",))
+    finally:
+        ctx.set_option("no_affine_band", 0)
+    rows = np.array([len(r) for r in reads], dtype=np.int64)
+    line = dict(bench="affine_pairs_bench", mode="extend_zdrop", band_half_widths=widths, zdrops=zdrops, chimeric=args.chimeric, pairs=args.pairs,
+                read_len=READ_LEN, window=READ_LEN + FLANK, ref_len=args.ref_len, scoring="%g/%g/%g/%g" % tuple(scoring.values()),
+                steps=args.steps, rows_of_the_list=int(rows.sum()), wavefront_rows_of_the_list=int(((rows.sum() + 3) // 4)),
+                results_equal_exact_path=equal)
+    for side, w, z in sides:
+        k_us, c_ms = statistics.median(t[side]["kernel_us"]), statistics.median(t[side]["call_ms"])
+        line[side] = dict(info[side], kernel_ms=k_us / 1e3, call_ms=c_ms, mean_score=float(results[side]["score"].mean()),
+                          kernel_ms_min=min(t[side]["kernel_us"]) / 1e3, kernel_ms_max=max(t[side]["kernel_us"]) / 1e3,
+                          call_ms_min=min(t[side]["call_ms"]), call_ms_max=max(t[side]["call_ms"]))
+        if z is None:
+            continue
+        b, base = line[side], line["band_w%d" % w]
+        b["stopped_share"] = float((results[side]["rows_done"] < rows).mean())
+        b["rows_done_sum"] = int(results[side]["rows_done"].sum())
+        b["same_score_as_banded"] = float((results[side]["score"] == results["band_w%d" % w]["score"]).mean())
+        # a wavefront holds four pairs and runs to the last of them: its rows against a quarter of the rows of the list
+        b["wavefront_rows_share"] = b["zdrop_rows_run"] / max(1.0, rows.sum() / 4.0)
+        b["kernel_ratio_zdrop_over_banded"] = b["kernel_ms"] / max(base["kernel_ms"], 1e-9)
+        b["call_ratio_zdrop_over_banded"] = b["call_ms"] / max(base["call_ms"], 1e-9)
+        b["model_ratio_zdrop_over_banded_all_rows"] = b["valu_ops_per_cell"] / base["valu_ops_per_cell"]
+    ctx.close()
+    text = json.dumps(line)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    print(text)
+    return 0 if all(equal.values()) else 1
 
 
 def banded_against_local(args, ctx, reads, query, lefts, rights, diag):
