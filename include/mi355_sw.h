@@ -601,7 +601,10 @@ int mi355_sw_affine_global_trace(mi355_sw_ctx *ctx, const mi355_sw_extend_list *
  * mi355_sw_last_path: "affine_band_extz[R=..]" once per instance that ran, "affine_exact_band_rows" and "affine_exact_band" for the
  * exact path's two steps, "affine_trace" as before.  mi355_sw_last_kernel names "sw_affine_band_extz_kernel<R=..>" with its ops
  * per cell.  mi355_sw_last_counter: "zdrop_stopped" = pairs with rows_done < m; "zdrop_rows_run" = the sum over the z-drop
- * instance's wavefronts of the rows their loops ran (four pairs share a wavefront, which leaves when all four are done). */
+ * instance's wavefronts of the rows their loops ran (four pairs share a wavefront, which leaves when all four are done).
+ * Every affine call also counts its launches of the exact kernels: "exact_launches" = launches of any sw_affine_exact_* kernel
+ * (at most 65 536 problems each; the rows instance included, which is also cut at 2^24 row words), "trace_launches" = launches of
+ * any sw_affine_trace_* kernel (at most 65 536 problems and 2^30 decision bytes each).  Both are 0 where no such kernel ran. */
 int mi355_sw_affine_extend_run_zdrop(mi355_sw_ctx *ctx, const mi355_sw_extend_list *list, const int64_t *band_lo,
                                      const int64_t *band_hi, float zdrop, const mi355_sw_affine_params *params, float *score,
                                      int64_t *end_x, int64_t *end_y, float *to_end_score, int64_t *to_end_y,

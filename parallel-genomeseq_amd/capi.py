@@ -706,7 +706,7 @@ class Context:
         out = dict(requeried=int(c[0]), whole_batch_again=int(c[1]), candidates=int(c[2]), left_window=int(c[3]))
         for name in ("first_settled", "saved_locates", "saved_traces", "saved_fallbacks", "walk_widened", "wait_retries", "early_settled", "beyond_f16", "prefix_certified",
                      "prefix_second_pass", "prefix_thinned", "prefix_thin_items", "pooled_loops", "prefix_seeded", "prefix_seed_hits", "prefix_calibrated", "seed_certified",
-                     "zdrop_stopped", "zdrop_rows_run"):
+                     "zdrop_stopped", "zdrop_rows_run", "exact_launches", "trace_launches"):
             v = C.c_uint64(0)
             rc = self._L.mi355_sw_last_counter(self._ctx, name.encode(), C.byref(v))
             if rc:

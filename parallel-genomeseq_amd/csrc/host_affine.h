@@ -200,6 +200,7 @@ int run_affine_exact(const AffineCall &c, std::vector<Job> &jobs, size_t lo, siz
   { int rc = affine_scoring(ctx, c.p, sc); if (rc) return rc; }
   launch_dyn_lds(affine_exact_instance(c, pr.data()), dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<Problem>(), sc);
   HIPCHK(ctx, hipGetLastError());
+  ctx->exact_launches += 1;
   std::vector<float> bf(n);
   std::vector<int64_t> ci(2 * n);
   HIPCHK(ctx, hipMemcpyAsync(bf.data(), ctx->outs_f.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -568,6 +569,7 @@ int affine_trace(const AffineCall &c, const std::vector<AffineTraceItem> &items,
     else kern = c.e2e() ? &sw_affine_trace_kernel<true> : &sw_affine_trace_kernel<false>;
     launch_dyn_lds(kern, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<Problem>(), sc);
     HIPCHK(ctx, hipGetLastError());
+    ctx->trace_launches += 1;
     HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     std::vector<int64_t> wo(3 * n);
     std::vector<char> cons(cons_total);
@@ -1399,6 +1401,7 @@ int affine_ext_rows_stage(const AffineCall &c, std::vector<AffineExtItem> &jobs,
     HIPCHK(ctx, hipMemcpyAsync(ctx->probs.p, pr.data(), n * sizeof(ExactBandProblem), hipMemcpyHostToDevice, ctx->stream));
     launch_dyn_lds(&sw_affine_exact_rows_band_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactBandProblem>(), sc);
     HIPCHK(ctx, hipGetLastError());
+    ctx->exact_launches += 1;
     std::vector<float> rows(words);
     std::vector<int32_t> cols;
     HIPCHK(ctx, hipMemcpyAsync(rows.data(), ctx->hmat.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1461,6 +1464,7 @@ int affine_ext_exact_stage(const AffineCall &c, const std::vector<AffineExtItem>
     else if constexpr (BAND) launch_dyn_lds(&sw_affine_exact_ext_band_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<Problem>(), sc);
     else launch_dyn_lds(&sw_affine_exact_ext_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->probs.as<ExactProblem>(), sc);
     HIPCHK(ctx, hipGetLastError());
+    ctx->exact_launches += 1;
     std::vector<float> bf(NO * n);
     std::vector<int64_t> ci(2 * NO * n);
     HIPCHK(ctx, hipMemcpyAsync(bf.data(), ctx->outs_f.p, NO * n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1568,6 +1572,7 @@ int affine_ext_trace(const AffineCall &c, const std::vector<AffineExtItem> &pair
     if constexpr (BAND) launch_dyn_lds(&sw_affine_trace_ext_band_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<Problem>(), sc);
     else launch_dyn_lds(&sw_affine_trace_ext_kernel, dim3((unsigned)n), dim3(64), lds, ctx->stream, ctx->wprobs.as<AffineTraceProblem>(), sc);
     HIPCHK(ctx, hipGetLastError());
+    ctx->trace_launches += 1;
     HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     std::vector<int64_t> wo(3 * n);
     std::vector<char> cons(cons_total);

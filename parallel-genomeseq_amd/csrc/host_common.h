@@ -378,6 +378,8 @@ struct mi355_sw_ctx {
   size_t walk_widened = 0;        // times a traceback window's budget was multiplied by 4 in the running call (walk status 1)
   size_t zdrop_stopped = 0;       // pairs of the running z-drop extension call with rows_done < m
   size_t zdrop_rows_run = 0;      // ... and the rows the row loops of its sw_affine_band_extz_kernel wavefronts ran, summed over the wavefronts
+  size_t exact_launches = 0;      // launches of any sw_affine_exact_* kernel in the running call (the rows instance included)
+  size_t trace_launches = 0;      // launches of any sw_affine_trace_* kernel in the running call
   DevBuf thin_items, thin_out, thin_vals;   // the thin stage's item list, its survivors (count, then the list) and the test hook's value rows
   // the seed stage of the chained prefix filter (sw_seed_kernel.h, host_pipeline.h prefix_seeded)
   DevBuf seed_tab, seed_hits;               // the batch's seed table as one blob; hit counts, then the hit lists

@@ -2208,6 +2208,7 @@ void reset_timings(mi355_sw_ctx *ctx) {
   ctx->hook_ids.clear(); ctx->hook_nsub = 0;
   ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->walk_widened = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
   ctx->zdrop_stopped = 0; ctx->zdrop_rows_run = 0;
+  ctx->exact_launches = 0; ctx->trace_launches = 0;
   ctx->path.clear();
 }
 

@@ -830,6 +830,8 @@ int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *o
   else if (k == "walk_widened") *out = ctx->walk_widened;
   else if (k == "zdrop_stopped") *out = ctx->zdrop_stopped;
   else if (k == "zdrop_rows_run") *out = ctx->zdrop_rows_run;
+  else if (k == "exact_launches") *out = ctx->exact_launches;
+  else if (k == "trace_launches") *out = ctx->trace_launches;
   else if (k == "pooled_loops") *out = tl_pooled_loops;            // (the calling thread's last call: this function opens no OptScope)
   else return MI355_SW_EINVAL;
   return 0;
