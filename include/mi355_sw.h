@@ -737,6 +737,23 @@ uint32_t mi355_sw_seed_hash(const uint8_t *codes, int k);
 int mi355_sw_seed_cluster(size_t n_hits, const int64_t *starts, const int32_t *offsets, int64_t width, int64_t *lo, int64_t *hi, int *distinct);
 int mi355_sw_seed_hits(mi355_sw_ctx *ctx, int64_t left, int64_t right, int k, uint32_t *counts, int64_t *starts, int32_t *offsets, int *k_used);
 
+/* The tile length of a pass of the seeded flow by how its launch fills the chip.  The passes of the groups ("prefix_group"
+ * tags, their second passes included) on a range of at least "prefix_fill_min_cols" columns (default 4 Mi) take the cheapest tile under
+ *   cost(c) = ceil((warm + c + lanes) / 64) x 64 x (workgroups / slots + f0),   f0: the tail of a launch, in rounds,
+ * with workgroups = pairs x ceil(ceil(cols / c) / (256 / lanes)) against slots = cus x resident (the resident workgroups per CU of the
+ * instance, asked of the runtime), among the multiples of the sub-chunk length from the shortest tile whose warm-up redundancy
+ * (warm + lanes) / c stays under `cap` up to old_len, the length of the rule before — and only for a predicted gain of at least 4 %.
+ * A launch of more than 2 rounds (workgroups / slots) at old_len keeps old_len: nothing deeper has been measured.
+ * "no_prefix_fill" gives the rule before (the A/B, whatever else is set), "prefix_group_chunk" forces the length of these passes alone
+ * (tuning aid; whole sub-chunks, at most 64 of them and at most the range).  Results
+ * are the same either way; counters that depend on where tiles are cut ("candidates", "prefix_thin_items") may differ; "prefix_fill_moved" counts
+ * the passes of the call whose tile the rule shortened, "prefix_fill_resident" is the resident count it took for the largest group.
+ * mi355_sw_prefix_group_tile_len (test hook, no device): the rule.  resident <= 0 or any argument out of range: old_len.  f0 <= 0 /
+ * cap <= 0: the library's constants, which mi355_sw_prefix_fill_constants returns with the gain threshold. */
+int64_t mi355_sw_prefix_group_tile_len(int64_t pairs, int64_t cols, int64_t sub_len, int64_t warm, int lanes, int cus, int resident,
+                                       int64_t old_len, double f0, double cap);
+void mi355_sw_prefix_fill_constants(double *f0, double *cap, double *gain);
+
 /* Which kernels and pipeline decisions the last call used: space-separated tags, each at most once, e.g.
  * "score[cell=f16,SL=8,R=19,...,sampled=1,...] strip[R=3,mode=max,...] wave[orient=0,...,dirs=1,...] walk_wave" — what the parity
  * tests assert a switch of mi355_sw_set_option ENGAGED with.  A call whose single-alignment chain declined after its launches

@@ -32,6 +32,7 @@ EXPORTS = [
     "mi355_sw_affine_extend_run_zdrop", "mi355_sw_affine_extend_trace_zdrop",
     "mi355_sw_seed_k", "mi355_sw_seed_hash", "mi355_sw_seed_cluster", "mi355_sw_seed_hits",
     "mi355_sw_seed_usable", "mi355_sw_seed_certify_ok", "mi355_sw_seed_certify_window",
+    "mi355_sw_prefix_group_tile_len", "mi355_sw_prefix_fill_constants",
 ]
 SEED_HIT_CAP = 32                                       # hits listed per read by the seed scan (kSeedHitCap of sw_seed_kernel.h)
 AFFINE_LOCAL, AFFINE_END_TO_END = 0, 1                 # mode of the affine pairs calls (include/mi355_sw.h)
@@ -106,6 +107,8 @@ def lib():
         L.mi355_sw_option_names.restype = C.c_char_p
         L.mi355_sw_last_path.restype = C.c_char_p
         L.mi355_sw_seed_hash.restype = C.c_uint32
+        L.mi355_sw_prefix_group_tile_len.restype = C.c_int64
+        L.mi355_sw_prefix_fill_constants.restype = None
         for name in EXPORTS:
             getattr(L, name)
         _LIB = L
@@ -706,7 +709,7 @@ class Context:
         out = dict(requeried=int(c[0]), whole_batch_again=int(c[1]), candidates=int(c[2]), left_window=int(c[3]))
         for name in ("first_settled", "saved_locates", "saved_traces", "saved_fallbacks", "walk_widened", "wait_retries", "early_settled", "beyond_f16", "prefix_certified",
                      "prefix_second_pass", "prefix_thinned", "prefix_thin_items", "pooled_loops", "prefix_seeded", "prefix_seed_hits", "prefix_calibrated", "seed_certified",
-                     "zdrop_stopped", "zdrop_rows_run", "exact_launches", "trace_launches"):
+                     "zdrop_stopped", "zdrop_rows_run", "exact_launches", "trace_launches", "prefix_fill_moved", "prefix_fill_resident"):
             v = C.c_uint64(0)
             rc = self._L.mi355_sw_last_counter(self._ctx, name.encode(), C.byref(v))
             if rc:
@@ -913,6 +916,20 @@ def seed_certify_window(start, m, d, smax, g, n):
     if rc < 0:
         raise MI355Error(rc, "mi355_sw_seed_certify_window")
     return (lo.value, hi.value) if rc == 1 else None
+
+
+def prefix_group_tile_len(pairs, cols, sub_len, warm, lanes, cus, resident, old_len, f0=0.0, cap=0.0):
+    """mi355_sw_prefix_group_tile_len: the tile length of a seeded group's pass by the launch's fill (no device needed).
+    f0 / cap of 0: the library's constants (prefix_fill_constants)."""
+    return int(lib().mi355_sw_prefix_group_tile_len(C.c_int64(pairs), C.c_int64(cols), C.c_int64(sub_len), C.c_int64(warm), C.c_int(lanes),
+                                                    C.c_int(cus), C.c_int(resident), C.c_int64(old_len), C.c_double(f0), C.c_double(cap)))
+
+
+def prefix_fill_constants():
+    """mi355_sw_prefix_fill_constants: (f0, cap, gain) — what a partly filled round costs, the redundancy cap, the switching threshold."""
+    f0, cap, gain = C.c_double(0), C.c_double(0), C.c_double(0)
+    lib().mi355_sw_prefix_fill_constants(C.byref(f0), C.byref(cap), C.byref(gain))
+    return f0.value, cap.value, gain.value
 
 
 def seed_cluster(hits, width):

@@ -15,8 +15,8 @@ constexpr size_t kExactLdsMax = 159 * 1024;    // dynamic part; the wide instanc
   X(no_f16) X(no_unsat) X(no_sample) X(no_satflag) X(no_solo) X(no_wave) X(no_comb) X(no_twin) X(no_wide) X(no_strip) \
   X(no_quant) X(no_devlist) X(no_ref_cache) X(no_strip_groups) X(u8_long_twin) X(long_twin) X(no_long) \
   X(no_requery) X(force_f32) X(no_long_p32) X(no_opt_margin) X(no_wave_prof) X(no_wave_window) X(no_first) X(no_long_save) X(u8_sample_short) X(no_wave_pieces) X(no_u8_early) X(no_wave_f16) X(no_devlist_by_id) X(no_f16_mirror) X(no_f16m_int_diag) X(no_affine_sweep) X(no_affine_prof) X(no_affine_pairs) X(no_prefix) X(trace) \
-  X(no_prefix_low) X(no_prefix_cascade) X(no_prefix_step) X(no_affine_band) X(no_prefix_thin) X(no_prefix_seed) X(no_seed_certify)
-#define MI355_SW_INT_OPTIONS(X) X(strip_r) X(slot) X(few_r) X(chunk) X(long_pipes) X(long_wgs) X(long_sub) X(long_r) X(long_groups) X(assume_cus) X(long_save_what) X(prefix_min_cols) X(prefix_thin_min_cols) X(prefix_seed_min_cols) X(seed_certify_min_cols) X(seed_ride)
+  X(no_prefix_low) X(no_prefix_cascade) X(no_prefix_step) X(no_affine_band) X(no_prefix_thin) X(no_prefix_seed) X(no_seed_certify) X(no_prefix_fill)
+#define MI355_SW_INT_OPTIONS(X) X(strip_r) X(slot) X(few_r) X(chunk) X(long_pipes) X(long_wgs) X(long_sub) X(long_r) X(long_groups) X(assume_cus) X(long_save_what) X(prefix_min_cols) X(prefix_thin_min_cols) X(prefix_seed_min_cols) X(seed_certify_min_cols) X(seed_ride) X(prefix_fill_min_cols) X(prefix_group_chunk)
 struct Options {
 #define X(n) bool n = false;
   MI355_SW_BOOL_OPTIONS(X)
@@ -390,6 +390,8 @@ struct mi355_sw_ctx {
   PrefixBackground pbg;
   size_t prefix_seeded = 0;                 // reads of the running call whose B0 came from seed hits, before any sweep
   size_t seed_certified = 0;                // ... of them, the reads settled by the windows of their hits alone (lemma L21): kept apart from prefix_certified
+  size_t prefix_fill_moved = 0;             // passes of the seeded flow whose tile the fill rule shortened (host_score.h prefix_group_tile_len)
+  size_t prefix_fill_resident = 0;          // resident workgroups per CU the rule took for the pass that last_kernel names (0: not asked)
   size_t prefix_seed_hits = 0;              // ... and the hits the scan reported for the call's reads
   size_t prefix_calibrated = 0;             // background tables the running call measured (0: the context's table stood)
   DevBuf pkeys, pthr, psel, psel2, qcnt, sel2, gcnt, wlut, ckpt, first, keys, ranges, stab, ftab, ftab_s, htab, htab8, soloblk, flags, submax, lut, probs, dirs, outs_f, outs_i, cons, walkp, hmat, brow, wprobs, scan;
@@ -403,6 +405,8 @@ struct mi355_sw_ctx {
   // event pairs around the score launches of a call, read back after the call's first synchronisation
   std::vector<hipEvent_t> score_ev;
   size_t score_ev_used = 0;
+  // resident workgroups per CU of a sw_score_kernel instance, by (kernel, dynamic LDS bytes): host_score.h score_resident
+  std::map<std::pair<const void *, size_t>, int> score_resident;
   // D2H consensus buffers of the running call (TraceOut points into them); cleared when the next call starts
   std::vector<std::vector<char>> arenas;
   // pinned staging: problem / walk descriptors (up), small results (down), and a pool of consensus buffers that

@@ -1157,6 +1157,9 @@ double background_flags(const PrefixBackground &g, int R, long d) {
 // passes were measured to cost, 2.2 - 2.5 us per read-row on 64 - 150 reads: at 2.5 against 1.85 a pass of its own loses whenever
 // P / P' > 0.74, which holds for every pair of neighbouring heights (16 / 20, 20 / 26, 26 / 32, 32 / 38).  No pass between 150 and
 // 960 reads has been measured; 256 is where a pass fills the chip with one tile per slot several times over and is taken as bulk.
+// (The 2.2 - 2.6 us per read-row of a small pass were measured on the main pass's 16384-column tiles.  Since prefix_group_tile_len,
+// host_score.h, a group's pass on a long range takes tiles by its launch's fill — kPrefixFillF0, kPrefixFillCap there, beside the
+// rule that score_launch needs them for: 121 reads at P = 26 then run at 2.3 us per read-row, profiles/prefix_group_tiles_ab.json.)
 constexpr int64_t kPrefixSeedMinCols = (int64_t)4 << 20;
 constexpr size_t kSeedGroupMin = 256;
 // The size gate of the settled reads (option seed_certify_min_cols), apart from prefix_seed_min_cols.  It has no performance reason:
@@ -2204,7 +2207,7 @@ void reset_timings(mi355_sw_ctx *ctx) {
   for (double &t : ctx->timings) t = 0;
   ctx->score_ev_used = 0; ctx->arenas.clear(); ctx->cons_used = 0;
   ctx->last_kernel = mi355_sw_kernel_info{};
-  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->prefix_seeded = 0; ctx->prefix_seed_hits = 0; ctx->seed_certified = 0; ctx->prefix_calibrated = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
+  ctx->requeried = 0; ctx->whole_again = 0; ctx->candidates = 0; ctx->prefix_certified = 0; ctx->prefix_second_pass = 0; ctx->prefix_thinned = 0; ctx->prefix_thin_items = 0; ctx->prefix_seeded = 0; ctx->prefix_seed_hits = 0; ctx->seed_certified = 0; ctx->prefix_calibrated = 0; ctx->prefix_fill_moved = 0; ctx->prefix_fill_resident = 0; ctx->prefix_named = false; ctx->left_window = 0; ctx->beyond_f16 = 0; ctx->first_settled = 0;
   ctx->hook_ids.clear(); ctx->hook_nsub = 0;
   ctx->saved_locates = 0; ctx->saved_traces = 0; ctx->saved_fallbacks = 0; ctx->walk_widened = 0; ctx->wait_retries = 0; ctx->early_settled = 0;
   ctx->zdrop_stopped = 0; ctx->zdrop_rows_run = 0;

@@ -508,24 +508,42 @@ double valu_ops_per_cell(const Bucket &b) {
   return per_step / (double)(cells_per_row * R);
 }
 
+// The compiled instance `want`; nullptr: there is none
+ScoreKernel score_kernel_of(const ScoreInst &want) {
+  for (size_t k = 0; k < kScoreInsts.size(); ++k)
+    if (kScoreInsts[k] == want) return kScoreKernels[k];
+  for (size_t k = 0; low_step_inst(want) && k < std::size(kR2Step); ++k)
+    if (kR2Step[k] == want.R) return kLowStepKernels[k];
+  return nullptr;
+}
+
 // Launches the compiled instance `want`; -1: there is none
 int launch_score(const ScoreInst &want, dim3 grid, size_t shmem, hipStream_t st, const ScoreArgs &a) {
-  for (size_t k = 0; k < kScoreInsts.size(); ++k) {
-    if (!(kScoreInsts[k] == want)) continue;
-    // large alphabets x many rows per lane need more than the default 64 KiB of dynamic LDS
-    if (shmem > 48 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kScoreKernels[k]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    hipLaunchKernelGGL(kScoreKernels[k], grid, dim3(256), shmem, st, a);
-    return 0;
-  }
-  for (size_t k = 0; low_step_inst(want) && k < std::size(kR2Step); ++k) {
-    if (kR2Step[k] != want.R) continue;
-    if (shmem > 48 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kLowStepKernels[k]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    hipLaunchKernelGGL(kLowStepKernels[k], grid, dim3(256), shmem, st, a);
-    return 0;
-  }
-  return -1;
+  const ScoreKernel kernel = score_kernel_of(want);
+  if (!kernel) return -1;
+  // large alphabets x many rows per lane need more than the default 64 KiB of dynamic LDS
+  if (shmem > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), shmem, st, a);
+  return 0;
+}
+
+// Workgroups of 256 threads of the instance that one CU holds at once with `shmem` bytes of dynamic LDS (the runtime's occupancy
+// rule: registers, LDS, wave slots), asked once per (instance, LDS size) and kept on the context; 0: unknown — the caller keeps the
+// rule that does not need it.
+int score_resident(mi355_sw_ctx *ctx, const ScoreInst &want, size_t shmem) {
+  const ScoreKernel kernel = score_kernel_of(want);
+  if (!kernel) return 0;
+  const std::pair<const void *, size_t> key{reinterpret_cast<const void *>(kernel), shmem};
+  auto at = ctx->score_resident.find(key);
+  if (at != ctx->score_resident.end()) return at->second;
+  if (shmem > 48 * 1024)
+    (void)hipFuncSetAttribute(key.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, key.first, 256, shmem) != hipSuccess) { (void)hipGetLastError(); n = 0; }
+  n = std::max(0, n);
+  ctx->score_resident[key] = n;
+  return n;
 }
 
 // The kernel's cell type of bucket b: a kSemF16 bucket on mirrored cells takes kSemF16M, or kSemF16MF (option no_f16m_int_diag)
@@ -706,6 +724,63 @@ int64_t pick_chunk_len(int64_t max_range_len, size_t npairs, int64_t warm, int S
   }
   { const long v = opt().chunk; if (v >= 64) cl = v / 64 * 64; }   // tuning aid
   return cl;
+}
+
+// The tile length of a pass of the seeded flow (Bucket::bulk) by how its launch fills the chip.  A launch of
+//   workgroups = pairs x ceil(ceil(n / c) / (256 / SL))
+// keeps `slots` = CUs x resident of them on the chip at once, and a tile costs segments(c) = ceil((warm + c + SL) / 64) segments of
+// 64 steps.  What the device shows (tools/prefix_group_tiles.py, profiles/prefix_group_tiles_ab.json; CHANGELOG.md): a launch's
+// time follows the workgroups it holds per slot PLUS a tail of about half a round, whatever the length of a round — while the
+// last workgroups drain, the SIMDs hold one or two wavefronts and a step is bound by the latency of the dependent row chain, not
+// by issue.  A launch of one or two rounds of long tiles pays that tail on a long round, one of six rounds of short tiles on a short one:
+//   cost(c) = segments(c) x 64 x (workgroups / slots + kPrefixFillF0)
+// (The form first proposed, whole rounds plus max(fill, f0) for the last, does not describe the device: it puts 61 pairs x 50 Mbp on
+// 11520-column tiles, 1.62 rounds, which ran no faster than 16384.)  Candidates are the multiples of the sub-chunk length E from the
+// floor up to `old_len`, what pick_chunk_len gave: never a longer tile.  The floor is the shortest tile whose warm-up redundancy
+// (warm + SL) / c stays under `cap`, and at least E: below 3072 columns (4.2 % at a warm-up of 128) no group measured got faster and
+// the tiles' borders list more flags.  The cheapest candidate wins (the longer of two equal ones), and only with a predicted gain of
+// at least 4 % over old_len, the threshold of pick_chunk_len's refinement: a launch many rounds deep has nothing to gain and
+// stays (992 pairs x 50 Mbp: 16384).  resident <= 0 (unknown): old_len.
+// The rule moves only what was measured: launches of at most kPrefixFillMaxRounds rounds at old_len.  The sweeps cover 0.05 - 1.65
+// rounds there (1 - 88 pairs x 50 Mbp); the model states about twice the gain the device shows (21 / 17 % stated, 9.6 / 5.8 %
+// measured), so for a group of some hundred reads, 2 - 8 rounds deep, its 4 - 9 % may be nothing at all, and no such group has
+// been swept at any tile length (host_pipeline.h kSeedGroupMin: nothing between 150 and 960 reads).  Those keep old_len.
+// kPrefixFillCap is fitted at a warm-up of 128 columns (P = 26 / 32 / 38: the floor is 3072); at 64 (P = 16 / 20) it puts the floor
+// at 1536 columns, at 192 at 4352, and no sweep covers either — 64 runs in tests/test_gpu_prefix_group_tiles.py alone, for
+// exactness, not speed.
+constexpr double kPrefixFillF0 = 0.5;                                   // the tail of a launch, in rounds
+constexpr double kPrefixFillCap = 0.045;                                // warm-up redundancy a tile may have
+constexpr double kPrefixFillGain = 0.04;
+constexpr double kPrefixFillMaxRounds = 2.0;                            // workgroups / slots at old_len beyond which nothing moves
+constexpr int64_t kPrefixFillMinCols = (int64_t)4 << 20;               // the seeded flow's own gate value (kPrefixSeedMinCols)
+inline int64_t prefix_fill_cols_min() { const long v = opt().prefix_fill_min_cols; return v > 0 ? (int64_t)v : kPrefixFillMinCols; }
+struct PrefixFill { int64_t wgs = 0, slots = 0; double rounds = 0.0, cost = 0.0; };
+PrefixFill prefix_fill_cost(int64_t pairs, int64_t n, int64_t c, int64_t warm, int SL, int cus, int resident, double f0) {
+  PrefixFill f;
+  const int64_t tiles = (n + c - 1) / c, per_wg = 256 / SL;
+  f.wgs = pairs * ((tiles + per_wg - 1) / per_wg);
+  f.slots = (int64_t)cus * (int64_t)resident;
+  f.rounds = (double)f.wgs / (double)f.slots + f0;
+  f.cost = (double)((warm + c + SL + 63) / 64 * 64) * f.rounds;
+  return f;
+}
+int64_t prefix_group_tile_len(int64_t pairs, int64_t n, int64_t E, int64_t warm, int SL, int cus, int resident, int64_t old_len,
+                              double f0 = kPrefixFillF0, double cap = kPrefixFillCap) {
+  if (pairs < 1 || n < 1 || E < 1 || warm < 0 || SL < 1 || SL > 256 || cus < 1 || resident < 1 || old_len < E || !(f0 >= 0.0) || !(cap > 0.0))
+    return old_len;
+  int64_t lo = E;
+  while (lo <= old_len && (double)(warm + SL) >= cap * (double)lo) lo += E;   // redundancy (warm + SL) / c strictly under the cap
+  const PrefixFill before = prefix_fill_cost(pairs, n, old_len, warm, SL, cus, resident, f0);
+  if ((double)before.wgs > kPrefixFillMaxRounds * (double)before.slots) return old_len;
+  const double base = before.cost;
+  int64_t best = old_len;
+  double best_cost = base;
+  for (int64_t c = old_len / E * E; c >= lo; c -= E) {
+    if (c == old_len) continue;
+    const double cost = prefix_fill_cost(pairs, n, c, warm, SL, cus, resident, f0).cost;
+    if (cost < best_cost) { best_cost = cost; best = c; }
+  }
+  return best_cost <= (1.0 - kPrefixFillGain) * base ? best : old_len;
 }
 
 // The score tables of a call on the device (sent again only when they change), and the scale of the float32 instance.
@@ -1044,11 +1119,51 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
     const int64_t cl0 = pick_chunk_len(maxlen, npairs * nr, b.warm, b.SL, b.twin, b.maxlen, b.sub_len, 0);
     while (2 * cl0 / b.sub_len > 64) b.sub_len *= 2;
   }
-  // (the groups of the seeded flow take the main pass's tiles at every size: the bench batch's four groups of 1119, 526, 355 and 48
-  // reads under option chunk = 16384 / 32768 / 65536 for all of them: 90.76 / 99.41 / 114.82 ms per call, against 93.24 with 16384
-  // for the largest group alone — profiles/prefix_seed_tile_lengths.json)
+  // (the groups of the seeded flow start from the main pass's tiles: the bench batch's four groups of 1119, 526, 355 and 48 reads
+  // under option chunk = 16384 / 32768 / 65536 for all of them: 90.76 / 99.41 / 114.82 ms per call, against 93.24 with 16384 for the
+  // largest group alone — profiles/prefix_seed_tile_lengths.json.  That was measured on groups many rounds deep and on nothing
+  // below 16384 columns; since the settled reads the groups are 121 / 39 / 3 reads, one round or less, and prefix_group_tile_len
+  // below shortens their tiles by the launch's fill)
   const bool chain_main = b.prefix && b.rowp && b.step && b.SL == kPrefixLanes && (b.bulk || (!b.second && b.count >= kPrefixChain - kPrefixProbe));
   b.chunk_len = pick_chunk_len(maxlen, npairs * nr, b.warm, b.SL, b.twin, b.maxlen, b.sub_len, free_sub ? 64 * kSeg : b.sub_len, chain_main);
+  // A prefix pass sweeps the first P = SL R rows only, and L1 on THAT matrix asks for cols(P) columns in front of a tile, not the
+  // cols(m) of the whole read (150 rows at 3 / -3 / 2: 384; P = 26: 128) — what thin_plan does with warm2.  pick_chunk_len above and
+  // the windows of the locate stage (prefix_bucket: qwarm) keep the bucket's own margin.
+  int64_t prefix_warm = b.warm;
+  if (b.prefix && !b.strips && prefix_warm > 0) {
+    const Margin pmg = t.margin(b.SL * b.R);
+    if (pmg.finite()) prefix_warm = std::min(prefix_warm, (pmg.cols(b.SL * b.R) + 63) / 64 * 64);
+  }
+  // The seeded flow's passes: on a long range the tile by the launch's fill, on the warm-up the pass really runs.  Option
+  // prefix_group_chunk forces the length of these passes alone (tuning aid: tools/prefix_group_tiles.py) at any range length, within
+  // one sub-chunk .. 64 sub-chunks (16384 columns, the longest the old rule gives them) and the range; no_prefix_fill is the rule
+  // before whatever else is set.
+  if (chain_main && b.bulk && nr == 1 && b.sub_len > 0 && b.chunk_len % b.sub_len == 0 && opt().chunk < 64) {
+    const int64_t old_len = b.chunk_len, E = b.sub_len;
+    const bool on = !opt().no_prefix_fill;
+    const int64_t forced = on && opt().prefix_group_chunk >= E
+                             ? std::min<int64_t>({(int64_t)opt().prefix_group_chunk / E * E, 64 * E, (maxlen + E - 1) / E * E}) : 0;
+    const bool fill = on && forced == 0 && maxlen >= prefix_fill_cols_min();
+    int resident = 0;
+    if (forced || fill) {
+      const ScoreInst inst{b.R, sem, false, b.SL, false, false, 1, true};
+      const size_t lds = profile_lds_bytes(ref.ncodes, b.R, b.SL, b.twin, b.comb) + (size_t)(256 / b.SL) * codebuf_bytes(b.SL);
+      resident = score_resident(ctx, inst, lds);
+    }
+    if (forced) b.chunk_len = forced;
+    else if (fill) {
+      b.chunk_len = prefix_group_tile_len((int64_t)npairs, maxlen, E, prefix_warm, b.SL, dev_cus(), resident, old_len);
+      if (b.chunk_len != old_len) ctx->prefix_fill_moved += 1;
+      if (!b.second) ctx->prefix_fill_resident = (size_t)resident;
+    }
+    if (opt().trace) {                                               // (slots and rounds 0: the rule did not ask for the resident count)
+      PrefixFill f;
+      if (resident > 0) f = prefix_fill_cost((int64_t)npairs, maxlen, b.chunk_len, prefix_warm, b.SL, dev_cus(), resident, kPrefixFillF0);
+      else f.wgs = (int64_t)npairs * (((maxlen + b.chunk_len - 1) / b.chunk_len + 256 / b.SL - 1) / (256 / b.SL));
+      std::fprintf(stderr, "[mi355_sw] prefix fill: R=%d pairs=%zu tile=%lld workgroups=%lld slots=%lld rounds=%.2f old=%lld%s\n", b.R, npairs,
+                   (long long)b.chunk_len, (long long)f.wgs, (long long)f.slots, f.rounds, (long long)old_len, forced ? " (forced)" : "");
+    }
+  }
   if (free_sub && b.chunk_len % (64 * kSeg) == 0) b.sub_len = b.chunk_len / 64;
   if (b.strips) while (b.chunk_len / b.sub_len > 64) b.sub_len *= 2;      // the strip-mined instances keep <= 64 sub-chunk maxima in LDS
   if (b.sub_len > b.chunk_len || b.chunk_len % b.sub_len != 0) b.sub_len = b.chunk_len;
@@ -1065,13 +1180,7 @@ int score_launch(mi355_sw_ctx *ctx, const RefData &ref, const QueryBatch &q, con
   a.chunk_len = b.chunk_len;
   a.sub_len = b.sub_len;
   a.warm = (cpr == 1) ? 0 : b.warm;              // a single tile per range starts at the range's own border
-  // A prefix pass sweeps the first P = SL R rows only, and L1 on THAT matrix asks for cols(P) columns in front of a tile, not the
-  // cols(m) of the whole read (150 rows at 3 / -3 / 2: 384; P = 26: 128) — what thin_plan does with warm2.  The tile length above and
-  // the windows of the locate stage (prefix_bucket: qwarm) keep the bucket's own margin.
-  if (b.prefix && !b.strips && a.warm > 0) {
-    const Margin pmg = t.margin(b.SL * b.R);
-    if (pmg.finite()) a.warm = std::min(a.warm, (pmg.cols(b.SL * b.R) + 63) / 64 * 64);
-  }
+  if (a.warm > 0) a.warm = prefix_warm;          // (a prefix pass: the margin of its own rows, above)
   a.chunks_per_range = (int)cpr;
   a.qbytes = q.bytes.as<uint8_t>();
   a.qoff = q.offs.as<int64_t>();
@@ -1257,6 +1366,7 @@ int score_fetch(mi355_sw_ctx *ctx, size_t count, std::vector<unsigned long long>
     float ms = 0;
     HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->score_ev[e], ctx->score_ev[e + 1]));
     ctx->timings[0] += (double)ms * 1000.0;
+    if (opt().trace) std::fprintf(stderr, "[mi355_sw] score launch: %.3f ms on the device\n", ms);   // (after the "prefix fill" line of its pass)
   }
   ctx->score_ev_used = 0;
   return 0;

@@ -819,6 +819,8 @@ int mi355_sw_last_counter(const mi355_sw_ctx *ctx, const char *name, uint64_t *o
   else if (k == "prefix_seed_hits") *out = ctx->prefix_seed_hits;
   else if (k == "seed_certified") *out = ctx->seed_certified;
   else if (k == "prefix_calibrated") *out = ctx->prefix_calibrated;
+  else if (k == "prefix_fill_moved") *out = ctx->prefix_fill_moved;
+  else if (k == "prefix_fill_resident") *out = ctx->prefix_fill_resident;
   else if (k == "left_window") *out = ctx->left_window;
   else if (k == "beyond_f16") *out = ctx->beyond_f16;
   else if (k == "first_settled") *out = ctx->first_settled;
@@ -919,6 +921,17 @@ int mi355_sw_seed_usable(const uint8_t *read, int32_t len, int k, const uint8_t 
 }
 
 int mi355_sw_seed_certify_ok(int64_t d, int64_t smax, int64_t g, int64_t u) { return seed_certify_ok(d, smax, g, u) ? 1 : 0; }
+
+int64_t mi355_sw_prefix_group_tile_len(int64_t pairs, int64_t cols, int64_t sub_len, int64_t warm, int lanes, int cus, int resident,
+                                       int64_t old_len, double f0, double cap) {
+  return prefix_group_tile_len(pairs, cols, sub_len, warm, lanes, cus, resident, old_len, f0 > 0.0 ? f0 : kPrefixFillF0, cap > 0.0 ? cap : kPrefixFillCap);
+}
+
+void mi355_sw_prefix_fill_constants(double *f0, double *cap, double *gain) {
+  if (f0) *f0 = kPrefixFillF0;
+  if (cap) *cap = kPrefixFillCap;
+  if (gain) *gain = kPrefixFillGain;
+}
 
 int mi355_sw_seed_certify_window(int64_t start, int64_t m, int64_t d, int64_t smax, int64_t g, int64_t n, int64_t *lo, int64_t *hi) {
   if (!lo || !hi) return MI355_SW_EINVAL;
